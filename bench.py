@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: full-gate propagators/s (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config C] [--scaling weak|strong] [--batch B] [--check]
+    python bench.py --gpus N --steps K --warmup W [--config C] [--scaling weak|strong] [--batch B] [--check] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic pulse-parameter samples:
 U[b] = FR_b * prod_n exp(-i H_b[n] dt) for all b (Lindblad configs: the D^2 x D^2 superoperator).  Default = the
@@ -157,7 +157,43 @@ def parse_args(argv=None):
                     help="give the second control operator an imaginary (Hermitian) part: the general complex-Hamiltonian instances instead of the real fast path")
     ap.add_argument("--exchange", choices=("gather", "goal"), default="gather",
                     help="multi-GPU exchange: all-gather of the U slabs (default) or the gather-free optimiser loop: fused fidelity per sample + ONE all-reduce of the goal per step")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step computed as DIR/<name>.npy (float64; see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, U, goal, rank, world, lo, limit=DUMP_LIMIT_BYTES):
+    """Write what the timed path returned in its last step, so that two builds can be compared output for output (the inputs
+    are seeded per global sample: the same arguments give the same inputs).  U [B, Dm, Dm] complex128 -> U.npy, float64
+    [B, Dm, Dm, 2] (real, imaginary); with --exchange goal also goal.npy = {sum of infidelities, samples}.  Each rank writes
+    its own shard (U_rank<r>.npy at N > 1).  The files of all ranks stay under `limit` bytes: beyond that a fixed, seeded
+    sample of the batch rows is written, with their global sample indices in U_index.npy (float64).  Returns {file: shape}."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    arrays = {}
+    u = torch.view_as_real(U.detach()).cpu().numpy().astype(np.float64, copy=False)
+    per_row = int(np.prod(u.shape[1:])) * 8
+    budget = limit // world - 4096  # room for the .npy headers and the goal
+    if len(u) * per_row > budget:
+        keep = max(1, budget // per_row - 1)  # one row of the budget goes to the index file
+        idx = np.sort(np.random.default_rng(20240).choice(len(u), size=keep, replace=False))
+        u = u[idx]
+        arrays["U_index" + sfx] = (lo + idx).astype(np.float64)
+    arrays["U" + sfx] = u
+    if goal is not None:
+        arrays["goal" + sfx] = goal.detach().cpu().numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name + ".npy": list(a.shape) for name, a in arrays.items()}
 
 
 def self_launch(n, argv):
@@ -330,6 +366,7 @@ def main():
     if standin:
         args.no_e2e = args.no_cpu_baseline = True
     goal_state = {}
+    last_step = {}  # what the most recent timed step returned (--dump-outputs)
 
     def make_schedule(exchange, gather_every, overlap=False):
         """(ring, compute) of one exchange schedule: `gather` = all-gather of the U slabs of `gather_every` steps in one
@@ -384,11 +421,12 @@ def main():
         if ev0 is not None:
             ev0.record()  # HIP events on the stream the kernels are launched on (torch's current stream), over the timed region
         for _ in range(steps):
-            ring.step(compute)
+            last = ring.step(compute)
         if ev1 is not None:
             ev1.record()
         ring.drain()
         sync()
+        last_step["U"] = last[:B]
         # The K steps end here on this rank (the last all-gather inside drain() has already waited for every rank's
         # slabs); the closing barrier follows and the MAX over ranks of the per-rank times is reported, so the
         # barrier's own latency is not booked as step time.
@@ -438,6 +476,10 @@ def main():
     sync()
     elapsed, device_ms_per_step, elapsed_min = time_schedule(ring, compute, args.steps, args.warmup)
     goal_last = [goal_state.get("last")]
+    dumped = None
+    if args.dump_outputs:
+        # before anything else runs on the device: the slot of the last step is reused by the check below
+        dumped = dump_outputs(args.dump_outputs, last_step["U"], goal_last[0] if goal_mode else None, rank, world, lo)
     # The other exchange schedules, timed the same way right after the headline one and reported as extra keys of the
     # SAME line (multi-GPU runs only): the amortised all-gather (32 steps per collective) and the gather-free goal
     # exchange (fused fidelity + one all-reduce per step; unitary configurations).
@@ -639,6 +681,8 @@ def main():
         if goal_mode and goal_last[0] is not None:
             g = goal_last[0].cpu().numpy()
             out["goal"] = {"mean_unitary_infidelity_vs_identity": float(g[0] / max(g[1], 1.0)), "samples": int(g[1])}
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if err is not None:
             out["max_fro_err_vs_oracle"] = err
             out["oracle_samples_checked"] = nchk

@@ -46,6 +46,31 @@ def test_bench_json_line(lib):
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_are_what_the_timed_path_computed(lib, tmp_path):
+    """--dump-outputs DIR: U of the last timed step (float64, real / imaginary on the last axis), equal to the oracle on the
+    same seeded inputs"""
+    import numpy as np
+
+    from c3_amd import _lib, workloads
+    from oracle import c3_oracle
+
+    _lib.require_gpu()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-check",
+                          "--no-cpu-baseline", "--no-e2e", "--ramp-ms", "0", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout)
+    assert d["steps"] == 3 and d["dumped_outputs"] == {"U.npy": [256, 9, 9, 2]}
+    U = np.load(tmp_path / "U.npy")
+    assert U.dtype == np.float64
+    wl = workloads.make_workload(2, B=256)
+    idx = np.array([0, 97, 255])
+    ref = c3_oracle.propagate_batch(wl.h0, wl.hks, wl.signals[idx], wl.dt, fr_phase=wl.fr_phase[idx])
+    for i, b in enumerate(idx):
+        assert np.linalg.norm(U[b, ..., 0] + 1j * U[b, ..., 1] - ref[i]) < 1e-10
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_on_the_visible_devices(lib):
     """`python bench.py --gpus 2` launches its own two ranks.  On a one-GPU box they share the device (RCCL refuses that, so the
     slabs travel over gloo through host memory -- flagged `oversubscribed`); on a node with >= 2 GPUs the same command is the

@@ -213,3 +213,53 @@ def test_bench_under_torchrun_two_ranks():
 def test_bench_self_launch_propagates_a_failing_rank():
     out, d = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "0", "--config", "99"])
     assert out.returncode != 0 and d is None
+
+
+# --------------------------------------------------------------------------
+# `bench.py --dump-outputs DIR`: what the timed path returned in its last step, for output-for-output A/B of two builds
+# --------------------------------------------------------------------------
+
+
+def _standin_U(lo, B, Dm=9):
+    g = np.arange(lo, lo + B, dtype=np.float64).reshape(B, 1, 1)
+    e = np.arange(Dm * Dm, dtype=np.float64).reshape(1, Dm, Dm)
+    return np.stack([np.broadcast_to(g + 1e-3 * e, (B, Dm, Dm)), np.broadcast_to(-1e-6 * e, (B, Dm, Dm))], axis=-1)
+
+
+def test_bench_dump_outputs_one_rank(tmp_path):
+    out, d = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--ramp-ms", "0", "--dump-outputs", str(tmp_path)])
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert d["steps"] == 3 and d["dumped_outputs"] == {"U.npy": [4, 9, 9, 2]}
+    U = np.load(tmp_path / "U.npy")
+    assert U.dtype == np.float64 and np.array_equal(U, _standin_U(0, 4))
+
+
+def test_bench_dump_outputs_two_ranks(tmp_path):
+    out, d = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "3", "--ramp-ms", "0", "--no-alt-schedules",
+                         "--dump-outputs", str(tmp_path)])
+    assert out.returncode == 0, out.stderr[-3000:]
+    for r in range(2):
+        assert np.array_equal(np.load(tmp_path / f"U_rank{r}.npy"), _standin_U(3 * r, 3))
+
+
+def test_bench_dump_outputs_sample_is_bounded_and_fixed(tmp_path):
+    import bench
+
+    U = torch.complex(torch.randn(50, 9, 9, dtype=torch.float64), torch.randn(50, 9, 9, dtype=torch.float64))
+    limit = 20 * 9 * 9 * 16
+    files = bench.dump_outputs(str(tmp_path / "a"), U, None, 0, 1, lo=100, limit=limit)
+    bench.dump_outputs(str(tmp_path / "b"), U, None, 0, 1, lo=100, limit=limit)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= limit
+    idx = np.load(tmp_path / "a" / "U_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == files["U.npy"][0] > 0 and np.all(np.diff(idx) > 0)
+    Ua = np.load(tmp_path / "a" / "U.npy")
+    assert np.array_equal(Ua, torch.view_as_real(U).numpy()[idx.astype(int) - 100])
+    assert np.array_equal(Ua, np.load(tmp_path / "b" / "U.npy")) and np.array_equal(idx, np.load(tmp_path / "b" / "U_index.npy"))
+
+
+def test_bench_steps_must_be_positive():
+    import bench
+
+    assert bench.parse_args(["--steps", "7"]).steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
