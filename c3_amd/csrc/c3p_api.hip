@@ -26,6 +26,7 @@
 #include "c3p_tiled.h"
 #include "c3p_signal.h"
 #include "c3p_grad.h"
+#include "c3p_seq.h"
 
 namespace {
 
@@ -92,7 +93,7 @@ int fail(const char* fmt, ...) {
   } while (0)
 
 // Per-device workspace slots, grown lazily, freed by c3p_shutdown().
-enum Slot { SL_SEG_A = 0, SL_SEG_B, SL_SCRATCH, SL_CLP, SL_TABLES, SL_COUNTERS, SL_COUNTERS2, SL_IN0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_SEG_F, SL_COUNT };
+enum Slot { SL_SEG_A = 0, SL_SEG_B, SL_SCRATCH, SL_CLP, SL_TABLES, SL_COUNTERS, SL_COUNTERS2, SL_IN0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_SEG_F, SL_SEQ_FLAG, SL_COUNT };
 
 struct DeviceWs {
   std::mutex mu;  // one lock per device: calls on different GPUs of one process do not serialise
@@ -3232,6 +3233,81 @@ int c3p_gate_infid(const void* U, int B, int D, const int32_t* comp_rows, int L,
                                 (double*)part, (double*)d_sum, st));
   }
   if (flags & C3P_HOST_PTRS) return sg.finish();
+  return 0;
+}
+
+int c3p_seq_chain(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
+                  const int32_t* lengths, int mode, const void* psi0, int flags, void* out, void* stream) {
+  if (P < 0 || S < 0 || n_gates < 0 || Lmax < 0 || M <= 0 || M > C3P_SEQ_MAX_M || G_bstride < 0)
+    return fail("bad sizes P=%d S=%d n_gates=%d M=%d Lmax=%d G_bstride=%lld (M <= %d)", P, S, n_gates, M, Lmax,
+                (long long)G_bstride, C3P_SEQ_MAX_M);
+  if (mode != C3P_SEQ_PRODUCT && mode != C3P_SEQ_STATE && mode != C3P_SEQ_POPULATION)
+    return fail("unknown sequence output mode %d (0 = product, 1 = state, 2 = population)", mode);
+  if (P > 65535) return fail("P=%d parameter samples: at most 65535 per call", P);
+  if (P == 0 || S == 0) return 0;
+  if (!lengths || !out) return fail("NULL lengths / output pointer");
+  if (mode == C3P_SEQ_STATE && !psi0) return fail("state mode needs psi0");
+  if (Lmax > 0 && !seqs) return fail("seqs is NULL but Lmax=%d", Lmax);
+  if (n_gates > 0 && !G) return fail("gate table is NULL");
+  const size_t cs = sizeof(cplx);
+  const size_t table = (size_t)n_gates * M * M;
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  DeviceWs* w = lk.w;
+  if (!w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  Stage sg{w, st};
+  const void *d_G = G, *d_seqs = seqs, *d_len = lengths, *d_psi = psi0;
+  void* d_out = out;
+  const size_t out_bytes = mode == C3P_SEQ_PRODUCT ? (size_t)P * S * M * M * cs
+                           : mode == C3P_SEQ_STATE ? (size_t)P * S * M * cs
+                                                   : (size_t)P * S * sizeof(double);
+  if (flags & C3P_HOST_PTRS) {
+    // host memory: every length and every index used is checked here, before anything is staged
+    for (int s = 0; s < S; ++s) {
+      const int L = lengths[s];
+      if (L < 0 || L > Lmax) return fail("sequence %d has length %d outside [0, %d]", s, L, Lmax);
+      for (int t = 0; t < L; ++t) {
+        const int g = seqs[(size_t)s * Lmax + t];
+        if (g < 0 || g >= n_gates) return fail("sequence %d, position %d: gate index %d outside [0, %d)", s, t, g, n_gates);
+      }
+    }
+    const size_t g_elems = G_bstride ? (size_t)(P - 1) * G_bstride + table : table;
+    if (sg.in(G, g_elems * cs, &d_G)) return -1;
+    if (sg.in(seqs, (size_t)S * Lmax * sizeof(int32_t), &d_seqs)) return -1;
+    if (sg.in(lengths, (size_t)S * sizeof(int32_t), &d_len)) return -1;
+    if (sg.in(mode == C3P_SEQ_STATE ? psi0 : nullptr, (size_t)M * cs, &d_psi)) return -1;
+    if (sg.out(out, out_bytes, &d_out)) return -1;
+  }
+  void* flag;
+  if (ws_get(w, SL_SEQ_FLAG, sizeof(int), &flag)) return -1;
+  HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), st));
+  SeqArgs a = {};
+  a.G = (const cplx*)d_G;
+  a.G_bstride = (long)G_bstride;
+  a.n_gates = n_gates;
+  a.M = M;
+  a.P = P;
+  a.seqs = (const int*)d_seqs;
+  a.lengths = (const int*)d_len;
+  a.S = S;
+  a.Lmax = Lmax;
+  a.mode = mode;
+  a.superop = (flags & C3P_SEQ_SUPEROP) ? 1 : 0;
+  a.psi0 = (const cplx*)d_psi;
+  a.out = d_out;
+  a.bad = (int*)flag;
+  g_last_kernel = C3P_KERNEL_SEQ;
+  HIP_TRY(c3p_launch_seq(a, st));
+  // device memory: the kernel checked every length and index it met; one int comes back (a stream synchronisation)
+  int bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (flags & C3P_HOST_PTRS) {
+    if (sg.finish()) return -1;
+  } else {
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  if (bad) return fail("a sequence has a length outside [0, %d] or a gate index outside [0, %d): its outputs are NaN", Lmax, n_gates);
   return 0;
 }
 

@@ -285,3 +285,7 @@ def lindbladian_unitary_infid_cotangent(ideal, actual, index: List[int] = [0], d
         tv = np.asarray(tv)
         Sbar = (-(tv / np.abs(tv)) / L**2)[:, None, None] * emb[None]
     return (Sbar[0] if squeeze else Sbar), 1 - abs(t) / L**2
+
+
+# RB, ORBIT and the analytical EPC live with the sequence chain; importing them registers them here
+from . import sequences as _sequences  # noqa: E402,F401

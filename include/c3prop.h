@@ -56,6 +56,7 @@ extern "C" {
                                  of pwc, use_control_fields=False (propagation.py:295-308) */
 #define C3P_ORDER_RIGHT 0x4   /* c3p_matmul_chain: elems[0]@...@elems[N-1] (tf_matmul_right) */
 #define C3P_FORCE_GENERIC 0x8 /* use the generic LDS kernel even where a specialised one exists */
+#define C3P_SEQ_SUPEROP 0x20  /* c3p_seq_chain, population mode: the table holds superoperators, population = |x[0]| */
 #define C3P_HERMITIAN_H 0x10  /* c3p_pwc_lindblad: the caller DECLARES h0 and every hk Hermitian (the library does not check
                                  device memory).  The Lindblad generator is then real in a basis of Hermitian matrices and the
                                  chain of one qubit / qutrit or two qubits (D = 2, 3, 4) runs in real arithmetic (c3p_smallr.hip); other shapes
@@ -73,6 +74,7 @@ extern "C" {
 #define C3P_KERNEL_ODE_ROW 6 /* lane-row ODE kernels (c3p_ode_row.hip, c3p_ode_rowq.hip)  */
 #define C3P_KERNEL_ODE_MFMA 7 /* matrix-core rho-valued ODE kernel, 17 <= D <= 48 (c3p_ode_rhoq.hip) */
 #define C3P_KERNEL_ODE_ROW_OR_WG 8 /* both launched; the DEVICE picks: real operators -> lane rows, complex -> workgroup kernel */
+#define C3P_KERNEL_SEQ 9 /* indexed gate-sequence chains (c3p_seq.hip)                          */
 
 /* ODE solver / step ids (propagation.py:27-32 solver_slicing; :886-904 steps) */
 #define C3P_SOLVER_RK4 0
@@ -357,6 +359,28 @@ int c3p_gate_overlap(const void* U, int B, int D, const int32_t* comp_rows, int 
  */
 int c3p_gate_infid(const void* U, int B, int D, const int32_t* comp_rows, int L, const void* ideal, int kind,
                    int flags, double* infid_out, double* sum_out, void* stream);
+
+/* Gate sequences evaluated by index (evaluate_sequences, c3/libraries/propagation.py:588-627, as used by RB, ORBIT and
+ * epc_analytical, c3/libraries/fidelities.py:437-591,754-791): for every parameter sample p and sequence s
+ *   U_seq[p,s] = G[p, i_{L-1}] ... G[p, i_1] G[p, i_0]        (first gate applied first, as tf_matmul_left)
+ * without gathering the factors: every chain reads its indices and then the gates from the table.  One launch per call.
+ *   G        c128 [P, n_gates, M, M]; element stride between samples G_bstride (0 = one table shared by every sample).
+ *            M = D for unitaries, D^2 for superoperators; 1 <= M <= 256 (M <= 9: one lane per chain, table in LDS)
+ *   seqs     int32 [S, Lmax] gate indices (row s uses its first lengths[s] entries); lengths int32 [S], 0 = identity.
+ *            Shared by all P samples.
+ *   mode     C3P_SEQ_PRODUCT:    out c128 [P,S,M,M] = U_seq
+ *            C3P_SEQ_STATE:      out c128 [P,S,M]   = U_seq psi0, psi0 c128 [M]
+ *            C3P_SEQ_POPULATION: out f64  [P,S]     = |(U_seq e_0)[0]|^2, or with C3P_SEQ_SUPEROP in flags |(U_seq e_0)[0]|
+ *                                (the Lindblad population of vec(|0><0|), fidelities.py:460-470)
+ *            The state and population modes are matrix-vector chains: no matrix product is formed.
+ * A negative length, a length above Lmax or an index outside [0, n_gates) is an error (never a fault): checked on the
+ * host for C3P_HOST_PTRS, otherwise by the kernel, which writes NaN for that sequence and raises a flag the call reads
+ * back -- so every call synchronises its stream once (not capturable into a graph). */
+#define C3P_SEQ_PRODUCT 0
+#define C3P_SEQ_STATE 1
+#define C3P_SEQ_POPULATION 2
+int c3p_seq_chain(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
+                  const int32_t* lengths, int mode, const void* psi0, int flags, void* out, void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -2,6 +2,7 @@
 """The dispatch table of libc3prop as DATA: which kernels a call shape lands in.
 
   measure (GPU):   python tools/dispatch_table.py --measure profiles/r06/dispatch_table.json
+                   python tools/dispatch_table.py --measure-entry seq_chain profiles/r06/dispatch_table.json   (one entry's rows only)
                    every row is one REAL call through the host layer on cuda:0; the kernels are read back from the library's
                    launch log (c3p_last_kernel_detail: host function pointers resolved to kernel names -- what ran, not what
                    the dispatcher meant to run)
@@ -82,6 +83,14 @@ def probe(entry, D, B=4, K=2, N=64, real=True, flags="", seed=0):
         p.ode_solve_batch(t(h0), t(hks), t(sig), dt, t(init), "rk4", step, col_ops=t(col) if step == "lindblad" else None, final_only="final" in flags)
     elif entry == "expm":
         p.expm(t(np.stack([-1j * dt * h0] * B)))
+    elif entry == "seq_chain":
+        # D = M (the table's matrix size), B = parameter samples, N = sequences of random lengths 0 .. 199 over 4 gates
+        from c3_amd import sequences as sq
+
+        G = np.stack([np.linalg.qr(rng.normal(size=(D, D)) + 1j * rng.normal(size=(D, D)))[0] for _ in range(B * 4)]).reshape(B, 4, D, D)
+        lengths = rng.integers(0, 200, size=N).astype(np.int32)
+        seqs = rng.integers(0, 4, size=(N, 200)).astype(np.int32)
+        sq.seq_chain(t(G), t(seqs), t(lengths), flags or "population")
     elif entry == "matmul_chain":
         M = np.stack([np.linalg.qr(rng.normal(size=(D, D)) + 1j * rng.normal(size=(D, D)))[0] for _ in range(N)])
         p.tf_matmul_left(t(np.stack([M] * B)))
@@ -113,12 +122,17 @@ GRID = [
     ("ode_lindblad", "rk4, rho states, one collapse operator, K = 2, B = 64, N = 100", dict(B=64, K=2, N=100), [3, 9, 16, 17, 27, 36, 48, 49]),
     ("expm", "B = 64 matrices", dict(B=64), [3, 9, 12, 13, 27, 40, 41, 81, 93]),
     ("matmul_chain", "ordered product of N = 64 matrices, B = 8", dict(B=8, N=64), [3, 9, 12, 13, 27, 40, 41, 81, 93]),
+    ("seq_chain", "indexed sequences, populations: 4-gate table per sample, B = 64 samples, N = 600 sequences (D = M)", dict(B=64, N=600, flags="population"), [2, 3, 4, 9, 10, 16, 81]),
+    ("seq_chain", "indexed sequences, full products: B = 8 samples, N = 64 sequences (D = M)", dict(B=8, N=64, flags="product"), [2, 3, 9, 10, 16, 81]),
 ]
 
 
-def measure(path):
+def measure(path, only=None):
+    """all GRID rows, or (`only` = an entry name) the rows of that entry, replacing / appending them in an existing file"""
     rows = []
     for entry, label, fixed, dims in GRID:
+        if only is not None and entry != only:
+            continue
         for D in dims:
             kw = dict(fixed)
             flags = kw.pop("flags", "")
@@ -129,6 +143,8 @@ def measure(path):
                 fam, det = "refused", str(e)[:160]
             rows.append({"entry": entry, "regime": label, "D": D, "family": fam, "kernels": det})
             print(entry, label[:40], D, fam, det[:120], flush=True)
+    if only is not None:
+        rows = [r for r in json.load(open(path))["rows"] if r["entry"] != only] + rows
     json.dump({"_comment": "tools/dispatch_table.py --measure on one MI355X: launch logs (c3p_last_kernel_detail) of real calls", "rows": rows}, open(path, "w"), indent=1)
 
 
@@ -179,6 +195,9 @@ def main():
         raise SystemExit(__doc__)
     if a[0] == "--measure":
         measure(a[1])
+        return
+    if a[0] == "--measure-entry":
+        measure(a[2], only=a[1])
         return
     if a[0] == "--probe":
         kw = {}
