@@ -27,6 +27,7 @@
 #include "c3p_signal.h"
 #include "c3p_grad.h"
 #include "c3p_seq.h"
+#include "c3p_seq_vjp.h"
 
 namespace {
 
@@ -40,6 +41,7 @@ struct LaunchNote {
 };
 thread_local LaunchNote g_notes[48];
 thread_local int g_nnotes = 0;
+thread_local std::string g_note_plan;  // a plan parameter the last call reports beside its kernels (c3p_seq_chain_vjp: the checkpoint interval)
 thread_local hipStream_t g_call_stream = nullptr;  // stream of the call in flight (capture check on workspace growth)
 thread_local bool g_dry = false;  // c3p_reserve: run the planning and size the workspace, launch nothing
 
@@ -93,7 +95,7 @@ int fail(const char* fmt, ...) {
   } while (0)
 
 // Per-device workspace slots, grown lazily, freed by c3p_shutdown().
-enum Slot { SL_SEG_A = 0, SL_SEG_B, SL_SCRATCH, SL_CLP, SL_TABLES, SL_COUNTERS, SL_COUNTERS2, SL_IN0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_SEG_F, SL_SEQ_FLAG, SL_COUNT };
+enum Slot { SL_SEG_A = 0, SL_SEG_B, SL_SCRATCH, SL_CLP, SL_TABLES, SL_COUNTERS, SL_COUNTERS2, SL_IN0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_SEG_F, SL_SEQ_FLAG, SL_SEQ_VJP_WS, SL_SEQ_VJP_SLAB, SL_COUNT };
 
 struct DeviceWs {
   std::mutex mu;  // one lock per device: calls on different GPUs of one process do not serialise
@@ -139,6 +141,7 @@ struct WsLock {
     w->mu.lock();
     locked = true;
     g_call_stream = stream;
+    if (order) g_note_plan.clear();
     if (order) g_nnotes = 0;  // a compute call starts a new launch log (c3p_last_kernel_ms looks with order = false)
     // a capturing stream takes no dependency on work outside its graph: the caller orders other streams before the capture
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -2126,6 +2129,7 @@ int c3p_last_kernel_detail(char* buf, int cap) {
     out += std::string(base ? base + 1 : n.file) + ": " + name;
     if (n.count > 1) out += " x" + std::to_string(n.count);
   }
+  if (!g_note_plan.empty()) out += (out.empty() ? "" : "; ") + g_note_plan;
   if (buf && cap > 0) {
     const size_t m = std::min(out.size(), (size_t)cap - 1);
     memcpy(buf, out.data(), m);
@@ -3308,6 +3312,106 @@ int c3p_seq_chain(const void* G, int64_t G_bstride, int n_gates, int M, int P, c
     HIP_TRY(hipStreamSynchronize(st));
   }
   if (bad) return fail("a sequence has a length outside [0, %d] or a gate index outside [0, %d): its outputs are NaN", Lmax, n_gates);
+  return 0;
+}
+
+int c3p_seq_chain_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
+                      const int32_t* lengths, int mode, const void* psi0, const void* out_bar, int flags, void* G_bar, void* out,
+                      void* stream) {
+  if (P < 0 || S < 0 || n_gates < 0 || Lmax < 0 || M <= 0 || M > C3P_SEQ_MAX_M || G_bstride < 0)
+    return fail("bad sizes P=%d S=%d n_gates=%d M=%d Lmax=%d G_bstride=%lld (M <= %d)", P, S, n_gates, M, Lmax,
+                (long long)G_bstride, C3P_SEQ_MAX_M);
+  if (mode != C3P_SEQ_PRODUCT && mode != C3P_SEQ_STATE && mode != C3P_SEQ_POPULATION)
+    return fail("unknown sequence output mode %d (0 = product, 1 = state, 2 = population)", mode);
+  if (P > 65535) return fail("P=%d parameter samples: at most 65535 per call", P);
+  if (P == 0) return 0;
+  // an empty table (n_gates = 0) still runs the chains: lengths and indices are checked and `out` is written
+  if (n_gates > 0 && !G_bar) return fail("G_bar is NULL");
+  if (S > 0 && (!lengths || !out_bar)) return fail("NULL lengths / out_bar pointer");
+  if (S > 0 && mode == C3P_SEQ_STATE && !psi0) return fail("state mode needs psi0");
+  if (S > 0 && Lmax > 0 && !seqs) return fail("seqs is NULL but Lmax=%d", Lmax);
+  if (n_gates > 0 && !G) return fail("gate table is NULL");
+  const size_t cs = sizeof(cplx);
+  const size_t table = (size_t)n_gates * M * M;
+  const int shared = G_bstride == 0;
+  const size_t gbar_bytes = (shared ? 1 : (size_t)P) * table * cs;
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  DeviceWs* w = lk.w;
+  if (!w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  Stage sg{w, st};
+  const void *d_G = G, *d_seqs = seqs, *d_len = lengths, *d_psi = psi0, *d_ob = out_bar;
+  void *d_gbar = G_bar, *d_out = out;
+  const size_t out_bytes = mode == C3P_SEQ_PRODUCT ? (size_t)P * S * M * M * cs
+                           : mode == C3P_SEQ_STATE ? (size_t)P * S * M * cs
+                                                   : (size_t)P * S * sizeof(double);
+  if (flags & C3P_HOST_PTRS) {
+    // host memory: every length and every index used is checked here, before anything is staged
+    for (int s = 0; s < S; ++s) {
+      const int L = lengths[s];
+      if (L < 0 || L > Lmax) return fail("sequence %d has length %d outside [0, %d]", s, L, Lmax);
+      for (int t = 0; t < L; ++t) {
+        const int g = seqs[(size_t)s * Lmax + t];
+        if (g < 0 || g >= n_gates) return fail("sequence %d, position %d: gate index %d outside [0, %d)", s, t, g, n_gates);
+      }
+    }
+    const size_t g_elems = G_bstride ? (size_t)(P - 1) * G_bstride + table : table;
+    if (sg.in(G, g_elems * cs, &d_G)) return -1;
+    if (S > 0) {
+      if (sg.in(seqs, (size_t)S * Lmax * sizeof(int32_t), &d_seqs)) return -1;
+      if (sg.in(lengths, (size_t)S * sizeof(int32_t), &d_len)) return -1;
+      if (sg.in(mode == C3P_SEQ_STATE ? psi0 : nullptr, (size_t)M * cs, &d_psi)) return -1;
+      if (sg.in(out_bar, out_bytes, &d_ob)) return -1;
+      if (sg.out(out, out ? out_bytes : 0, &d_out)) return -1;
+    }
+    if (sg.out(G_bar, gbar_bytes, &d_gbar)) return -1;
+  }
+  g_last_kernel = C3P_KERNEL_SEQ_VJP;
+  if (S == 0) {  // no sequence: a zero gradient
+    if (gbar_bytes) HIP_TRY(hipMemsetAsync(d_gbar, 0, gbar_bytes, st));
+    if (flags & C3P_HOST_PTRS) return sg.finish();
+    return 0;
+  }
+  const SeqVjpPlan pl = c3p_seq_vjp_plan(n_gates, M, P, S, Lmax, mode);
+  void *flag, *ws, *slab;
+  if (ws_get(w, SL_SEQ_FLAG, sizeof(int), &flag)) return -1;
+  if (ws_get(w, SL_SEQ_VJP_WS, pl.ws_elems * cs, &ws)) return -1;
+  if (ws_get(w, SL_SEQ_VJP_SLAB, pl.slab_elems * cs, &slab)) return -1;
+  HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), st));
+  SeqVjpArgs a = {};
+  a.f.G = (const cplx*)d_G;
+  a.f.G_bstride = (long)G_bstride;
+  a.f.n_gates = n_gates;
+  a.f.M = M;
+  a.f.P = P;
+  a.f.seqs = (const int*)d_seqs;
+  a.f.lengths = (const int*)d_len;
+  a.f.S = S;
+  a.f.Lmax = Lmax;
+  a.f.mode = mode;
+  a.f.superop = (flags & C3P_SEQ_SUPEROP) ? 1 : 0;
+  a.f.psi0 = (const cplx*)d_psi;
+  a.f.out = d_out;
+  a.f.bad = (int*)flag;
+  a.out_bar = d_ob;
+  a.C = pl.C;
+  a.nck = pl.nck;
+  a.nblk = pl.nblk;
+  a.ws = (cplx*)ws;
+  a.slab = (cplx*)slab;
+  a.G_bar = (cplx*)d_gbar;
+  a.shared = shared;
+  g_note_plan = "checkpoint interval C=" + std::to_string(pl.C) + " nblk=" + std::to_string(pl.nblk);
+  HIP_TRY(c3p_launch_seq_vjp(a, pl, st));
+  int bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (flags & C3P_HOST_PTRS) {
+    if (sg.finish()) return -1;
+  } else {
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  if (bad) return fail("a sequence has a length outside [0, %d] or a gate index outside [0, %d): the gradient is not valid", Lmax, n_gates);
   return 0;
 }
 

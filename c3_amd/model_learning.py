@@ -36,6 +36,25 @@ def g_LL_prime_combined(gs, weights):
     return np.sum(np.array(weights) * np.asarray(gs)) / K
 
 
+def g_LL_prime_grad(exp_values, sim_values, exp_stds, shots):
+    """d g_LL_prime / d sim_values, analytically: with r = m - s and v = s (1 - s),
+    d/ds [r^2 shots / v] = -shots (2 r / v + r^2 (1 - 2 s) / v^2), halved and divided by the number of values."""
+    m = np.asarray(exp_values, dtype=np.float64)
+    s = np.asarray(sim_values, dtype=np.float64)
+    sh = np.asarray(shots, dtype=np.float64)
+    r, v = m - s, s * (1.0 - s)
+    return -sh * (2.0 * r / v + r**2 * (1.0 - 2.0 * s) / v**2) / (2.0 * s.size)
+
+
+def dv_g_LL_prime(gs, dv_gs, weights):
+    """estimators.py:160-165: the gradient of `g_LL_prime_combined`, sum_i w_i dv_gs[i] / sum_i w_i."""
+    K = np.sum(weights)
+    g = 0
+    for ii in range(len(weights)):
+        g = g + weights[ii] * dv_gs[ii]
+    return g / K
+
+
 def propagate_parameter_sets(h0, hks, gate_signals: Dict[str, np.ndarray], dt: float, *, fr_phase: Optional[Dict] = None, device=None) -> Dict:
     """U[gate] [P,D,D] for P parameter sets: one `propagate_batch` call per gate (the reference recomputes every
     gate inside the `ipar` loop, modellearning.py:236-237).  `h0` / `hks` may carry a leading P axis (a model
@@ -142,6 +161,99 @@ def goal_run_batched(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence
     goals = np.array([g_LL_prime(d["results"], sim[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)])
     weights = [len(seqs)] * P
     return {"goal": g_LL_prime_combined(goals, weights), "goals": goals, "sim_vals": sim}
+
+
+def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence[Dict], psi_init, label_indices, *, fr_phase: Optional[Dict] = None, device=None) -> Dict:
+    """`goal_run_batched` and the gradient of its combined goal -- what `ModelLearning.goal_run_with_grad` tapes
+    (modellearning.py:362-440): model operators -> propagators -> sequence states -> label populations -> g_LL_prime,
+    the per-set gradients combined by `dv_g_LL_prime`.
+
+    1. U[gate] [P,D,D] by `propagate_parameter_sets`;
+    2. the sequence states U_seq psi0 [P,S,D] on the indexed path (c3p_seq_chain, state mode), and from the cotangent
+       xbar = 2 simbar x on the label rows the propagator cotangents by ONE c3p_seq_chain_vjp call (with
+       `label_indices` None every population is a simulated value, sim_vals [P,S,D] and results [S,D] per set);
+    3. per gate, `propagate_batch_vjp(..., want_model_grads=True)`;
+    4. the operator cotangents summed over the gates.
+
+    Returns {"goal", "goals" [P], "sim_vals" [P,S]} as `goal_run_batched` and
+      "grad_h0" [P,D,D], "grad_hks" [P,K,D,D]: row p is d goal / d h0[p] (d goal = Re sum conj(grad) dh) of the COMBINED
+          goal, the weights w_p / sum w folded in (a model shared by every set: sum over p, or `model_param_grads`);
+      "grad_signals" {gate: [P,K,N]}; "grad_fr_phase" {gate: [P,D]} or None.
+    With `device` everything up to the populations stays there (gradients are tensors on it).  Closed systems only.
+    """
+    P = len(data_sets)
+    seqs = data_sets[0]["seqs"]
+    for d in data_sets:
+        if d["seqs"] != seqs:
+            raise C3PropError("C3:Error: batched model learning needs the same sequences for every parameter set")
+    from . import sequences as sq
+
+    Us = propagate_parameter_sets(h0, hks, gate_signals, dt, fr_phase=fr_phase, device=device)
+    first = next(iter(Us.values()))
+    if int(first.shape[0]) != P:
+        raise C3PropError("C3:Error: number of data sets and parameter sets differ")
+    D = int(first.shape[-1])
+    psi = np.asarray(psi_init, dtype=np.complex128).reshape(-1)
+    if device is not None:
+        import torch
+
+        psi = torch.as_tensor(psi, device=device)
+    x = sq.evaluate_sequences_indexed(Us, seqs, "state", psi)  # [P,S,D]
+    pops = x.real**2 + x.imag**2
+    sim = process_batch(pops, label_indices)
+    sim_h = sim.cpu().numpy() if propagation._is_torch(sim) else np.asarray(sim)
+    goals = np.array([g_LL_prime(d["results"], sim_h[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)])
+    weights = [len(seqs)] * P
+    dgs = [g_LL_prime_grad(d["results"], sim_h[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)]
+    if any(np.shape(g) != sim_h.shape[1:] for g in dgs):
+        raise C3PropError(f"C3:Error: the results of a data set do not have the shape of its simulated values {sim_h.shape[1:]}")
+    # combined goal: d goal / d sim[p] = w_p / sum w * d g_p / d sim[p]
+    sim_bar = np.stack([w / np.sum(weights) * g for w, g in zip(weights, dgs)])
+    # sim = sum over the label rows of |x|^2 ([P,S]), or every population |x|^2 itself ([P,S,D], no labels):
+    # x_bar = 2 sim_bar x on the rows that enter
+    if label_indices is None:
+        pop_bar = sim_bar
+    else:
+        rows = np.zeros(D)
+        np.add.at(rows, list(label_indices), 1.0)  # a label listed twice counts twice, as in process_batch
+        pop_bar = sim_bar[..., None] * rows
+    x_bar = 2.0 * (torch.as_tensor(pop_bar, device=device) if device is not None else pop_bar) * x
+    U_bar = sq.evaluate_sequences_indexed_vjp(Us, seqs, "state", x_bar, psi)
+    grad_h0 = grad_hks = None
+    grad_signals, grad_ph = {}, ({} if fr_phase is not None else None)
+    for gate, sig in gate_signals.items():
+        ph = None if fr_phase is None else fr_phase.get(gate)
+        if device is not None:
+            to = lambda v, dt_: v.to(device) if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=dt_), device=device)
+            args = (to(h0, np.complex128), to(hks, np.complex128), to(sig, np.float64))
+            ph = None if ph is None else to(ph, np.float64)
+        else:
+            args = (h0, hks, sig)
+        g_sig, g0, gk = propagation.propagate_batch_vjp(*args, dt, U_bar[gate], fr_phase=ph, want_model_grads=True)
+        grad_signals[gate] = g_sig
+        grad_h0 = g0 if grad_h0 is None else grad_h0 + g0
+        grad_hks = gk if grad_hks is None else grad_hks + gk
+        if grad_ph is not None:
+            Ug, Ub = Us[gate], U_bar[gate]
+            # U = diag(e^{i phi}) P  =>  d loss / d phi_i = -Im sum_j conj(Ubar_ij) U_ij (optimal_control.goal_run_with_grad)
+            grad_ph[gate] = None if ph is None else (-(Ub.conj() * Ug).sum(-1).imag)
+    return {"goal": g_LL_prime_combined(goals, weights), "goals": goals, "sim_vals": sim_h, "grad_h0": grad_h0, "grad_hks": grad_hks,
+            "grad_signals": grad_signals, "grad_fr_phase": grad_ph}
+
+
+def model_param_grads(grad_h0, grad_hks, dh0, dhks=None):
+    """Gradient w.r.t. T model parameters theta from the operator cotangents of `goal_run_batched_with_grad`:
+    Re sum conj(grad_h0) dh0/dtheta (+ Re sum conj(grad_hks) dhks/dtheta).  `dh0` [T,D,D] (a model shared by the P sets:
+    result [T], summed over the sets) or [P,T,D,D] (per set: result [P,T]); `dhks` [T,K,D,D] or [P,T,K,D,D], or None."""
+    tonp = lambda a: a.detach().cpu().numpy() if propagation._is_torch(a) else np.asarray(a)
+    g0, gk = tonp(grad_h0), tonp(grad_hks)
+    dh0 = np.asarray(tonp(dh0), dtype=np.complex128)
+    per_set = dh0.ndim == 4
+    out = np.einsum("pij,ptij->pt" if per_set else "pij,tij->pt", g0.conj(), dh0).real
+    if dhks is not None:
+        dk = np.asarray(tonp(dhks), dtype=np.complex128)
+        out = out + np.einsum("pkij,ptkij->pt" if dk.ndim == 5 else "pkij,tkij->pt", gk.conj(), dk).real
+    return out if per_set else out.sum(axis=0)
 
 
 def sensitivity_sweep(h0_of, hks_of, sweep_values: Sequence[float], gate_signals_one: Dict, dt: float, data_set: Dict, psi_init, label_indices, *, device=None) -> Dict:

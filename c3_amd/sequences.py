@@ -198,6 +198,66 @@ def seq_chain(G, seqs, lengths, mode: str = "product", psi0=None, *, P: Optional
     return out
 
 
+def seq_chain_vjp(G, seqs, lengths, mode: str, out_bar, psi0=None, *, P: Optional[int] = None, superop: bool = False, want_out: bool = False):
+    """Direct binding of c3p_seq_chain_vjp: the cotangent of the gate table G from the cotangent `out_bar` of what
+    `seq_chain(G, seqs, lengths, mode, psi0, P=P, superop=superop)` returns (d loss = Re sum conj(out_bar) d out).
+
+    Returns G_bar with G's layout: [P, n_gates, M, M] for per-sample tables, [n_gates, M, M] (summed over the samples)
+    for a shared one; with `want_out`, (G_bar, out) where out is the forward output of the same pass.  numpy in -> numpy
+    out (host pointers); CUDA tensors in -> CUDA tensors out, on the current stream."""
+    if mode not in MODES:
+        raise C3PropError(f"C3:Error: unknown sequence mode {mode!r}; one of {sorted(MODES)}")
+    call = _Call(G, psi0, out_bar)
+    Gt = call.c128(G)
+    if Gt.ndim == 3:
+        Pn, bstride = (1 if P is None else int(P)), 0
+    elif Gt.ndim == 4:
+        Pn = int(Gt.shape[0])
+        if P is not None and int(P) != Pn:
+            raise C3PropError(f"C3:Error: P={P} but the gate table has {Pn} samples")
+        bstride = int(Gt.shape[1] * Gt.shape[2] * Gt.shape[3])
+    else:
+        raise C3PropError(f"C3:Error: gate table must be [n,M,M] or [P,n,M,M], got {tuple(Gt.shape)}")
+    n, M = int(Gt.shape[-3]), int(Gt.shape[-1])
+    if int(Gt.shape[-2]) != M:
+        raise C3PropError(f"C3:Error: gates must be square, got {tuple(Gt.shape[-2:])}")
+    if call.device:
+        tt = call.torch
+        sq = tt.as_tensor(seqs, device=call.dev).to(tt.int32).contiguous() if not _is_torch(seqs) else seqs.to(call.dev, tt.int32).contiguous()
+        ln = tt.as_tensor(lengths, device=call.dev).to(tt.int32).contiguous() if not _is_torch(lengths) else lengths.to(call.dev, tt.int32).contiguous()
+    else:
+        sq = np.ascontiguousarray(seqs.cpu().numpy() if _is_torch(seqs) else seqs, dtype=np.int32)
+        ln = np.ascontiguousarray(lengths.cpu().numpy() if _is_torch(lengths) else lengths, dtype=np.int32)
+    if sq.ndim != 2 or ln.ndim != 1 or int(ln.shape[0]) != int(sq.shape[0]):
+        raise C3PropError(f"C3:Error: seqs must be [S,Lmax] and lengths [S], got {tuple(sq.shape)} and {tuple(ln.shape)}")
+    S, Lmax = int(sq.shape[0]), int(sq.shape[1])
+    psi = None
+    if mode == "state":
+        if psi0 is None:
+            raise C3PropError("C3:Error: state mode needs psi0")
+        psi = call.c128(psi0).reshape(-1)
+        if int(psi.shape[0]) != M:
+            raise C3PropError(f"C3:Error: psi0 has {int(psi.shape[0])} entries, expected {M}")
+    shape = {"product": (Pn, S, M, M), "state": (Pn, S, M), "population": (Pn, S)}[mode]
+    ob = call.f64(out_bar) if mode == "population" else call.c128(out_bar)
+    if tuple(ob.shape) != shape:
+        raise C3PropError(f"C3:Error: out_bar must be {list(shape)} for mode {mode!r}, got {list(ob.shape)}")
+    out = None
+    if want_out:
+        if mode == "population":
+            out = call.torch.empty(shape, dtype=call.torch.float64, device=call.dev) if call.device else np.empty(shape, dtype=np.float64)
+        else:
+            out = call.empty(shape)
+    G_bar = call.empty((n, M, M) if bstride == 0 else (Pn, n, M, M))
+    flags = call.flags | (_lib.SEQ_SUPEROP if superop else 0)
+    _lib.check(
+        _lib.load().c3p_seq_chain_vjp(
+            _ptr(Gt), bstride, n, M, Pn, _ptr(sq), S, Lmax, _ptr(ln), MODES[mode], _ptr(psi), _ptr(ob), flags, _ptr(G_bar), _ptr(out), call.stream
+        )
+    )
+    return (G_bar, out) if want_out else G_bar
+
+
 def _gate_table(gate_Us: Dict):
     """names, G [P, n, M, M] (or [n, M, M] when every propagator is a single [M, M]) in the dict's order."""
     names = list(gate_Us.keys())
@@ -220,6 +280,21 @@ def evaluate_sequences_indexed(gate_Us: Dict, sequences: Sequence[Sequence[str]]
     names, G = _gate_table(gate_Us)
     seqs, lengths = index_table(sequences, {k: i for i, k in enumerate(names)})
     return seq_chain(G, seqs, lengths, mode, psi0, superop=superop)
+
+
+def evaluate_sequences_indexed_vjp(gate_Us: Dict, sequences: Sequence[Sequence[str]], mode: str, out_bar, psi0=None, *, superop: bool = False, want_out: bool = False):
+    """Vector-Jacobian product of `evaluate_sequences_indexed` (same dict, name lists, mode and psi0): {name: U_bar}
+    with each propagator's shape ([P,M,M], or [M,M] for unbatched input), from the cotangent `out_bar` of its output.
+    One c3p_seq_chain_vjp launch.  With `want_out`: ({name: U_bar}, forward output)."""
+    names, G = _gate_table(gate_Us)
+    seqs, lengths = index_table(sequences, {k: i for i, k in enumerate(names)})
+    unbatched = G.ndim == 3
+    if unbatched:  # a [M,M] propagator per name is one sample (P = 1) with its own table: G_bar keeps its shape
+        G = G[None]
+    r = seq_chain_vjp(G, seqs, lengths, mode, out_bar, psi0, superop=superop, want_out=want_out)
+    G_bar = r[0] if want_out else r
+    grads = {k: (G_bar[0, i] if unbatched else G_bar[:, i]) for i, k in enumerate(names)}
+    return (grads, r[1]) if want_out else grads
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -376,6 +451,33 @@ def orbit_infid(propagators, RB_number: int = 30, RB_length: int = 20, lindbladi
     out = vals.mean(axis=-1)
     squeeze = all(np.ndim(v) == 2 for v in propagators.values())
     return float(out[0]) if squeeze else out
+
+
+def orbit_infid_with_grad(propagators, RB_number: int = 30, RB_length: int = 20, lindbladian=False, seqs=None, *, rng=None, shots=None, noise=None):
+    """`orbit_infid` and its gradient: (infid [P], {name: U_bar}) with d infid[p] = Re sum conj(U_bar[p]) dU[p] for every
+    propagator (a float and [M,M] cotangents for unbatched input).  The value equals `orbit_infid` for the same `seqs`;
+    both come from one population-mode c3p_seq_chain_vjp call.  `shots` and `noise` are random draws without a
+    gradient and are refused."""
+    if shots or noise:
+        raise C3PropError("C3:Error: orbit_infid_with_grad has no gradient through `shots` / `noise` (random draws); "
+                          "use orbit_infid for a sampled value")
+    r = _rng(rng)
+    if not seqs:
+        seqs = single_length_RB(RB_number=RB_number, RB_length=RB_length, rng=r)
+    squeeze = all(np.ndim(v) == 2 for v in propagators.values())
+    P = 1 if squeeze else int(next(iter(propagators.values())).shape[0])
+    S = len(seqs)
+    # infid[p] = mean_s (1 - pop[p, s])  =>  pop_bar = -1 / S
+    first = next(iter(propagators.values()))
+    if _is_torch(first):
+        import torch
+
+        pop_bar = torch.full((P, S), -1.0 / S, dtype=torch.float64, device=first.device)
+    else:
+        pop_bar = np.full((P, S), -1.0 / S)
+    grads, pop = evaluate_sequences_indexed_vjp(propagators, seqs, "population", pop_bar, superop=bool(lindbladian), want_out=True)
+    out = (1.0 - _to_numpy(pop)).mean(axis=-1)
+    return (float(out[0]) if squeeze else out), grads
 
 
 def match_cliffords(U, rows, superop: bool = False) -> np.ndarray:

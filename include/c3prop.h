@@ -75,6 +75,7 @@ extern "C" {
 #define C3P_KERNEL_ODE_MFMA 7 /* matrix-core rho-valued ODE kernel, 17 <= D <= 48 (c3p_ode_rhoq.hip) */
 #define C3P_KERNEL_ODE_ROW_OR_WG 8 /* both launched; the DEVICE picks: real operators -> lane rows, complex -> workgroup kernel */
 #define C3P_KERNEL_SEQ 9 /* indexed gate-sequence chains (c3p_seq.hip)                          */
+#define C3P_KERNEL_SEQ_VJP 10 /* reverse sweep of the indexed gate-sequence chains (c3p_seq_vjp.hip)  */
 
 /* ODE solver / step ids (propagation.py:27-32 solver_slicing; :886-904 steps) */
 #define C3P_SOLVER_RK4 0
@@ -381,6 +382,25 @@ int c3p_gate_infid(const void* U, int B, int D, const int32_t* comp_rows, int L,
 #define C3P_SEQ_POPULATION 2
 int c3p_seq_chain(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
                   const int32_t* lengths, int mode, const void* psi0, int flags, void* out, void* stream);
+
+/* Vector-Jacobian product of c3p_seq_chain w.r.t. the gate table: the reverse sweep of the same chains
+ * (x_{t+1} = G[i_t] x_t, first gate applied first), with d loss = Re sum conj(Xbar) dX as c3p_pwc_unitary_vjp.
+ * Arguments, flags (C3P_HOST_PTRS, C3P_SEQ_SUPEROP) and validation as c3p_seq_chain, plus
+ *   out_bar  the cotangent of what c3p_seq_chain returns in `mode`:
+ *            C3P_SEQ_PRODUCT:    c128 [P,S,M,M] (column c = the cotangent of the chain started at e_c)
+ *            C3P_SEQ_STATE:      c128 [P,S,M]
+ *            C3P_SEQ_POPULATION: f64  [P,S]; the chain's cotangent is 2 pbar x_L[0] e_0, or with C3P_SEQ_SUPEROP
+ *                                pbar x_L[0] / |x_L[0]| e_0 (0 where x_L[0] = 0)
+ *   G_bar    c128 [P,n_gates,M,M]: Gbar[i_t] += xbar_{t+1} x_t^H over every sequence and position,
+ *            xbar_t = G[i_t]^H xbar_{t+1}.  G_bstride == 0 (shared table): [n_gates,M,M] summed over the samples.
+ *   out      NULL, or the forward output of `mode` (as c3p_seq_chain), from the same pass.
+ * No unitarity is assumed: the states are recomputed from checkpoints kept every C ~ sqrt(Lmax) steps (the kernel and C
+ * are reported by c3p_last_kernel_detail).  Workspace O(P S (Lmax / C + C) M) at most, from the library's workspace.
+ * Bitwise reproducible: partial sums per workgroup, reduced in a fixed order (no float atomics).  Two launches per call
+ * whatever the lengths; a bad length or index is an error as in c3p_seq_chain (the stream is synchronised once). */
+int c3p_seq_chain_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
+                      const int32_t* lengths, int mode, const void* psi0, const void* out_bar, int flags, void* G_bar,
+                      void* out, void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
