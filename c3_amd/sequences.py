@@ -11,12 +11,17 @@ RB and ORBIT only need |<0|U_seq|0>|^2, a chain of matrix-vector products (O(L M
 
 The single-qubit Clifford group is derived here, not tabulated: a breadth-first search over products of the ideal
 rx90p, rx90m, ry90p, ry90m (c3/libraries/constants.py:52-56) modulo global phase gives each of the 24 Cliffords as a
-shortest word; the identity is kept as rx90p rx90m, as the reference does, so no `Id` propagator is needed.  The order
-of this table differs from the reference's `cliffords_decomp`.  RB and ORBIT do not depend on it (they draw uniformly
-from the group and append the recovery element found by search), nor does `epc_analytical` from the generators (it
-averages over all 24 elements).  Where numbers meet the reference's -- `epc_analytical(cliffords=True)` with gates keyed
-C1..C24 -- each supplied gate is paired with its ideal element by process fidelity (`match_cliffords`), so its
-numbering does not matter.  `inverseC` takes and returns numbers into THIS table.
+shortest word; the identity is kept as rx90p rx90m, as the reference does, so no `Id` propagator is needed.  This table
+is NOT the reference's `cliffords_decomp` (c3/utils/qt_utils.py:528-553): it is in another order, and two elements are
+spelled with other words (the reference's C4 is ry90p rx90p rx90p, C16 ry90m rx90p rx90p).  With imperfect generators
+the results depend on the words: a Clifford's actual propagator is the product of its word's actual gates, so
+`epc_analytical` and `lindbladian_epc_analytical` from the generators change with the table, and RB / ORBIT sequences
+from the same seed differ.  Every function that draws or spells Cliffords therefore takes `clifford_words` (24 lists of
+generator names; `clifford_table`); a C3 binding passes c3.utils.qt_utils.cliffords_decomp for the reference's numbers,
+and, with rng=None after the same np.random.seed, its exact RB sequences.  With `cliffords=True` (gates keyed C1..C24)
+each supplied gate is paired with its ideal element by process fidelity (`match_cliffords`), so its numbering does not
+matter.  `inverseC` takes and returns numbers into the table it is given.  DESIGN section 5.9 lists every difference from
+the reference.
 """
 from __future__ import annotations
 
@@ -82,50 +87,100 @@ def _derive_cliffords():
     return table, np.stack([word_matrix(w, gens) for w in table])
 
 
+class CliffordTable:
+    """The single-qubit Clifford group as 24 words over GENERATORS (first gate applied first), numbered in their order:
+    `matrices` [24,2,2], `product[a, b]` = the index of C_b C_a (C_a applied first), `inverse[a]`, `identity`.
+    Any decomposition of the group works; it is checked to give 24 distinct elements closed under products."""
+
+    def __init__(self, words):
+        gens = _ideal_generators()
+        self.words = [list(w) for w in words]
+        bad = [g for w in self.words for g in w if g not in GENERATORS]
+        if len(self.words) != 24 or bad or not all(self.words):
+            raise C3PropError(f"C3:Error: a Clifford table is 24 non-empty words over {GENERATORS}; got {len(self.words)} words"
+                              + (f", unknown names {sorted(set(bad))}" if bad else ""))
+        self.matrices = np.stack([word_matrix(w, gens) for w in self.words])
+        self.index = {_phase_key(U): i for i, U in enumerate(self.matrices)}
+        if len(self.index) != 24:
+            raise C3PropError("C3:Error: the 24 Clifford words do not give 24 distinct elements")
+        try:
+            self.product = np.array([[self.index[_phase_key(self.matrices[b] @ self.matrices[a])] for b in range(24)] for a in range(24)], dtype=np.int64)
+            self.identity = self.index[_phase_key(np.eye(2, dtype=np.complex128))]
+        except KeyError:
+            raise C3PropError("C3:Error: the 24 Clifford words are not closed under products (not the Clifford group)") from None
+        self.inverse = np.array([int(np.argmax(self.product[a] == self.identity)) for a in range(24)], dtype=np.int64)
+
+
+_TABLES = {}
+
+
+def clifford_table(clifford_words=None) -> CliffordTable:
+    """The table of `clifford_words` (24 lists of generator names, first applied first; None: this project's derived
+    CLIFFORD_WORDS).  A C3 binding passes c3.utils.qt_utils.cliffords_decomp to number and spell the Cliffords as the
+    reference does."""
+    key = tuple(tuple(w) for w in (CLIFFORD_WORDS if clifford_words is None else clifford_words))
+    if key not in _TABLES:
+        _TABLES[key] = CliffordTable(key)
+    return _TABLES[key]
+
+
 CLIFFORD_WORDS, CLIFFORD_MATRICES = _derive_cliffords()
-_CLIFFORD_INDEX = {_phase_key(U): i for i, U in enumerate(CLIFFORD_MATRICES)}
-# multiplication table: _PRODUCT[a, b] = index of C_b C_a (C_a applied first)
-_PRODUCT = np.array([[_CLIFFORD_INDEX[_phase_key(CLIFFORD_MATRICES[b] @ CLIFFORD_MATRICES[a])] for b in range(24)] for a in range(24)], dtype=np.int64)
-_INVERSE = np.array([int(np.argmax(_PRODUCT[a] == 0)) for a in range(24)], dtype=np.int64)  # element 0 is the identity
+_DEFAULT = clifford_table()
+_CLIFFORD_INDEX = _DEFAULT.index
+_PRODUCT = _DEFAULT.product  # _PRODUCT[a, b] = index of C_b C_a (C_a applied first)
+_INVERSE = _DEFAULT.inverse  # element 0 is the identity
 
 
-def clifford_index(U: np.ndarray) -> int:
-    """0-based index of an ideal 2x2 Clifford (any global phase) in CLIFFORD_MATRICES."""
-    return _CLIFFORD_INDEX[_phase_key(np.asarray(U, dtype=np.complex128))]
+def clifford_index(U: np.ndarray, clifford_words=None) -> int:
+    """0-based index of an ideal 2x2 Clifford (any global phase) in the table of `clifford_words`."""
+    return clifford_table(clifford_words).index[_phase_key(np.asarray(U, dtype=np.complex128))]
 
 
-def inverseC(sequence) -> int:
-    """qt_utils.py:494-505 on this project's table: the 1-based number into CLIFFORD_MATRICES (C_k = CLIFFORD_MATRICES[k-1])
-    of the Clifford that returns the product of `sequence` -- 1-based numbers into the same table, first applied first --
-    to the identity.  The numbers are NOT the reference's C1..C24 (its table is in another order)."""
-    acc = 0
+def inverseC(sequence, clifford_words=None) -> int:
+    """qt_utils.py:480-491 on the table of `clifford_words` (default: this project's): the 1-based number of the
+    Clifford that returns the product of `sequence` -- 1-based numbers into the same table, first applied first -- to
+    the identity.  With the reference's words the numbers are its C1..C24."""
+    tab = clifford_table(clifford_words)
+    acc = tab.identity
     for c in sequence:
-        acc = _PRODUCT[acc, int(c) - 1]
-    return int(_INVERSE[acc]) + 1
+        acc = tab.product[acc, int(c) - 1]
+    return int(tab.inverse[acc]) + 1
 
 
 def _rng(rng):
-    return np.random if rng is None else (rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng))
+    """None: numpy's global stream, as the reference; np.random itself, a Generator or a RandomState: used as given (so
+    that a stream resolved once can be handed on); anything else: a seed."""
+    if rng is None:
+        return np.random
+    if rng is np.random or isinstance(rng, (np.random.Generator, np.random.RandomState)):
+        return rng
+    return np.random.default_rng(rng)
 
 
-def _rb_cliffords(RB_number: int, RB_length: int, rng) -> np.ndarray:
-    """[RB_number, RB_length] 0-based Clifford indices: RB_length - 1 uniform draws and the recovery element."""
+def _rb_cliffords(RB_number: int, RB_length: int, rng, clifford_words=None) -> np.ndarray:
+    """[RB_number, RB_length] 0-based Clifford indices: RB_length - 1 uniform draws and the recovery element.  One
+    choice(24, size=(RB_number, RB_length - 1)) takes the same numbers from a stream as the reference's RB_number calls
+    of size RB_length - 1 (qt_utils.py:470)."""
+    tab = clifford_table(clifford_words)
     r = _rng(rng)
     body = r.choice(24, size=(RB_number, max(RB_length - 1, 0)))
-    acc = np.zeros(RB_number, dtype=np.int64)
+    acc = np.full(RB_number, tab.identity, dtype=np.int64)
     for j in range(body.shape[1]):
-        acc = _PRODUCT[acc, body[:, j]]
-    return np.concatenate([body, _INVERSE[acc][:, None]], axis=1)
+        acc = tab.product[acc, body[:, j]]
+    return np.concatenate([body, tab.inverse[acc][:, None]], axis=1)
 
 
-def single_length_RB(RB_number: int, RB_length: int, target: int = 0, rng=None) -> List[List[str]]:
+def single_length_RB(RB_number: int, RB_length: int, target: int = 0, rng=None, clifford_words=None) -> List[List[str]]:
     """qt_utils.py:448-491: RB_number sequences of RB_length Cliffords (the last one the recovery), as gate keys
-    "rx90p[target]" ...  `rng`: None (numpy's global generator, as the reference), a seed or a Generator."""
+    "rx90p[target]" ...  `rng`: None (numpy's global generator, as the reference), a seed or a Generator.
+    `clifford_words`: the decomposition the drawn numbers index (default: this project's table); with the reference's
+    `cliffords_decomp` and rng=None the same np.random.seed gives the reference's sequences exactly."""
+    words = clifford_table(clifford_words).words
     out = []
-    for row in _rb_cliffords(RB_number, RB_length, rng):
+    for row in _rb_cliffords(RB_number, RB_length, rng, clifford_words):
         seq = []
         for c in row:
-            seq.extend(f"{g}[{target}]" for g in CLIFFORD_WORDS[c])
+            seq.extend(f"{g}[{target}]" for g in words[c])
         out.append(seq)
     return out
 
@@ -323,9 +378,10 @@ def _generator_table(propagators: Dict, target=None):
     return G, G.ndim == 3
 
 
-def _rb_index_table(cliffs: np.ndarray):
-    """Clifford indices [S, n] -> gate indices into GENERATORS order [S, Lmax] and lengths [S], fully vectorised."""
-    word_idx = [np.array([GENERATORS.index(g) for g in w], dtype=np.int32) for w in CLIFFORD_WORDS]
+def _rb_index_table(cliffs: np.ndarray, clifford_words=None):
+    """Clifford indices [S, n] (into the table of `clifford_words`) -> gate indices into GENERATORS order [S, Lmax] and
+    lengths [S], fully vectorised."""
+    word_idx = [np.array([GENERATORS.index(g) for g in w], dtype=np.int32) for w in clifford_table(clifford_words).words]
     wl = np.array([len(w) for w in word_idx], dtype=np.int32)
     pad = np.zeros((24, int(wl.max())), dtype=np.int32)
     for c, w in enumerate(word_idx):
@@ -344,15 +400,16 @@ def _to_numpy(x):
     return x.detach().cpu().numpy() if _is_torch(x) else np.asarray(x)
 
 
-def rb_survival(propagators: Dict, lengths: Sequence[int], num_seqs: int, *, lindbladian: bool = False, rng=None, target=None) -> np.ndarray:
+def rb_survival(propagators: Dict, lengths: Sequence[int], num_seqs: int, *, lindbladian: bool = False, rng=None, target=None, clifford_words=None) -> np.ndarray:
     """Survival probabilities [P, n_lengths, num_seqs] of random Clifford sequences (RB_length Cliffords each, the last
-    the recovery), every length and sequence in one population-mode call; the sequences are shared by the samples."""
+    the recovery), every length and sequence in one population-mode call; the sequences are shared by the samples.
+    The draws, length after length, are those of single_length_RB(num_seqs, L, rng=..., clifford_words=...)."""
     G, squeeze = _generator_table(propagators, target)
     r = _rng(rng)
-    cl = [_rb_cliffords(num_seqs, int(L), r) for L in lengths]
+    cl = [_rb_cliffords(num_seqs, int(L), r, clifford_words) for L in lengths]
     rows = []
     for c in cl:  # ragged Clifford counts -> per-sequence gate lists (padding is never read: lengths say how much is used)
-        seqs, ln = _rb_index_table(c)
+        seqs, ln = _rb_index_table(c, clifford_words)
         rows.append((seqs, ln))
     Lmax = max(s.shape[1] for s, _ in rows)
     seqs = np.concatenate([np.pad(s, ((0, 0), (0, Lmax - s.shape[1]))) for s, _ in rows])
@@ -382,16 +439,18 @@ def rb_fit(lengths, surv: np.ndarray):
 
 
 @fid_reg_deco
-def RB(propagators, min_length: int = 5, max_length: int = 500, num_lengths: int = 20, num_seqs: int = 30, logspace=False, lindbladian=False, padding="", *, rng=None, max_retries: int = 8, return_fit: bool = False):
+def RB(propagators, min_length: int = 5, max_length: int = 500, num_lengths: int = 20, num_seqs: int = 30, logspace=False, lindbladian=False, padding="", *, rng=None, max_retries: int = 8, return_fit: bool = False, clifford_words=None):
     """fidelities.py:515-591 for every parameter sample: propagators {key: [P,M,M]} (or [M,M]) -> error per gate [P]
     (a float for unbatched input).  A sample whose fit fails is refitted, as in the reference, after adding num_lengths
     longer lengths (max_length + min_length .. 2 max_length, max_length doubling each time); after `max_retries` such
     rounds it raises instead of looping for ever.  `padding` is accepted for the signature and not used (single-qubit
-    RB without idle padding).  With `return_fit`: (epg, r) arrays."""
+    RB without idle padding).  `clifford_words`: the Clifford decomposition the sequences are drawn from (default: this
+    project's table; the reference's `cliffords_decomp` with rng=None reproduces its draws).  With `return_fit`: (epg, r)
+    arrays."""
     G, squeeze = _generator_table(propagators)
     r_ = _rng(rng)
     lengths = _rb_lengths(min_length, max_length, num_lengths, logspace)
-    surv = rb_survival(propagators, lengths, num_seqs, lindbladian=lindbladian, rng=r_)
+    surv = rb_survival(propagators, lengths, num_seqs, lindbladian=lindbladian, rng=r_, clifford_words=clifford_words)
     P = surv.shape[0]
     rs = np.empty(P)
     for p in range(P):
@@ -406,7 +465,7 @@ def RB(propagators, min_length: int = 5, max_length: int = 500, num_lengths: int
                 new = _rb_lengths(mx + min_length, mx * 2, num_lengths, logspace)
                 mx *= 2
                 one = {k: (v[p] if not squeeze else v) for k, v in zip(GENERATORS, _unstack(G))}
-                extra = rb_survival(one, new, num_seqs, lindbladian=lindbladian, rng=r_)[0]
+                extra = rb_survival(one, new, num_seqs, lindbladian=lindbladian, rng=r_, clifford_words=clifford_words)[0]
                 sp = np.concatenate([sp, extra])
                 lens = np.append(lens, new)
     epc = 0.5 * (1 - rs)
@@ -422,27 +481,30 @@ def _unstack(G):
 
 
 @fid_reg_deco
-def lindbladian_RB_left(propagators: dict, gate: str = None, index=None, dims=None, proj: bool = False, **kw):
-    """fidelities.py:594-603 on superoperators [P,D^2,D^2]: RB with the Lindblad population |(S vec(|0><0|))[0]|."""
-    return RB(propagators, lindbladian=True, padding="left", **kw)
+def lindbladian_RB_left(propagators: dict, gate: str = None, index=None, dims=None, proj: bool = False, clifford_words=None, **kw):
+    """fidelities.py:594-603 on superoperators [P,D^2,D^2]: RB with the Lindblad population |(S vec(|0><0|))[0]|.  The
+    reference calls RB without lindbladian=True, so it fits |(S vec(|0><0|))[0]|^2, and passes "left" as the target
+    of single_length_RB; here the population is |.| and the target is found from the keys."""
+    return RB(propagators, lindbladian=True, padding="left", clifford_words=clifford_words, **kw)
 
 
 @fid_reg_deco
-def lindbladian_RB_right(propagators: dict, gate: str = None, index=None, dims=None, proj: bool = False, **kw):
+def lindbladian_RB_right(propagators: dict, gate: str = None, index=None, dims=None, proj: bool = False, clifford_words=None, **kw):
     """fidelities.py:606-608, as lindbladian_RB_left."""
-    return RB(propagators, lindbladian=True, padding="right", **kw)
+    return RB(propagators, lindbladian=True, padding="right", clifford_words=clifford_words, **kw)
 
 
 @fid_reg_deco
-def orbit_infid(propagators, RB_number: int = 30, RB_length: int = 20, lindbladian=False, shots: int = None, seqs=None, noise=None, *, rng=None):
+def orbit_infid(propagators, RB_number: int = 30, RB_length: int = 20, lindbladian=False, shots: int = None, seqs=None, noise=None, *, rng=None, clifford_words=None):
     """fidelities.py:754-791: mean over RB sequences of 1 - pop0, per parameter sample [P] (a float for unbatched input).
     The populations come from one population-mode call; with `shots`, each sequence's value is the mean of `shots`
     Bernoulli draws (one binomial draw on the host), and `noise` adds Gaussian noise per sequence, as the reference.
     `rng` (seed or Generator) makes both reproducible.  With `lindbladian` the propagators are superoperators and
-    pop0 = |(S vec(|0><0|))[0]| (the reference computes |.|^2 of that entry whatever the flag)."""
+    pop0 = |(S vec(|0><0|))[0]| (the reference computes |.|^2 of that entry whatever the flag).  Without `seqs` they
+    are drawn by single_length_RB(RB_number, RB_length, rng=rng, clifford_words=clifford_words)."""
     r = _rng(rng)
     if not seqs:
-        seqs = single_length_RB(RB_number=RB_number, RB_length=RB_length, rng=r)
+        seqs = single_length_RB(RB_number=RB_number, RB_length=RB_length, rng=r, clifford_words=clifford_words)
     pop = _to_numpy(evaluate_sequences_indexed(propagators, seqs, "population", superop=bool(lindbladian)))
     p1 = np.clip(1.0 - pop, 0.0, 1.0) if shots else 1.0 - pop
     vals = r.binomial(int(shots), p1) / float(shots) if shots else p1
@@ -453,7 +515,7 @@ def orbit_infid(propagators, RB_number: int = 30, RB_length: int = 20, lindbladi
     return float(out[0]) if squeeze else out
 
 
-def orbit_infid_with_grad(propagators, RB_number: int = 30, RB_length: int = 20, lindbladian=False, seqs=None, *, rng=None, shots=None, noise=None):
+def orbit_infid_with_grad(propagators, RB_number: int = 30, RB_length: int = 20, lindbladian=False, seqs=None, *, rng=None, shots=None, noise=None, clifford_words=None):
     """`orbit_infid` and its gradient: (infid [P], {name: U_bar}) with d infid[p] = Re sum conj(U_bar[p]) dU[p] for every
     propagator (a float and [M,M] cotangents for unbatched input).  The value equals `orbit_infid` for the same `seqs`;
     both come from one population-mode c3p_seq_chain_vjp call.  `shots` and `noise` are random draws without a
@@ -463,7 +525,7 @@ def orbit_infid_with_grad(propagators, RB_number: int = 30, RB_length: int = 20,
                           "use orbit_infid for a sampled value")
     r = _rng(rng)
     if not seqs:
-        seqs = single_length_RB(RB_number=RB_number, RB_length=RB_length, rng=r)
+        seqs = single_length_RB(RB_number=RB_number, RB_length=RB_length, rng=r, clifford_words=clifford_words)
     squeeze = all(np.ndim(v) == 2 for v in propagators.values())
     P = 1 if squeeze else int(next(iter(propagators.values())).shape[0])
     S = len(seqs)
@@ -480,8 +542,9 @@ def orbit_infid_with_grad(propagators, RB_number: int = 30, RB_length: int = 20,
     return (float(out[0]) if squeeze else out), grads
 
 
-def match_cliffords(U, rows, superop: bool = False) -> np.ndarray:
-    """For 24 supplied Clifford propagators U [P,24,M,M] (numpy), the index into CLIFFORD_MATRICES of the ideal element each
+def match_cliffords(U, rows, superop: bool = False, clifford_words=None) -> np.ndarray:
+    """For 24 supplied Clifford propagators U [P,24,M,M] (numpy), the index into the table of `clifford_words` (default
+    CLIFFORD_MATRICES) of the ideal element each
     one implements: the element of largest process fidelity on the computational block `rows` (2 row indices), averaged
     over the samples -- so a set keyed C1..C24 in ANY numbering (the reference's, this table's, a permutation) is paired
     with its own ideal gates.  For superoperators (`superop`) the block is the rows / columns i D + j of the computational
@@ -489,15 +552,16 @@ def match_cliffords(U, rows, superop: bool = False) -> np.ndarray:
     supplied gates must each be closer than that to exactly one ideal element, and all 24 elements must be met."""
     U = np.asarray(U)
     rows = np.asarray(rows, dtype=np.int64)
+    CM = clifford_table(clifford_words).matrices
     if superop:
         D = int(round(np.sqrt(U.shape[-1])))
         idx = (rows[:, None] * D + rows[None, :]).reshape(-1)
         B = U[..., idx[:, None], idx[None, :]]  # [P,24,4,4]
-        Cs = np.einsum("cij,ckl->cikjl", CLIFFORD_MATRICES, CLIFFORD_MATRICES.conj()).reshape(24, 4, 4)
+        Cs = np.einsum("cij,ckl->cikjl", CM, CM.conj()).reshape(24, 4, 4)
         F = np.abs(np.einsum("pkij,cij->pkc", B, Cs.conj())) / 4
     else:
         B = U[..., rows[:, None], rows[None, :]]  # [P,24,2,2]
-        F = np.abs(np.einsum("pkij,cij->pkc", B, CLIFFORD_MATRICES.conj())) ** 2 / 4
+        F = np.abs(np.einsum("pkij,cij->pkc", B, CM.conj())) ** 2 / 4
     F = F.mean(axis=0)  # [24 supplied, 24 ideal]
     best = F.argmax(axis=1)
     if F.max(axis=1).min() <= 0.5 or len(set(best.tolist())) != 24:
@@ -506,11 +570,13 @@ def match_cliffords(U, rows, superop: bool = False) -> np.ndarray:
     return best
 
 
-def clifford_products(propagators: Dict, cliffords: bool = False, target=None, *, rows=None, superop: bool = False):
-    """(U [P,24,M,M], ideal [24]): the 24 Clifford propagators (product mode) and, for each, the index into
-    CLIFFORD_MATRICES of the ideal gate it stands for.  From the generators the products follow CLIFFORD_WORDS, so
-    ideal[c] = c.  With `cliffords` the propagators are keyed "C1".."C24" themselves; their numbering is not assumed to
-    be this table's: each is paired with its ideal element by `match_cliffords` on the computational `rows`."""
+def clifford_products(propagators: Dict, cliffords: bool = False, target=None, *, rows=None, superop: bool = False, clifford_words=None):
+    """(U [P,24,M,M], ideal [24]): the 24 Clifford propagators (product mode) and, for each, the index into the table of
+    `clifford_words` (default CLIFFORD_MATRICES) of the ideal gate it stands for.  From the generators the products
+    follow that table's words, so ideal[c] = c: the EPC averages over these products of the actual generators, and so
+    depends on the words whenever the generators are not ideal.  With `cliffords` the propagators are keyed "C1".."C24"
+    themselves; their numbering is not assumed to be the table's: each is paired with its ideal element by
+    `match_cliffords` on the computational `rows`."""
     if cliffords:
         keys = [f"C{i}" for i in range(1, 25)]
         missing = [k for k in keys if k not in propagators]
@@ -518,10 +584,11 @@ def clifford_products(propagators: Dict, cliffords: bool = False, target=None, *
             raise C3PropError(f"C3:Error: cliffords=True needs propagators keyed C1..C24; missing {missing}")
         U = evaluate_sequences_indexed({k: propagators[k] for k in keys}, [[k] for k in keys], "product")
         Un = _to_numpy(U)
-        return U, match_cliffords(Un if Un.ndim == 4 else Un[None], rows, superop)
+        return U, match_cliffords(Un if Un.ndim == 4 else Un[None], rows, superop, clifford_words)
     keys = _generator_keys(propagators, target)
     name = dict(zip(GENERATORS, keys))
-    U = evaluate_sequences_indexed({k: propagators[k] for k in keys}, [[name[g] for g in w] for w in CLIFFORD_WORDS], "product")
+    words = clifford_table(clifford_words).words
+    U = evaluate_sequences_indexed({k: propagators[k] for k in keys}, [[name[g] for g in w] for w in words], "product")
     return U, np.arange(24)
 
 
@@ -546,31 +613,35 @@ def _per_clifford(U):
 
 
 @fid_reg_deco
-def epc_analytical(propagators: dict, index, dims, proj: bool, cliffords=False):
+def epc_analytical(propagators: dict, index, dims, proj: bool, cliffords=False, clifford_words=None):
     """fidelities.py:437-457 per parameter sample: 1 - mean over the 24 Cliffords of the average fidelity
-    (c3p_gate_infid, kind = average, on the computational subspace of `index`).  [P] (a float for unbatched input)."""
+    (c3p_gate_infid, kind = average, on the computational subspace of `index`).  [P] (a float for unbatched input).
+    From the generators, the Cliffords are the products of the words of `clifford_words` (default: this project's table;
+    the reference's `cliffords_decomp` gives its numbers); with imperfect generators the value depends on the words."""
     index, dims = _single_qubit_dims(index, dims)
     from .fidelities import computational_rows
 
-    U, ideal = clifford_products(propagators, cliffords, rows=computational_rows(dims, index))
-    infids = [_to_numpy(infid_sum(CLIFFORD_MATRICES[ideal[c]], Uc, index, dims, kind="average", want_each=True)["each"]) for c, Uc in enumerate(_per_clifford(U))]
+    CM = clifford_table(clifford_words).matrices
+    U, ideal = clifford_products(propagators, cliffords, rows=computational_rows(dims, index), clifford_words=clifford_words)
+    infids = [_to_numpy(infid_sum(CM[ideal[c]], Uc, index, dims, kind="average", want_each=True)["each"]) for c, Uc in enumerate(_per_clifford(U))]
     out = np.mean(infids, axis=0)
     squeeze = all(np.ndim(v) == 2 for v in propagators.values())
     return float(out[0]) if squeeze else out
 
 
 @fid_reg_deco
-def lindbladian_epc_analytical(propagators: dict, index, dims, proj: bool, cliffords=False):
+def lindbladian_epc_analytical(propagators: dict, index, dims, proj: bool, cliffords=False, clifford_words=None):
     """fidelities.py:460-480 per parameter sample, on superoperators [P,D^2,D^2]: the average fidelity of each Clifford
     from its process fidelity against tf_super(ideal), |(conj(t)/d + 1)/(d + 1)| with t = tr(S_c tf_super(C)^+) on
-    the computational subspace (c3p_gate_overlap; d = 2)."""
+    the computational subspace (c3p_gate_overlap; d = 2).  `clifford_words` as in epc_analytical."""
     index, dims = _single_qubit_dims(index, dims)
     from .fidelities import computational_rows
 
-    S, ideal = clifford_products(propagators, cliffords, rows=computational_rows(dims, index), superop=True)
+    CM = clifford_table(clifford_words).matrices
+    S, ideal = clifford_products(propagators, cliffords, rows=computational_rows(dims, index), superop=True, clifford_words=clifford_words)
     fids = []
     for c, Sc in enumerate(_per_clifford(S)):
-        t, L = _super_overlap(CLIFFORD_MATRICES[ideal[c]], Sc, index, dims)[:2]
+        t, L = _super_overlap(CM[ideal[c]], Sc, index, dims)[:2]
         t = _to_numpy(t)
         fids.append(np.abs((np.conj(t) / L + 1) / (L + 1)))
     out = 1 - np.mean(fids, axis=0)

@@ -1051,6 +1051,171 @@ def average_infid_set(propagators: Dict, ideals: Dict, index, dims):
 
 
 # --------------------------------------------------------------------------
+# Sequence fidelities: RB, ORBIT, analytical EPC (fidelities.py:436-480,
+# 483-493, 514-590, 753-791; qt_utils.py:448-491).  The Clifford decomposition
+# is an argument (`words`: 24 lists of generator names, first applied first),
+# never a table of this module: the reference's own is read by the tests from
+# tests/golden/clifford_rb.json.  Gate dicts are keyed "name[target]" as in
+# the reference's sequences; propagators are single [M, M] matrices.
+# --------------------------------------------------------------------------
+
+# the four ideal generators (constants.py:52-56)
+_S2 = 1 / np.sqrt(2)
+RB_GENERATORS = {
+    "rx90p": np.array([[1, -1j], [-1j, 1]], dtype=np.complex128) * _S2,
+    "rx90m": np.array([[1, 1j], [1j, 1]], dtype=np.complex128) * _S2,
+    "ry90p": np.array([[1, -1], [1, 1]], dtype=np.complex128) * _S2,
+    "ry90m": np.array([[1, 1], [-1, 1]], dtype=np.complex128) * _S2,
+}
+
+
+def clifford_table(words) -> np.ndarray:
+    """[24, 2, 2]: the ideal matrix of each word, first gate applied first, as CLIFFORDS (constants.py:96-121) is
+    written from cliffords_decomp (qt_utils.py:528-553): C4 = x90p @ x90p @ y90p for the word ry90p, rx90p, rx90p."""
+    out = []
+    for w in words:
+        U = np.eye(2, dtype=np.complex128)
+        for g in w:
+            U = RB_GENERATORS[g] @ U
+        out.append(U)
+    return np.stack(out)
+
+
+def inverseC(sequence, words) -> int:
+    """qt_utils.py:480-491: the product of the 1-based Clifford numbers (first applied first), then the first C_i whose
+    trace with it is 2 in modulus (to 1e-4)."""
+    C = clifford_table(words)
+    operation = np.eye(2, dtype=np.complex128)
+    for cliff in sequence:
+        operation = C[int(cliff) - 1] @ operation
+    for i in range(1, 25):
+        if abs(2 - abs(np.trace(C[i - 1] @ operation))) < 0.0001:
+            return i
+    raise AssertionError("no Clifford inverts the sequence: `words` is not the Clifford group")
+
+
+def single_length_RB(RB_number: int, RB_length: int, target, words) -> List[List[str]]:
+    """qt_utils.py:448-478: per sequence, RB_length - 1 draws of np.random.choice(24) + 1 from numpy's GLOBAL stream,
+    the recovery number from inverseC, each number spelled out as its word's "name[target]" keys."""
+    S = []
+    for _ in range(RB_number):
+        seq = np.random.choice(24, size=RB_length - 1) + 1
+        seq = np.append(seq, inverseC(seq, words))
+        gates = []
+        for c in seq:
+            gates.extend(f"{g}[{target}]" for g in words[c - 1])
+        S.append(gates)
+    return S
+
+
+def populations(state, lindbladian: bool):
+    """fidelities.py:483-493: |diagonal of the vectorised density matrix| or |state|^2."""
+    state = np.asarray(state).reshape(-1)
+    if lindbladian:
+        dim = int(np.sqrt(len(state)))
+        return np.abs(state[[n * dim + n for n in range(dim)]])
+    return np.abs(state) ** 2
+
+
+def rb_pop0(propagators: Dict, sequences, lindbladian: bool = False) -> np.ndarray:
+    """The survival of each sequence as RB computes it (fidelities.py:528-542): populations(U e_0)[0]."""
+    Us = evaluate_sequences(propagators, sequences)
+    out = []
+    for U in Us:
+        psi_init = np.zeros((U.shape[0], 1), dtype=np.complex128)
+        psi_init[0] = 1
+        out.append(float(populations(U @ psi_init, lindbladian)[0]))
+    return np.array(out)
+
+
+def rb_fit(lengths, surv_prob):
+    """fidelities.py:544-560: A r^L + B fitted to the mean survival per length, sigma the standard error, bounds (0, 1),
+    initial guess (0.9, 0.5, 0.5).  Returns (r, A, B)."""
+    from scipy.optimize import curve_fit
+
+    def RB_fit(len, r, A, B):  # noqa: A002 -- the reference's argument name
+        return A * r ** (len) + B
+
+    means = np.mean(surv_prob, axis=1)
+    stds = np.std(surv_prob, axis=1) / np.sqrt(len(surv_prob[0]))
+    solution, _ = curve_fit(RB_fit, lengths, means, sigma=stds, bounds=(0, 1), p0=[0.9, 0.5, 0.5])
+    return tuple(float(x) for x in solution)
+
+
+def RB(propagators: Dict, lengths, sequences_per_length, lindbladian: bool = False):
+    """fidelities.py:514-590 with the sequences given (one list per length, as single_length_RB draws them): survival
+    per sequence, the fit, then epc = (1 - r) / 2 and epg = 1 - (1 - epc)^(1/4).  The reference's retry with longer
+    sequences (:561-584) is not restated: a failed fit raises.  Returns (epg, r, surv [n_lengths, num_seqs])."""
+    surv_prob = np.array([rb_pop0(propagators, seqs, lindbladian) for seqs in sequences_per_length])
+    r, A, B = rb_fit(np.asarray(lengths), surv_prob)
+    epc = 0.5 * (1 - r)
+    epg = 1 - ((1 - epc) ** (1 / 4))
+    return epg, r, surv_prob
+
+
+def orbit_infid(propagators: Dict, sequences, lindblad_population: bool = False) -> float:
+    """fidelities.py:753-791 without shots or noise: the mean over the sequences of 1 - |(U e_0)[0]|^2.  The reference
+    squares that entry whatever its `lindbladian` flag (:775); `lindblad_population` instead takes
+    populations(lindbladian=True)[0] = |(S vec(|0><0|))[0]|, the population of a superoperator S."""
+    Us = evaluate_sequences(propagators, sequences)
+    infids = []
+    for U in Us:
+        x0 = U[0, 0]  # (U psi_init)[0] with psi_init = e_0
+        pop0 = abs(x0) if lindblad_population else abs(x0) ** 2
+        infids.append(1 - pop0)
+    return float(np.mean(infids))
+
+
+def tf_superoper_average_fidelity(A, B, lvls=None):
+    """tf_utils.py:388-393: lambda = project_to_comp(A, lvls, to_super)^+ B, then tf_super_to_fid.  The reference
+    passes True positionally, into the `index` slot of tf_project_to_comp, where `projector` cannot use it (`i in True`
+    raises); it is read here as the superoperator projection (to_super=True) on every subsystem."""
+    if lvls is None:
+        lvls = [int(np.sqrt(np.sqrt(B.shape[0])))]
+    lambda_super = np.conj(tf_project_to_comp(A, list(lvls), to_super=True).T) @ B
+    return tf_super_to_fid(lambda_super, lvls)
+
+
+def _clifford_set(propagators: Dict, words, target, cliffords: bool):
+    """the 24 actual Cliffords in the order of `words` (fidelities.py:439-446 / 463-470): the products of the words'
+    generators, or the supplied propagators "C1".."C24" (cliffords_string, qt_utils.py:501-526)."""
+    if cliffords:
+        return evaluate_sequences(propagators, [[f"C{i}"] for i in range(1, 25)])
+    return evaluate_sequences(propagators, [[f"{g}[{target}]" for g in w] for w in words])
+
+
+def epc_analytical(propagators: Dict, index, dims, words, cliffords: bool = False, target=0) -> float:
+    """fidelities.py:436-457: 1 - mean over the 24 Cliffords of tf_average_fidelity(C_real, C_ideal, lvls=dims).
+
+    Two points where the reference's formula is not defined, and what is computed instead:
+      - it reads the ideal gates as `perfect_cliffords(...)[C_indx]`, an integer index into the dict CLIFFORDS; the
+        ideal of Clifford k is taken here as CLIFFORDS["C{k+1}"], the matrix of word k;
+      - tf_average_fidelity multiplies C_real^+ by C_ideal, which is defined only for a 2 x 2 actual gate.  With more
+        levels (dims [3]: a 3 x 3 actual against a 2 x 2 ideal) C_real is first projected on the computational block of
+        `index` (tf_project_to_comp), as average_infid does (fidelities.py:290-313).
+    """
+    dims = list(dims)
+    ideal = clifford_table(words)
+    fids = []
+    for k, C_real in enumerate(_clifford_set(propagators, words, target, cliffords)):
+        if C_real.shape[0] != ideal.shape[-1]:
+            C_real = tf_project_to_comp(C_real, dims, list(index))
+        fids.append(tf_average_fidelity(C_real, ideal[k], lvls=dims))
+    return float(1 - np.mean(fids))
+
+
+def lindbladian_epc_analytical(propagators: Dict, index, dims, words, cliffords: bool = False, target=0) -> float:
+    """fidelities.py:460-480: 1 - mean over the 24 Cliffords of tf_superoper_average_fidelity(S_real, tf_super(C_ideal),
+    lvls=dims) (the ideal of Clifford k read as in epc_analytical).  Any level count: the superoperator is projected on
+    the computational block inside tf_superoper_average_fidelity (see there for the reference's argument slip)."""
+    ideal = clifford_table(words)
+    fids = []
+    for k, S_real in enumerate(_clifford_set(propagators, words, target, cliffords)):
+        fids.append(tf_superoper_average_fidelity(S_real, tf_super(ideal[k]), lvls=list(dims)))
+    return float(1 - np.mean(fids))
+
+
+# --------------------------------------------------------------------------
 # Signal synthesis for the standard line LO + AWG -> DAC -> Mixer -> VoltsToHertz
 # (SURVEY 8f rank 2: the step immediately before the propagator path)
 # --------------------------------------------------------------------------

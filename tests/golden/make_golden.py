@@ -15,13 +15,22 @@ Outputs (committed):
   transmon_expanded.npz  <- test/transmon_expanded.pickle (test_transmon_expanded.py:252-280)
   tunable_coupler.npz    <- test/tunable_coupler_data.pickle (test_tunable_coupler.py:393-403)
   tf_utils.npz           <- test/test_tf_utils.pickle    (test_tf_utils.py:79-111)
+  clifford_rb.json       <- the 24 words of `cliffords_decomp` (c3/utils/qt_utils.py:528-553), C1..C24, each a list
+                            of generator names, first applied first.  The assignment is located with `ast.parse` and
+                            its list read with `ast.literal_eval`: the module is neither imported nor run.
+
+    python tests/golden/make_golden.py clifford   # only clifford_rb.json (no pickles needed)
 """
+import ast
+import json
 import os
 import pickle
+import sys
 
 import numpy as np
 
 REF = "/root/reference/test"
+QT_UTILS = "/root/reference/c3/utils/qt_utils.py"
 OUT = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -37,7 +46,29 @@ def load(name):
         return _DataUnpickler(f).load()
 
 
+def clifford_words():
+    """the list assigned to `cliffords_decomp` at module level of qt_utils.py, as data"""
+    with open(QT_UTILS) as f:
+        tree = ast.parse(f.read())
+    hits = [n.value for n in tree.body if isinstance(n, ast.Assign) and [getattr(t, "id", None) for t in n.targets] == ["cliffords_decomp"]]
+    if len(hits) != 1:
+        raise SystemExit(f"expected one assignment to cliffords_decomp in {QT_UTILS}, found {len(hits)}")
+    words = ast.literal_eval(hits[0])
+    if len(words) != 24 or not all(isinstance(w, list) and w and all(isinstance(g, str) for g in w) for w in words):
+        raise SystemExit("cliffords_decomp is not 24 non-empty lists of names")
+    return words
+
+
+def write_clifford_words():
+    text = "[\n" + ",\n".join("  " + json.dumps(w) for w in clifford_words()) + "\n]\n"
+    with open(os.path.join(OUT, "clifford_rb.json"), "w") as f:
+        f.write(text)
+
+
 def main():
+    write_clifford_words()
+    if sys.argv[1:] == ["clifford"]:
+        return
     d = load("two_qubit_data.pickle")
     np.savez_compressed(
         os.path.join(OUT, "two_qubit.npz"),
@@ -99,7 +130,7 @@ def main():
             out[f"{key}_{i}_desired"] = np.asarray(el["desired"])
     np.savez_compressed(os.path.join(OUT, "tf_utils.npz"), **out)
     for f in sorted(os.listdir(OUT)):
-        if f.endswith(".npz"):
+        if f.endswith((".npz", ".json")):
             print(f, os.path.getsize(os.path.join(OUT, f)))
 
 

@@ -176,3 +176,84 @@ def test_epc_refuses_more_than_one_subsystem():
     for fn in (sq.epc_analytical, sq.lindbladian_epc_analytical):
         with pytest.raises(_lib.C3PropError, match="single-qubit"):
             fn(gates, [0], [3, 3], True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the reference's Clifford decomposition (tests/golden/clifford_rb.json), selectable by clifford_words
+# ---------------------------------------------------------------------------------------------------------------------------
+def _fixture_words():
+    import json
+
+    with open(os.path.join(ROOT, "tests", "golden", "clifford_rb.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("seed", [0, 7, 2026])
+def test_reference_words_reproduce_the_reference_sequences(seed):
+    """with the reference's words and numpy's global stream, single_length_RB returns exactly the oracle's restatement
+    of qt_utils.py:448-478 for the same seed (one [n, L-1] draw takes the numbers of n draws of L - 1)"""
+    from oracle import c3_oracle as o
+
+    words = _fixture_words()
+    for L in (1, 2, 9, 40):
+        np.random.seed(seed)
+        got = sq.single_length_RB(6, L, target=1, clifford_words=words)
+        np.random.seed(seed)
+        want = o.single_length_RB(6, L, 1, words)
+        assert got == want, (seed, L)
+    np.random.seed(seed)
+    default = [sq.single_length_RB(6, L, target=1) for L in (9, 40)]
+    np.random.seed(seed)
+    assert default == [o.single_length_RB(6, L, 1, sq.CLIFFORD_WORDS) for L in (9, 40)]
+
+
+def test_inverseC_with_the_reference_words_is_the_trace_search():
+    from oracle import c3_oracle as o
+
+    words = _fixture_words()
+    rng = np.random.default_rng(8)
+    for _ in range(50):
+        seq = rng.integers(1, 25, size=int(rng.integers(0, 8)))
+        assert sq.inverseC(seq, clifford_words=words) == o.inverseC(seq, words)
+        assert sq.inverseC(seq) == o.inverseC(seq, sq.CLIFFORD_WORDS)
+
+
+def test_default_table_spells_two_elements_differently():
+    """the derived table names the reference's 24 elements, in another order, and spells C4 and C16 with other words:
+    the difference epc_analytical sees under coherent errors"""
+    ref = sq.clifford_table(_fixture_words())
+    dft = sq.clifford_table()
+    assert dft is sq.clifford_table(None) and dft.words == sq.CLIFFORD_WORDS
+    differ = []
+    for k in range(24):
+        j = sq.clifford_index(ref.matrices[k])
+        assert _equal_up_to_phase(dft.matrices[j], ref.matrices[k])
+        if dft.words[j] != ref.words[k]:
+            differ.append((k + 1, dft.words[j]))
+    assert differ == [(4, ["rx90p", "rx90p", "ry90m"]), (16, ["rx90p", "rx90p", "ry90p"])]
+    assert ref.identity == 0 and np.array_equal(ref.product[ref.inverse, np.arange(24)], np.zeros(24))
+
+
+def test_clifford_table_refuses_what_is_not_the_group():
+    words = _fixture_words()
+    with pytest.raises(_lib.C3PropError, match="C3:Error"):
+        sq.clifford_table(words[:23])
+    with pytest.raises(_lib.C3PropError, match="distinct"):
+        sq.clifford_table(words[:23] + [words[0]])
+    with pytest.raises(_lib.C3PropError, match="unknown names"):
+        sq.clifford_table(words[:23] + [["rz90p"]])
+
+
+def test_global_stream_is_handed_on():
+    """RB and rb_survival resolve rng=None to numpy's global stream once and pass it on: it must stay that stream (it
+    was once re-read as a seed, so RB(rng=None), the reference's default, raised before drawing)"""
+    r = sq._rng(None)
+    assert r is np.random and sq._rng(r) is np.random
+    np.random.seed(12)
+    a = sq._rb_cliffords(4, 6, sq._rng(None))
+    np.random.seed(12)
+    assert np.array_equal(a, sq._rb_cliffords(4, 6, None))
+    rs = np.random.RandomState(3)
+    assert sq._rng(rs) is rs
+    g = np.random.default_rng(3)
+    assert sq._rng(g) is g
