@@ -192,6 +192,52 @@ def test_oracle_synthesis_vjp_matches_finite_differences():
     assert abs((f(comps, v_=v * (1 + 1e-6)) - f(comps, v_=v * (1 - 1e-6))) / (2e-6 * v) - gc["v_to_hz"]) < 1e-7 * abs(gc["v_to_hz"])
 
 
+DRIVEN_SHAPES = ["rect", "gaussian_nonorm", "flattop", "flattop_risefall", "cosine", "gaussian_sigma", "gaussian", "trapezoid"]
+# (t_start, window, awg_res, sim_res, delay): a short pulse from t = 0, and a long one on an offset window whose 72 AWG
+# samples each feed 83.3 simulation samples
+VJP_GRIDS = {"12ns": (0.0, 12e-9, 2.4e9, 100e9, 0.5e-9), "60ns_from_3ns": (3e-9, 60e-9, 1.2e9, 100e9, 1.2e-9)}
+
+
+def _close(fd, an, rtol):
+    # a parameter the line does not depend on (delta without DRAG, rect's zero slope, rect minus its own t_before offset)
+    # has a central difference and a gradient that are both exactly zero
+    return abs(fd - an) < rtol * abs(fd) or fd == an == 0.0
+
+
+@pytest.mark.parametrize("drag", [False, True])
+@pytest.mark.parametrize("use_t_before", [False, True])
+@pytest.mark.parametrize("grid", list(VJP_GRIDS))
+@pytest.mark.parametrize("shape", DRIVEN_SHAPES)
+def test_oracle_synthesis_vjp_every_shape(shape, grid, use_t_before, drag):
+    """The oracle VJP the device VJP is pinned to, against central differences of the oracle synthesis: every driven shape
+    and flag setting, one delayed component per line."""
+    t0, window, awg_res, sim_res, delay = VJP_GRIDS[grid]
+    t1 = t0 + window
+    T = 0.85 * (window - delay)
+    comp = dict(shape=sg.ENV_SHAPES[shape], amp=0.4, xy_angle=0.3, freq_offset=-50e6 * TWO_PI, delta=0.7, t_final=T, sigma=T / 5,
+                t_up=0.15 * T, t_down=0.8 * T, risefall=0.07 * T, delay=delay, use_t_before=use_t_before, drag=drag)
+    if shape == "trapezoid":
+        # the trapezoid and its slope have kinks at 2.5 risefall and t_final - 2.5 risefall: no AWG sample lies near either
+        ts_off = o.create_ts(t0, t1, awg_res) - (t0 + delay)
+        w = 2.5 * comp["risefall"]
+        assert min(np.abs(ts_off - w).min(), np.abs(ts_off - (T - w)).min()) > 0.2 * (ts_off[1] - ts_off[0])
+    lo, v = 5.05e9 * TWO_PI, 1e9 * TWO_PI
+    gs = np.random.default_rng(2).normal(size=sg.slice_num(t0, t1, sim_res))
+    (gr,), gc = o.generate_signal_vjp([comp], lo, v, t0, t1, awg_res, sim_res, gs)
+    f = lambda c, lo_=lo, v_=v: float(np.sum(gs * o.generate_signal([c], lo_, v_, t0, t1, awg_res, sim_res)["values"]))
+    # freq_offset steps by 1e3 rad/s (as in test_gradient's goal test): at 1e2 the rounding of f (~1e-5) over 2h swamps
+    # gradients that nearly cancel, such as the trapezoid's -0.14 on the 12 ns grid (the median is 1.9e3)
+    for key, h in (("amp", 1e-6), ("xy_angle", 1e-6), ("freq_offset", 1e3), ("delta", 1e-6)):
+        fd = (f(dict(comp, **{key: comp[key] + h})) - f(dict(comp, **{key: comp[key] - h}))) / (2 * h)
+        assert _close(fd, gr[key], 1e-7), (key, fd, gr[key])
+    if not drag:
+        assert gr["delta"] == 0.0
+    fd = (f(comp, lo_=lo + 1e2) - f(comp, lo_=lo - 1e2)) / 2e2
+    assert _close(fd, gc["lo_freq"], 1e-6), ("lo_freq", fd, gc["lo_freq"])
+    fd = (f(comp, v_=v * (1 + 1e-6)) - f(comp, v_=v * (1 - 1e-6))) / (2e-6 * v)
+    assert _close(fd, gc["v_to_hz"], 1e-7), ("v_to_hz", fd, gc["v_to_hz"])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("device_resident", [False, True])
 def test_synthesis_vjp_vs_oracle(prop, device_resident):
