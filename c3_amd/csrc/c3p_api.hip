@@ -315,7 +315,10 @@ int run_chain_generic(DeviceWs* w, ChainArgs base, cplx* U_out, hipStream_t st, 
 // ---------------------------------------------------------------------------
 // Small-D MFMA path (Dm <= C3P_SMALLD_LIMIT): tables -> segment chains -> ordered combine
 // ---------------------------------------------------------------------------
-const int kSmallDLimit = 12;
+const int kSmallDLimit = 12;  // D = 11, 12 spill ~100 registers but still beat the generic kernel
+
+// the no_t18n option as the kernels' argument structs carry it: its value when set to a positive number, else 0
+static inline int opt_no_t18n() { return c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0; }
 
 // Unitary gradients at 41 <= D <= 64: the VALU sweep (c3p_grad.hip, ~D^3 B) against the tiled sweep (c3p_tiled.hip: matrix cores,
 // padded to 64-multiples, so D = 48 and D = 64 cost the same there, and ~35 launches per slice whatever B is).  Measured on one
@@ -328,7 +331,7 @@ static inline bool tiled_unitary_grad(int D, int B) {
   if (c3p_opt_on(C3P_OPT_tiled_grad)) return true;
   const double r = (double)D / 48.0, valu = 1.66 * B * r * r * r, tiled = std::max(220.0, 1.97 * B);
   return valu > tiled;
-}  // D = 11, 12 spill ~100 registers but still beat the generic kernel
+}
 
 int record_start(DeviceWs* w, hipStream_t st) {
   if (!w->profiling || g_dry) return 0;
@@ -472,7 +475,7 @@ int run_pwc_smallr(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, lon
   p.lindblad = 1;
   LAUNCH_TRY(c3p_launch_smallr_prep(p, nsamp, tabs, flags, st));
   SmallRArgs a = {};
-  a.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+  a.no_t18n = opt_no_t18n();
   a.tables = tabs;
   a.tab_per_sample = per_sample ? 1 : 0;
   a.signals = signals;
@@ -513,7 +516,7 @@ int run_pwc_smalld(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const 
     counters = (int*)cv;
   }
   SmallArgs a = {};
-  a.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+  a.no_t18n = opt_no_t18n();
   if (inline_tables) {
     // unitary mode: the chain kernel builds its tables itself (no dependent launch in front of it)
     a.inline_tables = 1;
@@ -719,7 +722,7 @@ int run_xg_midd(DeviceWs* w, const cplx* hs, long hs_bstride, double coef_r, dou
   a.mode = C3P_MODE_EXPM;
   a.dUs_out = dUs_out;
   a.no_t18 = c3p_opt_on(C3P_OPT_no_t18) ? 1 : 0;
-  a.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+  a.no_t18n = opt_no_t18n();
   a.no_real = c3p_opt_on(C3P_OPT_no_real) ? 1 : 0;
   if (S == 1) {
     a.seg_out = U_out;
@@ -747,7 +750,7 @@ int run_xg_smalld(DeviceWs* w, const cplx* hs, long hs_bstride, double coef_r, d
   if (ws_get(w, SL_TABLES, (size_t)B * N * 4 * sizeof(double), &mv)) return -1;
   LAUNCH_TRY(c3p_launch_hmeta(hs, hs_bstride, (long)B * N, N, D, coef_r, coef_i, (double*)mv, st));
   SmallArgs a = {};
-  a.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+  a.no_t18n = opt_no_t18n();
   a.hs = hs;
   a.hs_bstride = hs_bstride;
   a.meta = (const double*)mv;
@@ -820,7 +823,7 @@ int run_vjp_smalld(DeviceWs* w, GradArgs& G, hipStream_t st) {
     if (ws_get(w, SL_SEG_F, 2 * segb, &fv)) return -1;
   }
   SmallArgs a = {};
-  a.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+  a.no_t18n = opt_no_t18n();
   a.tables = p.tables;
   a.tab_per_sample = per_sample ? 1 : 0;
   a.signals = G.signals;
@@ -955,8 +958,7 @@ int lind_small_forward(DeviceWs* w, const LindSmallBufs& bf, const cplx* h0, lon
     rp.lindblad = 1;
     LAUNCH_TRY(c3p_launch_smallr_prep(rp, nsamp, (double*)tv, reinterpret_cast<int*>(static_cast<char*>(tv) + fl_off), st));
     SmallRArgs ra = {};
-    ra.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
-  ra.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+    ra.no_t18n = opt_no_t18n();
     ra.tables = (const double*)tv;
     ra.tab_per_sample = per_sample ? 1 : 0;
     ra.signals = signals;
@@ -972,7 +974,7 @@ int lind_small_forward(DeviceWs* w, const LindSmallBufs& bf, const cplx* h0, lon
     return 0;
   }
   SmallArgs a = {};
-  a.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+  a.no_t18n = opt_no_t18n();
   a.tables = bf.tabs;
   a.tab_per_sample = per_sample ? 1 : 0;
   a.signals = signals;
@@ -1085,7 +1087,7 @@ int lind_smallr_forward(const LindSmallRBufs& bf, const cplx* h0, long h0_bs, co
   rp.lindblad = 1;
   LAUNCH_TRY(c3p_launch_smallr_prep_pair(rp, nsamp, bf.tabs, bf.tabs_t, bf.flags, st));
   SmallRArgs ra = {};
-  ra.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+  ra.no_t18n = opt_no_t18n();
   ra.tables = bf.tabs;
   ra.tab_per_sample = per_sample ? 1 : 0;
   ra.signals = signals;
@@ -1111,7 +1113,7 @@ int lind_smallr_backward(DeviceWs* w, const LindSmallRBufs& bf, bool per_sample,
   LAUNCH_TRY(c3p_launch_hb_ubar(Ubar, fr_phase, B, D, (double*)uv, st));
   LAUNCH_TRY(c3p_launch_smallr_scan(bf.seg, (const double*)uv, B, S, Dm, (double*)pv, (double*)sv, st));
   SmallRGradArgs g = {};
-  g.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+  g.no_t18n = opt_no_t18n();
   g.tables = bf.tabs;
   g.tables_t = bf.tabs_t;
   g.tab_per_sample = per_sample ? 1 : 0;
@@ -1250,7 +1252,7 @@ int run_pwc_midd(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cp
   a.mode = lindblad ? C3P_MODE_LINDBLAD : C3P_MODE_UNITARY;
   a.dUs_out = dUs_out;
   a.no_t18 = c3p_opt_on(C3P_OPT_no_t18) ? 1 : 0;
-  a.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+  a.no_t18n = opt_no_t18n();
   a.no_real = c3p_opt_on(C3P_OPT_no_real) ? 1 : 0;
   if (S == 1) {
     a.seg_out = U_out;
@@ -1329,7 +1331,7 @@ int run_vjp_lind_midd(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, 
   a.seg_out = (cplx*)sv;
   a.dUs_out = dUs;
   a.no_t18 = c3p_opt_on(C3P_OPT_no_t18) ? 1 : 0;
-  a.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+  a.no_t18n = opt_no_t18n();
   a.no_real = 1;
   LAUNCH_TRY(c3p_launch_midd_chain(a, st));
   GradArgs G = {};
@@ -1399,7 +1401,7 @@ int run_vjp_xg_general(DeviceWs* w, const cplx* hs, long hs_bstride, double coef
   const int Lmax = (int)((N + S - 1) / S);
   if (small) {
     SmallArgs a = {};
-    a.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+    a.no_t18n = opt_no_t18n();
     a.hs = hs;
     a.hs_bstride = hs_bstride;
     a.meta = (const double*)mv;
@@ -1430,7 +1432,7 @@ int run_vjp_xg_general(DeviceWs* w, const cplx* hs, long hs_bstride, double coef
     a.seg_out = (cplx*)sv;
     a.dUs_out = dUs;
     a.no_t18 = c3p_opt_on(C3P_OPT_no_t18) ? 1 : 0;
-    a.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+    a.no_t18n = opt_no_t18n();
     a.no_real = 1;
     LAUNCH_TRY(c3p_launch_midd_chain(a, st));
   }
@@ -1622,7 +1624,7 @@ int run_pwc_regd(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cp
     a.hb_tables = rtables;
     a.hb_tabflag = tabflag;
   }
-  a.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+  a.no_t18n = opt_no_t18n();
   cplx* seg = U_out;
   if (S > 1) {
     void* sv;
@@ -1807,7 +1809,7 @@ int lind_regr_forward(DeviceWs* w, const LindRegrBufs& bf, const cplx* h0, long 
   a.hb_tables = bf.tab_f;
   a.hb_tabflag = bf.flag_f;
   a.hb_qT = bf.qT;
-  a.no_t18n = c3p_opt_on(C3P_OPT_no_t18n) ? (int)c3p_opt(C3P_OPT_no_t18n) : 0;
+  a.no_t18n = opt_no_t18n();
   a.seg_out = bf.seg;
   LAUNCH_TRY(c3p_launch_regr_chain(a, av, st));
   return 0;

@@ -462,15 +462,7 @@ __global__ void __launch_bounds__(512, 2) bigd_chain_kernel(MidArgs A, double* a
       nrm = fma(cmax, cm.tabs[(long)(k + 1) * (IMG + 4) + IMG + 2], nrm);
     }
     nrm = bd_rfl(nrm);
-    int s18 = 0;
-    {
-      double p = C3P_T18_THETA;
-      while (p < nrm && s18 < 40) {
-        p *= 2.0;
-        ++s18;
-      }
-    }
-    cm.ps = __builtin_amdgcn_readfirstlane(s18);
+    cm.ps = __builtin_amdgcn_readfirstlane(c3p_squarings(nrm, C3P_T18_THETA));
     cm.scale = ldexp(1.0, -cm.ps);
     __syncthreads();
     bigd_body<NIG, NJ, W, DUS>(A, cm, chain);

@@ -86,18 +86,25 @@ __host__ __device__ __forceinline__ TaylorPlan c3p_pick_plan(double norm) {
   return p;
 }
 
+// Squarings for a polynomial of radius theta: the smallest s with theta * 2^s >= nrm, at most 40 (a NaN norm gives 0).
+// Repeated doubling rather than log2, so that host and device agree.
+__host__ __device__ __forceinline__ int c3p_squarings(double nrm, double theta) {
+  int s = 0;
+  double p = theta;
+  while (p < nrm && s < 40) {
+    p *= 2.0;
+    ++s;
+  }
+  return s;
+}
+
 // q = 4 only (powers X..X^4, Horner in X^4): degree 4r, r = 1..5.  Thresholds are the Taylor
 // backward-error bounds for unit roundoff 2^-52 (theta_m * 2^(1/m)).
 __host__ __device__ __forceinline__ TaylorPlan c3p_pick_plan_q4(double nrm) {
   const double th[5] = {4.0e-4, 5.45e-2, 3.18e-1, 8.16e-1, 1.49};
   int best_r = 5, best_s = 0, best_cost = 1 << 30;
   for (int i = 0; i < 5; ++i) {
-    int si = 0;
-    double p = th[i];
-    while (p < nrm && si < 40) {
-      p *= 2.0;
-      ++si;
-    }
+    const int si = c3p_squarings(nrm, th[i]);
     const int cost = i + si;
     if (cost < best_cost || (cost == best_cost && si <= best_s)) {
       best_cost = cost;
@@ -187,12 +194,7 @@ struct MfmaPlan {
 // ties with 5 + (s - 1) go to T18N's smaller truncation error)
 __host__ __device__ __forceinline__ MfmaPlan c3p_pick_plan_mfma(double nrm, double theta18 = C3P_T18_THETA, bool normal = false) {
   const TaylorPlan q = c3p_pick_plan_q4(nrm);
-  int s18 = 0;
-  double p = theta18;
-  while (p < nrm && s18 < 40) {
-    p *= 2.0;
-    ++s18;
-  }
+  const int s18 = c3p_squarings(nrm, theta18);
   MfmaPlan m;
   const int cost_q = 3 + (q.r - 1) + q.s, cost_t = 5 + s18;
   if (cost_t < cost_q) {
@@ -205,12 +207,7 @@ __host__ __device__ __forceinline__ MfmaPlan c3p_pick_plan_mfma(double nrm, doub
     m.s = q.s;
   }
   if (normal) {
-    int s4 = 0;
-    double p4 = C3P_E4N_THETA;
-    while (p4 < nrm && s4 < 40) {
-      p4 *= 2.0;
-      ++s4;
-    }
+    const int s4 = c3p_squarings(nrm, C3P_E4N_THETA);
     const int cost = m.t18 ? 5 + m.s : 3 + (m.r - 1) + m.s;
     if (4 + s4 < cost) {
       m.t18 = 2;

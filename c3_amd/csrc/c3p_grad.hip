@@ -288,12 +288,7 @@ __device__ void assemble(const GMem<GLOBAL>& M, const GradArgs& A, Shared& sh, i
   if (tid == 0) {
     double nrm = 0.0;
     for (int t = 0; t < nt; ++t) nrm = fmax(nrm, sh.red[t]);
-    int s = 0;
-    double p = C3P_T18_THETA;
-    while (p < nrm && s < 40) {
-      p *= 2.0;
-      ++s;
-    }
+    int s = c3p_squarings(nrm, C3P_T18_THETA);
     sh.s = s;
   }
   __syncthreads();

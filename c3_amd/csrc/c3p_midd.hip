@@ -61,12 +61,6 @@
 #ifndef C3P_MMR_PRIO
 #define C3P_MMR_PRIO 0  // s_setprio inside the K loops of mm_real (the classes other than the pinwheel one)
 #endif
-#ifndef C3P_PW_SPLITK
-#define C3P_PW_SPLITK 0  // single pinwheel products: odd K-steps in a second accumulator set (measured: -1.4 %)
-#endif
-#ifndef C3P_PW_ROT
-#define C3P_PW_ROT 0  // wave roles of the pinwheel class rotated by blockIdx % this (0 = off)
-#endif
 #ifndef C3P_PW_PRIO
 #define C3P_PW_PRIO 2  // s_setprio inside the K loops of the pinwheel products
 #endif
@@ -76,9 +70,6 @@
 #ifndef C3P_PW_CPL
 #define C3P_PW_CPL 1  // K-step pair whose matrix instructions the centre block's operand reads go out with
 #define C3P_PW_CPF 2  // ... and the pair its two K-packed instructions follow
-#endif
-#ifndef C3P_PW_TIMING
-#define C3P_PW_TIMING 0  // 1: timing-only build (WRONG results): one 4-column fragment per K-step instead of three
 #endif
 #ifndef C3P_PW_WGS
 #define C3P_PW_WGS 3  // workgroups per CU of the pinwheel class (forward kernel)
@@ -439,10 +430,10 @@ __device__ __forceinline__ void md_stage_signals(const MidArgs& A, const MidComm
 
 // ---------------------------------------------------------------------------------------------
 // Real-Hamiltonian path (unitary mode, every table purely imaginary: H real).  X = -iY with Y real, so
-//   exp(X) = cos Y - i sin Y,  cos Y = p_c(W),  sin Y = Y p_s(W),  W = Y^2  (Taylor degree 18 / 17, the
-// T18 scaling rule), all in REAL D x D products: a real image has 16 NIGR rows (NIGR = ceil(NIG / 2)) and
+//   exp(X) = cos Y - i sin Y,  cos Y = p_c(W),  sin Y = Y p_s(W),  W = Y^2  (the economised degree-8 pair of
+// c3p_common.h, radius C3P_MM8_THETA), all in REAL D x D products: a real image has 16 NIGR rows (NIGR = ceil(NIG / 2)) and
 // a real product runs ceil(D / 4) K-steps -- a quarter of the complex product's MFMA work.  Per slice
-// 8 + 2 s + 4 real products (W, W^2, W^3, two paired Horner steps in W^3, Y p_s; squarings
+// 7 + 2 s + 4 real products (W, W^2, {W^3, W^4}, one paired Horner step in W^4, Y p_s; squarings
 // cos 2Y = 2 C^2 - I, sin 2Y = 2 S C; chain Ur' = C Ur + S Ui, Ui' = C Ui - S Ur) instead of
 // (5 + s + 1) complex = 24 + 4 s real-equivalent ones.  Products that share an operand are issued
 // together (MODE 1: shared left operand, MODE 2: shared right operand) and share its LDS reads.
@@ -523,15 +514,9 @@ __device__ __forceinline__ void mm_real_pw(const MidCommon& cm, Regs& acc1, Regs
     f1[st_] = *reinterpret_cast<const d2*>(qfm[(P) & 3] + IF1 * IMGR + (P) * 256);                         \
     if constexpr (TWOF) f2[st_] = *reinterpret_cast<const d2*>(qfm[(P) & 3] + IF2 * IMGR + (P) * 256);     \
     _Pragma("unroll") for (int e = 0; e < 3; ++e) {                                                        \
-      const int j_ = (C3P_PW_TIMING ? 0 : e) ^ ((P) & 3);  /* timing builds: one fragment, read once */                                                  \
+      const int j_ = e ^ ((P) & 3);                                                                        \
       s1[st_][e] = *reinterpret_cast<const d2*>(q4j[j_] + I41 * IMGR + (P) * 256);                         \
       if constexpr (TWO4) s2[st_][e] = *reinterpret_cast<const d2*>(q4j[j_] + I42 * IMGR + (P) * 256);     \
-      if constexpr (C3P_PW_TIMING == 2 && true) {  /* same registers as the real build, one LDS read */   \
-        if (e > 0) {                                                                                       \
-          asm volatile("" : "+v"(s1[st_][e]));                                                             \
-          if constexpr (TWO4) asm volatile("" : "+v"(s2[st_][e]));                                         \
-        }                                                                                                  \
-      }                                                                                                    \
     }                                                                                                      \
   }
 #define C3P_MMP_FMAS(P, H)                                                                                 \
@@ -551,21 +536,18 @@ __device__ __forceinline__ void mm_real_pw(const MidCommon& cm, Regs& acc1, Regs
         const double a_ = TALL ? f2[st_][H] : s2[st_][e][H], b_ = TALL ? s1[st_][e][H] : f1[st_][H];       \
         acc2.sm[e] = MODE == 3 ? md_mfma4n(a_, b_, acc2.sm[e]) : md_mfma4(a_, b_, acc2.sm[e]);             \
       }                                                                                                    \
-    } else if constexpr (MODE == 0 && C3P_PW_SPLITK != 0 && (H) == 1) {                                    \
-      _Pragma("unroll") for (int e = 0; e < 3; ++e)                                                        \
-        odd[e] = TALL ? md_mfma4(f1[st_][H], s1[st_][e][H], odd[e]) : md_mfma4(s1[st_][e][H], f1[st_][H], odd[e]); \
     } else {                                                                                               \
-    _Pragma("unroll") for (int e = 0; e < 3; ++e) {                                                        \
-      if constexpr (TALL) {                                                                                \
-        acc1.sm[e] = md_mfma4(f1[st_][H], s1[st_][e][H], acc1.sm[e]);                                      \
-        if constexpr (TWOB) acc2.sm[e] = md_mfma4(f1[st_][H], s2[st_][e][H], acc2.sm[e]);                  \
-        if constexpr (TWOA) acc2.sm[e] = md_mfma4(f2[st_][H], s1[st_][e][H], acc2.sm[e]);                  \
-      } else {                                                                                             \
-        acc1.sm[e] = md_mfma4(s1[st_][e][H], f1[st_][H], acc1.sm[e]);                                      \
-        if constexpr (TWOB) acc2.sm[e] = md_mfma4(s1[st_][e][H], f2[st_][H], acc2.sm[e]);                  \
-        if constexpr (TWOA) acc2.sm[e] = md_mfma4(s2[st_][e][H], f1[st_][H], acc2.sm[e]);                  \
+      _Pragma("unroll") for (int e = 0; e < 3; ++e) {                                                      \
+        if constexpr (TALL) {                                                                              \
+          acc1.sm[e] = md_mfma4(f1[st_][H], s1[st_][e][H], acc1.sm[e]);                                    \
+          if constexpr (TWOB) acc2.sm[e] = md_mfma4(f1[st_][H], s2[st_][e][H], acc2.sm[e]);                \
+          if constexpr (TWOA) acc2.sm[e] = md_mfma4(f2[st_][H], s1[st_][e][H], acc2.sm[e]);                \
+        } else {                                                                                           \
+          acc1.sm[e] = md_mfma4(s1[st_][e][H], f1[st_][H], acc1.sm[e]);                                    \
+          if constexpr (TWOB) acc2.sm[e] = md_mfma4(s1[st_][e][H], f2[st_][H], acc2.sm[e]);                \
+          if constexpr (TWOA) acc2.sm[e] = md_mfma4(s2[st_][e][H], f1[st_][H], acc2.sm[e]);                \
+        }                                                                                                  \
       }                                                                                                    \
-    }                                                                                                      \
     }                                                                                                      \
   }
   // centre block (wave 1): operands fetched with pair 1's, its two K-packed instructions (+ two of the paired product) go
@@ -573,9 +555,6 @@ __device__ __forceinline__ void mm_real_pw(const MidCommon& cm, Regs& acc1, Regs
   // three waves would wait at the barrier
   constexpr int CP_LOAD = C3P_PW_CPL, CP_FMA = C3P_PW_CPF;
   double c1 = 0.0, c2 = 0.0;
-  // single products: the odd K-steps accumulate in a second register set (three dependent chains of a 4 x 4 x 4 instruction
-  // leave no slack: 45 cycles of latency against 3 x 16 of issue)
-  double odd[3] = {0.0, 0.0, 0.0};
   md_unroll<0, PFP>([&](auto Pc) { constexpr int P = decltype(Pc)::value; C3P_MMP_LOAD(P) });
   if constexpr (C3P_PW_PRIO != 0) __builtin_amdgcn_s_setprio(C3P_PW_PRIO);
   md_unroll<0, NP>([&](auto Pc) {
@@ -622,10 +601,6 @@ __device__ __forceinline__ void mm_real_pw(const MidCommon& cm, Regs& acc1, Regs
 #undef C3P_MMP_LOAD
 #undef C3P_MMP_FMAS
   if constexpr (C3P_PW_PRIO != 0) __builtin_amdgcn_s_setprio(0);
-  if constexpr (MODE == 0 && C3P_PW_SPLITK != 0) {
-#pragma unroll
-    for (int e = 0; e < 3; ++e) acc1.sm[e] += odd[e];
-  }
   if constexpr (WV == 1) {
     c1 += md_row_ror<4>(c1);
     c1 += md_row_ror<8>(c1);
@@ -778,12 +753,6 @@ struct MDR {
   static constexpr int WGS = (AREA * 8 + 6144) * 3 <= 160 * 1024 ? 3 : (C3P_MDR_BIG_WGS);
 };
 
-// doubles of the real image area: the pinwheel class runs its unsquared degree-20 slices on SIX images (see PLAN6 below)
-template <int NIG, int NJ, int W>
-constexpr int mdr_area() {
-  return MDR<NIG, W>::AREA + (Sched<MDR<NIG, W>::NIGR, NJ>::PW ? 16 * MDR<NIG, W>::NIGR * MDR<NIG, W>::WI : 0);
-}
-
 template <int NIG, int NJ, int W, bool DUS, int WV>
 __device__ __forceinline__ void midd_real_body(const MidArgs& A, const MidCommon& cm, long chain) {
   constexpr int NIGR = MDR<NIG, W>::NIGR;
@@ -872,16 +841,8 @@ __device__ __forceinline__ void midd_real_body(const MidArgs& A, const MidCommon
     tmu_r[k] = md_rfl(k <= K ? tk[IMG + 0] : 0.0);
     tmu_i[k] = md_rfl(k <= K ? tk[IMG + 1] : 0.0);
   }
-  // instantiated per polynomial variant with the branch outside the loop (as in the small-D kernel): below
-  // theta_16 = 0.816 the degree-16 / 17 polynomials are exact to roundoff and W^3, W^4 are one paired product
-  auto real_loop = [&](auto var_tag, auto plan_tag) {
-  constexpr int VAR = decltype(var_tag)::value;  // Taylor degree of cos: 16, 18 or 20
-  constexpr bool DEG16 = VAR == 16, DEG20 = VAR == 20;
-  // Pinwheel class, degree 20 without squarings (cfg3): six images.  Y keeps image 0 for the whole slice (W^5 goes to image 5),
-  // so sin Y = Y (sin Y / Y) reads it there -- no second store of Y -- and the operands of the chain step (C, S, Ur, Ui ->
-  // images 1, 3, 4, 5) are none of the two that product reads: the barrier in front of their stores goes (7 instead of 8
-  // per slice, 12 tile-set stores instead of 13).
-  constexpr bool PLAN6 = decltype(plan_tag)::value != 0;
+  // One polynomial form serves every norm: the economised degree-8 cos / sin pair of c3p_common.h (radius C3P_MM8_THETA) with
+  // cm.ps squarings; W^3 and W^4 are one paired product.
   for (int t = 0; t < cm.len; ++t) {
     if ((t & (SGC - 1)) == 0) md_stage_signals<WV>(A, cm, t);
     double mu_r = 0.0, mu_i = 0.0;
@@ -935,104 +896,28 @@ __device__ __forceinline__ void midd_real_body(const MidArgs& A, const MidCommon
     };
     Regs Sn;
     zero(Sn);
-    // cos: c_j = (-1)^j / (2j)!;  sin / Y: s_j = (-1)^j / (2j+1)!
-    if constexpr (DEG20) {
-      // q = 5 (theta_20 = 1.49: cfg3 / cfg5 need no squaring): {W^3, W^4} as in the degree-16 variant, W^5 = W^2 W^3,
-      // then ONE paired Horner step in W^5:  p = B0(W..W^4) + W^5 (B1(W..W^4) + c10 W^5)
-      Regs W4, W5;
-      zero(W4);
-      zero(W5);
-      mm_real<NIGR, NJ, W, WV, 2, 1, 2, 2, 2>(cm, W3, W4);
-      store_tiles(IC<3>{}, W3);
-      // everything W .. W^4 feed is formed BEFORE the W^5 product, whose operands come from the images: the four power
-      // tile sets are dead while it runs and afterwards (16 -> 12 live tile sets at the peak; the slice loop is register-bound)
-      rc(Cm, 1.0, -c3p_inv_fact[2], c3p_inv_fact[4], -c3p_inv_fact[6]);
-      rc(Sp, 1.0, -c3p_inv_fact[3], c3p_inv_fact[5], -c3p_inv_fact[7]);
+    // q = 4: {W^3, W^4} = {W, W^2} W^2 as one paired product, then ONE paired Horner step in W^4 (coefficients: c3p_mm8_cos / c3p_mm8_sinc)
+    Regs W4;
+    zero(W4);
+    mm_real<NIGR, NJ, W, WV, 2, 1, 2, 2, 2>(cm, W3, W4);
+    rc(acc, c3p_mm8_cos[4], c3p_mm8_cos[5], c3p_mm8_cos[6], c3p_mm8_cos[7]);
+    rc(acs, c3p_mm8_sinc[4], c3p_mm8_sinc[5], c3p_mm8_sinc[6], c3p_mm8_sinc[7]);
 #pragma unroll
-      for (int e = 0; e < NE; ++e) {
-        Cm.set(e, fma(c3p_inv_fact[8], W4.get(e), Cm.get(e)));
-        Sp.set(e, fma(c3p_inv_fact[9], W4.get(e), Sp.get(e)));
-        double a = -c3p_inv_fact[10] * dmask(e), s = -c3p_inv_fact[11] * dmask(e);
-        a = fma(c3p_inv_fact[12], W1.get(e), a), s = fma(c3p_inv_fact[13], W1.get(e), s);
-        a = fma(-c3p_inv_fact[14], W2.get(e), a), s = fma(-c3p_inv_fact[15], W2.get(e), s);
-        a = fma(c3p_inv_fact[16], W3.get(e), a), s = fma(c3p_inv_fact[17], W3.get(e), s);
-        acc.set(e, fma(-c3p_inv_fact[18], W4.get(e), a));
-        acs.set(e, fma(-c3p_inv_fact[19], W4.get(e), s));
-      }
-      md_bar();
-      mm_real<NIGR, NJ, W, WV, 0, 2, 2, 3, 3>(cm, W5, dummy);
-#pragma unroll
-      for (int e = 0; e < NE; ++e) {
-        acc.set(e, fma(c3p_inv_fact[20], W5.get(e), acc.get(e)));
-        acs.set(e, fma(c3p_inv_fact[21], W5.get(e), acs.get(e)));
-      }
-      if constexpr (PLAN6) {
-        store_tiles(IC<5>{}, W5);
-        store_tiles(IC<1>{}, acc);
-        store_tiles(IC<4>{}, acs);
-        md_bar();
-        mm_real<NIGR, NJ, W, WV, 1, 5, 5, 1, 4>(cm, Cm, Sp);  // Cm = cos Y, Sp = sin(Y) / Y
-        store_tiles(IC<2>{}, Sp);
-        md_bar();
-        mm_real<NIGR, NJ, W, WV, 0, 0, 0, 2, 2>(cm, Sn, dummy);  // sin Y
-      } else {
-        store_tiles(IC<0>{}, W5);
-        store_tiles(IC<1>{}, acc);
-        store_tiles(IC<4>{}, acs);
-        md_bar();
-        mm_real<NIGR, NJ, W, WV, 1, 0, 0, 1, 4>(cm, Cm, Sp);  // Cm = cos Y, Sp = sin(Y) / Y
-        store_tiles(IC<2>{}, Sp);
-        store_tiles(IC<3>{}, Y);
-        md_bar();
-        mm_real<NIGR, NJ, W, WV, 0, 3, 3, 2, 2>(cm, Sn, dummy);  // sin Y
-      }
-    } else if constexpr (DEG16) {
-      // q = 4: {W^3, W^4} = {W, W^2} W^2 as one paired product, then ONE paired Horner step in W^4
-      Regs W4;
-      zero(W4);
-      mm_real<NIGR, NJ, W, WV, 2, 1, 2, 2, 2>(cm, W3, W4);
-      // (round 6: the ECONOMISED degree-8 pair of c3p_common.h -- same products, valid to ||Y|| = 1.85 instead of 0.816)
-      rc(acc, c3p_mm8_cos[4], c3p_mm8_cos[5], c3p_mm8_cos[6], c3p_mm8_cos[7]);
-      rc(acs, c3p_mm8_sinc[4], c3p_mm8_sinc[5], c3p_mm8_sinc[6], c3p_mm8_sinc[7]);
-#pragma unroll
-      for (int e = 0; e < NE; ++e) {
-        acc.set(e, fma(c3p_mm8_cos[8], W4.get(e), acc.get(e)));
-        acs.set(e, fma(c3p_mm8_sinc[8], W4.get(e), acs.get(e)));
-      }
-      store_tiles(IC<3>{}, W4);
-      store_tiles(IC<0>{}, acc);
-      store_tiles(IC<4>{}, acs);
-      md_bar();
-      rc(Cm, c3p_mm8_cos[0], c3p_mm8_cos[1], c3p_mm8_cos[2], c3p_mm8_cos[3]);
-      rc(Sp, c3p_mm8_sinc[0], c3p_mm8_sinc[1], c3p_mm8_sinc[2], c3p_mm8_sinc[3]);
-      mm_real<NIGR, NJ, W, WV, 1, 3, 3, 0, 4>(cm, Cm, Sp);  // Cm = cos Y, Sp = sin(Y) / Y
-      store_tiles(IC<1>{}, Sp);
-      store_tiles(IC<2>{}, Y);
-      md_bar();
-      mm_real<NIGR, NJ, W, WV, 0, 2, 2, 1, 1>(cm, Sn, dummy);  // sin Y
-    } else {
-      // degree 18 / 17: two paired Horner steps in W^3
-      mm_real<NIGR, NJ, W, WV, 0, 1, 1, 2, 2>(cm, W3, dummy);  // W^3
-      rc(Cm, c3p_inv_fact[12], -c3p_inv_fact[14], c3p_inv_fact[16], -c3p_inv_fact[18]);
-      rc(Sp, c3p_inv_fact[13], -c3p_inv_fact[15], c3p_inv_fact[17], 0.0);
-      store_tiles(IC<3>{}, W3);
-      store_tiles(IC<0>{}, Cm);
-      store_tiles(IC<4>{}, Sp);
-      md_bar();
-      rc(acc, -c3p_inv_fact[6], c3p_inv_fact[8], -c3p_inv_fact[10], 0.0);
-      rc(acs, -c3p_inv_fact[7], c3p_inv_fact[9], -c3p_inv_fact[11], 0.0);
-      mm_real<NIGR, NJ, W, WV, 1, 3, 3, 0, 4>(cm, acc, acs);
-      store_tiles(IC<1>{}, acc);
-      store_tiles(IC<2>{}, acs);
-      md_bar();
-      rc(Cm, 1.0, -c3p_inv_fact[2], c3p_inv_fact[4], 0.0);
-      rc(Sp, 1.0, -c3p_inv_fact[3], c3p_inv_fact[5], 0.0);
-      mm_real<NIGR, NJ, W, WV, 1, 3, 3, 1, 2>(cm, Cm, Sp);  // Cm = cos Y, Sp = sin(Y) / Y
-      store_tiles(IC<0>{}, Sp);
-      store_tiles(IC<4>{}, Y);
-      md_bar();
-      mm_real<NIGR, NJ, W, WV, 0, 4, 4, 0, 0>(cm, Sn, dummy);  // sin Y
+    for (int e = 0; e < NE; ++e) {
+      acc.set(e, fma(c3p_mm8_cos[8], W4.get(e), acc.get(e)));
+      acs.set(e, fma(c3p_mm8_sinc[8], W4.get(e), acs.get(e)));
     }
+    store_tiles(IC<3>{}, W4);
+    store_tiles(IC<0>{}, acc);
+    store_tiles(IC<4>{}, acs);
+    md_bar();
+    rc(Cm, c3p_mm8_cos[0], c3p_mm8_cos[1], c3p_mm8_cos[2], c3p_mm8_cos[3]);
+    rc(Sp, c3p_mm8_sinc[0], c3p_mm8_sinc[1], c3p_mm8_sinc[2], c3p_mm8_sinc[3]);
+    mm_real<NIGR, NJ, W, WV, 1, 3, 3, 0, 4>(cm, Cm, Sp);  // Cm = cos Y, Sp = sin(Y) / Y
+    store_tiles(IC<1>{}, Sp);
+    store_tiles(IC<2>{}, Y);
+    md_bar();
+    mm_real<NIGR, NJ, W, WV, 0, 2, 2, 1, 1>(cm, Sn, dummy);  // sin Y
     // ---- squarings in real form: cos 2Y = 2 C^2 - I, sin 2Y = 2 S C (image pairs alternate: no extra barrier) ----
     auto square = [&](auto ia, auto ib) {
       constexpr int IA = decltype(ia)::value, IB = decltype(ib)::value;
@@ -1050,13 +935,11 @@ __device__ __forceinline__ void midd_real_body(const MidArgs& A, const MidCommon
       }
     };
     for (int it = 0; it < cm.ps; ++it) {
-      // the image pair not read by the previous product (sin Y reads images 2, 1 / 4, 0 / 3, 2 at degree 16 / 18 / 20)
+      // the image pair not read by the previous product (sin Y reads images 2, 1)
       if ((it & 1) != 0)
-        DEG16 ? square(IC<1>{}, IC<2>{}) : square(IC<3>{}, IC<4>{});
-      else if constexpr (DEG20)
-        square(IC<0>{}, IC<1>{});
+        square(IC<1>{}, IC<2>{});
       else
-        DEG16 ? square(IC<3>{}, IC<4>{}) : square(IC<1>{}, IC<2>{});
+        square(IC<3>{}, IC<4>{});
     }
     if constexpr (DUS) {
       // dU = e^{mu} (C - iS)
@@ -1086,11 +969,11 @@ __device__ __forceinline__ void midd_real_body(const MidArgs& A, const MidCommon
       mus_i = c3p_phase_add(0.0, mu_i);
       md_bar();  // image 0 is rewritten by the next slice
     } else {
-      if constexpr (!PLAN6) md_bar();  // the last product's operands are no longer read
+      md_bar();  // the last product's operands are no longer read
       store_tiles(IC<1>{}, Cm);
-      store_tiles(IC<PLAN6 ? 3 : 2>{}, Sn);
-      store_tiles(IC<PLAN6 ? 4 : 3>{}, Ur);
-      store_tiles(IC<PLAN6 ? 5 : 4>{}, Ui);
+      store_tiles(IC<2>{}, Sn);
+      store_tiles(IC<3>{}, Ur);
+      store_tiles(IC<4>{}, Ui);
       md_bar();
       Regs Vr, Vi;
       zero(Vr);
@@ -1098,10 +981,8 @@ __device__ __forceinline__ void midd_real_body(const MidArgs& A, const MidCommon
       // (the 48-row classes take the four-product pass of the pinwheel class too: cfg5 +0.6 %, D = 36 / 40 at 256 samples +1.5 - 2 %;
       // no gain on the 16- / 32-row classes)
       constexpr bool QUADC = PW || NIGR >= 3;
-      if constexpr (PLAN6) {
-        mm_real<NIGR, NJ, W, WV, 3, 1, 3, 4, 5>(cm, Vr, Vi);  // all four products in one pass over the operands
-      } else if constexpr (QUADC) {
-        mm_real<NIGR, NJ, W, WV, 3, 1, 2, 3, 4>(cm, Vr, Vi);
+      if constexpr (QUADC) {
+        mm_real<NIGR, NJ, W, WV, 3, 1, 2, 3, 4>(cm, Vr, Vi);  // all four products in one pass over the operands
       } else {
         mm_real<NIGR, NJ, W, WV, 1, 2, 2, 4, 3>(cm, Vr, Vi);  // S Ui, S Ur
 #pragma unroll
@@ -1113,17 +994,6 @@ __device__ __forceinline__ void midd_real_body(const MidArgs& A, const MidCommon
       mus_r += mu_r;
       mus_i = c3p_phase_add(mus_i, mu_i);
     }
-  }
-  };
-  if (cm.t18 == 2) {  // (reused as the variant flag on the real path: 1 = degree 16, 0 = degree 18, 2 = degree 20)
-    if (PW && cm.ps == 0)
-      real_loop(IC<20>{}, IC<PW ? 1 : 0>{});
-    else
-      real_loop(IC<20>{}, IC<0>{});
-  } else if (cm.t18 == 1) {
-    real_loop(IC<16>{}, IC<0>{});
-  } else {
-    real_loop(IC<18>{}, IC<0>{});
   }
   // ---- segment result: e^{sum mu} (Ur + i Ui), optional row phases ----
   double sn, cs;
@@ -1464,7 +1334,7 @@ __global__ void __launch_bounds__(256, (REAL ? (Sched<MDR<NIG, W>::NIGR, NJ>::PW
   cm.nbkR = (cm.D + 3) / 4;
   cm.K = A.K;
   const int K = A.K;
-  constexpr int AREA = REAL ? mdr_area<NIG, NJ, W>() : 3 * IMG;  // image area: 3 complex images or the real pipeline's
+  constexpr int AREA = REAL ? MDR<NIG, W>::AREA : 3 * IMG;  // image area: 3 complex images or the real pipeline's
 
   cm.buf0 = c3p_md_lds;
   cm.buf1 = cm.buf0 + IMG;
@@ -1566,35 +1436,15 @@ __global__ void __launch_bounds__(256, (REAL ? (Sched<MDR<NIG, W>::NIGR, NJ>::PW
       cm.ps = __builtin_amdgcn_readfirstlane(q.s);
     }
     if constexpr (REAL) {
-      // Taylor degree 16 / 18 / 20 of cos (theta = 0.816 / 1.13 / 1.49: backward error below 2^-53) with s squarings:
-      // 7 / 8 / 8 + 2 s real products; the cheapest, the lower degree on ties (variant kept in t18: 1 / 0 / 2)
-      auto squarings = [&](double theta) {
-        int s = 0;
-        while (theta < nrm && s < 40) {
-          theta *= 2.0;
-          ++s;
-        }
-        return s;
-      };
-      // Round 6: the 7-product variant evaluates the Chebyshev-economised degree-8 polynomials (theta = 1.85: Y is real symmetric,
-      // so the scalar error on [0, theta^2] is the matrix error) -- it dominates the degree-18 / 20 Taylor variants below
-      const int s16 = squarings(C3P_MM8_THETA), s18 = squarings(C3P_T18_THETA), s20 = squarings(1.49);
-      int var = 1, s = s16, cost = 7 + 2 * s16;
-      if (8 + 2 * s18 < cost) var = 0, s = s18, cost = 8 + 2 * s18;
-      // (degree 20 only in the 16- and 32-row classes: at D >= 33 its extra dependent product and two more live tile sets
-      // cost more than the squaring they save -- cfg5 measured 3 % slower with it, cfg3 3.6 % faster)
-      if (MDR<NIG, W>::NIGR <= 2 && 8 + 2 * s20 < cost) var = 2, s = s20, cost = 8 + 2 * s20;
-      cm.ps = __builtin_amdgcn_readfirstlane(s);
-      cm.t18 = __builtin_amdgcn_readfirstlane(var);
+      // the economised degree-8 cos / sin pair (Y is real symmetric, so the scalar error on [0, theta^2] is the matrix error):
+      // 7 + 2 s real products
+      cm.ps = __builtin_amdgcn_readfirstlane(c3p_squarings(nrm, C3P_MM8_THETA));
     }
     cm.scale = ldexp(1.0, -cm.ps);
     __syncthreads();
   }
   if constexpr (REAL) {
-    // (pinwheel class: the role that also carries the centre block moves with the workgroup, so that the workgroups of a CU
-    // do not put it on one SIMD)
-    const int role = (Sched<MDR<NIG, W>::NIGR, NJ>::PW && C3P_PW_ROT) ? ((wave + (int)(blockIdx.x % (C3P_PW_ROT ? C3P_PW_ROT : 1))) & 3) : wave;
-    switch (role) {
+    switch (wave) {
       case 0: midd_real_body<NIG, NJ, W, DUS, 0>(A, cm, chain); break;
       case 1: midd_real_body<NIG, NJ, W, DUS, 1>(A, cm, chain); break;
       case 2: midd_real_body<NIG, NJ, W, DUS, 2>(A, cm, chain); break;
@@ -1773,7 +1623,7 @@ hipError_t launch_t(const MidArgs& A, hipStream_t st) {
 #if C3P_MIDD_HAS(2)
 template <int NIG, int NJ, int W>
 hipError_t launch_real_t(const MidArgs& A, hipStream_t st) {
-  const size_t ldsr = (size_t)(mdr_area<NIG, NJ, W>() + A.K * SGC) * sizeof(double);
+  const size_t ldsr = (size_t)(MDR<NIG, W>::AREA + A.K * SGC) * sizeof(double);
   return A.dUs_out ? md_go(midd_chain_kernel<NIG, NJ, W, false, true, false, true>, A, ldsr, st)
                    : md_go(midd_chain_kernel<NIG, NJ, W, false, false, false, true>, A, ldsr, st);
 }
@@ -1993,23 +1843,13 @@ __device__ __forceinline__ void midd_grad_body(const MidGradArgs& A, const MidCo
   }
 }
 
-// real-Hamiltonian backward sweep (midd_grad_real_kernel below): squarings kept, image slots, scaling rule (theta_16)
+// real-Hamiltonian backward sweep (midd_grad_real_kernel below): squarings kept, image slots
 constexpr int MGR_SLOTS = 8;
 // squaring levels kept in registers: two, one for the 48-row classes (D >= 33, register-bound)
 template <int NIG>
 struct MGR {
   static constexpr int MAXS = (NIG + 1) / 2 >= 3 ? 1 : 2;
 };
-
-__device__ __forceinline__ int mgr_squarings(double nrm) {
-  int ps = 0;
-  double p = C3P_MM8_THETA;  // round 6: the economised degree-8 pair (c3p_common.h) instead of theta_16 = 0.816
-  while (p < nrm && ps < 40) {
-    p *= 2.0;
-    ++ps;
-  }
-  return ps;
-}
 
 template <int NIG, int NJ, int W>
 __global__ void __launch_bounds__(256, 1) midd_grad_kernel(MidGradArgs A) {
@@ -2064,19 +1904,12 @@ __global__ void __launch_bounds__(256, 1) midd_grad_kernel(MidGradArgs A) {
     nrm = fma(cmax, cm.tabs[(long)(k + 1) * (IMG + 4) + IMG + 2], nrm);
   }
   nrm = md_rfl(nrm);
-  int ps = 0;
-  {
-    double p = C3P_T18_THETA;
-    while (p < nrm && ps < 40) {
-      p *= 2.0;
-      ++ps;
-    }
-  }
+  int ps = c3p_squarings(nrm, C3P_T18_THETA);
   cm.ps = __builtin_amdgcn_readfirstlane(ps);
   if (A.skip_real) {  // the real-Hamiltonian sweep has taken this chain (same tables, same norm bound: same decision)
     bool realH = K <= MDR<NIG, W>::KP;
     for (int k = 0; k <= K; ++k) realH = realH && (cm.tabs[(long)k * (IMG + 4) + IMG + 3] == 0.0);
-    if (__builtin_amdgcn_readfirstlane((int)realH) != 0 && __builtin_amdgcn_readfirstlane(mgr_squarings(nrm)) <= MGR<NIG>::MAXS) return;
+    if (__builtin_amdgcn_readfirstlane((int)realH) != 0 && __builtin_amdgcn_readfirstlane(c3p_squarings(nrm, C3P_MM8_THETA)) <= MGR<NIG>::MAXS) return;
   }
   cm.pr = 0;
   cm.t18 = 1;
@@ -2453,14 +2286,7 @@ __global__ void __launch_bounds__(256, 1) midd_grad_general_kernel(MidGradArgs A
     nrm = fma(cmax, cm.tabs[(long)(k + 1) * (IMG + 4) + IMG + 2], nrm);
   }
   nrm = md_rfl(nrm);
-  int ps = 0;
-  {
-    double p = C3P_T18_THETA;
-    while (p < nrm && ps < 40) {
-      p *= 2.0;
-      ++ps;
-    }
-  }
+  int ps = c3p_squarings(nrm, C3P_T18_THETA);
   cm.ps = __builtin_amdgcn_readfirstlane(ps);
   cm.pr = 0;
   cm.t18 = 1;
@@ -2486,12 +2312,12 @@ __global__ void __launch_bounds__(256, 1) midd_grad_general_kernel(MidGradArgs A
 // (+ 2 forward and 3 backward per squaring) against 18 + 3 s COMPLEX ones of the pair evaluation above.
 // Eight real images: slots 0..3 hold the operands of the running product, 4 / 5 the products to be transposed,
 // 6 / 7 the product R = dU N for the update N <- R conj(dU) (stored transposed in the swizzled layout, whose left
-// operands are read in the B pattern).  Always the degree-16 / 17 polynomials, up to MGR<NIG>::MAXS squarings; other chains
+// operands are read in the B pattern).  Always the economised degree-8 pair, up to MGR<NIG>::MAXS squarings; other chains
 // are left to midd_grad_kernel (same tables, same norm bound: same decision).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ int mgr_tswz(int x) { return x & 15; }
 
-template <int NIG, int NJ, int W, int WV, bool DEG20>
+template <int NIG, int NJ, int W, int WV>
 __device__ __forceinline__ void midd_grad_real_body(const MidGradArgs& A, const MidCommon& cm, long chain, double* red) {
   constexpr int NIGR = MDR<NIG, W>::NIGR;
   constexpr int WI = MDR<NIG, W>::WI;
@@ -2614,7 +2440,7 @@ __device__ __forceinline__ void midd_grad_real_body(const MidGradArgs& A, const 
   }
   const int ps = cm.ps;
   for (int t = cm.len - 1; t >= 0; --t) {
-    // ---- forward: Y, W = Y^2, W^2, {W^3, W^4}, cos Y, sin(Y)/Y, sin Y (midd_real_body, degree 16 / 17) ----
+    // ---- forward: Y, W = Y^2, W^2, {W^3, W^4}, cos Y, sin(Y)/Y, sin Y (as in midd_real_body) ----
     Regs Y;
     tab_get(0, Y);
 #pragma unroll
@@ -2649,51 +2475,21 @@ __device__ __forceinline__ void midd_grad_real_body(const MidGradArgs& A, const 
         out.set(e, fma(c0, dmask(e), v));
       }
     };
-    // coefficients of W^j in cos Y / (sin Y / Y): Taylor for the degree-20 variant, the economised degree-8 pair (theta = 1.85,
-    // c3p_common.h) otherwise -- forward evaluation and its adjoint below use the same table
-    auto ca = [&](int j) { return DEG20 ? ((j & 1) ? -c3p_inv_fact[2 * j] : c3p_inv_fact[2 * j]) : c3p_mm8_cos[j]; };
-    auto sa = [&](int j) { return DEG20 ? ((j & 1) ? -c3p_inv_fact[2 * j + 1] : c3p_inv_fact[2 * j + 1]) : c3p_mm8_sinc[j]; };
-    // the power the Horner step runs in: W^4 (degree 16), W^5 = W^2 W^3 (degree 20, theta_20 = 1.49: one squaring less)
-    Regs H;
-    if constexpr (DEG20) {
-      st(IC<3>{}, W3);
-      md_bar();
-      zero(H);
-      mm_real<NIGR, NJ, W, WV, 0, 2, 2, 3, 3>(cm, H, dummy);
+    // coefficients of W^j in cos Y / (sin Y / Y): the economised degree-8 pair (theta = 1.85, c3p_common.h); the forward evaluation
+    // and its adjoint below use the same tables.  The Horner step runs in W^4.
+    rc(acc, c3p_mm8_cos[4], c3p_mm8_cos[5], c3p_mm8_cos[6], c3p_mm8_cos[7]);
+    rc(acs, c3p_mm8_sinc[4], c3p_mm8_sinc[5], c3p_mm8_sinc[6], c3p_mm8_sinc[7]);
 #pragma unroll
-      for (int e = 0; e < NE; ++e) {
-        double a = -c3p_inv_fact[10] * dmask(e), s = -c3p_inv_fact[11] * dmask(e);
-        a = fma(c3p_inv_fact[12], W1.get(e), a), s = fma(c3p_inv_fact[13], W1.get(e), s);
-        a = fma(-c3p_inv_fact[14], W2.get(e), a), s = fma(-c3p_inv_fact[15], W2.get(e), s);
-        a = fma(c3p_inv_fact[16], W3.get(e), a), s = fma(c3p_inv_fact[17], W3.get(e), s);
-        a = fma(-c3p_inv_fact[18], W4.get(e), a), s = fma(-c3p_inv_fact[19], W4.get(e), s);
-        acc.set(e, fma(c3p_inv_fact[20], H.get(e), a));
-        acs.set(e, fma(c3p_inv_fact[21], H.get(e), s));
-      }
-      st(IC<7>{}, H);
-    } else {
-      H = W4;
-      rc(acc, ca(4), ca(5), ca(6), ca(7));
-      rc(acs, sa(4), sa(5), sa(6), sa(7));
-#pragma unroll
-      for (int e = 0; e < NE; ++e) {
-        acc.set(e, fma(ca(8), W4.get(e), acc.get(e)));
-        acs.set(e, fma(sa(8), W4.get(e), acs.get(e)));
-      }
-      st(IC<7>{}, H);
+    for (int e = 0; e < NE; ++e) {
+      acc.set(e, fma(c3p_mm8_cos[8], W4.get(e), acc.get(e)));
+      acs.set(e, fma(c3p_mm8_sinc[8], W4.get(e), acs.get(e)));
     }
+    st(IC<7>{}, W4);
     st(IC<4>{}, acc);
     st(IC<5>{}, acs);
     md_bar();
-    rc(Cm, ca(0), ca(1), ca(2), ca(3));
-    rc(Sp, sa(0), sa(1), sa(2), sa(3));
-    if constexpr (DEG20) {
-#pragma unroll
-      for (int e = 0; e < NE; ++e) {
-        Cm.set(e, fma(c3p_inv_fact[8], W4.get(e), Cm.get(e)));
-        Sp.set(e, fma(c3p_inv_fact[9], W4.get(e), Sp.get(e)));
-      }
-    }
+    rc(Cm, c3p_mm8_cos[0], c3p_mm8_cos[1], c3p_mm8_cos[2], c3p_mm8_cos[3]);
+    rc(Sp, c3p_mm8_sinc[0], c3p_mm8_sinc[1], c3p_mm8_sinc[2], c3p_mm8_sinc[3]);
     mm_real<NIGR, NJ, W, WV, 1, 7, 7, 4, 5>(cm, Cm, Sp);
     st(IC<6>{}, Sp);
     md_bar();
@@ -2814,29 +2610,29 @@ __device__ __forceinline__ void midd_grad_real_body(const MidGradArgs& A, const 
       mirror(IC<4>{}, Pa, 1.0, Yb2);
       mirror(IC<5>{}, Pb, 0.5, Spb);
     }
-    // ---- Cm = Cm0 + H acc, Sp = Sp0 + H acs (W4b2: twice the cotangent of H from these two) ----
+    // ---- Cm = Cm0 + W4 acc, Sp = Sp0 + W4 acs (W4b2: twice the cotangent of W4 from these two) ----
     Regs W4b2, accb, acsb;
     {
       st(IC<0>{}, Cb);
       st(IC<1>{}, acc);
-      st(IC<2>{}, H);
+      st(IC<2>{}, W4);
       md_bar();
       Regs Pc, Pd;
       zero(Pc);
       zero(Pd);
-      mm_real<NIGR, NJ, W, WV, 1, 0, 0, 1, 2>(cm, Pc, Pd);  // C_bar acc, C_bar H
+      mm_real<NIGR, NJ, W, WV, 1, 0, 0, 1, 2>(cm, Pc, Pd);  // C_bar acc, C_bar W4
       st_T(IC<4>{}, Pc);
       st_T(IC<5>{}, Pd);
       md_bar();
       mirror(IC<4>{}, Pc, 1.0, W4b2);
       mirror(IC<5>{}, Pd, 0.5, accb);
       st(IC<0>{}, Spb);
-      st(IC<1>{}, acs);  // (image 2 still holds H)
+      st(IC<1>{}, acs);  // (image 2 still holds W4)
       md_bar();
       Regs Pe, Pf;
       zero(Pe);
       zero(Pf);
-      mm_real<NIGR, NJ, W, WV, 1, 0, 0, 1, 2>(cm, Pe, Pf);  // Sp_bar acs, Sp_bar H
+      mm_real<NIGR, NJ, W, WV, 1, 0, 0, 1, 2>(cm, Pe, Pf);  // Sp_bar acs, Sp_bar W4
       st_T(IC<4>{}, Pe);
       st_T(IC<5>{}, Pf);
       md_bar();
@@ -2847,46 +2643,13 @@ __device__ __forceinline__ void midd_grad_real_body(const MidGradArgs& A, const 
       for (int e = 0; e < NE; ++e) W4b2.set(e, W4b2.get(e) + tmp.get(e));
     }
     Regs W1b, W2b, W3b, W4b;
-    if constexpr (DEG20) {
-      Regs W5b;
 #pragma unroll
-      for (int e = 0; e < NE; ++e) {
-        const double ab = accb.get(e), sb = acsb.get(e), cb = Cb.get(e), pb = Spb.get(e);
-        W1b.set(e, -(c3p_inv_fact[2] * cb + c3p_inv_fact[3] * pb) + (c3p_inv_fact[12] * ab + c3p_inv_fact[13] * sb));
-        W2b.set(e, (c3p_inv_fact[4] * cb + c3p_inv_fact[5] * pb) - (c3p_inv_fact[14] * ab + c3p_inv_fact[15] * sb));
-        W3b.set(e, -(c3p_inv_fact[6] * cb + c3p_inv_fact[7] * pb) + (c3p_inv_fact[16] * ab + c3p_inv_fact[17] * sb));
-        W4b.set(e, (c3p_inv_fact[8] * cb + c3p_inv_fact[9] * pb) - (c3p_inv_fact[18] * ab + c3p_inv_fact[19] * sb));
-        W5b.set(e, 0.5 * W4b2.get(e) + c3p_inv_fact[20] * ab + c3p_inv_fact[21] * sb);
-      }
-      // ---- W5 = W2 W3:  W2_bar += sym(W5_bar W3),  W3_bar += sym(W5_bar W2) ----
-      st(IC<0>{}, W5b);
-      st(IC<1>{}, W2);
-      st(IC<2>{}, W3);
-      md_bar();
-      Regs Pm, Pn;
-      zero(Pm);
-      zero(Pn);
-      mm_real<NIGR, NJ, W, WV, 1, 0, 0, 1, 2>(cm, Pm, Pn);  // W5_bar W2, W5_bar W3
-      st_T(IC<4>{}, Pm);
-      st_T(IC<5>{}, Pn);
-      md_bar();
-      Regs q, h;
-      mirror(IC<4>{}, Pm, 0.5, q);
-      mirror(IC<5>{}, Pn, 0.5, h);
-#pragma unroll
-      for (int e = 0; e < NE; ++e) {
-        W3b.set(e, W3b.get(e) + q.get(e));
-        W2b.set(e, W2b.get(e) + h.get(e));
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < NE; ++e) {
-        const double ab = accb.get(e), sb = acsb.get(e), cb = Cb.get(e), pb = Spb.get(e);
-        W1b.set(e, ca(1) * cb + sa(1) * pb + ca(5) * ab + sa(5) * sb);
-        W2b.set(e, ca(2) * cb + sa(2) * pb + ca(6) * ab + sa(6) * sb);
-        W3b.set(e, ca(3) * cb + sa(3) * pb + ca(7) * ab + sa(7) * sb);
-        W4b.set(e, 0.5 * W4b2.get(e) + ca(8) * ab + sa(8) * sb);
-      }
+    for (int e = 0; e < NE; ++e) {
+      const double ab = accb.get(e), sb = acsb.get(e), cb = Cb.get(e), pb = Spb.get(e);
+      W1b.set(e, c3p_mm8_cos[1] * cb + c3p_mm8_sinc[1] * pb + c3p_mm8_cos[5] * ab + c3p_mm8_sinc[5] * sb);
+      W2b.set(e, c3p_mm8_cos[2] * cb + c3p_mm8_sinc[2] * pb + c3p_mm8_cos[6] * ab + c3p_mm8_sinc[6] * sb);
+      W3b.set(e, c3p_mm8_cos[3] * cb + c3p_mm8_sinc[3] * pb + c3p_mm8_cos[7] * ab + c3p_mm8_sinc[7] * sb);
+      W4b.set(e, 0.5 * W4b2.get(e) + c3p_mm8_cos[8] * ab + c3p_mm8_sinc[8] * sb);
     }
     // ---- W4 = W2^2, W3 = W W2:  W2_bar += {W4_bar, W2} + sym(W3_bar W),  W_bar += sym(W3_bar W2) ----
     {
@@ -3032,11 +2795,8 @@ __global__ void __launch_bounds__(256, (MDR<NIG, W>::SWZ ? 2 : 1)) midd_grad_rea
     nrm = fma(cmax, cm.tabs[(long)(k + 1) * (IMG + 4) + IMG + 2], nrm);
   }
   nrm = md_rfl(nrm);
-  cm.ps = __builtin_amdgcn_readfirstlane(mgr_squarings(nrm));
+  cm.ps = __builtin_amdgcn_readfirstlane(c3p_squarings(nrm, C3P_MM8_THETA));
   if (cm.ps > MGR<NIG>::MAXS) return;
-  // degree 20 (theta_20 = 1.49) where it saves a squaring: 8 + 13 products against 7 + 11 + 5 per squaring
-  const int deg20 = __builtin_amdgcn_readfirstlane((int)(cm.ps > 0 && ldexp(nrm, 1 - cm.ps) <= 1.49));
-  cm.ps -= deg20;
   for (int e = tid; e < MGR_SLOTS * IMGR; e += 256) c3p_md_lds[e] = 0.0;
   for (int k = 0; k < K; ++k) {
     const double* s = A.signals + ((long)cm.sample * K + k) * A.N + cm.n0;
@@ -3046,20 +2806,11 @@ __global__ void __launch_bounds__(256, (MDR<NIG, W>::SWZ ? 2 : 1)) midd_grad_rea
   cm.t18 = 1;
   cm.scale = ldexp(1.0, -cm.ps);
   __syncthreads();
-  if (deg20) {
-    switch (wave) {
-      case 0: midd_grad_real_body<NIG, NJ, W, 0, true>(A, cm, chain, red); break;
-      case 1: midd_grad_real_body<NIG, NJ, W, 1, true>(A, cm, chain, red); break;
-      case 2: midd_grad_real_body<NIG, NJ, W, 2, true>(A, cm, chain, red); break;
-      default: midd_grad_real_body<NIG, NJ, W, 3, true>(A, cm, chain, red); break;
-    }
-  } else {
-    switch (wave) {
-      case 0: midd_grad_real_body<NIG, NJ, W, 0, false>(A, cm, chain, red); break;
-      case 1: midd_grad_real_body<NIG, NJ, W, 1, false>(A, cm, chain, red); break;
-      case 2: midd_grad_real_body<NIG, NJ, W, 2, false>(A, cm, chain, red); break;
-      default: midd_grad_real_body<NIG, NJ, W, 3, false>(A, cm, chain, red); break;
-    }
+  switch (wave) {
+    case 0: midd_grad_real_body<NIG, NJ, W, 0>(A, cm, chain, red); break;
+    case 1: midd_grad_real_body<NIG, NJ, W, 1>(A, cm, chain, red); break;
+    case 2: midd_grad_real_body<NIG, NJ, W, 2>(A, cm, chain, red); break;
+    default: midd_grad_real_body<NIG, NJ, W, 3>(A, cm, chain, red); break;
   }
 }
 

@@ -487,15 +487,7 @@ __global__ void __launch_bounds__(RG_THREADS, 1) regd_chain_kernel(MidArgs A, cp
       nrm = fma(cmax, meta(k + 1)[2], nrm);
     }
     nrm = rg_rfl(nrm);
-    int s18 = 0;
-    {
-      double pth = C3P_T18_THETA;
-      while (pth < nrm && s18 < 40) {
-        pth *= 2.0;
-        ++s18;
-      }
-    }
-    const int ps = __builtin_amdgcn_readfirstlane(s18);
+    const int ps = __builtin_amdgcn_readfirstlane(c3p_squarings(nrm, C3P_T18_THETA));
     const double scale = ldexp(1.0, -ps);
 
     double mu_r = 0.0, mu_i = 0.0, mus_r = 0.0, mus_i = 0.0;

@@ -39,10 +39,7 @@ extern __shared__ __attribute__((aligned(16))) double c3p_rr_lds[];
 // (R, accumulators, X / B2, X^2 / B3, U = 250 registers) + operands did not fit the 256 VALU-addressable registers: the
 // compiler kept part of them in the accumulation registers and 23 doubles per lane in SCRATCH, and the s_memtime probes
 // (-DC3P_REGR_TIMING) showed the phases between products -- a few hundred instructions each -- taking 9 - 17 k cycles: scratch
-// round trips.  -DC3P_REGR_ULDS=0 builds the round-4 form.
-#ifndef C3P_REGR_ULDS
-#define C3P_REGR_ULDS 1
-#endif
+// round trips.
 
 namespace {
 
@@ -62,7 +59,7 @@ __device__ __forceinline__ void regr_chain_body(const MidArgs& A, long long* dbg
   constexpr int DM = G::DM, LD = G::LD, BS = G::BS, DMP = G::DMP;
   constexpr int TSET = G::TSET;
   constexpr int RR_THREADS = 64 * NW;
-  constexpr bool ULDS = (C3P_REGR_ULDS != 0) && !LEAN && NW == 4;  // U parked in LDS (see the top of the file)
+  constexpr bool ULDS = !LEAN && NW == 4;  // U parked in LDS (see the top of the file)
   constexpr bool UOUT = LEAN || ULDS;                              // U does not live in registers
   const bool second = jj0 != 0;                         // the second wave of a pair
   const bool col_owner = (NW == 4) || second;           // column DM-1 of a product: the lighter wave of the pair
@@ -222,12 +219,6 @@ __device__ __forceinline__ void regr_chain_body(const MidArgs& A, long long* dbg
           for (int Ig = 0; Ig < NRG; ++Ig) aC[Ig] = aN[Ig];
 #pragma unroll
           for (int jj = 0; jj < NJ; ++jj) br[jj] = brN[jj];
-          // (-DC3P_REGR_BB: a basic-block boundary per K-step -- an opaque scalar branch that jumps over an s_sleep -- as in rounds 2 - 4,
-          // when it kept the scheduler from merging K-steps; with the per-instruction sched_barrier above it only costs its taken
-          // branch: 108.9 -> 106.1 ms per 512-sample cfg4 batch without it)
-#ifdef C3P_REGR_BB
-          if (rr_opq(0) != 0) asm volatile("s_sleep 1");
-#endif
         });
         // row DM-1 (and, on one wave, the corner): partial sums over the k of each MFMA block
         {
@@ -408,15 +399,7 @@ __device__ __forceinline__ void regr_chain_body(const MidArgs& A, long long* dbg
     for (int k = 0; k < K; ++k) nsym = fma(kmaxv[k], meta(k + 1)[3], nsym);
     const int econ = __builtin_amdgcn_readfirstlane((int)(rr_rfl(nsym) <= C3P_T18N_MAX_NONNORMAL && !(A.no_t18n & 1)));
     const double* tc = c3p_t18_tab[econ];
-    int s18 = 0;
-    {
-      double pth = econ ? C3P_T18N_THETA : C3P_T18_THETA;
-      while (pth < nrm && s18 < 40) {
-        pth *= 2.0;
-        ++s18;
-      }
-    }
-    const int ps = __builtin_amdgcn_readfirstlane(s18);
+    const int ps = __builtin_amdgcn_readfirstlane(c3p_squarings(nrm, econ ? C3P_T18N_THETA : C3P_T18_THETA));
     const double scale = ldexp(1.0, -ps);
 #ifdef C3P_REGR_PLAN_PRINT
     if (blockIdx.x < 4 && tid == 0) printf("regr chain %d: norm bound %.4f, symmetric part %.4f, economised %d, squarings %d\n", (int)blockIdx.x, nrm, nsym, econ, ps);
@@ -823,7 +806,7 @@ __global__ void __launch_bounds__(256) hb_to_complex_kernel(cplx* mats, int mats
 
 template <int NRG, int NW, bool LEAN>
 hipError_t launch_rr(const MidArgs& A, void* arena, hipStream_t st) {
-  const size_t lds = ((size_t)RR<NRG>::LDS_D + ((C3P_REGR_ULDS != 0) && !LEAN && NW == 4 ? (size_t)RR<NRG>::TSET : 0)) * sizeof(double);
+  const size_t lds = ((size_t)RR<NRG>::LDS_D + (!LEAN && NW == 4 ? (size_t)RR<NRG>::TSET : 0)) * sizeof(double);
   const long nchains = (long)A.B * A.S;
   const long maxg = LEAN ? 2 * C3P_REGD_MAX_WGS : C3P_REGD_MAX_WGS;
   const unsigned grid = (unsigned)(nchains < maxg ? nchains : maxg);

@@ -196,9 +196,6 @@ __global__ void __launch_bounds__(256, 1) regr_grad_kernel(RegrGradArgs A) {
           for (int Ig = 0; Ig < NRG; ++Ig) aC[Ig] = aN[Ig];
 #pragma unroll
           for (int jj = 0; jj < NJ; ++jj) br[jj] = brN[jj];
-#ifdef C3P_REGR_BB
-          if (rr_opq(0) != 0) asm volatile("s_sleep 1");  // a basic-block boundary per K-step (rounds 2 - 4; see c3p_regr.hip)
-#endif
         });
         {
           const double va = pr[OFF];
@@ -313,12 +310,7 @@ __global__ void __launch_bounds__(256, 1) regr_grad_kernel(RegrGradArgs A) {
       for (int i = 0; i < 4; ++i) {
         const int Ji = 3 + 2 * i;
         if (A.degree != 0 && A.degree != 2 * Ji + 2) continue;
-        int si = 0;
-        double pth = th[i];
-        while (pth < nrm && si < 40) {
-          pth *= 2.0;
-          ++si;
-        }
+        int si = c3p_squarings(nrm, th[i]);
         const int cost = 3 * Ji + 3 * si;
         if (cost < best) best = cost, pJ = Ji, ps = si;
       }

@@ -105,28 +105,20 @@ __device__ __forceinline__ void mm_img(const double* img, int roff, unsigned neg
                                        const double (&zb)[SD<D>::NBI][SD<D>::NJ],
                                        double (&acc)[SD<D>::NBI][SD<D>::NJ]) {
   using C = SD<D>;
-#ifdef C3P_SD_ABSKIP
-  // TIMING-ONLY builds (wrong results; tools/ab_complex_border.sh): what a core + border form of the complex products could
-  // save at most.  1: no matrix instructions for the last column block (D = 9: the block that holds column 8 alone);
-  // 2: none for the last row block and the last K-step either (the 8 x 8 core alone, borders for free)
-  constexpr int SKJ = (D % 4 == 1 && D > 4) ? 1 : 0, SKI = (C3P_SD_ABSKIP >= 2 && D % 4 == 1 && D > 4) ? 1 : 0;
-#else
-  constexpr int SKJ = 0, SKI = 0;
-#endif
   // software pipelined: the A fragments of step K+1 are in flight while step K's MFMAs issue
   double ra[2][C::NBI];
 #pragma unroll
-  for (int I = 0; I < C::NBI - SKI; ++I) ra[0][I] = flip_sign(lds_ld(img + roff + I * 4 * C::W), negmask);
+  for (int I = 0; I < C::NBI; ++I) ra[0][I] = flip_sign(lds_ld(img + roff + I * 4 * C::W), negmask);
 #pragma unroll
-  for (int K = 0; K < C::NBI - SKI; ++K) {
-    if (K + 1 < C::NBI - SKI) {
+  for (int K = 0; K < C::NBI; ++K) {
+    if (K + 1 < C::NBI) {
 #pragma unroll
-      for (int I = 0; I < C::NBI - SKI; ++I) ra[(K + 1) & 1][I] = flip_sign(lds_ld(img + roff + I * 4 * C::W + (K + 1) * 2), negmask);
+      for (int I = 0; I < C::NBI; ++I) ra[(K + 1) & 1][I] = flip_sign(lds_ld(img + roff + I * 4 * C::W + (K + 1) * 2), negmask);
     }
 #pragma unroll
-    for (int I = 0; I < C::NBI - SKI; ++I)
+    for (int I = 0; I < C::NBI; ++I)
 #pragma unroll
-      for (int J = 0; J < C::NJ - SKJ; ++J) acc[I][J] = mfma4(ra[K & 1][I], zb[K][J], acc[I][J]);
+      for (int J = 0; J < C::NJ; ++J) acc[I][J] = mfma4(ra[K & 1][I], zb[K][J], acc[I][J]);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -188,10 +180,10 @@ __device__ __forceinline__ void lincomb6(double (&out)[SD<D>::NBI][SD<D>::NJ], d
 // Real-Hamiltonian fast path.  When h0 and every hk are real (lab-frame transmon models in the dressed
 // basis are: model.py:453-534 dresses with the real eigenvectors of a real symmetric matrix),
 // X = -i Y with Y = dt (H - tr H / D) real symmetric and
-//     exp(X) = cos Y - i sin Y,   cos Y = sum_j (-1)^j W^j/(2j)!,  sin Y = Y sum_j (-1)^j W^j/(2j+1)!,  W = Y^2,
-// i.e. the even and odd parts of the SAME degree-18 Taylor polynomial the complex path evaluates (T18), so
-// the truncation / scaling rule (theta = 1.13) is unchanged.  Everything up to the chain product is REAL
-// D x D arithmetic: 8 real products (27 MFMAs each at D = 9) instead of 5 complex ones (75 each).
+//     exp(X) = cos Y - i sin Y,   cos Y = p_c(W),  sin Y = Y p_s(W),  W = Y^2,
+// with p_c, p_s the Chebyshev-economised polynomials of c3p_common.h (degree 8 in W, radius C3P_MM8_THETA = 1.85; the core +
+// border form takes the degree-6 pair below C3P_MM6_THETA).  Everything up to the chain product is REAL
+// D x D arithmetic: 7 real products (27 MFMAs each at D = 9) instead of 5 complex ones (75 each).
 // Real matrices live in registers as NB x NB tiles of 4x4 (lane (r,c) of the chain's block holds
 // M[4I+r][4J+c]); the left operand is read from a row-major LDS image (A layout: M[4I+c][4K+r]).
 // ---------------------------------------------------------------------------------------------
@@ -415,23 +407,6 @@ struct GMat {
   double s;
 };
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-// sum over the four lanes of a quad (the column index c), result in all four
-__device__ __forceinline__ double quad_sum(double v) {
-#if defined(C3P_SD_ABL) && (C3P_SD_ABL & 16)
-  return v * 4.0;  // TIMING-ONLY (wrong results): no quad reductions
-#endif
-  v += dpp_f64<0xB1>(v);  // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);  // quad_perm [2,3,0,1]
-  return v;
-}
-
 template <int NC>
 __device__ __forceinline__ void s8_zero(SMat<NC>& a) {
 #pragma unroll
@@ -443,14 +418,13 @@ __device__ __forceinline__ void s8_zero(SMat<NC>& a) {
   a.s = 0.0;
 }
 
-// Border sums on the matrix cores (round 6).  On gfx950 a wave's vector instructions and the fp64 matrix instructions of its
+// Border sums on the matrix cores.  On gfx950 a wave's vector instructions and the fp64 matrix instructions of its
 // SIMD do not overlap (tools/ubench_coissue.hip: 8 MFMAs + 32 v_mov_dpp take the SUM of their issue times), a quad reduction of a
 // double costs four v_mov_b32_dpp + two v_add_f64 = ~29 cycles, one v_mfma_f64_4x4x4_4b 16.7 -- and the instruction contracts over
 // the lane's r index for free.  So the partial products of a border are formed with the sum index ON r (for a symmetric left
 // operand: its transposed tile, the register the lane holds anyway, times the r form of the vector) and reduced by ONE matrix
 // instruction against a tile of ones: A = partials, B = 1 -> D[i][j] = sum_r t(r, c = i), i.e. the r form of the result in every lane,
-// with the rest of the border update (a.vr b.s + c.vr) riding in as the accumulator.  -DC3P_SD_QUADSUM builds the DPP reductions.
-#ifndef C3P_SD_QUADSUM
+// with the rest of the border update (a.vr b.s + c.vr) riding in as the accumulator.
 // C += A B for symmetric commuting A, B (upper core tiles, vr, s of C; s8_finish completes the operand form of C)
 template <int NC>
 __device__ __forceinline__ void mm_s8(const SMat<NC>& a, const SMat<NC>& b, SMat<NC>& c) {
@@ -517,85 +491,9 @@ __device__ __forceinline__ void mm_s8x2(const SMat<NC>& a, const SMat<NC>& b1, S
   c1.s = mfma4(cs1, 1.0, fma(a.s, b1.s, c1.s));
   c2.s = mfma4(cs2, 1.0, fma(a.s, b2.s, c2.s));
 }
-#else
-// C += A B for symmetric commuting A, B (upper core tiles, vr, s of C; s8_finish completes the operand form of C)
-template <int NC>
-__device__ __forceinline__ void mm_s8(const SMat<NC>& a, const SMat<NC>& b, SMat<NC>& c) {
-#pragma unroll
-  for (int K = 0; K < NC; ++K)
-#pragma unroll
-    for (int I = 0; I < NC; ++I)
-#pragma unroll
-      for (int J = I; J < NC; ++J) c.m[I][J] = mfma4(a.m[K][I], b.m[K][J], c.m[I][J]);
-  double t[NC], cs = 0.0;
-#pragma unroll
-  for (int I = 0; I < NC; ++I) {
-    t[I] = 0.0;
-#pragma unroll
-    for (int K = 0; K < NC; ++K) t[I] = fma(a.m[I][K], b.vc[K], t[I]);
-    cs = fma(a.vc[I], b.vc[I], cs);
-  }
-#pragma unroll
-  for (int I = 0; I < NC; ++I) c.vr[I] += fma(a.vr[I], b.s, quad_sum(t[I]));
-  c.s += fma(a.s, b.s, quad_sum(cs));
-#pragma unroll
-  for (int I = 0; I < NC; ++I)
-#pragma unroll
-    for (int J = I; J < NC; ++J) c.m[I][J] = fma(a.vr[I], b.vc[J], c.m[I][J]);
-}
-// two products with one left operand, interleaved (C1 += A B1, C2 += A B2)
-template <int NC>
-__device__ __forceinline__ void mm_s8x2(const SMat<NC>& a, const SMat<NC>& b1, SMat<NC>& c1, const SMat<NC>& b2, SMat<NC>& c2) {
-#pragma unroll
-  for (int K = 0; K < NC; ++K)
-#pragma unroll
-    for (int I = 0; I < NC; ++I)
-#pragma unroll
-      for (int J = I; J < NC; ++J) {
-        c1.m[I][J] = mfma4(a.m[K][I], b1.m[K][J], c1.m[I][J]);
-        c2.m[I][J] = mfma4(a.m[K][I], b2.m[K][J], c2.m[I][J]);
-      }
-  double t1[NC], t2[NC], cs1 = 0.0, cs2 = 0.0;
-#pragma unroll
-  for (int I = 0; I < NC; ++I) {
-    t1[I] = t2[I] = 0.0;
-#pragma unroll
-    for (int K = 0; K < NC; ++K) {
-      t1[I] = fma(a.m[I][K], b1.vc[K], t1[I]);
-      t2[I] = fma(a.m[I][K], b2.vc[K], t2[I]);
-    }
-    cs1 = fma(a.vc[I], b1.vc[I], cs1);
-    cs2 = fma(a.vc[I], b2.vc[I], cs2);
-  }
-#pragma unroll
-  for (int I = 0; I < NC; ++I) {
-    c1.vr[I] += fma(a.vr[I], b1.s, quad_sum(t1[I]));
-    c2.vr[I] += fma(a.vr[I], b2.s, quad_sum(t2[I]));
-  }
-  c1.s += fma(a.s, b1.s, quad_sum(cs1));
-  c2.s += fma(a.s, b2.s, quad_sum(cs2));
-#pragma unroll
-  for (int I = 0; I < NC; ++I)
-#pragma unroll
-    for (int J = I; J < NC; ++J) {
-      c1.m[I][J] = fma(a.vr[I], b1.vc[J], c1.m[I][J]);
-      c2.m[I][J] = fma(a.vr[I], b2.vc[J], c2.m[I][J]);
-    }
-}
-#endif
 // operand form of a product: lower core tiles by the in-chain lane swap, the c form of the border column
 template <int NC>
 __device__ __forceinline__ void s8_finish(SMat<NC>& a, int swap_lane, int tail_lane) {
-#if defined(C3P_SD_ABL) && (C3P_SD_ABL & 1)
-  // TIMING-ONLY (wrong results): no lane swaps in the symmetric stage
-#pragma unroll
-  for (int I = 1; I < NC; ++I)
-#pragma unroll
-    for (int J = 0; J < I; ++J) a.m[I][J] = a.m[J][I];
-#pragma unroll
-  for (int J = 0; J < NC; ++J) a.vc[J] = a.vr[J];
-  return;
-#endif
 #pragma unroll
   for (int I = 1; I < NC; ++I)
 #pragma unroll
@@ -617,7 +515,6 @@ __device__ __forceinline__ void s8_finish_vc(SMat<NC>& a, int tail_lane) {
 #pragma unroll
   for (int J = 0; J < NC; ++J) a.vc[J] = __shfl(a.vr[J], tail_lane);
 }
-#ifndef C3P_SD_QUADSUM
 // two products with one RIGHT operand, interleaved (C1 += A1 B, C2 += A2 B): A1, A2 in left-operand form
 template <int NC>
 __device__ __forceinline__ void mm_s8x2r(const SMat<NC>& a1, const SMat<NC>& a2, const SMat<NC>& b, SMat<NC>& c1, SMat<NC>& c2) {
@@ -657,7 +554,6 @@ __device__ __forceinline__ void mm_s8x2r(const SMat<NC>& a1, const SMat<NC>& a2,
   c1.s = mfma4(cs1, 1.0, fma(a1.s, b.s, c1.s));
   c2.s = mfma4(cs2, 1.0, fma(a2.s, b.s, c2.s));
 }
-#endif
 // out = c0 I + c1 W1 + c2 W2 (+ c3 W3), every part (operands are complete: the combination is too); ACCUM: only what a
 // product accumulates into (upper core tiles, vr, s) -- the initial value of an accumulation that s8_finish completes later
 template <int NC, bool WITH3, bool ACCUM = false>
@@ -688,7 +584,6 @@ __device__ __forceinline__ void s8_comb(SMat<NC>& out, double c0, double c1, dou
 // against ones (see mm_s8; the partial products use the TRANSPOSED tile of the symmetric left operand and the r form `cr` of the
 // state's column border, so the c form `cc` is not carried any more); the row border comes out of its matrix instructions already
 // replicated over r, because the A tile holds the border row of the left operand in EVERY row instead of row 0 alone.
-#ifndef C3P_SD_QUADSUM
 template <int NC>
 __device__ __forceinline__ void chain_step8(const SMat<NC>& Cc, const SMat<NC>& Sc, GMat<NC>& Ur, GMat<NC>& Ui, const LanePos& lp,
                                             int tail_lane, int row0_lane) {
@@ -781,111 +676,6 @@ __device__ __forceinline__ void chain_step8(const SMat<NC>& Cc, const SMat<NC>& 
   Ur.s = sr;
   Ui.s = si;
 }
-#else
-template <int NC>
-__device__ __forceinline__ void chain_step8(const SMat<NC>& Cc, const SMat<NC>& Sc, GMat<NC>& Ur, GMat<NC>& Ui, const LanePos& lp,
-                                            int tail_lane, int row0_lane) {
-  SMat<NC> Dm;
-  GMat<NC> Us;
-#pragma unroll
-  for (int I = 0; I < NC; ++I) {
-#pragma unroll
-    for (int J = 0; J < NC; ++J) {
-      Dm.m[I][J] = Cc.m[I][J] - Sc.m[I][J];
-      Us.m[I][J] = Ur.m[I][J] + Ui.m[I][J];
-    }
-    Dm.vr[I] = Cc.vr[I] - Sc.vr[I];
-    Dm.vc[I] = Cc.vc[I] - Sc.vc[I];
-    Us.cc[I] = Ur.cc[I] + Ui.cc[I];
-    Us.rc[I] = Ur.rc[I] + Ui.rc[I];
-  }
-  Dm.s = Cc.s - Sc.s;
-  Us.s = Ur.s + Ui.s;
-  double T1[NC][NC], T2[NC][NC], T3[NC][NC], R1[NC], R2[NC], R3[NC];
-  double aC[NC], aS[NC], aD[NC];
-#pragma unroll
-  for (int I = 0; I < NC; ++I) {
-#pragma unroll
-    for (int J = 0; J < NC; ++J) T1[I][J] = T2[I][J] = T3[I][J] = 0.0;
-    R1[I] = R2[I] = R3[I] = 0.0;
-    // A tile whose only row (i = 0: lanes c = 0) is the border row of the symmetric left operand
-    aC[I] = lp.c == 0 ? Cc.vr[I] : 0.0;
-    aS[I] = lp.c == 0 ? Sc.vr[I] : 0.0;
-    aD[I] = lp.c == 0 ? Dm.vr[I] : 0.0;
-  }
-#pragma unroll
-  for (int K = 0; K < NC; ++K) {
-#pragma unroll
-    for (int I = 0; I < NC; ++I)
-#pragma unroll
-      for (int J = 0; J < NC; ++J) {
-        T1[I][J] = mfma4(Cc.m[K][I], Ur.m[K][J], T1[I][J]);
-        T2[I][J] = mfma4(Sc.m[K][I], Ui.m[K][J], T2[I][J]);
-        T3[I][J] = mfma4(Dm.m[K][I], Us.m[K][J], T3[I][J]);
-      }
-#pragma unroll
-    for (int J = 0; J < NC; ++J) {
-      R1[J] = mfma4(aC[K], Ur.m[K][J], R1[J]);
-      R2[J] = mfma4(aS[K], Ui.m[K][J], R2[J]);
-      R3[J] = mfma4(aD[K], Us.m[K][J], R3[J]);
-    }
-  }
-  // column border and corner: partial sums over the lane's column index, reduced after the three products are combined
-  double pr[NC], pi[NC], cr_ = 0.0, ci_ = 0.0;
-#pragma unroll
-  for (int I = 0; I < NC; ++I) {
-    double p1 = 0.0, p2 = 0.0, p3 = 0.0;
-#pragma unroll
-    for (int K = 0; K < NC; ++K) {
-      p1 = fma(Cc.m[I][K], Ur.cc[K], p1);
-      p2 = fma(Sc.m[I][K], Ui.cc[K], p2);
-      p3 = fma(Dm.m[I][K], Us.cc[K], p3);
-    }
-    pr[I] = p1 + p2;
-    pi[I] = (p3 - p1) + p2;
-    const double c1 = Cc.vc[I] * Ur.cc[I], c2 = Sc.vc[I] * Ui.cc[I], c3 = Dm.vc[I] * Us.cc[I];
-    cr_ += c1 + c2;
-    ci_ += (c3 - c1) + c2;
-  }
-  const double e1 = Cc.s * Ur.s, e2 = Sc.s * Ui.s, e3 = Dm.s * Us.s;
-  const double sr = quad_sum(cr_) + (e1 + e2), si = quad_sum(ci_) + ((e3 - e1) + e2);
-  double colr[NC], coli[NC], rowr[NC], rowi[NC];
-#pragma unroll
-  for (int I = 0; I < NC; ++I) {
-    const double q1 = Cc.vr[I] * Ur.s, q2 = Sc.vr[I] * Ui.s, q3 = Dm.vr[I] * Us.s;
-    colr[I] = quad_sum(pr[I]) + (q1 + q2);
-    coli[I] = quad_sum(pi[I]) + ((q3 - q1) + q2);
-    // row border: the k = D-1 term on top of the matrix-core sums (lanes r = 0 hold the row)
-    const double r1 = fma(Cc.s, Ur.rc[I], R1[I]), r2 = fma(Sc.s, Ui.rc[I], R2[I]), r3 = fma(Dm.s, Us.rc[I], R3[I]);
-    rowr[I] = r1 + r2;
-    rowi[I] = (r3 - r1) + r2;
-  }
-#pragma unroll
-  for (int I = 0; I < NC; ++I)
-#pragma unroll
-    for (int J = 0; J < NC; ++J) {
-      const double t1 = fma(Cc.vr[I], Ur.rc[J], T1[I][J]), t2 = fma(Sc.vr[I], Ui.rc[J], T2[I][J]), t3 = fma(Dm.vr[I], Us.rc[J], T3[I][J]);
-      Ur.m[I][J] = t1 + t2;
-      Ui.m[I][J] = (t3 - t1) + t2;
-    }
-#pragma unroll
-  for (int I = 0; I < NC; ++I) {
-    Ur.cr[I] = colr[I];
-    Ui.cr[I] = coli[I];
-#if defined(C3P_SD_ABL) && (C3P_SD_ABL & 8)
-    Ur.cc[I] = colr[I], Ui.cc[I] = coli[I], Ur.rc[I] = rowr[I], Ui.rc[I] = rowi[I];  // TIMING-ONLY: no lane swaps in the chain step
-#else
-    Ur.cc[I] = __shfl(colr[I], tail_lane);
-    Ui.cc[I] = __shfl(coli[I], tail_lane);
-    Ur.rc[I] = __shfl(rowr[I], row0_lane);
-    Ui.rc[I] = __shfl(rowi[I], row0_lane);
-#endif
-  }
-  Ur.s = sr;
-  Ui.s = si;
-}
-
-#endif
 
 // q = 4 plan: degree 4r, s squarings, from a bound on ||X||_1
 __device__ __forceinline__ void plan_q4(double nrm, int& r, int& s) {
@@ -894,12 +684,7 @@ __device__ __forceinline__ void plan_q4(double nrm, int& r, int& s) {
   int best_r = 5, best_s = 0, best_cost = 1 << 30;
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
-    int si = 0;
-    double p = th[i];
-    while (p < nrm && si < 40) {
-      p *= 2.0;
-      ++si;
-    }
+    int si = c3p_squarings(nrm, th[i]);
     const int cost = i + si;
     if (cost < best_cost || (cost == best_cost && si <= best_s)) {
       best_cost = cost;
@@ -1297,27 +1082,10 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
     if (realH) {
       constexpr int NB = RD<D>::NB;
       typedef double RMat[NB][NB];
-      // Round 6: the 7-product variant of the padded-tile loop below evaluates the economised degree-8 pair (theta = 1.85,
-      // c3p_common.h) and serves every norm; -DC3P_SD_QUADSUM keeps round 5's Taylor variants (theta_16 = 0.816 / 1.13)
-#ifndef C3P_SD_QUADSUM
-#define C3P_SD_CA(j) c3p_mm8_cos[j]
-#define C3P_SD_SA(j) c3p_mm8_sinc[j]
-      constexpr double theta_real = C3P_MM8_THETA, theta_deg16 = C3P_MM8_THETA;
-#else
-#define C3P_SD_CA(j) (((j) & 1) ? -c3p_inv_fact[2 * (j)] : c3p_inv_fact[2 * (j)])
-#define C3P_SD_SA(j) (((j) & 1) ? -c3p_inv_fact[2 * (j) + 1] : c3p_inv_fact[2 * (j) + 1])
-      constexpr double theta_real = C3P_T18_THETA, theta_deg16 = 8.16e-1;
-#endif
-      int ps18 = 0;
-      {
-        double p = theta_real;
-        while (p < nrm && ps18 < 40) {
-          p *= 2.0;
-          ++ps18;
-        }
-      }
-      ps18 = __builtin_amdgcn_readfirstlane(ps18);
-      const double rscale = ldexp(1.0, -ps18);
+      // Both loops below evaluate the economised cos / sin pairs of c3p_common.h (Y is real symmetric, so the polynomial error on
+      // [0, theta^2] IS the matrix error), scaled against the radius of the degree-8 pair.
+      const int ps_r = __builtin_amdgcn_readfirstlane(c3p_squarings(nrm, C3P_MM8_THETA));
+      const double rscale = ldexp(1.0, -ps_r);
       const int swap_lane = 16 * lp.c + 4 * lp.b + lp.r;  // (r, c) <-> (c, r) inside the chain's block
       const int tail_lane = 16 * lp.c + 4 * lp.b;         // lane (c, 0): source of the rank-1 tail's row vector
       const int row0_lane = 4 * lp.b + lp.c;               // lane (0, c): row D-1 of a general right operand
@@ -1330,10 +1098,6 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
         yo[I] = (2 * (ok ? 4 * I + lp.r : 0) + 1) * W + lp.c;
         ymask[I] = ok ? 1.0 : 0.0;
       }
-      // theta_16 (unit roundoff 2^-52) = 0.816: below it the degree-16 / 17 polynomials are exact to roundoff and the
-      // shallower 7-product evaluation is used.  The variant is chosen per segment OUTSIDE the slice loop (the loop is
-      // instantiated twice) so that neither variant's registers burden the other's schedule.
-      const bool deg16 = __builtin_amdgcn_readfirstlane((int)(nrm * rscale <= theta_deg16)) != 0;
       if constexpr (SPLIT) {
         // ---- core + border form (D = 4 NC + 1; see SMat / GMat above): the same polynomial evaluation and chain step ----
         static_assert(!SPLIT || (D % 4 == 1 && D > 4 && !DUS), "core + border form: D = 5, 9 without slice output");
@@ -1348,32 +1112,16 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
           sco[I] = (2 * (4 * I + lp.c) + 1) * W + (D - 1);
         }
         constexpr int sso = (2 * (D - 1) + 1) * W + (D - 1);
-#ifndef C3P_SD_QUADSUM
-        // Round 6: the ECONOMISED polynomials of c3p_common.h (Y is real symmetric, so the polynomial error on [0, theta^2] IS the
-        // matrix error).  Scaling against theta_8 = 1.85; a scaled norm below theta_6 = 0.83 (cfg2: 0.81) takes the degree-6 pair:
-        // W, W^2, W^3, ONE paired Horner step in W^3, sin = (sin Y / Y) Y -- 6 products at dependency depth 5 (the degree-8 Taylor
-        // pair needed W^4: 7); above it the degree-8 pair with W^4 (7 products where the degree-9 / 8 Taylor pair, theta 1.13, took 8).
-        int ps_s = 0;
-        {
-          double p = C3P_MM8_THETA;
-          while (p < nrm && ps_s < 40) {
-            p *= 2.0;
-            ++ps_s;
-          }
-        }
-        ps_s = __builtin_amdgcn_readfirstlane(ps_s);
-        const double rscale_s = ldexp(1.0, -ps_s);
-        const bool small_var = __builtin_amdgcn_readfirstlane((int)(nrm * rscale_s <= C3P_MM6_THETA)) != 0;
-#else
-        const int ps_s = ps18;
-        const double rscale_s = rscale;
-        const bool small_var = deg16;
-#endif
-        auto split_loop = [&](auto deg16_tag) {
-          constexpr bool DEG16 = decltype(deg16_tag)::value;  // (round-6 build: true = the degree-6 pair, false = the degree-8 pair)
+        // A scaled norm below C3P_MM6_THETA (cfg2: 0.81) takes the degree-6 pair: W, W^2, W^3, ONE paired Horner step in W^3,
+        // sin = (sin Y / Y) Y -- 6 products at dependency depth 5; above it the degree-8 pair with W^4 (7 products).  The form is
+        // chosen per segment OUTSIDE the slice loop (the loop is instantiated twice) so that neither form's registers burden the
+        // other's schedule.
+        const bool deg6 = __builtin_amdgcn_readfirstlane((int)(nrm * rscale <= C3P_MM6_THETA)) != 0;
+        auto split_loop = [&](auto deg6_tag) {
+          constexpr bool DEG6 = decltype(deg6_tag)::value;  // true = the degree-6 pair, false = the degree-8 pair
           for (int t = 0; t < tmax; ++t) {
             const bool act = valid && t < len;
-            const double sc = act ? rscale_s : 0.0;
+            const double sc = act ? rscale : 0.0;
             const double muw = act ? 1.0 : 0.0;
             double mu_r = muw * tab[MAT + 0], mu_i = muw * tab[MAT + 1];
             SM Y;
@@ -1409,52 +1157,10 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
             s8_finish(W1, swap_lane, tail_lane);
             mm_s8(W1, W1, W2);  // W^2
             s8_finish(W2, swap_lane, tail_lane);
-#ifdef C3P_SD_QUADSUM
-            if constexpr (DEG16) {
-              SM W4;
-              s8_zero(W4);
-              mm_s8(W1, W2, W3);
-              mm_s8(W2, W2, W4);
-              s8_finish(W3, swap_lane, tail_lane);
-              s8_finish(W4, swap_lane, tail_lane);
-              s8_comb<NC, true>(acc, c3p_inv_fact[8], -c3p_inv_fact[10], c3p_inv_fact[12], -c3p_inv_fact[14], W1, W2, W3, lp);
-              s8_comb<NC, true>(acs, c3p_inv_fact[9], -c3p_inv_fact[11], c3p_inv_fact[13], -c3p_inv_fact[15], W1, W2, W3, lp);
-#pragma unroll
-              for (int I = 0; I < NC; ++I) {
-#pragma unroll
-                for (int J = 0; J < NC; ++J) {
-                  acc.m[I][J] = fma(c3p_inv_fact[16], W4.m[I][J], acc.m[I][J]);
-                  acs.m[I][J] = fma(c3p_inv_fact[17], W4.m[I][J], acs.m[I][J]);
-                }
-                acc.vr[I] = fma(c3p_inv_fact[16], W4.vr[I], acc.vr[I]);
-                acs.vr[I] = fma(c3p_inv_fact[17], W4.vr[I], acs.vr[I]);
-                acc.vc[I] = fma(c3p_inv_fact[16], W4.vc[I], acc.vc[I]);
-                acs.vc[I] = fma(c3p_inv_fact[17], W4.vc[I], acs.vc[I]);
-              }
-              acc.s = fma(c3p_inv_fact[16], W4.s, acc.s);
-              acs.s = fma(c3p_inv_fact[17], W4.s, acs.s);
-              s8_comb<NC, true, true>(Cm, 1.0, -c3p_inv_fact[2], c3p_inv_fact[4], -c3p_inv_fact[6], W1, W2, W3, lp);
-              s8_comb<NC, true, true>(Sp, 1.0, -c3p_inv_fact[3], c3p_inv_fact[5], -c3p_inv_fact[7], W1, W2, W3, lp);
-              mm_s8x2(W4, acc, Cm, acs, Sp);  // Cm = cos Y, Sp = sin(Y) / Y
-            } else {
-              mm_s8(W1, W2, W3);  // W^3
-              s8_finish(W3, swap_lane, tail_lane);
-              s8_comb<NC, true>(Cm, c3p_inv_fact[12], -c3p_inv_fact[14], c3p_inv_fact[16], -c3p_inv_fact[18], W1, W2, W3, lp);
-              s8_comb<NC, false>(Sp, c3p_inv_fact[13], -c3p_inv_fact[15], c3p_inv_fact[17], 0.0, W1, W2, W3, lp);
-              s8_comb<NC, false, true>(acc, -c3p_inv_fact[6], c3p_inv_fact[8], -c3p_inv_fact[10], 0.0, W1, W2, W3, lp);
-              s8_comb<NC, false, true>(acs, -c3p_inv_fact[7], c3p_inv_fact[9], -c3p_inv_fact[11], 0.0, W1, W2, W3, lp);
-              mm_s8x2(W3, Cm, acc, Sp, acs);
-              s8_finish(acc, swap_lane, tail_lane);
-              s8_finish(acs, swap_lane, tail_lane);
-              s8_comb<NC, false, true>(Cm, 1.0, -c3p_inv_fact[2], c3p_inv_fact[4], 0.0, W1, W2, W3, lp);
-              s8_comb<NC, false, true>(Sp, 1.0, -c3p_inv_fact[3], c3p_inv_fact[5], 0.0, W1, W2, W3, lp);
-              mm_s8x2(W3, acc, Cm, acs, Sp);  // Cm = cos Y, Sp = sin(Y) / Y
-            }
-#else
             // The Horner factors are the LEFT operands of the paired product (everything commutes): they are combined on the 6
             // registers a product accumulates into (upper core tiles, r-form border, corner) and completed by ONE lane swap each;
             // the shared right operand (W^3 / W^4) is completed in full; a power that is never a product operand is not completed.
-            if constexpr (DEG16) {
+            if constexpr (DEG6) {
               // degree 6: cos = (c0 + c1 W + c2 W^2) + W^3 (c3 + c4 W + c5 W^2 + c6 W^3)
               mm_s8(W1, W2, W3);
               s8_finish(W3, swap_lane, tail_lane);
@@ -1492,14 +1198,6 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
               s8_comb<NC, true, true>(Sp, c3p_mm8_sinc[0], c3p_mm8_sinc[1], c3p_mm8_sinc[2], c3p_mm8_sinc[3], W1, W2, W3, lp);
               mm_s8x2r(acc, acs, W4, Cm, Sp);  // Cm = cos Y, Sp = sin(Y) / Y
             }
-#endif
-#ifdef C3P_SD_QUADSUM
-            s8_finish(Cm, swap_lane, tail_lane);
-            s8_finish(Sp, swap_lane, tail_lane);
-            s8_zero(acc);
-            mm_s8(Y, Sp, acc);  // acc = sin Y
-            s8_finish(acc, swap_lane, tail_lane);
-#else
             // cos Y, sin Y / Y and sin Y are LEFT operands from here on (sin Y = (sin Y / Y) Y, the chain step): lower tiles only;
             // their c-form borders are only fetched for the squarings and the first slice of a segment
             s8_finish_lower(Cm, swap_lane);
@@ -1507,13 +1205,12 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
             s8_zero(acc);
             mm_s8(Sp, Y, acc);  // acc = sin Y
             s8_finish_lower(acc, swap_lane);
-            if (ps_s > 0 || t == 0) {
+            if (ps_r > 0 || t == 0) {
               s8_finish_vc(Cm, tail_lane);
               s8_finish_vc(acc, tail_lane);
             }
-#endif
             // squarings: cos 2Y = (C - S)(C + S), sin 2Y = 2 S C
-            for (int it = 0; it < ps_s; ++it) {
+            for (int it = 0; it < ps_r; ++it) {
               SM Dm, Sm, C2, SC;
 #pragma unroll
               for (int I = 0; I < NC; ++I) {
@@ -1563,25 +1260,13 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
               mus_r = mu_r;
               mus_i = c3p_phase_add(0.0, mu_i);
             } else {
-#if defined(C3P_SD_ABL) && (C3P_SD_ABL & 2)
-              // TIMING-ONLY (wrong results): no chain product
-#pragma unroll
-              for (int I = 0; I < NC; ++I) {
-#pragma unroll
-                for (int J = 0; J < NC; ++J) Gr.m[I][J] += Cm.m[I][J], Gi.m[I][J] -= acc.m[I][J];
-                Gr.cr[I] += Cm.vr[I], Gr.cc[I] += Cm.vc[I], Gr.rc[I] += Cm.vc[I];
-                Gi.cr[I] -= acc.vr[I], Gi.cc[I] -= acc.vc[I], Gi.rc[I] -= acc.vc[I];
-              }
-              Gr.s += Cm.s, Gi.s -= acc.s;
-#else
               chain_step8(Cm, acc, Gr, Gi, lp, tail_lane, row0_lane);
-#endif
               mus_r += mu_r;
               mus_i = c3p_phase_add(mus_i, mu_i);
             }
           }
         };
-        if (small_var)
+        if (deg6)
           split_loop(std::true_type{});
         else
           split_loop(std::false_type{});
@@ -1617,8 +1302,6 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
           for (int J = 0; J < NJ; ++J) U[I][J] = img[woff + I * 4 * W + J * 4];
         wave_sync();
       } else {
-      auto real_loop = [&](auto deg16_tag) {
-      constexpr bool DEG16 = decltype(deg16_tag)::value;
       for (int t = 0; t < tmax; ++t) {
         // (Two waves share a SIMD and the arbiter serves the OLDER one first: wave w finishes its segment at ~64 % of the
         // kernel time and wave w + 4 then runs alone -- wall_clock64 probes, -DC3P_SD_TIMING.  Alternating s_setprio per
@@ -1658,46 +1341,30 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
         sym_fill<D>(W1, swap_lane);
         mm_sym<D>(W1, W1, W2, tail_lane);  // W^2
         sym_fill<D>(W2, swap_lane);
-        if constexpr (DEG16) {
-          // cos to W^8, sin/Y to W^8 (Taylor degree 16 / 17), Paterson-Stockmeyer with q = 4: W^3 = W W^2 and
-          // W^4 = W^2 W^2 are independent, then ONE paired Horner step  P = B0 + W^4 (B1 + c8 W^4):
-          // 7 products, dependency depth 5 (Y^2, W^2, {W^3, W^4}, {cos, sin/Y}, sin) instead of 8 and 7.
-          RMat W4;
+        // the degree-8 pair (c3p_mm8_cos / c3p_mm8_sinc), Paterson-Stockmeyer with q = 4: W^3 = W W^2 and W^4 = W^2 W^2 are
+        // independent, then ONE paired Horner step  P = B0 + W^4 (B1 + c8 W^4): 7 products, dependency depth 5
+        // (Y^2, W^2, {W^3, W^4}, {cos, sin/Y}, sin)
+        RMat W4;
 #pragma unroll
-          for (int I = 0; I < NB; ++I)
+        for (int I = 0; I < NB; ++I)
 #pragma unroll
-            for (int J = 0; J < NB; ++J) W4[I][J] = 0.0;
-          mm_sym<D>(W1, W2, W3, tail_lane);
-          mm_sym<D>(W2, W2, W4, tail_lane);
-          sym_fill<D>(W3, swap_lane);
-          sym_fill<D>(W4, swap_lane);
-          rcomb<D, true>(acc, C3P_SD_CA(4), C3P_SD_CA(5), C3P_SD_CA(6), C3P_SD_CA(7), W1, W2, W3, lp);
-          rcomb<D, true>(acs, C3P_SD_SA(4), C3P_SD_SA(5), C3P_SD_SA(6), C3P_SD_SA(7), W1, W2, W3, lp);
-#pragma unroll
-          for (int I = 0; I < NB; ++I)
-#pragma unroll
-            for (int J = sym_j0<D>(I); J < NB; ++J) {
-              acc[I][J] = fma(C3P_SD_CA(8), W4[I][J], acc[I][J]);
-              acs[I][J] = fma(C3P_SD_SA(8), W4[I][J], acs[I][J]);
-            }
-          rcomb<D, true, true>(Cm, C3P_SD_CA(0), C3P_SD_CA(1), C3P_SD_CA(2), C3P_SD_CA(3), W1, W2, W3, lp);
-          rcomb<D, true, true>(Sp, C3P_SD_SA(0), C3P_SD_SA(1), C3P_SD_SA(2), C3P_SD_SA(3), W1, W2, W3, lp);
-          mm_sym2<D>(W4, acc, Cm, acs, Sp, tail_lane);  // Cm = cos Y, Sp = sin(Y) / Y
-        } else {
-        mm_sym<D>(W1, W2, W3, tail_lane);  // W^3
+          for (int J = 0; J < NB; ++J) W4[I][J] = 0.0;
+        mm_sym<D>(W1, W2, W3, tail_lane);
+        mm_sym<D>(W2, W2, W4, tail_lane);
         sym_fill<D>(W3, swap_lane);
-        // cos: c_j = (-1)^j / (2j)!;  sin / Y: s_j = (-1)^j / (2j+1)!;  both by Horner in W^3, interleaved
-        rcomb<D, true>(Cm, c3p_inv_fact[12], -c3p_inv_fact[14], c3p_inv_fact[16], -c3p_inv_fact[18], W1, W2, W3, lp);
-        rcomb<D, false>(Sp, c3p_inv_fact[13], -c3p_inv_fact[15], c3p_inv_fact[17], 0.0, W1, W2, W3, lp);
-        rcomb<D, false, true>(acc, -c3p_inv_fact[6], c3p_inv_fact[8], -c3p_inv_fact[10], 0.0, W1, W2, W3, lp);
-        rcomb<D, false, true>(acs, -c3p_inv_fact[7], c3p_inv_fact[9], -c3p_inv_fact[11], 0.0, W1, W2, W3, lp);
-        mm_sym2<D>(W3, Cm, acc, Sp, acs, tail_lane);
-        sym_fill<D>(acc, swap_lane);
-        sym_fill<D>(acs, swap_lane);
-        rcomb<D, false, true>(Cm, 1.0, -c3p_inv_fact[2], c3p_inv_fact[4], 0.0, W1, W2, W3, lp);
-        rcomb<D, false, true>(Sp, 1.0, -c3p_inv_fact[3], c3p_inv_fact[5], 0.0, W1, W2, W3, lp);
-        mm_sym2<D>(W3, acc, Cm, acs, Sp, tail_lane);  // Cm = cos Y, Sp = sin(Y) / Y
-        }
+        sym_fill<D>(W4, swap_lane);
+        rcomb<D, true>(acc, c3p_mm8_cos[4], c3p_mm8_cos[5], c3p_mm8_cos[6], c3p_mm8_cos[7], W1, W2, W3, lp);
+        rcomb<D, true>(acs, c3p_mm8_sinc[4], c3p_mm8_sinc[5], c3p_mm8_sinc[6], c3p_mm8_sinc[7], W1, W2, W3, lp);
+#pragma unroll
+        for (int I = 0; I < NB; ++I)
+#pragma unroll
+          for (int J = sym_j0<D>(I); J < NB; ++J) {
+            acc[I][J] = fma(c3p_mm8_cos[8], W4[I][J], acc[I][J]);
+            acs[I][J] = fma(c3p_mm8_sinc[8], W4[I][J], acs[I][J]);
+          }
+        rcomb<D, true, true>(Cm, c3p_mm8_cos[0], c3p_mm8_cos[1], c3p_mm8_cos[2], c3p_mm8_cos[3], W1, W2, W3, lp);
+        rcomb<D, true, true>(Sp, c3p_mm8_sinc[0], c3p_mm8_sinc[1], c3p_mm8_sinc[2], c3p_mm8_sinc[3], W1, W2, W3, lp);
+        mm_sym2<D>(W4, acc, Cm, acs, Sp, tail_lane);  // Cm = cos Y, Sp = sin(Y) / Y
         sym_fill<D>(Cm, swap_lane);
         sym_fill<D>(Sp, swap_lane);
 #pragma unroll
@@ -1708,7 +1375,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
         sym_fill<D>(acc, swap_lane);
         // ---- E = cos Y - i sin Y (Cm, acc) ; squarings in real form.  C and S are polynomials in Y and commute:
         //      cos 2Y = C^2 - S^2 = (C - S)(C + S) (ONE product, symmetric result), sin 2Y = 2 S C ----
-        for (int it = 0; it < ps18; ++it) {
+        for (int it = 0; it < ps_r; ++it) {
           RMat Dm, Sm, C2, SC;
 #pragma unroll
           for (int I = 0; I < NB; ++I)
@@ -1789,11 +1456,6 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
           mus_i = c3p_phase_add(mus_i, mu_i);
         }
       }
-      };
-      if (deg16)
-        real_loop(std::true_type{});
-      else
-        real_loop(std::false_type{});
       // back to the complex half-image layout of the epilogue (once per segment, through the chain's image)
       wave_sync();
 #pragma unroll
@@ -2412,19 +2074,8 @@ __device__ __forceinline__ void mat_zero(double (&m)[SD<D>::NBI][SD<D>::NJ]) {
 }
 
 // squarings of the real-Hamiltonian backward sweep (smalld_grad_real_kernel below): the economised degree-8 cos / sin pair of
-// c3p_common.h (round 6: theta = 1.85 on the product structure of the degree-8 Taylor pair, theta_16 = 0.816)
+// c3p_common.h (radius C3P_MM8_THETA)
 constexpr int SDG_MAXS = 3;
-
-template <int D>
-__device__ __forceinline__ int sdg_real_squarings(double nrm) {
-  int ps = 0;
-  double p = C3P_MM8_THETA;
-  while (p < nrm && ps < 40) {
-    p *= 2.0;
-    ++ps;
-  }
-  return ps;
-}
 
 template <int D>
 __global__ void __launch_bounds__(64, 1) smalld_grad_kernel(SmallGradArgs A) {
@@ -2481,19 +2132,12 @@ __global__ void __launch_bounds__(64, 1) smalld_grad_kernel(SmallGradArgs A) {
   nrm = fmax(nrm, __shfl_xor(nrm, 4));
   nrm = fmax(nrm, __shfl_xor(nrm, 8));
   nrm = readfirstlane_f64(nrm);
-  int ps = 0;
-  {
-    double p = C3P_T18_THETA;
-    while (p < nrm && ps < 40) {
-      p *= 2.0;
-      ++ps;
-    }
-  }
+  int ps = c3p_squarings(nrm, C3P_T18_THETA);
   ps = __builtin_amdgcn_readfirstlane(ps);
   if (A.skip_real) {  // the real-Hamiltonian sweep has taken this wave's chains (same tables, same norm bound: same decision)
     bool realH = true;
     for (int k = 0; k <= K; ++k) realH = realH && (tab[k * (MAT + 4) + MAT + 3] == 0.0);
-    if (__builtin_amdgcn_readfirstlane((int)realH) != 0 && __builtin_amdgcn_readfirstlane(sdg_real_squarings<D>(nrm)) <= SDG_MAXS)
+    if (__builtin_amdgcn_readfirstlane((int)realH) != 0 && __builtin_amdgcn_readfirstlane(c3p_squarings(nrm, C3P_MM8_THETA)) <= SDG_MAXS)
       return;
   }
   const double scale = ldexp(1.0, -ps);
@@ -2732,14 +2376,7 @@ __global__ void __launch_bounds__(64, 1) smalld_grad_general_kernel(SmallGradArg
   nrm = fmax(nrm, __shfl_xor(nrm, 4));
   nrm = fmax(nrm, __shfl_xor(nrm, 8));
   nrm = readfirstlane_f64(nrm);
-  int ps = 0;
-  {
-    double p = C3P_T18_THETA;
-    while (p < nrm && ps < 40) {
-      p *= 2.0;
-      ++ps;
-    }
-  }
+  int ps = c3p_squarings(nrm, C3P_T18_THETA);
   ps = __builtin_amdgcn_readfirstlane(ps);
   const double scale = ldexp(1.0, -ps);
   __syncthreads();
@@ -2992,8 +2629,8 @@ __global__ void __launch_bounds__(64, 1) smalld_grad_general_kernel(SmallGradArg
 //   (two upper-triangle products whose left operands come from registers, as in the forward kernel);
 //   grad[k, n] = scale <Y_bar, Y_k> + Re(mu_k conj(tr N));   N <- R conj(dU)  (the only product with a general LEFT operand:
 //   R goes through a real LDS image).
-// ~600 MFMAs per slice at D = 9 against ~1500 of the complex pair evaluation.  Always the degree-16 / 17 polynomials
-// (theta_16 = 0.816) with up to SDG_MAXS squarings; samples that are not real, or need more squarings, are left to the
+// ~600 MFMAs per slice at D = 9 against ~1500 of the complex pair evaluation.  Always the economised degree-8 cos / sin pair
+// (radius C3P_MM8_THETA) with up to SDG_MAXS squarings; samples that are not real, or need more squarings, are left to the
 // complex kernel (same norm bound, same decision).
 // ---------------------------------------------------------------------------------------------
 template <int D>
@@ -3048,7 +2685,7 @@ __global__ void __launch_bounds__(64, 1) smalld_grad_real_kernel(SmallGradArgs A
   for (int k = 0; k <= K; ++k) realH = realH && (tab[k * (MAT + 4) + MAT + 3] == 0.0);
   // (without per-sample tables the four chains of a wave may belong to different samples, but then all samples share
   // the tables; with per-sample tables S % 4 == 0 and the wave has one sample)
-  const int ps = __builtin_amdgcn_readfirstlane(sdg_real_squarings<D>(nrm));
+  const int ps = __builtin_amdgcn_readfirstlane(c3p_squarings(nrm, C3P_MM8_THETA));
   if (!(__builtin_amdgcn_readfirstlane((int)realH) != 0) || ps > SDG_MAXS) return;
   const double scale = ldexp(1.0, -ps);
   __syncthreads();

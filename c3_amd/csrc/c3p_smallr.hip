@@ -194,23 +194,11 @@ __global__ void __launch_bounds__(64) smallr_chain_kernel(SmallRArgs A) {
   // round 6: economised T18 parameters (radius 2.0) while the generator is skew-symmetric up to a small symmetric part
   const int econ = __builtin_amdgcn_readfirstlane((int)(nsym <= C3P_T18N_MAX_NONNORMAL && !(A.no_t18n & 1)));
   const double* tc = c3p_t18_tab[econ];
-  int ps = 0;
-  {
-    double pth = econ ? C3P_T18N_THETA : C3P_T18_THETA;
-    while (pth < nrm && ps < 40) {
-      pth *= 2.0;
-      ++ps;
-    }
-  }
+  int ps = c3p_squarings(nrm, econ ? C3P_T18N_THETA : C3P_T18_THETA);
   // ... or the four-product scheme for normal generators (c3p_common.h: c3p_e4n, radius 1.35) where it saves a product
   int e4 = 0;
   if (econ && !(A.no_t18n & 2)) {
-    int s4 = 0;
-    double pth = C3P_E4N_THETA;
-    while (pth < nrm && s4 < 40) {
-      pth *= 2.0;
-      ++s4;
-    }
+    int s4 = c3p_squarings(nrm, C3P_E4N_THETA);
     if (4 + s4 < 5 + ps) e4 = 1, ps = s4;
   }
   e4 = __builtin_amdgcn_readfirstlane(e4);
@@ -651,14 +639,7 @@ __global__ void __launch_bounds__(64, (DM <= 9 ? 2 : 1)) smallr_grad_kernel(Smal
   nsym = fmax(nsym, __shfl_xor(nsym, 8));
   const int econ = __builtin_amdgcn_readfirstlane((int)(nsym <= C3P_T18N_MAX_NONNORMAL && !(A.no_t18n & 1)));  // as in the forward kernel
   const double* tc = c3p_t18_tab[econ];
-  int ps = 0;
-  {
-    double pth = econ ? C3P_T18N_THETA : C3P_T18_THETA;
-    while (pth < nrm && ps < 40) {
-      pth *= 2.0;
-      ++ps;
-    }
-  }
+  int ps = c3p_squarings(nrm, econ ? C3P_T18N_THETA : C3P_T18_THETA);
   ps = __builtin_amdgcn_readfirstlane(ps);
   const double scale = ldexp(1.0, -ps);
 

@@ -210,10 +210,10 @@ def test_lindblad_vjp_hermitian_basis_strong_dissipation_and_long_chain(prop):
 
 
 @pytest.mark.parametrize("D,B,N,amp,mw", [
-    (9, 256, 96, 1.0, True),     # cfg2's shape: workgroup per sample, degree-16 variant
+    (9, 256, 96, 1.0, True),     # cfg2's shape: workgroup per sample, degree-6 pair
     (9, 8, 250, 1.0, True),      # uneven segments (eight waves per sample)
     (9, 7, 37, 1.0, False),      # one-wave workgroups + ticket, ragged chains (7 x S not a multiple of four)
-    (9, 5, 40, 2.6, False),      # stronger drive: degree-18 variant
+    (9, 5, 40, 2.6, False),      # stronger drive: scaled norm above the degree-6 radius
     (9, 4, 30, 14.0, False),     # squarings
     (5, 6, 64, 1.0, True),       # 4 + 1
     (5, 3, 21, 9.0, False),

@@ -195,7 +195,7 @@ def _sym(rng, D, s=1.0):
 @pytest.mark.parametrize("D", [25, 26, 27, 28])
 @pytest.mark.parametrize("amp,K", [(0.3, 2), (1.0, 3), (1.4, 2), (3.0, 4), (9.0, 5)])
 def test_pinwheel_class_forward_matches_oracle(prop, D, amp, K):
-    """All three polynomial variants, 0..3 squarings, the six-image plan (degree 20, no squaring), control lines beyond the
+    """The single polynomial form of the real instance (economised degree-8 pair) with 0..3 squarings, control lines beyond the
     three whose tables stay in registers, slice propagators, frame-rotation row phases; N = 37 slices in 1..3 segments."""
     rng = np.random.default_rng(100 * D + K)
     h0 = _sym(rng, D, amp * 1e10)

@@ -57,7 +57,7 @@ def test_launch_log_names_the_headline_kernel(prop):
 @pytest.mark.parametrize("squarings", [0, 1, 3])
 def test_border_sums_on_the_matrix_cores_all_variants(prop, D, squarings):
     """round 6's form of the core + border loop (reductions against a tile of ones, chain step without lane swaps, Horner factors as
-    left operands) against the oracle: both polynomial variants (norm below / above theta_16), squarings (the c-form borders are
+    left operands) against the oracle: both polynomial forms (the degree-6 pair for a scaled norm below 0.83, the degree-8 pair above), squarings (the c-form borders are
     only fetched there and on the first slice), workgroup-per-sample and one-wave workgroups, frame-rotation phases."""
     import torch
 
@@ -67,7 +67,7 @@ def test_border_sums_on_the_matrix_cores_all_variants(prop, D, squarings):
     rng = np.random.default_rng(600 + D + squarings)
     herm = lambda s: (lambda m: s * (m + m.T) / 2)(rng.normal(size=(D, D))).astype(np.complex128)
     K, N = 2, 96
-    for B, scale in ((64, 0.25), (3, 0.25), (64, 0.42)):  # MW / one-wave workgroups; degree-16 and degree-18 variants
+    for B, scale in ((64, 0.25), (3, 0.25), (64, 0.42)):  # MW / one-wave workgroups; a weaker and a stronger drive
         h0 = np.diag(rng.uniform(0, 1, D)).astype(np.complex128) + herm(0.02)
         hks = np.stack([herm(0.3) for _ in range(K)])
         sig = rng.uniform(-1, 1, size=(B, K, N))
