@@ -21,7 +21,7 @@ FORCE_GENERIC = 0x8
 SEQ_SUPEROP = 0x20  # c3p_seq_chain population mode: the table holds superoperators (population = |x[0]|)
 HERMITIAN_H = 0x10  # c3p_pwc_lindblad: the caller declares h0 / hks Hermitian (D = 2, 3: real arithmetic in the Hermitian basis)
 
-KERNEL_NAMES = {0: "none", 1: "generic_lds", 2: "generic_global", 3: "smalld", 4: "mfma", 5: "ode_wg", 6: "ode_row", 7: "ode_mfma", 8: "ode_row_or_wg", 9: "seq", 10: "seq_vjp"}
+KERNEL_NAMES = {0: "none", 1: "generic_lds", 2: "generic_global", 3: "smalld", 4: "mfma", 5: "ode_wg", 6: "ode_row", 7: "ode_mfma", 8: "ode_row_or_wg", 9: "seq", 10: "seq_vjp", 11: "ode_vjp"}
 
 SOLVERS = {"rk4": 0, "rk38": 1, "rk5": 2, "tsit5": 3}
 STEPS = {"schrodinger": 0, "von_neumann": 1, "lindblad": 2}
@@ -65,6 +65,7 @@ SIGNATURES = {
     "c3p_seq_chain": (_i, [_vp, _i64, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "c3p_seq_chain_vjp": (_i, [_vp, _i64, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "c3p_ode_solve": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _i, _i, _i, _i, _i, _vp, _i64, _i, _i, _vp, _vp]),
+    "c3p_ode_solve_vjp": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

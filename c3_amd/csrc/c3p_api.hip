@@ -28,6 +28,7 @@
 #include "c3p_grad.h"
 #include "c3p_seq.h"
 #include "c3p_seq_vjp.h"
+#include "c3p_ode_vjp.h"
 
 namespace {
 
@@ -95,7 +96,7 @@ int fail(const char* fmt, ...) {
   } while (0)
 
 // Per-device workspace slots, grown lazily, freed by c3p_shutdown().
-enum Slot { SL_SEG_A = 0, SL_SEG_B, SL_SCRATCH, SL_CLP, SL_TABLES, SL_COUNTERS, SL_COUNTERS2, SL_IN0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_SEG_F, SL_SEQ_FLAG, SL_SEQ_VJP_WS, SL_SEQ_VJP_SLAB, SL_COUNT };
+enum Slot { SL_SEG_A = 0, SL_SEG_B, SL_SCRATCH, SL_CLP, SL_TABLES, SL_COUNTERS, SL_COUNTERS2, SL_IN0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_SEG_F, SL_SEQ_FLAG, SL_SEQ_VJP_WS, SL_SEQ_VJP_SLAB, SL_ODE_VJP_WS, SL_COUNT };
 
 struct DeviceWs {
   std::mutex mu;  // one lock per device: calls on different GPUs of one process do not serialise
@@ -2652,6 +2653,102 @@ int c3p_ode_solve(const void* h0, const void* hks, const double* signals, const 
     a.scratch_stride = (long)elems;
   }
   LAUNCH_TRY(c3p_launch_ode(a, global, st));
+  if (flags & C3P_HOST_PTRS) return sg.finish();
+  return 0;
+}
+
+int c3p_ode_solve_vjp(const void* h0, const void* hks, const double* signals, const void* col_ops, int C, double dt, int B, int K,
+                      int N, int D, int solver, int step, const void* init, int64_t init_bstride, const void* states_bar,
+                      int bar_all, const void* target, int64_t target_bstride, int flags, double* grad_signals, void* init_bar,
+                      double* infid_out, void* final_out, void* stream) {
+  if (B < 0 || N < 0 || D <= 0 || K < 0 || K > 32) return fail("bad sizes B=%d K=%d N=%d D=%d", B, K, N, D);
+  if (solver < 0 || solver > 3) return fail("unknown solver id %d", solver);
+  if (step < 0 || step > 2) return fail("unknown step function id %d", step);
+  if (B == 0) return 0;
+  if ((states_bar != nullptr) == (target != nullptr)) return fail("exactly one of states_bar and target must be given");
+  if (target && bar_all) return fail("bar_all needs states_bar");
+  if (init_bstride < 0 || target_bstride < 0) return fail("negative stride");
+  if (N < 2) return fail("the ODE solver needs at least two time samples (N=%d)", N);
+  if (!h0 || !init) return fail("NULL pointer argument");
+  if (K > 0 && (!hks || !signals || !grad_signals)) return fail("K > 0 but hks/signals/grad_signals missing");
+  if (step == C3P_STEP_LINDBLAD && (!col_ops || C <= 0)) return fail("lindblad step needs col_ops");
+  if (step != C3P_STEP_LINDBLAD) C = 0;
+  const int M = (step == C3P_STEP_SCHRODINGER) ? 1 : D;
+  const size_t cs = sizeof(cplx);
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  DeviceWs* w = lk.w;
+  if (!w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  Stage sg{w, st};
+  const void *d_h0 = h0, *d_hks = hks, *d_sig = signals, *d_col = col_ops, *d_init = init, *d_bar = states_bar, *d_tgt = target;
+  void *d_grad = grad_signals, *d_ib = init_bar, *d_inf = infid_out, *d_fin = final_out;
+  const size_t state_bytes = (size_t)B * D * M * cs;
+  if (flags & C3P_HOST_PTRS) {
+    const size_t init_elems = init_bstride ? (size_t)(B - 1) * init_bstride + (size_t)D * M : (size_t)D * M;
+    const size_t tgt_elems = target_bstride ? (size_t)(B - 1) * target_bstride + (size_t)D : (size_t)D;
+    if (sg.in(h0, (size_t)D * D * cs, &d_h0)) return -1;
+    if (sg.in(hks, (size_t)K * D * D * cs, &d_hks)) return -1;
+    if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
+    if (sg.in(col_ops, (size_t)C * D * D * cs, &d_col)) return -1;
+    if (sg.in(init, init_elems * cs, &d_init)) return -1;
+    if (states_bar && sg.in(states_bar, state_bytes * (bar_all ? (size_t)N : 1), &d_bar)) return -1;
+    if (target && sg.in(target, tgt_elems * cs, &d_tgt)) return -1;
+    if (sg.out(grad_signals, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
+    if (sg.out(init_bar, state_bytes, &d_ib)) return -1;
+    if (sg.out(infid_out, (size_t)B * sizeof(double), &d_inf)) return -1;
+    if (sg.out(final_out, state_bytes, &d_fin)) return -1;
+  }
+  const OdeVjpPlan pl = c3p_ode_vjp_plan(B, K, N, D, M, C, step);
+  OdeVjpArgs v = {};
+  v.f.h0 = (const cplx*)d_h0;
+  v.f.hks = (const cplx*)d_hks;
+  v.f.signals = (const double*)d_sig;
+  v.f.col_ops = (const cplx*)d_col;
+  v.f.init = (const cplx*)d_init;
+  v.f.init_bstride = init_bstride;
+  v.f.dt = dt;
+  v.f.B = B;
+  v.f.K = K;
+  v.f.N = N;
+  v.f.D = D;
+  v.f.M = M;
+  v.f.C = C;
+  v.f.solver = solver;
+  v.f.step = step;
+  v.f.n_steps = N;
+  v.f.u_stride = 1;
+  v.states_bar = (const cplx*)d_bar;
+  v.bar_all = bar_all ? 1 : 0;
+  v.target = (const cplx*)d_tgt;
+  v.target_bstride = (long)target_bstride;
+  v.grad_signals = (double*)d_grad;
+  v.init_bar = (cplx*)d_ib;
+  v.infid = (double*)d_inf;
+  v.final_out = (cplx*)d_fin;
+  v.Cint = pl.Cint;
+  v.nck = pl.nck;
+  v.rows = pl.rows;
+  // (the lane-row grid is rounded up to whole wavefronts of four rows: every launched row has its own checkpoints)
+  const size_t ws_rows = pl.row ? (size_t)((pl.rows + 3) / 4) * 4 : (size_t)pl.rows;
+  const size_t ws_bytes = ws_rows * pl.ws_elems * cs;
+  void* ws;
+  if (ws_get(w, SL_ODE_VJP_WS, ws_bytes, &ws)) return -1;
+  v.ws = (cplx*)ws;
+  v.ws_stride = (long)pl.ws_elems;
+  if (!pl.row && pl.wg_global) {
+    void* sc;
+    if (ws_get(w, SL_SCRATCH, (size_t)pl.rows * pl.wg_elems * cs, &sc)) return -1;
+    v.scratch = (cplx*)sc;
+    v.scratch_stride = (long)pl.wg_elems;
+  }
+  g_last_kernel = C3P_KERNEL_ODE_VJP;
+  g_note_plan = "checkpoint interval C=" + std::to_string(pl.Cint) + " checkpoints=" + std::to_string(pl.nck) + " workspace=" +
+                std::to_string(ws_bytes) + " bytes (cap " + std::to_string((size_t)C3P_ODE_VJP_WS_CAP) + ") rows=" +
+                std::to_string(pl.rows);
+  if (record_start(w, st)) return -1;
+  LAUNCH_TRY(c3p_launch_ode_vjp(v, pl, st));
+  if (record_stop(w, st)) return -1;
   if (flags & C3P_HOST_PTRS) return sg.finish();
   return 0;
 }

@@ -287,5 +287,106 @@ def lindbladian_unitary_infid_cotangent(ideal, actual, index: List[int] = [0], d
     return (Sbar[0] if squeeze else Sbar), 1 - abs(t) / L**2
 
 
+# --------------------------------------------------------------------------
+# state fidelities (fidelities.py:86-149,793-816): goals of the ODE state solvers
+# --------------------------------------------------------------------------
+
+
+def _xp(*arrays):
+    """torch if any argument is a torch tensor, else numpy (these epilogues are a handful of element-wise operations on D
+    numbers: they stay in the framework the states arrive in; the fused device path is propagation.ode_goal_vjp)."""
+    for a in arrays:
+        if hasattr(a, "detach"):
+            import torch
+
+            return torch, a
+    return np, None
+
+
+def _as(xp, like, a):
+    if xp is np:
+        return np.asarray(a, dtype=np.complex128)
+    return a.to(xp.complex128) if hasattr(a, "detach") else xp.as_tensor(np.asarray(a, dtype=np.complex128), device=like.device)
+
+
+def _dag(xp, a):
+    return xp.conj(a).transpose(-1, -2) if xp is not np else np.conj(np.swapaxes(a, -1, -2))
+
+
+@fid_reg_deco
+def calculate_state_overlap(psi1, psi2):
+    """fidelities.py:808-816.  A ket `psi1` [D,1]: tf_ketket_fid = |<psi1|psi2>| (tf_utils.py:325-327).  A matrix state `psi1`
+    [D,D] with a ket `psi2`: tf_dmket_fid = sqrt(<psi2|psi1|psi2>) (tf_utils.py:320-322).  The reference's square branch
+    (element-wise square roots of matrices, :808-814) is not mirrored -- see DESIGN's table of differences."""
+    xp, like = _xp(psi1, psi2)
+    a, b = _as(xp, like, psi1), _as(xp, like, psi2)
+    if a.shape[-2] == a.shape[-1] and a.shape[-1] > 1:
+        if b.shape[-1] != 1:
+            raise C3PropError("C3:Error: the overlap of two density matrices is not implemented (the reference's branch is marked 'needs fixing'); pass the target as a ket")
+        r = (_dag(xp, b) @ a @ b)[..., 0, 0].real
+        return xp.sqrt(r)
+    return abs((_dag(xp, a) @ b)[..., 0, 0])
+
+
+@fid_reg_deco
+def state_transfer_from_states(states, index, dims, params, n_eval=-1):
+    """fidelities.py:793-805: 1 - overlap of the final state of a trajectory [N,D,M] (or of a single state [D,M]) with
+    params["target"]."""
+    psi_0 = params["target"]
+    last = states[-1] if len(states.shape) > 2 else states
+    return 1 - calculate_state_overlap(last, psi_0)
+
+
+def _project(xp, like, actual, dims, index):
+    U = _as(xp, like, actual)
+    rows = computational_rows(dims, index)
+    if xp is np:
+        return U[..., rows[:, None], rows[None, :]], rows
+    r = xp.as_tensor(rows.astype(np.int64), device=U.device)
+    return U[..., r[:, None], r[None, :]], rows
+
+
+@fid_reg_deco
+def state_transfer_infid(ideal, actual, index, dims, psi_0):
+    """fidelities.py:118-149: 1 - |<ideal psi_0 | P^T actual P psi_0>|; `actual` may be a batch [B,D,D] (returns [B])."""
+    xp, like = _xp(actual, ideal, psi_0)
+    Uc, _ = _project(xp, like, actual, dims, index)
+    p0 = _as(xp, like, psi_0)
+    pi = _as(xp, like, ideal) @ p0
+    return 1 - abs((_dag(xp, pi) @ (Uc @ p0))[..., 0, 0])
+
+
+@fid_reg_deco
+def state_transfer_infid_set(propagators: dict, instructions: dict, index, dims, psi_0, n_eval=-1, proj=True):
+    """Mean over gates (fidelities.py:86-115)."""
+    return _mean_over_gates([state_transfer_infid(_ideal_of(instructions, g, dims, index), U, index, dims, psi_0) for g, U in propagators.items()])
+
+
+def state_transfer_infid_cotangent(ideal, actual, index, dims, psi_0):
+    """(U_bar, infid) in the convention of `propagation.propagate_batch_vjp` (d loss = Re sum conj(U_bar) dU): with
+    z = <ideal psi_0 | P^T U P psi_0>, infid = 1 - |z| and U_bar = -(z / |z|) (P ideal psi_0)(P psi_0)^+ -- rank one; zero
+    where the overlap is zero."""
+    xp, like = _xp(actual, ideal, psi_0)
+    Uc, rows = _project(xp, like, actual, dims, index)
+    p0 = _as(xp, like, psi_0)
+    pi = _as(xp, like, ideal) @ p0
+    z = (_dag(xp, pi) @ (Uc @ p0))[..., 0, 0]
+    az = abs(z)
+    D = int(np.prod(dims))
+    outer = pi @ _dag(xp, p0)  # [L,L]
+    if xp is np:
+        emb = np.zeros((D, D), dtype=np.complex128)
+        emb[np.ix_(rows, rows)] = outer
+        ph = np.where(az > 0, -z / np.where(az > 0, az, 1.0), 0.0)
+        Ubar = np.asarray(ph)[..., None, None] * emb
+    else:
+        emb = xp.zeros((D, D), dtype=xp.complex128, device=outer.device)
+        r = xp.as_tensor(rows.astype(np.int64), device=outer.device)
+        emb[r[:, None], r[None, :]] = outer
+        ph = xp.where(az > 0, -z / xp.where(az > 0, az, xp.ones_like(az)), xp.zeros_like(z))
+        Ubar = ph[..., None, None] * emb
+    return Ubar, 1 - az
+
+
 # RB, ORBIT and the analytical EPC live with the sequence chain; importing them registers them here
 from . import sequences as _sequences  # noqa: E402,F401

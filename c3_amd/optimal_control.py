@@ -115,6 +115,52 @@ def goal_run_with_grad(
     return {"goal": goal, "grad_env": g_env, "grad_carrier": g_car, "grad_fr_phase": g_ph, "U": U}
 
 
+def goal_run_ode_with_grad(
+    h0,
+    hks,
+    env_params,
+    env_shapes,
+    carrier,
+    t_start: float,
+    t_end: float,
+    awg_res: float,
+    sim_res: float,
+    init_state,
+    target,
+    *,
+    solver: str = "rk4",
+    step_function: str = "schrodinger",
+    col_ops=None,
+    device="cuda:0",
+) -> Dict:
+    """State-transfer goals [B] and their gradients through the ODE state solvers -- the body of `goal_run_ode_only_final`
+    (optimalcontrol.py:262-292: compute_final_state with an RK solver, then state_transfer_from_states, fidelities.py:793-816)
+    under the tape of `goal_run_with_grad` (optimizer.py:206-216):
+
+      envelope rows --synthesize--> signals --ode_goal_vjp--> goal[b], d/d signals --synth vjp--> d goal/d rows
+
+    `init_state` [D,M] or [B,D,M] (M = 1: state vector; M = D: density matrix, steps "von_neumann" / "lindblad"), `target` a
+    ket [D,1] or [B,D,1].  Returns {"goal": [B], "grad_env": [B,K,E,NPAR], "grad_carrier": [B,K,2], "init_bar": [B,D,M] (the
+    cotangent of the initial state: a preceding gate's sweep starts from it), "states": [B,D,M] (the final states)} as
+    torch CUDA tensors."""
+    import torch
+
+    ts = signals.create_ts(t_start, t_end, sim_res)
+    if ts.shape[0] < 2:
+        raise C3PropError("C3:Error: need at least two time slices")
+    dt = float(ts[1] - ts[0])
+    as_dev = lambda x, dt_: x.to(device) if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=dt_), device=device)
+    env = as_dev(env_params, np.float64)
+    car = as_dev(carrier, np.float64)
+    h0d, hkd = as_dev(h0, np.complex128), as_dev(hks, np.complex128)
+    cold = None if col_ops is None else as_dev(col_ops, np.complex128)
+    sig = signals.synthesize_signals(env, env_shapes, car, t_start, t_end, awg_res, sim_res)
+    r = propagation.ode_goal_vjp(h0d, hkd, sig, dt, as_dev(init_state, np.complex128), as_dev(target, np.complex128),
+                                 solver=solver, step_function=step_function, col_ops=cold)
+    g_env, g_car = signals.synthesize_signals_vjp(env, env_shapes, car, t_start, t_end, awg_res, sim_res, r["grad_signals"])
+    return {"goal": r["goal"], "grad_env": g_env, "grad_carrier": g_car, "init_bar": r["init_bar"], "states": r["states"]}
+
+
 def robust_goal_run_with_grad(*args, **kwargs) -> Dict:
     """Mean goal and mean gradient over the batch of noise instances (optimalcontrol_robust.py:49-70),
     plus the per-instance values and their standard deviation the reference logs (:64-69)."""

@@ -882,6 +882,91 @@ def ode_solve_batch(h0, hks, signals, dt, init_state, solver="rk4", step_functio
     return out
 
 
+def _ode_vjp_call(h0, hks, signals, dt, init_state, solver, step_function, col_ops, states_bar, target, want_states):
+    call = _Call(h0, hks, signals, init_state, col_ops, states_bar, target)
+    lib = _lib.load()
+    if solver not in solver_dict:
+        raise C3PropError(f"C3:Error: unknown solver '{solver}'")
+    if col_ops is not None:
+        step_function = "lindblad"
+    if step_function not in step_dict:
+        raise C3PropError(f"C3:Error: unknown step function '{step_function}'")
+    if (states_bar is None) == (target is None):
+        raise C3PropError("C3:Error: exactly one of states_bar and target must be given")
+    h0 = call.c128(h0)
+    hks = call.c128(hks)
+    sig = call.f64(signals)
+    if sig.ndim != 3:
+        raise C3PropError(f"C3:Error: signals must be [B,K,N], got {tuple(sig.shape)}")
+    B, K, N = (int(s) for s in sig.shape)
+    D = int(h0.shape[-1])
+    if h0.ndim != 2 or tuple(h0.shape) != (D, D):
+        raise C3PropError(f"C3:Error: ode solvers take one drift Hamiltonian [D,D], got {tuple(h0.shape)}")
+    if hks.ndim != 3 or tuple(hks.shape) != (K, D, D):
+        raise C3PropError(f"C3:Error: {K} signal channels need control Hamiltonians [{K},{D},{D}], got {tuple(hks.shape)}")
+    M = 1 if step_function == "schrodinger" else D
+    init = call.c128(init_state)
+    if tuple(init.shape[-2:]) != (D, M):
+        raise C3PropError(f"C3:Error: initial state must be [..,{D},{M}] for step '{step_function}', got {tuple(init.shape)}")
+    init_bs = _bstride(init, 2, B, "init_state")
+    col = None
+    Cn = 0
+    if step_function == "lindblad":
+        if col_ops is None:
+            raise C3PropError("C3:Error: the lindblad step needs collapse operators")
+        col = call.c128(col_ops if _is_torch(col_ops) else np.asarray(col_ops))
+        Cn = int(col.shape[0])
+    bar = tgt = None
+    bar_all = 0
+    tgt_bs = 0
+    if states_bar is not None:
+        bar = call.c128(states_bar)
+        if tuple(bar.shape) == (B, N, D, M):
+            bar_all = 1
+        elif tuple(bar.shape) != (B, D, M):
+            raise C3PropError(f"C3:Error: states_bar must be [{B},{D},{M}] or [{B},{N},{D},{M}], got {tuple(bar.shape)}")
+    else:
+        tgt = call.c128(target)
+        if tuple(tgt.shape) == (D, 1):
+            tgt_bs = 0
+        elif tuple(tgt.shape) == (B, D, 1):
+            tgt_bs = D
+        else:
+            raise C3PropError(f"C3:Error: target must be a ket [{D},1] or [{B},{D},1], got {tuple(tgt.shape)}")
+    if call.device:
+        t = call.torch
+        grad = t.empty((B, K, N), dtype=t.float64, device=call.dev)
+        goal = t.empty((B,), dtype=t.float64, device=call.dev) if tgt is not None else None
+    else:
+        grad = np.empty((B, K, N), dtype=np.float64)
+        goal = np.empty((B,), dtype=np.float64) if tgt is not None else None
+    init_bar = call.empty((B, D, M))
+    final = call.empty((B, D, M)) if want_states else None
+    rc = lib.c3p_ode_solve_vjp(
+        _ptr(h0), _ptr(hks), _ptr(sig), _ptr(col), Cn, float(dt), B, K, N, D, solver_dict[solver], step_dict[step_function],
+        _ptr(init), init_bs, _ptr(bar), bar_all, _ptr(tgt), tgt_bs, call.flags, _ptr(grad), _ptr(init_bar), _ptr(goal),
+        _ptr(final), call.stream,
+    )
+    _lib.check(rc)
+    return {"grad_signals": grad, "init_bar": init_bar, "goal": goal, "states": final}
+
+
+def ode_solve_batch_vjp(h0, hks, signals, dt, init_state, states_bar, solver="rk4", step_function="schrodinger", col_ops=None, want_states=True):
+    """Discrete adjoint of `ode_solve_batch` (c3p_ode_solve_vjp): `states_bar` is the cotangent of the final state [B,D,M]
+    or of every trajectory state [B,N,D,M] (d loss = Re sum conj(states_bar) d states).  Returns {"grad_signals" [B,K,N],
+    "init_bar" [B,D,M] (the cotangent of the initial state: consecutive gates chain through it), "goal": None,
+    "states" [B,D,M] (the final state of the call's own forward pass)}.  Torch CUDA tensors in give torch CUDA tensors out."""
+    return _ode_vjp_call(h0, hks, signals, dt, init_state, solver, step_function, col_ops, states_bar, None, want_states)
+
+
+def ode_goal_vjp(h0, hks, signals, dt, init_state, target, solver="rk4", step_function="schrodinger", col_ops=None, want_states=True):
+    """State-transfer goal and its gradient in one call: goal[b] = 1 - |<target|psi_N>| for state vectors (tf_ketket_fid),
+    1 - sqrt(Re <target|rho_N|target>) for density matrices (tf_dmket_fid) -- state_transfer_from_states
+    (fidelities.py:793-816) on the final state of the call's own forward pass; `target` is a ket [D,1] or [B,D,1].
+    Returns the dict of `ode_solve_batch_vjp` with "goal" [B]."""
+    return _ode_vjp_call(h0, hks, signals, dt, init_state, solver, step_function, col_ops, None, target, want_states)
+
+
 def _ode_gate(model, gen, instr, init_state, solver, step_function, final_only):
     signal = gen.generate_signals(instr)
     col = [np.asarray(c) for c in model.get_Lindbladians()] if model.lindbladian else None

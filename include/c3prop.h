@@ -76,6 +76,7 @@ extern "C" {
 #define C3P_KERNEL_ODE_ROW_OR_WG 8 /* both launched; the DEVICE picks: real operators -> lane rows, complex -> workgroup kernel */
 #define C3P_KERNEL_SEQ 9 /* indexed gate-sequence chains (c3p_seq.hip)                          */
 #define C3P_KERNEL_SEQ_VJP 10 /* reverse sweep of the indexed gate-sequence chains (c3p_seq_vjp.hip)  */
+#define C3P_KERNEL_ODE_VJP 11 /* discrete adjoint of the ODE state solvers (c3p_ode_vjp.hip)           */
 
 /* ODE solver / step ids (propagation.py:27-32 solver_slicing; :886-904 steps) */
 #define C3P_SOLVER_RK4 0
@@ -183,6 +184,28 @@ int c3p_ode_solve(const void* h0, const void* hks, const double* signals, const 
                   int C, double dt, int B, int K, int N, int D, int solver, int step,
                   const void* init, int64_t init_bstride, int want_all, int flags, void* states,
                   void* stream);
+
+/* Discrete adjoint of c3p_ode_solve: gradients with respect to the control signals and the initial state, exact for the
+ * arithmetic the forward kernels do.  Stands in for the tape over goal_run_ode / goal_run_ode_only_final
+ * (c3/optimizers/optimalcontrol.py:230-292, differentiated by c3/optimizers/optimizer.py:206-216) with the state fidelity
+ * state_transfer_from_states (c3/libraries/fidelities.py:793-816).
+ *   h0 .. init_bstride, flags   as for c3p_ode_solve (device pointers, or host pointers with C3P_HOST_PTRS)
+ *   states_bar   c128 [B,D,M] cotangent of the final state, or with bar_all c128 [B,N,D,M]: the cotangent of every
+ *                trajectory state, injected at its step boundary
+ *   target       c128 [D] (target_bstride = 0) or [B,D] (target_bstride = D): the call forms the state-transfer goal from
+ *                the final state of its own forward pass and starts the sweep from its cotangent --
+ *                M = 1: infid[b] = 1 - |<t|psi_N>| (tf_ketket_fid, tf_utils.py:325-327), psibar = -(z / |z|) t;
+ *                M = D: infid[b] = 1 - sqrt(Re <t|rho_N|t>) (tf_dmket_fid, tf_utils.py:320-322); zero where the overlap is zero.
+ *                Exactly one of states_bar / target is non-NULL.
+ *   grad_signals f64 [B,K,N]   (every element written by one owner in a fixed order: two calls are bitwise equal)
+ *   init_bar     c128 [B,D,M] or NULL: the cotangent of the initial state (consecutive gates chain through it)
+ *   infid_out    f64 [B] or NULL (target mode);  final_out  c128 [B,D,M] or NULL: the final state of the forward pass
+ * The forward pass of the call keeps checkpoints every C steps in a workspace slot of its own (capped at 1 GiB: above it
+ * a row / workgroup walks several samples); c3p_last_kernel_detail reports "checkpoint interval C=..." and the size. */
+int c3p_ode_solve_vjp(const void* h0, const void* hks, const double* signals, const void* col_ops, int C, double dt, int B,
+                      int K, int N, int D, int solver, int step, const void* init, int64_t init_bstride,
+                      const void* states_bar, int bar_all, const void* target, int64_t target_bstride, int flags,
+                      double* grad_signals, void* init_bar, double* infid_out, void* final_out, void* stream);
 
 /* RK4 "unitary" provider (propagation.py:71-101,221-255: rk4_unitary, gen_u_rk4, gen_dus_rk4,
  * gen_du_rk4, rk4_step; Hamiltonians from get_hs_of_t_ts :104-204 at prop_res = 2):
