@@ -62,6 +62,8 @@ SIGNATURES = {
     "c3p_pwc_lindblad_taped": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _d, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.c_size_t, _i, _vp]),
     "c3p_pwc_lindblad_vjp_taped": (_i, [_vp, C.c_size_t, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "c3p_synth_signals": (_i, [_vp, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "c3p_synth_chain": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "c3p_synth_chain_vjp": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "c3p_seq_chain": (_i, [_vp, _i64, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "c3p_seq_chain_vjp": (_i, [_vp, _i64, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "c3p_ode_solve": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _i, _i, _i, _i, _i, _vp, _i64, _i, _i, _vp, _vp]),

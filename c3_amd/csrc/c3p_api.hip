@@ -10,6 +10,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <cctype>
+#include <cmath>
 
 #include "../../include/c3prop.h"
 #include "c3p_kernels.h"
@@ -3847,6 +3848,153 @@ int c3p_synth_signals_vjp(const double* env_params, const int32_t* env_shapes, c
   A.iq = (double*)v;
   A.signals = nullptr;
   LAUNCH_TRY(c3p_launch_synth_vjp(A, (const double*)d_gs, A.iq + part, A.iq + 2 * part, (double*)d_ge, (double*)d_gc, st));
+  if (flags & C3P_HOST_PTRS) return sg.finish();
+  return 0;
+}
+
+
+// host-pointer checks shared by c3p_synth_chain and its vjp
+static int chain_check_host(const int32_t* line_kind, const double* line_params, int B, int K, double sim_res) {
+  for (int k = 0; k < K; ++k)
+    if (line_kind[k] < 0 || line_kind[k] >= C3P_LINE_NKINDS) return fail("line_kind[%d]=%d is not a C3P_LINE_KIND_* id", k, line_kind[k]);
+  for (long a = 0; a < (long)B * K; ++a) {
+    const double* lp = line_params + a * C3P_LINE_NPAR;
+    const double rt = lp[C3P_LINE_RISE_TIME];
+    if (rt > 0.0 && !(std::floor(rt * sim_res) >= 1.0))
+      return fail("line_params[%ld,%d]: rise_time=%g gives no Response tap at sim_res=%g (floor(rise_time * sim_res) = 0)",
+                  a / K, (int)(a % K), rt, sim_res);
+    if (line_kind[a % K] == C3P_LINE_KIND_FLUX && !(lp[C3P_LINE_PHI_0] != 0.0))
+      return fail("line_params[%ld,%d]: a flux line needs phi_0 != 0", a / K, (int)(a % K));
+  }
+  return 0;
+}
+
+int c3p_synth_chain(const double* env_params, const int32_t* env_shapes, const double* carrier, const int32_t* line_kind,
+                    const double* line_params, double t_start, double t_end, double awg_res, double sim_res, int B, int K,
+                    int E, int flags, double* awg_iq_out, double* signals_out, void* stream) {
+  if (B < 0 || K <= 0 || E <= 0) return fail("bad sizes B=%d K=%d E=%d", B, K, E);
+  if (!(awg_res > 0.0) || !(sim_res > 0.0)) return fail("resolutions must be positive");
+  const double span = t_end > t_start ? t_end - t_start : t_start - t_end;
+  const int N = (int)(span * sim_res), Na = (int)(span * awg_res);  // devices.py:72-84
+  if (N <= 0 || Na <= 1) return fail("empty time grid: N=%d Na=%d", N, Na);
+  if (B == 0) return 0;
+  if (!env_params || !env_shapes || !carrier || !line_kind || !line_params || !signals_out) return fail("NULL pointer argument");
+  if ((flags & C3P_HOST_PTRS) && chain_check_host(line_kind, line_params, B, K, sim_res)) return -1;  // before any device work
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  DeviceWs* w = lk.w;
+  if (!w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  Stage sg{w, st};
+  const void *d_env = env_params, *d_shape = env_shapes, *d_car = carrier, *d_kind = line_kind, *d_line = line_params;
+  void *d_iq = awg_iq_out, *d_sig = signals_out;
+  const size_t iq_elems = (size_t)B * K * 2 * Na;
+  if (flags & C3P_HOST_PTRS) {
+    for (int a = 0; a < K * E; ++a)
+      if (env_shapes[a] >= C3P_ENV_NSHAPES) return fail("env_shapes[%d]=%d is not a C3P_ENV_* id", a, env_shapes[a]);
+    if (sg.in(env_params, (size_t)B * K * E * C3P_ENV_NPAR * sizeof(double), &d_env)) return -1;
+    if (sg.in(env_shapes, (size_t)K * E * sizeof(int32_t), &d_shape)) return -1;
+    if (sg.in(carrier, (size_t)B * K * 2 * sizeof(double), &d_car)) return -1;
+    if (sg.in(line_kind, (size_t)K * sizeof(int32_t), &d_kind)) return -1;
+    if (sg.in(line_params, (size_t)B * K * C3P_LINE_NPAR * sizeof(double), &d_line)) return -1;
+    if (sg.out(signals_out, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
+    if (awg_iq_out && sg.out(awg_iq_out, iq_elems * sizeof(double), &d_iq)) return -1;
+  }
+  // scratch: taps [B,K,tap_stride] | iq (unless the caller takes it)
+  const size_t tap_stride = N > 1 ? (size_t)N - 1 : 1, tap_elems = (size_t)B * K * tap_stride;
+  void* v;
+  if (ws_get(w, SL_SCRATCH, (tap_elems + (d_iq ? 0 : iq_elems)) * sizeof(double), &v)) return -1;
+  SynthChainArgs C;
+  SynthArgs& A = C.S;
+  A.env = (const double*)d_env;
+  A.shape = (const int*)d_shape;
+  A.carrier = (const double*)d_car;
+  A.t_start = t_start;
+  A.t_end = t_end;
+  A.awg_res = awg_res;
+  A.sim_res = sim_res;
+  A.B = B;
+  A.K = K;
+  A.E = E;
+  A.Na = Na;
+  A.N = N;
+  A.iq = d_iq ? (double*)d_iq : (double*)v + tap_elems;
+  A.signals = (double*)d_sig;
+  C.kind = (const int*)d_kind;
+  C.line = (const double*)d_line;
+  C.taps = (double*)v;
+  C.tap_stride = (long)tap_stride;
+  LAUNCH_TRY(c3p_launch_chain(C, st));
+  if (flags & C3P_HOST_PTRS) return sg.finish();
+  return 0;
+}
+
+int c3p_synth_chain_vjp(const double* env_params, const int32_t* env_shapes, const double* carrier, const int32_t* line_kind,
+                        const double* line_params, double t_start, double t_end, double awg_res, double sim_res, int B,
+                        int K, int E, int flags, const double* grad_signals, double* grad_env, double* grad_carrier,
+                        double* grad_line, void* stream) {
+  if (B < 0 || K <= 0 || E <= 0) return fail("bad sizes B=%d K=%d E=%d", B, K, E);
+  if (!(awg_res > 0.0) || !(sim_res > 0.0)) return fail("resolutions must be positive");
+  const double span = t_end > t_start ? t_end - t_start : t_start - t_end;
+  const int N = (int)(span * sim_res), Na = (int)(span * awg_res);
+  if (N <= 0 || Na <= 1) return fail("empty time grid: N=%d Na=%d", N, Na);
+  if (B == 0) return 0;
+  if (!env_params || !env_shapes || !carrier || !line_kind || !line_params || !grad_signals || !grad_env || !grad_carrier || !grad_line)
+    return fail("NULL pointer argument");
+  if ((flags & C3P_HOST_PTRS) && chain_check_host(line_kind, line_params, B, K, sim_res)) return -1;  // before any device work
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  DeviceWs* w = lk.w;
+  if (!w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  Stage sg{w, st};
+  const void *d_env = env_params, *d_shape = env_shapes, *d_car = carrier, *d_kind = line_kind, *d_line = line_params, *d_gs = grad_signals;
+  void *d_ge = grad_env, *d_gc = grad_carrier, *d_gl = grad_line;
+  if (flags & C3P_HOST_PTRS) {
+    for (int a = 0; a < K * E; ++a)
+      if (env_shapes[a] >= C3P_ENV_NSHAPES) return fail("env_shapes[%d]=%d is not a C3P_ENV_* id", a, env_shapes[a]);
+    if (sg.in(env_params, (size_t)B * K * E * C3P_ENV_NPAR * sizeof(double), &d_env)) return -1;
+    if (sg.in(env_shapes, (size_t)K * E * sizeof(int32_t), &d_shape)) return -1;
+    if (sg.in(carrier, (size_t)B * K * 2 * sizeof(double), &d_car)) return -1;
+    if (sg.in(line_kind, (size_t)K * sizeof(int32_t), &d_kind)) return -1;
+    if (sg.in(line_params, (size_t)B * K * C3P_LINE_NPAR * sizeof(double), &d_line)) return -1;
+    if (sg.in(grad_signals, (size_t)B * K * N * sizeof(double), &d_gs)) return -1;
+    if (sg.out(grad_env, (size_t)B * K * E * C3P_ENV_NPAR * sizeof(double), &d_ge)) return -1;
+    if (sg.out(grad_carrier, (size_t)B * K * 2 * sizeof(double), &d_gc)) return -1;
+    if (sg.out(grad_line, (size_t)B * K * C3P_LINE_NPAR * sizeof(double), &d_gl)) return -1;
+  }
+  // scratch: taps | iq | giq | gcar_part (B*K*2*Na each) | gcs [B,K,2,N] | part [B,K,tiles,stride]
+  const size_t lines = (size_t)B * K, tap_stride = N > 1 ? (size_t)N - 1 : 1, tap_elems = lines * tap_stride;
+  const size_t awg = lines * 2 * Na, gcs_elems = lines * 2 * N;
+  const size_t part_elems = lines * c3p_chain_tiles(N) * c3p_chain_part_stride();
+  void* v;
+  if (ws_get(w, SL_SCRATCH, (tap_elems + 3 * awg + gcs_elems + part_elems) * sizeof(double), &v)) return -1;
+  double* p = (double*)v;
+  SynthChainArgs C;
+  SynthArgs& A = C.S;
+  A.env = (const double*)d_env;
+  A.shape = (const int*)d_shape;
+  A.carrier = (const double*)d_car;
+  A.t_start = t_start;
+  A.t_end = t_end;
+  A.awg_res = awg_res;
+  A.sim_res = sim_res;
+  A.B = B;
+  A.K = K;
+  A.E = E;
+  A.Na = Na;
+  A.N = N;
+  C.taps = p;
+  C.tap_stride = (long)tap_stride;
+  A.iq = p + tap_elems;
+  A.signals = nullptr;
+  C.kind = (const int*)d_kind;
+  C.line = (const double*)d_line;
+  double* giq = A.iq + awg;
+  double* gcar_part = giq + awg;
+  double* gcs = gcar_part + awg;
+  double* part = gcs + gcs_elems;
+  LAUNCH_TRY(c3p_launch_chain_vjp(C, (const double*)d_gs, gcs, part, giq, gcar_part, (double*)d_ge, (double*)d_gc, (double*)d_gl, st));
   if (flags & C3P_HOST_PTRS) return sg.finish();
   return 0;
 }

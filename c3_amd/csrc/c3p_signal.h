@@ -19,3 +19,19 @@ hipError_t c3p_launch_synth(const SynthArgs& A, hipStream_t st);
 // d loss/d carrier [B,K,2]; giq [B,K,2,Na] and gcar_part [B,K,Na,2] are scratch, A.iq is recomputed.
 hipError_t c3p_launch_synth_vjp(const SynthArgs& A, const double* gsig, double* giq, double* gcar_part, double* genv,
                                 double* gcar, hipStream_t st);
+
+// The device chain behind a line: AWG -> DAC -> Response -> Mixer -> VoltsToHertz (kind 0) or FluxTuning (kind 1).
+struct SynthChainArgs {
+  SynthArgs S;
+  const int* kind;     // [K] C3P_LINE_KIND_*
+  const double* line;  // [B,K,C3P_LINE_NPAR]
+  double* taps;        // [B,K,tap_stride] scratch: the normalised Response taps, tap_stride >= N - 1
+  long tap_stride;
+};
+int c3p_chain_tiles(int N);       // sample tiles per line
+int c3p_chain_part_stride(void);  // doubles per tile in `part`
+hipError_t c3p_launch_chain(const SynthChainArgs& C, hipStream_t st);
+// scratch: gcs [B,K,2,N], part [B,K,c3p_chain_tiles(N),c3p_chain_part_stride()], giq [B,K,2,Na], gcar_part [B,K,Na,2];
+// outputs genv [B,K,E,NPAR], gcar [B,K,2], gline [B,K,C3P_LINE_NPAR]
+hipError_t c3p_launch_chain_vjp(const SynthChainArgs& C, const double* gsig, double* gcs, double* part, double* giq, double* gcar_part,
+                                double* genv, double* gcar, double* gline, hipStream_t st);

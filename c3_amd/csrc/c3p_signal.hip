@@ -341,3 +341,305 @@ hipError_t c3p_launch_synth(const SynthArgs& A, hipStream_t st) {
   C3P_LAUNCH(mix_kernel, dim3((unsigned)((ts + 255) / 256)), dim3(256), 0, st, A);
   return hipGetLastError();
 }
+
+// ---- the device chain of a flux line: AWG -> DAC -> Response -> Mixer -> VoltsToHertz | FluxTuning --------------------------
+// (reference: c3/generator/devices.py:585-642 Response, c3/utils/tf_utils.py:476-518 tf_convolve_legacy, devices.py:457-525
+//  FluxTuning).  The reference's zero-padded FFT product with its [M-1 : N+M-1] window is the causal FIR with one sample of
+//  delay, y[n] = sum_{m < min(M, n)} h[m] x[n-1-m]; it is evaluated here in that form, m ascending.  x, the upsampled AWG
+//  I/Q, exists only in LDS: a block reads the AWG-resolution rows (L2) and keeps the stretch of x its tile's taps reach.
+namespace {
+
+constexpr int CH_TN = 256;  // samples per tile = threads per block
+constexpr int CH_TC = 256;  // taps per LDS chunk (one tap loaded per thread)
+constexpr int CH_NP = 7;    // partial sums per tile: LO frequency, V->Hz, phi_0, phi, omega_0, anhar, d
+constexpr int CH_PS = 8;    // their stride
+
+// M = floor(rise_time * sim_res) of the one double product (devices.py:614); 0 = no Response stage
+__device__ __forceinline__ int chain_tap_count(double rise_time, double sim_res) {
+  if (!(rise_time > 0.0)) return 0;
+  const double m = floor(__dmul_rn(rise_time, sim_res));
+  return m < 1073741824.0 ? (int)m : 1073741824;
+}
+
+// tap m of the rise function before normalisation (devices.py:615-627)
+__device__ __forceinline__ double rise_fun(double rt, double sim_res, int M, int m) {
+  const double cen = (rt + 1.0 / sim_res) / 2, sg = rt / 4;
+  const double u = linspace_at(0.0, rt, M, m) - cen, v = -1.0 - cen;
+  return exp(-(u * u) / (2 * sg * sg)) - exp(-(v * v) / (2 * sg * sg));
+}
+
+// one wavefront per line (b, k): all M terms summed in a fixed order (lane-strided, then the butterfly), the first
+// min(M, N - 1) normalised taps stored -- a later tap multiplies samples before the first one
+__global__ void __launch_bounds__(64) chain_taps_kernel(SynthChainArgs C) {
+  const long bk = blockIdx.x;
+  const int lane = threadIdx.x;
+  const double rt = C.line[bk * C3P_LINE_NPAR + C3P_LINE_RISE_TIME];
+  const int M = chain_tap_count(rt, C.S.sim_res);
+  if (M == 0) return;
+  double s = 0.0;
+  for (int m = lane; m < M; m += 64) s += rise_fun(rt, C.S.sim_res, M, m);
+  s = wave_sum(s);
+  const int Mt = M < C.S.N - 1 ? M : C.S.N - 1;
+  double* h = C.taps + bk * C.tap_stride;
+  for (int m = lane; m < Mt; m += 64) h[m] = rise_fun(rt, C.S.sim_res, M, m) / s;
+}
+
+// I, Q the mixer reads at sample n0 + threadIdx.x of line bk; every thread of the block calls it (Mt is block-uniform)
+__device__ __forceinline__ void chain_fir_tile(const SynthChainArgs& C, long bk, int n0, int Mt, double* s_h, double* s_xi,
+                                               double* s_xq, double& I, double& Q) {
+  const int i = threadIdx.x, n = n0 + i, Na = C.S.Na, N = C.S.N;
+  const double* iq = C.S.iq + bk * 2 * Na;
+  I = 0.0;
+  Q = 0.0;
+  if (Mt == 0) {
+    if (n < N) {
+      const int src = dac_src(n, Na, N);
+      I = iq[src];
+      Q = iq[Na + src];
+    }
+    return;
+  }
+  const double* h = C.taps + bk * C.tap_stride;
+  // taps from n0 + CH_TN - 1 on reach before sample 0 for the whole tile
+  const int Mtile = Mt < n0 + CH_TN - 1 ? Mt : n0 + CH_TN - 1;
+  double aI = 0.0, aQ = 0.0;
+  for (int c0 = 0; c0 < Mtile; c0 += CH_TC) {
+    __syncthreads();
+    const int nc = Mtile - c0 < CH_TC ? Mtile - c0 : CH_TC;
+    if (i < nc) s_h[i] = h[c0 + i];
+    const int base = n0 - c0 - CH_TC;  // sample index of s_x[0]
+    for (int p = i; p < CH_TN + CH_TC - 1; p += CH_TN) {
+      const int idx = base + p;
+      double xi = 0.0, xq = 0.0;
+      if (idx >= 0 && idx < N) {
+        const int src = dac_src(idx, Na, N);
+        xi = iq[src];
+        xq = iq[Na + src];
+      }
+      s_xi[p] = xi;
+      s_xq[p] = xq;
+    }
+    __syncthreads();
+    const int off = i + CH_TC - 1;  // x[n - 1 - (c0 + mm)] = s_x[off - mm]
+    for (int mm = 0; mm < nc; ++mm) {
+      const double hh = s_h[mm];
+      aI = fma(hh, s_xi[off - mm], aI);
+      aQ = fma(hh, s_xq[off - mm], aQ);
+    }
+  }
+  I = aI;
+  Q = aQ;
+}
+
+struct FluxP {
+  double phi0, phi, w0, anhar, d;
+};
+__device__ __forceinline__ FluxP load_flux(const double* lp) {
+  return FluxP{lp[C3P_LINE_PHI_0], lp[C3P_LINE_PHI], lp[C3P_LINE_OMEGA_0], lp[C3P_LINE_ANHAR], lp[C3P_LINE_D]};
+}
+// f = (cos^2 u + d^2 sin^2 u)^(1/4), u = pi x / phi_0 (devices.py:481-495; d = 0: the branch without d), with df/du, df/dd
+struct FluxV {
+  double f, du, dd, u;
+};
+__device__ __forceinline__ FluxV flux_parts(double x, const FluxP& p) {
+  FluxV r;
+  r.u = M_PI * x / p.phi0;
+  double s, c;
+  sincos(r.u, &s, &c);
+  r.f = sqrt(sqrt(c * c + p.d * p.d * (s * s)));
+  const double q34 = 0.5 / (r.f * r.f * r.f);
+  r.du = q34 * s * c * (p.d * p.d - 1.0);
+  r.dd = q34 * p.d * s * s;
+  return r;
+}
+// FluxTuning.get_freq (devices.py:497-502)
+__device__ __forceinline__ double flux_freq(double x, const FluxP& p) { return (p.w0 - p.anhar) * flux_parts(x, p).f + p.anhar; }
+
+// one block per tile of CH_TN consecutive samples of one line: DAC -> Response -> Mixer -> V->Hz | FluxTuning
+__global__ void __launch_bounds__(CH_TN) chain_fwd_kernel(SynthChainArgs C, int nt) {
+  __shared__ double s_h[CH_TC], s_xi[CH_TN + CH_TC - 1], s_xq[CH_TN + CH_TC - 1];
+  const SynthArgs& A = C.S;
+  const long bk = blockIdx.x / nt;
+  const int n0 = (int)(blockIdx.x % nt) * CH_TN, n = n0 + threadIdx.x;
+  const int k = (int)(bk % A.K);
+  const double* lp = C.line + bk * C3P_LINE_NPAR;
+  int Mt = chain_tap_count(lp[C3P_LINE_RISE_TIME], A.sim_res);
+  Mt = Mt < A.N - 1 ? Mt : A.N - 1;
+  double I, Q;
+  chain_fir_tile(C, bk, n0, Mt, s_h, s_xi, s_xq, I, Q);
+  if (n >= A.N) return;
+  const double dts = 1.0 / A.sim_res;
+  const double t = linspace_at(A.t_start + dts / 2, A.t_end - dts / 2, A.N, n);
+  const double w = A.carrier[bk * 2 + 0], v2hz = A.carrier[bk * 2 + 1];
+  double sn, cs;
+  sincos(w * t, &sn, &cs);
+  double out;
+  if (C.kind[k] == C3P_LINE_KIND_FLUX) {
+    const FluxP p = load_flux(lp);
+    out = flux_freq(p.phi + (cs * I + sn * Q), p) - flux_freq(p.phi, p);
+  } else {
+    out = (cs * I + sn * Q) * v2hz;
+  }
+  A.signals[bk * A.N + n] = out;
+}
+
+// backward step 1, same tiling: mixed[n] again, the cotangent of the mixer output times cos / sin (gcs [B,K,2,N]) and the
+// tile's partial sums for the LO frequency, V->Hz and the five line parameters (part [B,K,nt,CH_PS]); wavefront butterfly,
+// then the four wavefronts in order
+__global__ void __launch_bounds__(CH_TN) chain_bwd_sample_kernel(SynthChainArgs C, int nt, const double* gsig, double* gcs, double* part) {
+  __shared__ double s_h[CH_TC], s_xi[CH_TN + CH_TC - 1], s_xq[CH_TN + CH_TC - 1];
+  __shared__ double s_red[CH_TN / 64][CH_PS];
+  const SynthArgs& A = C.S;
+  const long bk = blockIdx.x / nt;
+  const int n0 = (int)(blockIdx.x % nt) * CH_TN, n = n0 + threadIdx.x;
+  const int k = (int)(bk % A.K);
+  const double* lp = C.line + bk * C3P_LINE_NPAR;
+  int Mt = chain_tap_count(lp[C3P_LINE_RISE_TIME], A.sim_res);
+  Mt = Mt < A.N - 1 ? Mt : A.N - 1;
+  double I, Q;
+  chain_fir_tile(C, bk, n0, Mt, s_h, s_xi, s_xq, I, Q);
+  double v[CH_NP];
+  for (int q = 0; q < CH_NP; ++q) v[q] = 0.0;
+  if (n < A.N) {
+    const double dts = 1.0 / A.sim_res;
+    const double t = linspace_at(A.t_start + dts / 2, A.t_end - dts / 2, A.N, n);
+    const double w = A.carrier[bk * 2 + 0], v2hz = A.carrier[bk * 2 + 1];
+    double sn, cs;
+    sincos(w * t, &sn, &cs);
+    const double mixed = cs * I + sn * Q;
+    const double g = gsig[bk * A.N + n];
+    double gm;
+    if (C.kind[k] == C3P_LINE_KIND_FLUX) {
+      const FluxP p = load_flux(lp);
+      const FluxV f1 = flux_parts(p.phi + mixed, p), f0 = flux_parts(p.phi, p);
+      const double a = p.w0 - p.anhar, kk = M_PI / p.phi0;
+      gm = g * a * f1.du * kk;
+      v[2] = g * a * (f0.du * f0.u - f1.du * f1.u) / p.phi0;
+      v[3] = g * a * kk * (f1.du - f0.du);
+      v[4] = g * (f1.f - f0.f);
+      v[5] = g * (f0.f - f1.f);
+      v[6] = g * a * (f1.dd - f0.dd);
+    } else {
+      gm = g * v2hz;
+      v[1] = g * mixed;
+    }
+    v[0] = gm * t * (cs * Q - sn * I);
+    gcs[(bk * 2 + 0) * A.N + n] = gm * cs;
+    gcs[(bk * 2 + 1) * A.N + n] = gm * sn;
+  }
+  for (int q = 0; q < CH_NP; ++q) v[q] = wave_sum(v[q]);
+  if ((threadIdx.x & 63) == 0)
+    for (int q = 0; q < CH_NP; ++q) s_red[threadIdx.x >> 6][q] = v[q];
+  __syncthreads();
+  if (threadIdx.x < CH_NP) {
+    double s = s_red[0][threadIdx.x];
+    for (int wv = 1; wv < CH_TN / 64; ++wv) s += s_red[wv][threadIdx.x];
+    part[(long)blockIdx.x * CH_PS + threadIdx.x] = s;
+  }
+}
+
+// backward step 2, one wavefront per AWG sample (b, k, j): the transposed FIR over the samples j feeds,
+//   gI[j] = sum_{i: src(i) = j} sum_m h[m] gc[i+1+m]   (likewise gQ),
+// lanes over i, then the butterfly.  The wavefront of j = 0 also folds the line's tile partials: the carrier pair goes to
+// gcar_part[.., 0, :] (zeros for j > 0, so awg_bwd_kernel's sum over j returns it), the line parameters to gline.
+__global__ void __launch_bounds__(64) chain_bwd_awg_kernel(SynthChainArgs C, int nt, const double* gcs, const double* part, double* giq,
+                                                           double* gcar_part, double* gline) {
+  const SynthArgs& A = C.S;
+  const long gid = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int j = (int)(gid % A.Na);
+  const long bk = gid / A.Na;
+  int n = (int)ceil((double)j * ((double)A.N / (double)A.Na) - 0.5);
+  n = n < 0 ? 0 : (n > A.N ? A.N : n);
+  while (n > 0 && dac_src(n - 1, A.Na, A.N) >= j) --n;
+  while (n < A.N && dac_src(n, A.Na, A.N) < j) ++n;
+  int Mt = chain_tap_count(C.line[bk * C3P_LINE_NPAR + C3P_LINE_RISE_TIME], A.sim_res);
+  Mt = Mt < A.N - 1 ? Mt : A.N - 1;
+  const double* gc = gcs + bk * 2 * A.N;
+  const double* gs = gc + A.N;
+  const double* h = C.taps + bk * C.tap_stride;
+  double gI = 0.0, gQ = 0.0;
+  for (int base = n; base < A.N && dac_src(base, A.Na, A.N) == j; base += 64) {
+    const int i = base + lane;
+    if (i < A.N && dac_src(i, A.Na, A.N) == j) {
+      if (Mt == 0) {
+        gI += gc[i];
+        gQ += gs[i];
+      } else {
+        const int mmax = Mt < A.N - 1 - i ? Mt : A.N - 1 - i;
+        double a = 0.0, b = 0.0;
+        for (int m = 0; m < mmax; ++m) {
+          a = fma(h[m], gc[i + 1 + m], a);
+          b = fma(h[m], gs[i + 1 + m], b);
+        }
+        gI += a;
+        gQ += b;
+      }
+    }
+  }
+  gI = wave_sum(gI);
+  gQ = wave_sum(gQ);
+  if (lane == 0) {
+    giq[bk * 2 * A.Na + j] = gI;
+    giq[bk * 2 * A.Na + A.Na + j] = gQ;
+  }
+  double* gp = gcar_part + (bk * A.Na + j) * 2;
+  if (j != 0) {
+    if (lane < 2) gp[lane] = 0.0;
+    return;
+  }
+  double v[CH_NP];
+  for (int q = 0; q < CH_NP; ++q) {
+    double s = 0.0;
+    for (int tl = lane; tl < nt; tl += 64) s += part[(bk * nt + tl) * CH_PS + q];
+    v[q] = wave_sum(s);
+  }
+  if (lane == 0) {
+    gp[0] = v[0];
+    gp[1] = v[1];
+    double* gl = gline + bk * C3P_LINE_NPAR;
+    gl[C3P_LINE_RISE_TIME] = 0.0;  // the tap count is a floor: not differentiated
+    gl[C3P_LINE_PHI_0] = v[2];
+    gl[C3P_LINE_PHI] = v[3];
+    gl[C3P_LINE_OMEGA_0] = v[4];
+    gl[C3P_LINE_ANHAR] = v[5];
+    gl[C3P_LINE_D] = v[6];
+  }
+}
+
+}  // namespace
+
+hipError_t c3p_launch_chain(const SynthChainArgs& C, hipStream_t st) {
+  const SynthArgs& A = C.S;
+  const long lines = (long)A.B * A.K, ta = lines * A.Na;
+  const int nt = (A.N + CH_TN - 1) / CH_TN;
+  if (ta == 0 || A.N == 0) return hipSuccess;
+  C3P_LAUNCH(awg_iq_kernel, dim3((unsigned)((ta + 127) / 128)), dim3(128), 0, st, A);
+  C3P_LAUNCH(chain_taps_kernel, dim3((unsigned)lines), dim3(64), 0, st, C);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  C3P_LAUNCH(chain_fwd_kernel, dim3((unsigned)(lines * nt)), dim3(CH_TN), 0, st, C, nt);
+  return hipGetLastError();
+}
+
+int c3p_chain_tiles(int N) { return (N + CH_TN - 1) / CH_TN; }
+int c3p_chain_part_stride() { return CH_PS; }
+
+hipError_t c3p_launch_chain_vjp(const SynthChainArgs& C, const double* gsig, double* gcs, double* part, double* giq, double* gcar_part,
+                                double* genv, double* gcar, double* gline, hipStream_t st) {
+  const SynthArgs& A = C.S;
+  const long lines = (long)A.B * A.K, ta = lines * A.Na;
+  const int nt = c3p_chain_tiles(A.N);
+  if (ta == 0 || A.N == 0) return hipSuccess;
+  C3P_LAUNCH(awg_iq_kernel, dim3((unsigned)((ta + 127) / 128)), dim3(128), 0, st, A);
+  C3P_LAUNCH(chain_taps_kernel, dim3((unsigned)lines), dim3(64), 0, st, C);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  C3P_LAUNCH(chain_bwd_sample_kernel, dim3((unsigned)(lines * nt)), dim3(CH_TN), 0, st, C, nt, gsig, gcs, part);
+  C3P_LAUNCH(chain_bwd_awg_kernel, dim3((unsigned)ta), dim3(64), 0, st, C, nt, (const double*)gcs, (const double*)part, giq,
+             gcar_part, gline);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  C3P_LAUNCH(awg_bwd_kernel, dim3((unsigned)lines), dim3(64), 0, st, A, (const double*)giq, (const double*)gcar_part, genv, gcar);
+  return hipGetLastError();
+}

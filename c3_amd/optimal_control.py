@@ -43,6 +43,8 @@ def goal_run_with_grad(
     col_ops=None,
     device="cuda:0",
     fused: Optional[bool] = None,
+    line_kinds=None,
+    line_params=None,
 ) -> Dict:
     """goals [B] and their gradients w.r.t. every envelope row, carrier pair and frame-rotation phase.
 
@@ -52,6 +54,10 @@ def goal_run_with_grad(
     `col_ops` [C,D,D] switches to the open-system path (model.lindbladian, propagation.py:551-585): U are the D^2 x D^2
     superoperators, `fid_func` an open-system goal ("lindbladian_unitary_infid", fidelities.py:221-249), `fr_phase` [B,D^2]
     the row phases of the superoperator, and the control gradient comes from `propagate_batch_lindblad_vjp`.
+
+    `line_kinds` [K] / `line_params` [B,K,LINE_NPAR] (signals.pack_lines) send every line through the chain AWG -> DAC ->
+    Response -> Mixer -> VoltsToHertz | FluxTuning instead of the standard drive line; the result then also holds
+    "grad_line" [B,K,LINE_NPAR] (phi_0, phi, omega_0, anhar, d; rise_time is not differentiated), on every route below.
 
     `fused` (closed systems; default: wherever the library serves the shape) takes goal and gradient from ONE pass over the
     chains (`propagation.propagate_batch_goal_vjp`); False runs forward pass, cotangent and vector-Jacobian product as three
@@ -70,7 +76,18 @@ def goal_run_with_grad(
     car = as_dev(carrier, np.float64)
     h0d, hkd = as_dev(h0, np.complex128), as_dev(hks, np.complex128)
     ph = None if fr_phase is None else as_dev(fr_phase, np.float64)
-    sig = signals.synthesize_signals(env, env_shapes, car, t_start, t_end, awg_res, sim_res)
+    chain = {}
+    if line_kinds is not None or line_params is not None:
+        if line_kinds is None or line_params is None:
+            raise C3PropError("C3:Error: line_kinds and line_params go together")
+        chain = {"line_kinds": line_kinds, "line_params": as_dev(line_params, np.float64)}
+    sig = signals.synthesize_signals(env, env_shapes, car, t_start, t_end, awg_res, sim_res, **chain)
+
+    def synth_vjp(g_sig):
+        """{"grad_env", "grad_carrier"[, "grad_line"]} from d goal / d signals"""
+        g = signals.synthesize_signals_vjp(env, env_shapes, car, t_start, t_end, awg_res, sim_res, g_sig, **chain)
+        return dict(zip(("grad_env", "grad_carrier", "grad_line"), g))
+
     if col_ops is not None:
         if not fid_func.startswith("lindbladian"):
             raise C3PropError(f"C3:Error: '{fid_func}' is a closed-system goal; the Lindblad path needs a lindbladian_* one")
@@ -102,17 +119,15 @@ def goal_run_with_grad(
             # ONE pass over the chains: the backward pass's scan of the segment products evaluates the goal and starts the
             # adjoint sweep from its cotangent (c3p_pwc_unitary_goal_vjp); no second forward pass, no host-framework ops
             r = propagation.propagate_batch_goal_vjp(h0d, hkd, sig, dt, ideal, index, dims, kind="unitary" if fid_func == "unitary_infid" else "average", fr_phase=ph)
-            g_env, g_car = signals.synthesize_signals_vjp(env, env_shapes, car, t_start, t_end, awg_res, sim_res, r["grad_signals"])
-            return {"goal": r["goal"], "grad_env": g_env, "grad_carrier": g_car, "grad_fr_phase": r["grad_fr_phase"], "U": r["U"]}
+            return {"goal": r["goal"], **synth_vjp(r["grad_signals"]), "grad_fr_phase": r["grad_fr_phase"], "U": r["U"]}
         U = propagation.propagate_batch(h0d, hkd, sig, dt, fr_phase=ph)["U"]
         U_bar, goal = _COTANGENTS[fid_func](ideal, U, index, dims)
         g_sig = propagation.propagate_batch_vjp(h0d, hkd, sig, dt, U_bar, fr_phase=ph)
-    g_env, g_car = signals.synthesize_signals_vjp(env, env_shapes, car, t_start, t_end, awg_res, sim_res, g_sig)
     g_ph = None
     if ph is not None:
         # U = diag(e^{i phi}) P  =>  d loss/d phi_i = Re sum_j conj(U_bar_ij) (i U_ij) = -Im sum_j conj(U_bar_ij) U_ij
         g_ph = -(torch.conj(U_bar) * U).sum(dim=-1).imag
-    return {"goal": goal, "grad_env": g_env, "grad_carrier": g_car, "grad_fr_phase": g_ph, "U": U}
+    return {"goal": goal, **synth_vjp(g_sig), "grad_fr_phase": g_ph, "U": U}
 
 
 def goal_run_ode_with_grad(
@@ -170,4 +185,6 @@ def robust_goal_run_with_grad(*args, **kwargs) -> Dict:
            "gradient_std": r["grad_env"].std(dim=0, unbiased=False)}
     if r["grad_fr_phase"] is not None:
         out["grad_fr_phase"] = r["grad_fr_phase"].mean(dim=0)
+    if "grad_line" in r:
+        out["grad_line"] = r["grad_line"].mean(dim=0)
     return out

@@ -46,6 +46,10 @@ ENV_SLOTS = {
 ENV_NPAR = 12
 ENVF_T_BEFORE = 1
 ENVF_DRAG = 2
+# what follows the mixer on a line, and the per-line parameter row of `c3p_synth_chain` (C3P_LINE_* of include/c3prop.h)
+LINE_KINDS = {"drive": 0, "flux": 1}
+LINE_SLOTS = {"rise_time": 0, "phi_0": 1, "phi": 2, "omega_0": 3, "anhar": 4, "d": 5}
+LINE_NPAR = 6
 
 
 def slice_num(t_start: float, t_end: float, resolution: float) -> int:
@@ -84,6 +88,52 @@ def pack_components(channels: Sequence[Sequence[Dict]], B: int = 1):
     return env, shapes
 
 
+def response_tap_count(rise_time: float, sim_res: float) -> int:
+    """Response (devices.py:614): floor(rise_time * resolution) taps, of that one double product."""
+    return int(np.floor(float(rise_time) * float(sim_res)))
+
+
+def _check_lines(kinds: np.ndarray, params: Optional[np.ndarray], sim_res: Optional[float]) -> None:
+    if kinds.size and (kinds.min() < 0 or kinds.max() >= len(LINE_KINDS)):
+        raise C3PropError(f"C3:Error: line_kinds holds an unknown kind id (have {LINE_KINDS})")
+    if sim_res is not None:
+        rt = params[..., LINE_SLOTS["rise_time"]]
+        bad = (rt > 0) & (np.floor(rt * float(sim_res)) < 1)
+        if bad.any():
+            b, k = (int(x) for x in np.argwhere(bad)[0])
+            raise C3PropError(f"C3:Error: rise_time={rt[b, k]:g} of line [{b},{k}] gives no Response tap at sim_res={sim_res:g}")
+
+
+def pack_lines(lines: Sequence[Dict], B: int = 1, sim_res: Optional[float] = None):
+    """What follows the AWG on each line -> (line_kinds int32 [K], line_params [B,K,LINE_NPAR]).
+
+    `lines[k]` is a dict: `kind` "drive" (Mixer -> VoltsToHertz, the default) or "flux" (Mixer -> FluxTuning,
+    devices.py:457-525, with `phi_0`, `phi`, `omega_0`, `anhar` and optionally `d`), and optionally `rise_time` > 0 for a
+    Response stage between DAC and Mixer (devices.py:585-642).  Values are scalars or arrays of B per-sample values.  With
+    `sim_res` a rise_time too short for one tap is refused here (the library refuses it on host-pointer calls).
+    """
+    K = len(lines)
+    kinds = np.zeros(K, dtype=np.int32)
+    params = np.zeros((B, K, LINE_NPAR), dtype=np.float64)
+    for k, line in enumerate(lines):
+        name = line.get("kind", "drive")
+        if name not in LINE_KINDS:
+            raise C3PropError(f"C3:Error: line kind {name!r} is not available on the device (have {sorted(LINE_KINDS)})")
+        kinds[k] = LINE_KINDS[name]
+        for key, val in line.items():
+            if key == "kind":
+                continue
+            if key not in LINE_SLOTS:
+                raise C3PropError(f"C3:Error: unknown line parameter {key!r}")
+            params[:, k, LINE_SLOTS[key]] = np.asarray(val, dtype=np.float64)
+        if name == "flux":
+            for key in ("phi_0", "phi", "omega_0", "anhar"):  # FluxTuning.__init__ (devices.py:475-479)
+                if key not in line:
+                    raise C3PropError(f"C3:Error: a flux line needs a '{key}' parameter")
+    _check_lines(kinds, params, sim_res)
+    return kinds, params
+
+
 _shapes_memo = TensorMemo()  # device shape tables: per tensor object (weak reference + version), never per address
 _shapes_upload: Dict[tuple, object] = {}  # content-keyed uploads of host tables
 
@@ -118,8 +168,35 @@ def _shapes(call, env_shapes, K: int, E: int):
     return shapes_np, shp
 
 
-def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, *, want_iq: bool = False, device=None):
+def _lines(call, line_kinds, line_params, B: int, K: int, sim_res: float):
+    """(kinds, params) as the library call takes them.  Host rows are checked here; the kind table is uploaded once per
+    distinct content (as the shape table is), device rows are taken as they are -- looking at them would synchronise."""
+    kinds_np = np.ascontiguousarray(np.asarray(line_kinds.cpu() if _is_torch(line_kinds) else line_kinds, dtype=np.int32))
+    if kinds_np.shape != (K,):
+        raise C3PropError(f"C3:Error: line_kinds must be [{K}], got {kinds_np.shape}")
+    par = call.f64(line_params)
+    if tuple(par.shape) != (B, K, LINE_NPAR):
+        raise C3PropError(f"C3:Error: line_params must be [{B},{K},{LINE_NPAR}], got {tuple(par.shape)}")
+    if _is_torch(line_params) and line_params.is_cuda:
+        _check_lines(kinds_np, None, None)
+    else:
+        _check_lines(kinds_np, np.asarray(line_params.numpy() if _is_torch(line_params) else line_params, dtype=np.float64), sim_res)
+    if not call.device:
+        return kinds_np, par
+    key = ("kinds", kinds_np.tobytes(), str(call.dev))
+    knd = _shapes_upload.get(key)
+    if knd is None:
+        if len(_shapes_upload) > 64:
+            _shapes_upload.clear()
+        knd = _shapes_upload[key] = call.torch.as_tensor(kinds_np, device=call.dev)
+    return knd, par
+
+
+def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, *, want_iq: bool = False, device=None, line_kinds=None, line_params=None):
     """signals [B,K,N] (and optionally the AWG-resolution I/Q [B,K,2,Na]) from parameter rows.
+
+    With `line_kinds` [K] int32 and `line_params` [B,K,LINE_NPAR] (see `pack_lines`) every line runs the chain
+    AWG -> DAC -> Response -> Mixer -> VoltsToHertz | FluxTuning (`c3p_synth_chain`); without them the standard drive line.
 
     env_params [B,K,E,NPAR] f64, env_shapes [K,E] int32, carrier [B,K,2] f64 = (LO angular
     frequency, V_to_Hz).  numpy in -> numpy out (staged by the library); with `device` (or any torch
@@ -129,7 +206,9 @@ def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: f
         import torch
 
         env_params = torch.as_tensor(np.asarray(env_params, dtype=np.float64) if not _is_torch(env_params) else env_params, device=device)
-    call = _Call(env_params, carrier)
+    if (line_kinds is None) != (line_params is None):
+        raise C3PropError("C3:Error: line_kinds and line_params go together")
+    call = _Call(env_params, carrier, line_params)
     env = call.f64(env_params)
     if env.ndim != 4 or env.shape[-1] != ENV_NPAR:
         raise C3PropError(f"C3:Error: env_params must be [B,K,E,{ENV_NPAR}], got {tuple(env.shape)}")
@@ -147,6 +226,14 @@ def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: f
     else:
         sig = np.empty((B, K, N), dtype=np.float64)
         iq = np.empty((B, K, 2, Na), dtype=np.float64) if want_iq else None
+    if line_kinds is not None:
+        knd, par = _lines(call, line_kinds, line_params, B, K, sim_res)
+        _lib.check(
+            _lib.load().c3p_synth_chain(
+                _ptr(env), _ptr(shp), _ptr(car), _ptr(knd), _ptr(par), float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags, _ptr(iq), _ptr(sig), call.stream
+            )
+        )
+        return (sig, iq) if want_iq else sig
     _lib.check(
         _lib.load().c3p_synth_signals(
             _ptr(env), _ptr(shp), _ptr(car), float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags, _ptr(iq), _ptr(sig), call.stream
@@ -155,14 +242,18 @@ def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: f
     return (sig, iq) if want_iq else sig
 
 
-def synthesize_signals_vjp(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, grad_signals):
-    """(grad_env [B,K,E,NPAR], grad_carrier [B,K,2]) from d loss / d signals [B,K,N].
+def synthesize_signals_vjp(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, grad_signals, *, line_kinds=None, line_params=None):
+    """(grad_env [B,K,E,NPAR], grad_carrier [B,K,2]) from d loss / d signals [B,K,N]; with `line_kinds` / `line_params`
+    (the chain of `synthesize_signals`) also grad_line [B,K,LINE_NPAR]: phi_0, phi, omega_0, anhar, d in their LINE_SLOTS,
+    0 for rise_time (the tap count is a floor) and, in grad_carrier, for V_to_Hz on a flux line.
 
     Differentiates amp, xy_angle, freq_offset, delta (their ENV_SLOTS) and the carrier pair; the
     reference gets the same numbers from the tape that also covers the propagation
     (optimizers/optimizer.py:206-216, gates.py:341-370).  Chain with `propagate_batch_vjp`.
     """
-    call = _Call(env_params, carrier, grad_signals)
+    if (line_kinds is None) != (line_params is None):
+        raise C3PropError("C3:Error: line_kinds and line_params go together")
+    call = _Call(env_params, carrier, grad_signals, line_params)
     env = call.f64(env_params)
     if env.ndim != 4 or env.shape[-1] != ENV_NPAR:
         raise C3PropError(f"C3:Error: env_params must be [B,K,E,{ENV_NPAR}], got {tuple(env.shape)}")
@@ -184,6 +275,15 @@ def synthesize_signals_vjp(env_params, env_shapes, carrier, t_start: float, t_en
     else:
         genv = np.empty((B, K, E, ENV_NPAR), dtype=np.float64)
         gcar = np.empty((B, K, 2), dtype=np.float64)
+    if line_kinds is not None:
+        knd, par = _lines(call, line_kinds, line_params, B, K, sim_res)
+        gline = call.torch.empty((B, K, LINE_NPAR), dtype=call.torch.float64, device=call.dev) if call.device else np.empty((B, K, LINE_NPAR), dtype=np.float64)
+        _lib.check(
+            _lib.load().c3p_synth_chain_vjp(
+                _ptr(env), _ptr(shp), _ptr(car), _ptr(knd), _ptr(par), float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags, _ptr(gs), _ptr(genv), _ptr(gcar), _ptr(gline), call.stream
+            )
+        )
+        return genv, gcar, gline
     _lib.check(
         _lib.load().c3p_synth_signals_vjp(
             _ptr(env), _ptr(shp), _ptr(car), float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags, _ptr(gs), _ptr(genv), _ptr(gcar), call.stream
@@ -204,10 +304,24 @@ def generate_signals(channels: Dict[str, Dict], t_start: float, t_end: float, aw
 
     `channels[name] = {"components": [envelope dicts], "lo_freq": w [rad/s], "v_to_hz": f}`;
     returns `{name: {"values": [N], "ts": [N]}}` -- what `pwc` reads (propagation.py:289-294).
+    A channel may carry `"response": {"rise_time": s}` (a Response device between DAC and Mixer) and
+    `"flux_tuning": {"phi_0", "phi", "omega_0", "anhar", "d"}` (FluxTuning in place of VoltsToHertz): the chains of the
+    reference's tunable-coupler generator (test/test_tunable_coupler.py:190-218).
     """
     names = list(channels)
     env, shapes = pack_components([channels[n]["components"] for n in names], B=1)
     carrier = np.array([[[channels[n]["lo_freq"], channels[n].get("v_to_hz", 1.0)] for n in names]], dtype=np.float64)
-    sig = synthesize_signals(env, shapes, carrier, t_start, t_end, awg_res, sim_res)
+    if any("response" in channels[n] or "flux_tuning" in channels[n] for n in names):
+        lines = []
+        for n in names:
+            ch = channels[n]
+            line = dict(ch["flux_tuning"], kind="flux") if "flux_tuning" in ch else {"kind": "drive"}
+            if "response" in ch:
+                line["rise_time"] = ch["response"]["rise_time"]
+            lines.append(line)
+        kinds, params = pack_lines(lines, B=1, sim_res=sim_res)
+        sig = synthesize_signals(env, shapes, carrier, t_start, t_end, awg_res, sim_res, line_kinds=kinds, line_params=params)
+    else:
+        sig = synthesize_signals(env, shapes, carrier, t_start, t_end, awg_res, sim_res)
     ts = create_ts(t_start, t_end, sim_res)
     return {n: {"values": np.asarray(sig[0, k]), "ts": ts} for k, n in enumerate(names)}

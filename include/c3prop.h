@@ -363,6 +363,49 @@ int c3p_synth_signals_vjp(const double* env_params, const int32_t* env_shapes, c
                           int E, int flags, const double* grad_signals, double* grad_env, double* grad_carrier,
                           void* stream);
 
+/* Signal synthesis through the device chain of a flux line (the reference's tunable-coupler generator,
+ * test/test_tunable_coupler.py:159-218): AWG -> DAC -> Response -> Mixer -> VoltsToHertz | FluxTuning.  The arguments of
+ * c3p_synth_signals plus, per line,
+ *   line_kind   int32 [K]                    C3P_LINE_KIND_DRIVE: values = V_to_Hz * mixed (devices.py:203-221)
+ *                                            C3P_LINE_KIND_FLUX:  values = F(phi + mixed) - F(phi) (devices.py:457-525),
+ *                                            F(x) = (omega_0 - anhar) (cos^2(pi x/phi_0) + d^2 sin^2(pi x/phi_0))^(1/4) + anhar
+ *                                            (d = 0: the reference's branch without d); the V_to_Hz slot of `carrier` is ignored
+ *   line_params f64 [B,K,C3P_LINE_NPAR]      rows laid out by the C3P_LINE_* slots below
+ * Response (devices.py:585-642, tf_utils.py:476-518), applied to the upsampled inphase and quadrature when rise_time > 0:
+ *   M = floor(rise_time * sim_res) taps h = r / sum r, r_m = exp(-(t_m - cen)^2 / 2 sigma^2) - exp(-(-1 - cen)^2 / 2 sigma^2),
+ *   t = linspace(0, rise_time, M), cen = (rise_time + 1/sim_res) / 2, sigma = rise_time / 4,
+ *   y[n] = sum_{m < min(M, n)} h[m] x[n-1-m]  (the reference's zero-padded FFT product and window; y[0] = 0).
+ * rise_time <= 0: no Response stage.  rise_time > 0 with M = 0 is an error on host-pointer calls (device-pointer calls
+ * cannot look: they run such a line without the stage).  With every kind C3P_LINE_KIND_DRIVE and no rise_time the result
+ * equals c3p_synth_signals'.
+ */
+#define C3P_LINE_KIND_DRIVE 0
+#define C3P_LINE_KIND_FLUX 1
+#define C3P_LINE_NKINDS 2
+
+#define C3P_LINE_RISE_TIME 0
+#define C3P_LINE_PHI_0 1
+#define C3P_LINE_PHI 2
+#define C3P_LINE_OMEGA_0 3
+#define C3P_LINE_ANHAR 4
+#define C3P_LINE_D 5
+#define C3P_LINE_NPAR 6
+
+int c3p_synth_chain(const double* env_params, const int32_t* env_shapes, const double* carrier, const int32_t* line_kind,
+                    const double* line_params, double t_start, double t_end, double awg_res, double sim_res, int B, int K,
+                    int E, int flags, double* awg_iq_out, double* signals_out, void* stream);
+
+/* Vector-Jacobian product of c3p_synth_chain: grad_env and grad_carrier as c3p_synth_signals_vjp (d/d V_to_Hz = 0 on a
+ * flux line), and
+ *   grad_line f64 [B,K,C3P_LINE_NPAR]   d loss / d {phi_0, phi, omega_0, anhar, d} in their slots (0 on a drive line);
+ *                                       the rise_time slot is 0: the tap count is a floor, rise_time is not differentiated.
+ * Every sum runs in a fixed order: repeated calls return the same bits.
+ */
+int c3p_synth_chain_vjp(const double* env_params, const int32_t* env_shapes, const double* carrier, const int32_t* line_kind,
+                        const double* line_params, double t_start, double t_end, double awg_res, double sim_res, int B,
+                        int K, int E, int flags, const double* grad_signals, double* grad_env, double* grad_carrier,
+                        double* grad_line, void* stream);
+
 /* Fidelity epilogue: overlap[b] = tr(P^T U[b] P G^+), the number behind
  * unitary_infid = 1 - |overlap/L|^2 (c3/libraries/fidelities.py:154-184, tf_unitary_overlap
  * c3/utils/tf_utils.py:330-366) and average_infid = 1 - (|overlap|^2/L + 1)/(L + 1)
