@@ -97,7 +97,7 @@ int fail(const char* fmt, ...) {
   } while (0)
 
 // Per-device workspace slots, grown lazily, freed by c3p_shutdown().
-enum Slot { SL_SEG_A = 0, SL_SEG_B, SL_SCRATCH, SL_CLP, SL_TABLES, SL_COUNTERS, SL_COUNTERS2, SL_IN0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_SEG_F, SL_SEQ_FLAG, SL_SEQ_VJP_WS, SL_SEQ_VJP_SLAB, SL_ODE_VJP_WS, SL_COUNT };
+enum Slot { SL_SEG_A = 0, SL_SEG_B, SL_SCRATCH, SL_CLP, SL_TABLES, SL_COUNTERS, SL_COUNTERS2, SL_IN0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_SEG_F, SL_SEQ_FLAG, SL_SEQ_VJP_WS, SL_SEQ_VJP_SLAB, SL_ODE_VJP_WS, SL_LMODEL_PART, SL_LMODEL_OUT, SL_COUNT };
 
 struct DeviceWs {
   std::mutex mu;  // one lock per device: calls on different GPUs of one process do not serialise
@@ -2914,6 +2914,74 @@ int c3p_gate_overlap(const void* U, int B, int D, const int32_t* comp_rows, int 
   return 0;
 }
 
+// The general-generator sweep in three VALU kernels on dense generator tables (c3p_grad.hip, general form), D^2 <= 36, one chunk
+// of nb samples.  `mo` set: the sweep also accumulates the model-operator cotangents, and the reduce kernel writes them.
+struct LindModelOut {
+  const cplx* col;  // [C,D,D]
+  int C;
+  cplx *g_h0, *g_hks, *g_col;  // [nb,D,D], [nb,K,D,D], [nb,C,D,D]
+};
+static int run_vjp_lind_valu(DeviceWs* w, const cplx* h0, int64_t h0_bstride, const cplx* hks, int64_t hks_bstride, const double* sig,
+                             const cplx* clp, double dt, int nb, int K, int N, int D, const double* ph, const cplx* ub, double* grad,
+                             const LindModelOut* mo, bool* global_out, hipStream_t st) {
+  const size_t cs = sizeof(cplx);
+  const int Dm = D * D;
+  const long gsz = (long)Dm * Dm;
+  const int nt = (h0_bstride || hks_bstride) ? nb : 1;
+  void* tab;
+  if (ws_get(w, SL_TABLES, (size_t)nt * (K + 1) * gsz * cs, &tab)) return -1;
+  LAUNCH_TRY(c3p_launch_lind_generators(h0, h0_bstride, hks, hks_bstride, clp, nt, K, D, (cplx*)tab, st));
+  GradArgs A = {};
+  A.h0 = (const cplx*)tab;
+  A.h0_bstride = nt > 1 ? (long)(K + 1) * gsz : 0;
+  A.hks = (const cplx*)tab + gsz;
+  A.hks_bstride = A.h0_bstride;
+  A.signals = sig;
+  A.fr_phase = ph;
+  A.Ubar = ub;
+  A.dt = dt;
+  A.B = nb;
+  A.K = K;
+  A.N = N;
+  A.D = Dm;
+  A.ld = Dm | 1;
+  A.grad = grad;
+  A.general = 1;
+  long S = 4096 / nb;
+  if (S > N / 8) S = N / 8;
+  if (S < 1) S = 1;
+  A.S = (int)S;
+  void* v;
+  if (ws_get(w, SL_SEG_A, (size_t)nb * A.S * gsz * cs, &v)) return -1;
+  A.seg = (cplx*)v;
+  if (ws_get(w, SL_SEG_B, (size_t)nb * A.S * gsz * cs, &v)) return -1;
+  A.Mb = (cplx*)v;
+  if (ws_get(w, SL_OUT1, ((size_t)nb * A.S + (size_t)nb * N) * gsz * cs, &v)) return -1;  // (SL_OUT0 stages grad_signals)
+  A.pre = (cplx*)v;
+  A.pstore = A.pre + (size_t)nb * A.S * gsz;
+  const bool global = c3p_grad_lds_bytes_general(Dm) > 150 * 1024;
+  *global_out = global;
+  if (global) {
+    A.scratch_stride = (long)C3P_GRAD_NMAT_GENERAL * A.ld * Dm;
+    if (ws_get(w, SL_SCRATCH, (size_t)nb * A.S * A.scratch_stride * cs, &v)) return -1;
+    A.scratch = (cplx*)v;
+  }
+  if (mo) {
+    if (ws_get(w, SL_LMODEL_PART, (size_t)nb * A.S * ((size_t)gsz + (size_t)(K + 1) * Dm) * cs, &v)) return -1;
+    A.mpart = (cplx*)v;
+    A.Dsys = D;
+  }
+  LAUNCH_TRY(c3p_launch_grad_seg(A, global, st));
+  LAUNCH_TRY(c3p_launch_grad_scan_general(A, global, st));
+  if (!mo) {
+    LAUNCH_TRY(c3p_launch_grad_bwd_general(A, global, st));
+    return 0;
+  }
+  LAUNCH_TRY(c3p_launch_grad_bwd_general_model(A, global, st));
+  LAUNCH_TRY(c3p_launch_lind_model_reduce(A.mpart, mo->col, mo->C, nb, A.S, K, D, dt, mo->g_h0, mo->g_hks, mo->g_col, st));
+  return 0;
+}
+
 int c3p_pwc_lindblad_vjp(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
                          const void* col_ops, int C, double dt, int B, int K, int N, int D, int flags, const double* fr_phase,
                          const void* U_bar, double* grad_signals, void* stream) {
@@ -3043,49 +3111,8 @@ int c3p_pwc_lindblad_vjp(const void* h0, int64_t h0_bstride, const void* hks, in
     // the same sweep in three VALU kernels on dense generator tables (c3p_grad.hip, general form): fallback and second opinion
     bool global = false;
     auto run_valu = [&](long b0, int nb) -> int {
-      const int nt = (h0_bstride || hks_bstride) ? nb : 1;
-      void* tab;
-      if (ws_get(w, SL_TABLES, (size_t)nt * (K + 1) * gsz * cs, &tab)) return -1;
-      LAUNCH_TRY(c3p_launch_lind_generators(p_h0 + b0 * h0_bstride, h0_bstride, p_hk + b0 * hks_bstride, hks_bstride, (const cplx*)clp, nt,
-                                            K, D, (cplx*)tab, st));
-      GradArgs A = {};
-      A.h0 = (const cplx*)tab;
-      A.h0_bstride = nt > 1 ? (long)(K + 1) * gsz : 0;
-      A.hks = (const cplx*)tab + gsz;
-      A.hks_bstride = A.h0_bstride;
-      A.signals = p_sig + b0 * K * N;
-      A.fr_phase = phase_at(b0);
-      A.Ubar = p_ub + b0 * gsz;
-      A.dt = dt;
-      A.B = nb;
-      A.K = K;
-      A.N = N;
-      A.D = Dm;
-      A.ld = Dm | 1;
-      A.grad = p_grad + b0 * K * N;
-      A.general = 1;
-      long S = 4096 / nb;
-      if (S > N / 8) S = N / 8;
-      if (S < 1) S = 1;
-      A.S = (int)S;
-      void* v;
-      if (ws_get(w, SL_SEG_A, (size_t)nb * A.S * gsz * cs, &v)) return -1;
-      A.seg = (cplx*)v;
-      if (ws_get(w, SL_SEG_B, (size_t)nb * A.S * gsz * cs, &v)) return -1;
-      A.Mb = (cplx*)v;
-      if (ws_get(w, SL_OUT1, ((size_t)nb * A.S + (size_t)nb * N) * gsz * cs, &v)) return -1;  // (SL_OUT0 stages grad_signals)
-      A.pre = (cplx*)v;
-      A.pstore = A.pre + (size_t)nb * A.S * gsz;
-      global = c3p_grad_lds_bytes_general(Dm) > 150 * 1024;
-      if (global) {
-        A.scratch_stride = (long)C3P_GRAD_NMAT_GENERAL * A.ld * Dm;
-        if (ws_get(w, SL_SCRATCH, (size_t)nb * A.S * A.scratch_stride * cs, &v)) return -1;
-        A.scratch = (cplx*)v;
-      }
-      LAUNCH_TRY(c3p_launch_grad_seg(A, global, st));
-      LAUNCH_TRY(c3p_launch_grad_scan_general(A, global, st));
-      LAUNCH_TRY(c3p_launch_grad_bwd_general(A, global, st));
-      return 0;
+      return run_vjp_lind_valu(w, p_h0 + b0 * h0_bstride, h0_bstride, p_hk + b0 * hks_bstride, hks_bstride, p_sig + b0 * K * N,
+                               (const cplx*)clp, dt, nb, K, N, D, phase_at(b0), p_ub + b0 * gsz, p_grad + b0 * K * N, nullptr, &global, st);
     };
     if (record_start(w, st)) return -1;
     if (in_chunks(run_valu) != 0) return -1;
@@ -3103,6 +3130,71 @@ int c3p_pwc_lindblad_vjp(const void* h0, int64_t h0_bstride, const void* hks, in
   if (run_vjp_tiled(w, 1, (const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, (const cplx*)clp, dt, B,
                     K, N, D, Dm, (const double*)d_ph, (const cplx*)d_ub, (double*)d_grad, st))
     return -1;
+  if (record_stop(w, st)) return -1;
+  if (flags & C3P_HOST_PTRS) return sg.finish();
+  return 0;
+}
+
+int c3p_pwc_lindblad_model_vjp(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
+                               const void* col_ops, int C, double dt, int B, int K, int N, int D, int flags, const double* fr_phase,
+                               const void* U_bar, double* grad_signals, void* grad_h0, void* grad_hks, void* grad_col_ops, void* stream) {
+  if (B < 0 || K <= 0 || N <= 0 || D <= 0 || C <= 0) return fail("bad sizes B=%d K=%d N=%d D=%d C=%d", B, K, N, D, C);
+  if (flags & (C3P_PER_SLICE_H | C3P_ORDER_RIGHT)) return fail("c3p_pwc_lindblad_model_vjp: unsupported flag");
+  if (D > 6)
+    return fail("c3p_pwc_lindblad_model_vjp: D=%d, the model-operator cotangents of the Lindblad path are served for D <= 6 "
+                "(superoperators up to 36 x 36)", D);
+  if (B == 0) return 0;
+  if (!h0 || !hks || !signals || !col_ops || !U_bar || !grad_h0 || !grad_hks || !grad_col_ops) return fail("NULL pointer argument");
+  if (h0_bstride < 0 || hks_bstride < 0) return fail("negative batch stride");
+  const size_t cs = sizeof(cplx);
+  const int Dm = D * D;
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  DeviceWs* w = lk.w;
+  if (!w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  Stage sg{w, st};
+  const void *d_h0 = h0, *d_hks = hks, *d_sig = signals, *d_ph = fr_phase, *d_ub = U_bar, *d_col = col_ops;
+  void* d_grad = grad_signals;
+  cplx *g_h0 = (cplx*)grad_h0, *g_hks = (cplx*)grad_hks, *g_col = (cplx*)grad_col_ops;
+  if (flags & C3P_HOST_PTRS) {
+    if (sg.in(h0, ((size_t)(B - 1) * (size_t)h0_bstride + (size_t)D * D) * cs, &d_h0)) return -1;
+    if (sg.in(hks, ((size_t)(B - 1) * (size_t)hks_bstride + (size_t)K * D * D) * cs, &d_hks)) return -1;
+    if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
+    if (sg.in(col_ops, (size_t)C * D * D * cs, &d_col)) return -1;
+    if (sg.in(U_bar, (size_t)B * Dm * Dm * cs, &d_ub)) return -1;
+    if (fr_phase && sg.in(fr_phase, (size_t)B * Dm * sizeof(double), &d_ph)) return -1;
+    if (sg.out(grad_signals, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;  // SL_OUT0 (SL_OUT1 is the sweep's store)
+    // the three operator cotangents are staged in one block of their own
+    void* blk;
+    const size_t n0 = (size_t)B * Dm, nk = (size_t)B * K * Dm, nc = (size_t)B * C * Dm;
+    if (ws_get(w, SL_LMODEL_OUT, (n0 + nk + nc) * cs, &blk)) return -1;
+    g_h0 = (cplx*)blk, g_hks = g_h0 + n0, g_col = g_hks + nk;
+    sg.backs.push_back({grad_h0, g_h0, n0 * cs});
+    sg.backs.push_back({grad_hks, g_hks, nk * cs});
+    sg.backs.push_back({grad_col_ops, g_col, nc * cs});
+  }
+  if (!d_grad) {  // grad_signals not wanted: the sweep still writes it
+    if (ws_get(w, SL_OUT0, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
+  }
+  void* clp;
+  if (ws_get(w, SL_CLP, (size_t)Dm * Dm * cs, &clp)) return -1;
+  LAUNCH_TRY(c3p_launch_clp((const cplx*)d_col, C, D, (cplx*)clp, st));
+  // chunks of samples as in c3p_pwc_lindblad_vjp: the sweep keeps 2 N D^4 complex per sample
+  long Bc = (long)(grad_store_budget(w, SL_OUT1) / (2 * (size_t)N * Dm * Dm * cs + 1));
+  if (c3p_opt(C3P_OPT_grad_chunk) > 0) Bc = c3p_opt(C3P_OPT_grad_chunk);
+  if (Bc < 1) Bc = 1;
+  bool global = false;
+  if (record_start(w, st)) return -1;
+  for (long b0 = 0; b0 < B; b0 += Bc) {
+    const int nb = (int)(B - b0 < Bc ? B - b0 : Bc);
+    const LindModelOut mo = {(const cplx*)d_col, C, g_h0 + b0 * Dm, g_hks + b0 * K * Dm, g_col + b0 * C * Dm};
+    if (run_vjp_lind_valu(w, (const cplx*)d_h0 + b0 * h0_bstride, h0_bstride, (const cplx*)d_hks + b0 * hks_bstride, hks_bstride,
+                          (const double*)d_sig + b0 * K * N, (const cplx*)clp, dt, nb, K, N, D, d_ph ? (const double*)d_ph + b0 * Dm : nullptr,
+                          (const cplx*)d_ub + b0 * (long)Dm * Dm, (double*)d_grad + b0 * K * N, &mo, &global, st))
+      return -1;
+  }
+  g_last_kernel = global ? C3P_KERNEL_GENERIC_GLOBAL : C3P_KERNEL_GENERIC_LDS;
   if (record_stop(w, st)) return -1;
   if (flags & C3P_HOST_PTRS) return sg.finish();
   return 0;

@@ -33,6 +33,9 @@ struct GradArgs {
   double* goal_infid;   // [B]
   double* goal_gphase;  // [B,D] or null: d infid / d fr_phase
   cplx* goal_U;         // [B,D,D] or null: the propagators themselves
+  // model-operator cotangents of the Lindblad path (c3p_launch_grad_bwd_general_model only)
+  cplx* mpart;  // [B,S, D^2 + (K+1) Dsys^2] partial sums of every workgroup: W0, T0, T_1 .. T_K (c3p_grad.hip)
+  int Dsys;     // system dimension, D = Dsys^2
 };
 #define C3P_GOAL_LMAX 64
 
@@ -48,6 +51,14 @@ hipError_t c3p_launch_grad_bwd(const GradArgs& A, bool global_scratch, hipStream
 size_t c3p_grad_lds_bytes_general(int D);
 hipError_t c3p_launch_grad_scan_general(const GradArgs& A, bool global_scratch, hipStream_t st);
 hipError_t c3p_launch_grad_bwd_general(const GradArgs& A, bool global_scratch, hipStream_t st);
+// the same sweep, which also leaves the partial sums of the model-operator cotangents in A.mpart (D = Dsys^2 <= C3P_MODEL_DM_MAX),
+// and the kernel that adds them in segment order and applies the adjoint of the dissipator map: grad_h0 [B,D,D],
+// grad_hks [B,K,D,D], grad_col [B,C,D,D] of the system dimension D, col [C,D,D]
+#define C3P_MODEL_DM_MAX 36
+#define C3P_MODEL_NW 6  // 36 * 36 elements of W0 on 256 threads
+hipError_t c3p_launch_grad_bwd_general_model(const GradArgs& A, bool global_scratch, hipStream_t st);
+hipError_t c3p_launch_lind_model_reduce(const cplx* mpart, const cplx* col, int C, int B, int S, int K, int D, double dt, cplx* g_h0,
+                                        cplx* g_hks, cplx* g_col, hipStream_t st);
 // dense Lindblad generators [nb][(K+1)][D^2 x D^2]: G_0 = -i (spre(h0) - spost(h0)) + clp, G_k = -i (spre(hk) - spost(hk))
 // (propagation.py:551-582); nb = B when an operator stride is non-zero, else 1
 // per-slice variant: out[b,n] = -i (spre(hs[b,n]) - spost(hs[b,n])) + clp for every slice Hamiltonian (branch B + lindbladian)

@@ -584,7 +584,16 @@ __global__ void __launch_bounds__(256) grad_scan_general_kernel(GradArgs A) {
   }
 }
 
-template <bool GLOBAL>
+// MODEL: the sweep also keeps the generator cotangent Z_n = e^{mu} dT of every slice (d loss = dt Re sum conj(Z_n) dG_n) and
+// accumulates, per workgroup (sample, segment), what the model operators need of it (Lindblad generators of lind_gen_kernel, row
+// (i,j), column (k,l), system dimension A.Dsys, A.D = Dsys^2):
+//   W0 = sum_n Z_n                                    [D^2 x D^2]  (the cotangent of the dissipator, without dt)
+//   T0 = sum_n tau(Z_n),  T_k = sum_n c_k(n) tau(Z_n)  [Dsys x Dsys] (the cotangents of h0 / hk, without dt)
+//   tau(Z)[a,b] = i (sum_j Z[(a,j),(b,j)] - sum_i Z[(i,b),(i,a)]),   the adjoint of H -> -i (H (x) 1 - 1 (x) H^T)
+// Every thread owns fixed elements (W0: up to C3P_MODEL_NW of them in registers, T: one (a,b) updated in place in the partial
+// block), the slices of a segment are added in sweep order: no atomics, the same bits on every run.  Partial block of workgroup
+// wg at A.mpart + wg * (D^4 + (K + 1) Dsys^2): W0, T0, T_1 .. T_K.
+template <bool GLOBAL, bool MODEL = false>
 __global__ void __launch_bounds__(256) grad_bwd_general_kernel(GradArgs A) {
   __shared__ Shared sh;
   const int tid = threadIdx.x, nt = blockDim.x;
@@ -626,6 +635,11 @@ __global__ void __launch_bounds__(256) grad_bwd_general_kernel(GradArgs A) {
   }
   __syncthreads();
   // backward
+  cplx w0[MODEL ? C3P_MODEL_NW : 1];
+  if constexpr (MODEL) {
+#pragma unroll
+    for (int u = 0; u < C3P_MODEL_NW; ++u) w0[u] = cmake(0, 0);
+  }
   copy_in(M, bA, A.Mb + (long)wg * D * D, D, ld, tid, nt);
   for (int n = n1 - 1; n >= n0; --n) {
     copy_in(M, bP, ps + (long)n * D * D, D, ld, tid, nt);
@@ -659,6 +673,37 @@ __global__ void __launch_bounds__(256) grad_bwd_general_kernel(GradArgs A) {
       }
       __syncthreads();
     }
+    if constexpr (MODEL) {
+      // (q.dT is read only: no barrier needed in front of the product below, which writes bV)
+#pragma unroll
+      for (int u = 0; u < C3P_MODEL_NW; ++u) {
+        const int e = tid + u * nt;
+        if (e < D * D) w0[u] = cadd(w0[u], cmul(ph, M.ld(q.dT + (e / D) * ld + (e % D))));
+      }
+      const int Ds = A.Dsys;
+      if (tid < Ds * Ds) {
+        const int a = tid / Ds, c = tid - a * Ds;
+        cplx sum = cmake(0, 0);
+        for (int j = 0; j < Ds; ++j) {
+          const cplx p = M.ld(q.dT + (a * Ds + j) * ld + (c * Ds + j));
+          const cplx m = M.ld(q.dT + (j * Ds + c) * ld + (j * Ds + a));
+          sum.x += p.x - m.x;
+          sum.y += p.y - m.y;
+        }
+        sum = cmul(ph, sum);
+        const cplx tau = cmake(-sum.y, sum.x);
+        cplx* tp = A.mpart + (long)wg * ((long)D * D + (long)(A.K + 1) * Ds * Ds) + (long)D * D + tid;
+        const double* sig = A.signals + (long)b * A.K * A.N + n;
+        const bool first = n == n1 - 1;
+        for (int k = 0; k <= A.K; ++k) {
+          const double cf = k == 0 ? 1.0 : sig[(long)(k - 1) * A.N];
+          cplx t = first ? cmake(0, 0) : tp[(long)k * Ds * Ds];
+          t.x = fma(cf, tau.x, t.x);
+          t.y = fma(cf, tau.y, t.y);
+          tp[(long)k * Ds * Ds] = t;
+        }
+      }
+    }
     if (n > n0) {
       mm(M, bV, q.T, bA, D, ld, tid, nt);  // A <- dU_n^H A
       for (int e = tid; e < D * D; e += nt) {
@@ -667,6 +712,65 @@ __global__ void __launch_bounds__(256) grad_bwd_general_kernel(GradArgs A) {
       }
       __syncthreads();
     }
+  }
+  if constexpr (MODEL) {
+    cplx* wp = A.mpart + (long)wg * ((long)D * D + (long)(A.K + 1) * A.Dsys * A.Dsys);
+#pragma unroll
+    for (int u = 0; u < C3P_MODEL_NW; ++u) {
+      const int e = tid + u * nt;
+      if (e < D * D) wp[e] = w0[u];
+    }
+  }
+}
+
+// Model-operator cotangents of the Lindblad path from the partial blocks of grad_bwd_general_kernel<., true>: one workgroup
+// per sample adds the S segment partials in segment order (the same bits on every run) and applies dt, then the adjoint of the
+// dissipator map of clp_kernel (propagation.py:570-581),  clp = sum_c C (x) C* - 1/2 (C^+C) (x) 1 - 1/2 1 (x) (C^+C)^T,
+// to W = dt W0.  With d loss = Re sum conj(grad) d(operator), every operator entry an independent complex number:
+//   R[p,q]      = sum_j W[(p,j),(q,j)] + sum_i W[(i,q),(i,p)]                       (the cotangent of C^+C is -R / 2)
+//   grad_C[a,b] = sum_jl W[(a,j),(b,l)] C[j,l] + sum_ik conj(W[(i,a),(k,b)]) C[i,k] - 1/2 (C (R + R^+))[a,b]
+__global__ void __launch_bounds__(256) lind_model_reduce_kernel(const cplx* mpart, const cplx* col, int C, int S, int K, int Ds, double dt,
+                                                                cplx* g_h0, cplx* g_hks, cplx* g_col) {
+  __shared__ cplx W[C3P_MODEL_DM_MAX * C3P_MODEL_DM_MAX];
+  __shared__ cplx R[C3P_MODEL_DM_MAX];
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int b = blockIdx.x;
+  const int Dm = Ds * Ds, nw = Dm * Dm, nh = (K + 1) * Dm;
+  const long pst = (long)nw + nh;
+  const cplx* pb = mpart + (long)b * S * pst;
+  for (int e = tid; e < nw + nh; e += nt) {
+    cplx acc = pb[e];
+    for (int s = 1; s < S; ++s) acc = cadd(acc, pb[(long)s * pst + e]);
+    acc = cscale(acc, dt);
+    if (e < nw)
+      W[e] = acc;
+    else if (e < nw + Dm)
+      g_h0[(long)b * Dm + (e - nw)] = acc;
+    else
+      g_hks[(long)b * K * Dm + (e - nw - Dm)] = acc;
+  }
+  __syncthreads();
+  for (int e = tid; e < Dm; e += nt) {
+    const int p = e / Ds, q = e - p * Ds;
+    cplx r = cmake(0, 0);
+    for (int j = 0; j < Ds; ++j) r = cadd(r, cadd(W[(p * Ds + j) * Dm + (q * Ds + j)], W[(j * Ds + q) * Dm + (j * Ds + p)]));
+    R[e] = r;
+  }
+  __syncthreads();
+  for (int e = tid; e < C * Dm; e += nt) {
+    const int c = e / Dm, ab = e - c * Dm, a = ab / Ds, bb = ab - a * Ds;
+    const cplx* Cc = col + (long)c * Dm;
+    cplx g = cmake(0, 0);
+    for (int j = 0; j < Ds; ++j)
+      for (int l = 0; l < Ds; ++l) {
+        cfma(g, W[(a * Ds + j) * Dm + (bb * Ds + l)], Cc[j * Ds + l]);
+        cfma(g, cconj(W[(j * Ds + a) * Dm + (l * Ds + bb)]), Cc[j * Ds + l]);
+      }
+    cplx h = cmake(0, 0);
+    for (int p = 0; p < Ds; ++p) cfma(h, Cc[a * Ds + p], cadd(R[p * Ds + bb], cconj(R[bb * Ds + p])));
+    g.x = fma(-0.5, h.x, g.x);
+    g.y = fma(-0.5, h.y, g.y);
+    g_col[((long)b * C + c) * Dm + ab] = g;
   }
 }
 
@@ -796,6 +900,19 @@ hipError_t c3p_launch_grad_scan_general(const GradArgs& A, bool global_scratch, 
 hipError_t c3p_launch_grad_bwd_general(const GradArgs& A, bool global_scratch, hipStream_t st) {
   return global_scratch ? launch_general(grad_bwd_general_kernel<true>, (unsigned)(A.B * A.S), A, true, st)
                         : launch_general(grad_bwd_general_kernel<false>, (unsigned)(A.B * A.S), A, false, st);
+}
+hipError_t c3p_launch_grad_bwd_general_model(const GradArgs& A, bool global_scratch, hipStream_t st) {
+  // the register accumulators of W0 cover C3P_MODEL_NW elements per thread
+  if (A.mpart == nullptr || A.Dsys * A.Dsys != A.D || A.D > C3P_MODEL_DM_MAX || A.D * A.D > C3P_MODEL_NW * c3p_grad_threads(A.D))
+    return hipErrorInvalidValue;
+  return global_scratch ? launch_general(grad_bwd_general_kernel<true, true>, (unsigned)(A.B * A.S), A, true, st)
+                        : launch_general(grad_bwd_general_kernel<false, true>, (unsigned)(A.B * A.S), A, false, st);
+}
+hipError_t c3p_launch_lind_model_reduce(const cplx* mpart, const cplx* col, int C, int B, int S, int K, int D, double dt, cplx* g_h0,
+                                        cplx* g_hks, cplx* g_col, hipStream_t st) {
+  if (D * D > C3P_MODEL_DM_MAX) return hipErrorInvalidValue;
+  C3P_LAUNCH(lind_model_reduce_kernel, dim3((unsigned)B), dim3(256), 0, st, mpart, col, C, S, K, D, dt, g_h0, g_hks, g_col);
+  return hipGetLastError();
 }
 hipError_t c3p_launch_lind_generators(const cplx* h0, long h0_bstride, const cplx* hks, long hks_bstride, const cplx* clp, int nb,
                                       int K, int D, cplx* out, hipStream_t st) {

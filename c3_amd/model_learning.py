@@ -11,6 +11,9 @@ simulated populations against the measured ones with `g_LL_prime` (libraries/est
   sequences  --c3p_matmul_chain over P x sequences-->  U_seq [P,S,D,D]  -->  |U_seq psi0|^2  -->  sim_vals [P,S]
 
 Everything up to the populations stays in HBM.  The likelihood is a few flops per value and stays on the host.
+
+Open systems (`col_ops` given): the propagators are Lindblad superoperators [P,D^2,D^2], the sequence states density vectors
+and the populations their diagonal; `thermal_initial_state` mirrors InitialiseGround (libraries/tasks.py:46-88).
 """
 from __future__ import annotations
 
@@ -20,6 +23,82 @@ import numpy as np
 
 from . import propagation
 from ._lib import C3PropError
+
+
+KB = 1.380649e-23  # libraries/constants.py
+HBAR = 1.054571817e-34
+
+
+def thermal_initial_state(h0_diag_or_h0, init_temp, lindbladian: bool = True):
+    """`InitialiseGround.initialise` (libraries/tasks.py:46-88): the initial state at temperature `init_temp` from the drift
+    Hamiltonian (a matrix, of which the diagonal is read, or that diagonal).  A finite temperature gives the Boltzmann weights
+    exp(-hbar (E_i - E_0) / (kb T)), normalised, on the diagonal of a density matrix, returned as the density vector [D^2]
+    (tf_dm_to_vec) -- this needs the Lindblad path, as in the reference; T = 0 gives the ground state, as vec(|0><0|) with
+    `lindbladian`, else as the ket [D].  Forward only: the temperature has no gradient through the initial state here."""
+    a = np.asarray(h0_diag_or_h0, dtype=np.complex128)
+    diag = np.diagonal(a) if a.ndim == 2 else a.reshape(-1)
+    dim = len(diag)
+    if abs(init_temp) > np.finfo(float).eps:
+        freq_diff = diag - diag[0]
+        beta = 1 / (init_temp * KB)
+        det_bal = np.exp(-HBAR * freq_diff * beta)
+        dm = np.diag(det_bal / np.sum(det_bal))
+        if not lindbladian:
+            raise C3PropError("C3:Error: a thermal initial state needs the Lindblad path (lindbladian=True)")
+        return dm.T.reshape(-1)
+    state = np.zeros(dim, dtype=np.complex128)
+    state[0] = 1.0
+    if lindbladian:
+        return np.outer(state, state).T.reshape(-1)
+    return state
+
+
+def _density_vector(psi_init, D: int) -> np.ndarray:
+    """vec(rho0) [D^2] from a ket [D] (vec(|psi><psi|), tf_state_to_dm / tf_dm_to_vec) or a density vector [D^2]."""
+    psi = np.asarray(psi_init, dtype=np.complex128).reshape(-1)
+    if psi.size == D * D:
+        return psi
+    if psi.size == D:
+        return np.outer(psi, psi.conj()).T.reshape(-1)
+    raise C3PropError(f"C3:Error: psi_init has {psi.size} entries, expected a ket [{D}] or a density vector [{D * D}]")
+
+
+def _check_data_sets(data_sets):
+    seqs = data_sets[0]["seqs"]
+    for d in data_sets:
+        if d["seqs"] != seqs:
+            raise C3PropError("C3:Error: batched model learning needs the same sequences for every parameter set")
+    return seqs
+
+
+def _open_system_states(h0, hks, gate_signals: Dict, dt: float, col_ops, P: int, seqs, psi_init, fr_phase, device):
+    """Superoperators S[gate] [P,D^2,D^2] by `propagate_batch(..., lindbladian=True)`, the sequence states
+    x = S_seq vec(rho0) [P,S,D^2] on the indexed path and their populations Re diag(vec_to_dm(x)) [P,S,D]
+    (experiment.py:619-622).  Returns (per-gate call arguments, S, vec(rho0), x, pops)."""
+    from . import sequences as sq
+
+    D = int(np.shape(h0)[-1])
+    rho0 = _density_vector(psi_init, D)
+    for gate, sig in gate_signals.items():
+        if int(sig.shape[0]) != P:
+            raise C3PropError(f"C3:Error: gate {gate!r} has {int(sig.shape[0])} parameter sets, but there are {P} data sets")
+    args, Us = {}, {}
+    if device is not None:
+        import torch
+
+        to = lambda v, dt_: v.to(device) if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=dt_), device=device)
+        rho0 = torch.as_tensor(rho0, device=device)
+    else:
+        to = lambda v, dt_: v
+    col = to(col_ops, np.complex128)
+    for gate, sig in gate_signals.items():
+        ph = None if fr_phase is None else fr_phase.get(gate)
+        args[gate] = (to(h0, np.complex128), to(hks, np.complex128), to(sig, np.float64), None if ph is None else to(ph, np.float64))
+        a = args[gate]
+        Us[gate] = propagation.propagate_batch(a[0], a[1], a[2], dt, col_ops=col, lindbladian=True, fr_phase=a[3])["U"]
+    x = sq.evaluate_sequences_indexed(Us, seqs, "state", rho0, superop=True)  # [P,S,D^2]
+    pops = x[..., :: D + 1].real  # the diagonal of vec_to_dm(x): entries n D + n
+    return args, col, Us, rho0, x, pops
 
 
 def g_LL_prime(exp_values, sim_values, exp_stds, shots):
@@ -140,15 +219,24 @@ def process_batch(pops, label_indices: Optional[Sequence[int]] = None):
     return pops[..., idx].sum(-1)
 
 
-def goal_run_batched(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence[Dict], psi_init, label_indices, *, fr_phase: Optional[Dict] = None, device=None) -> Dict:
+def goal_run_batched(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence[Dict], psi_init, label_indices, *, fr_phase: Optional[Dict] = None, device=None, col_ops=None) -> Dict:
     """`ModelLearning.goal_run` (modellearning.py:285-360) with the `ipar` loop as one batch.
 
     `data_sets[p]` = {"seqs": [...], "results": [...], "results_std": [...], "shots": [...]} for parameter set
     p, whose pulses are row p of every `gate_signals[gate]`.  All sets must use the same sequence list (the
     reference's `seqs_per_point`).  Returns {"goal", "goals" [P], "sim_vals" [P,S]}; the per-set goal is
     `g_LL_prime`, combined with the sequence counts as weights.
+
+    With `col_ops` [C,D,D] the system is open: Lindblad superoperators, `psi_init` a ket [D] (taken as |psi><psi|) or a density
+    vector [D^2] (`thermal_initial_state`), `fr_phase[gate]` [P,D^2], populations Re diag(vec_to_dm(S_seq vec(rho0))).
     """
     P = len(data_sets)
+    if col_ops is not None:
+        seqs = _check_data_sets(data_sets)
+        sim = process_batch(_open_system_states(h0, hks, gate_signals, dt, col_ops, P, seqs, psi_init, fr_phase, device)[-1], label_indices)
+        sim = sim.cpu().numpy() if propagation._is_torch(sim) else np.asarray(sim)
+        goals = np.array([g_LL_prime(d["results"], sim[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)])
+        return {"goal": g_LL_prime_combined(goals, [len(seqs)] * P), "goals": goals, "sim_vals": sim}
     seqs = data_sets[0]["seqs"]
     for d in data_sets:
         if d["seqs"] != seqs:
@@ -163,7 +251,7 @@ def goal_run_batched(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence
     return {"goal": g_LL_prime_combined(goals, weights), "goals": goals, "sim_vals": sim}
 
 
-def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence[Dict], psi_init, label_indices, *, fr_phase: Optional[Dict] = None, device=None) -> Dict:
+def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence[Dict], psi_init, label_indices, *, fr_phase: Optional[Dict] = None, device=None, col_ops=None) -> Dict:
     """`goal_run_batched` and the gradient of its combined goal -- what `ModelLearning.goal_run_with_grad` tapes
     (modellearning.py:362-440): model operators -> propagators -> sequence states -> label populations -> g_LL_prime,
     the per-set gradients combined by `dv_g_LL_prime`.
@@ -179,9 +267,17 @@ def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets
       "grad_h0" [P,D,D], "grad_hks" [P,K,D,D]: row p is d goal / d h0[p] (d goal = Re sum conj(grad) dh) of the COMBINED
           goal, the weights w_p / sum w folded in (a model shared by every set: sum over p, or `model_param_grads`);
       "grad_signals" {gate: [P,K,N]}; "grad_fr_phase" {gate: [P,D]} or None.
-    With `device` everything up to the populations stays there (gradients are tensors on it).  Closed systems only.
+    With `device` everything up to the populations stays there (gradients are tensors on it).
+
+    With `col_ops` [C,D,D] the system is open (D <= 6), as in `goal_run_batched`: the populations are LINEAR in the sequence
+    state x = S_seq vec(rho0), so x_bar is pop_bar on its diagonal entries n D + n; step 3 is
+    `propagate_batch_lindblad_vjp(..., want_model_grads=True)`, and the result also holds "grad_col_ops" [P,C,D,D], the cotangent
+    of the collapse operators (through which T1, T2* and the temperature of the bath act), `grad_fr_phase[gate]` is [P,D^2].
+    The initial state is a constant: no gradient flows through a thermal rho0.
     """
     P = len(data_sets)
+    if col_ops is not None:
+        return _goal_run_open_with_grad(h0, hks, gate_signals, dt, data_sets, psi_init, label_indices, fr_phase, device, col_ops)
     seqs = data_sets[0]["seqs"]
     for d in data_sets:
         if d["seqs"] != seqs:
@@ -241,10 +337,56 @@ def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets
             "grad_signals": grad_signals, "grad_fr_phase": grad_ph}
 
 
-def model_param_grads(grad_h0, grad_hks, dh0, dhks=None):
+def _goal_run_open_with_grad(h0, hks, gate_signals, dt, data_sets, psi_init, label_indices, fr_phase, device, col_ops) -> Dict:
+    """The open-system branch of `goal_run_batched_with_grad`."""
+    from . import sequences as sq
+
+    P = len(data_sets)
+    seqs = _check_data_sets(data_sets)
+    args, col, Us, rho0, x, pops = _open_system_states(h0, hks, gate_signals, dt, col_ops, P, seqs, psi_init, fr_phase, device)
+    D = int(pops.shape[-1])
+    sim = process_batch(pops, label_indices)
+    sim_h = sim.cpu().numpy() if propagation._is_torch(sim) else np.asarray(sim)
+    goals = np.array([g_LL_prime(d["results"], sim_h[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)])
+    weights = [len(seqs)] * P
+    dgs = [g_LL_prime_grad(d["results"], sim_h[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)]
+    if any(np.shape(g) != sim_h.shape[1:] for g in dgs):
+        raise C3PropError(f"C3:Error: the results of a data set do not have the shape of its simulated values {sim_h.shape[1:]}")
+    sim_bar = np.stack([w / np.sum(weights) * g for w, g in zip(weights, dgs)])
+    if label_indices is None:
+        pop_bar = sim_bar
+    else:
+        rows = np.zeros(D)
+        np.add.at(rows, list(label_indices), 1.0)  # a label listed twice counts twice, as in process_batch
+        pop_bar = sim_bar[..., None] * rows
+    # pops = Re x[n D + n]: x_bar is pop_bar on those entries (d loss = Re sum conj(x_bar) dx), zero elsewhere
+    x_bar = np.zeros(pop_bar.shape[:-1] + (D * D,), dtype=np.complex128)
+    x_bar[..., :: D + 1] = pop_bar
+    if device is not None:
+        import torch
+
+        x_bar = torch.as_tensor(x_bar, device=device)
+    U_bar = sq.evaluate_sequences_indexed_vjp(Us, seqs, "state", x_bar, rho0, superop=True)
+    grad_h0 = grad_hks = grad_col = None
+    grad_signals, grad_ph = {}, ({} if fr_phase is not None else None)
+    for gate in gate_signals:
+        a = args[gate]
+        g_sig, g0, gk, gc = propagation.propagate_batch_lindblad_vjp(a[0], a[1], a[2], dt, col, U_bar[gate], fr_phase=a[3], want_model_grads=True)
+        grad_signals[gate] = g_sig
+        grad_h0 = g0 if grad_h0 is None else grad_h0 + g0
+        grad_hks = gk if grad_hks is None else grad_hks + gk
+        grad_col = gc if grad_col is None else grad_col + gc
+        if grad_ph is not None:
+            grad_ph[gate] = None if a[3] is None else (-(U_bar[gate].conj() * Us[gate]).sum(-1).imag)
+    return {"goal": g_LL_prime_combined(goals, weights), "goals": goals, "sim_vals": sim_h, "grad_h0": grad_h0, "grad_hks": grad_hks,
+            "grad_col_ops": grad_col, "grad_signals": grad_signals, "grad_fr_phase": grad_ph}
+
+
+def model_param_grads(grad_h0, grad_hks, dh0, dhks=None, grad_col_ops=None, dcol_ops=None):
     """Gradient w.r.t. T model parameters theta from the operator cotangents of `goal_run_batched_with_grad`:
     Re sum conj(grad_h0) dh0/dtheta (+ Re sum conj(grad_hks) dhks/dtheta).  `dh0` [T,D,D] (a model shared by the P sets:
-    result [T], summed over the sets) or [P,T,D,D] (per set: result [P,T]); `dhks` [T,K,D,D] or [P,T,K,D,D], or None."""
+    result [T], summed over the sets) or [P,T,D,D] (per set: result [P,T]); `dhks` [T,K,D,D] or [P,T,K,D,D], or None.
+    Open systems: `grad_col_ops` [P,C,D,D] with `dcol_ops` [T,C,D,D] or [P,T,C,D,D] adds Re sum conj(grad_col_ops) dcol_ops/dtheta."""
     tonp = lambda a: a.detach().cpu().numpy() if propagation._is_torch(a) else np.asarray(a)
     g0, gk = tonp(grad_h0), tonp(grad_hks)
     dh0 = np.asarray(tonp(dh0), dtype=np.complex128)
@@ -253,6 +395,11 @@ def model_param_grads(grad_h0, grad_hks, dh0, dhks=None):
     if dhks is not None:
         dk = np.asarray(tonp(dhks), dtype=np.complex128)
         out = out + np.einsum("pkij,ptkij->pt" if dk.ndim == 5 else "pkij,tkij->pt", gk.conj(), dk).real
+    if (grad_col_ops is None) != (dcol_ops is None):
+        raise C3PropError("C3:Error: grad_col_ops and dcol_ops go together")
+    if dcol_ops is not None:
+        dc = np.asarray(tonp(dcol_ops), dtype=np.complex128)
+        out = out + np.einsum("pcij,ptcij->pt" if dc.ndim == 5 else "pcij,tcij->pt", tonp(grad_col_ops).conj(), dc).real
     return out if per_set else out.sum(axis=0)
 
 

@@ -508,10 +508,14 @@ def propagate_per_slice_vjp(hs, dt: float, U_bar, *, fr_phase=None):
     return (1j * dt) * Z
 
 
-def propagate_batch_lindblad_vjp(h0, hks, signals, dt: float, col_ops, U_bar, *, fr_phase=None, recheck_operators: bool = False):
+def propagate_batch_lindblad_vjp(h0, hks, signals, dt: float, col_ops, U_bar, *, fr_phase=None, recheck_operators: bool = False, want_model_grads: bool = False):
     """Vector-Jacobian product of `propagate_batch(..., lindbladian=True)` w.r.t. the control samples: the reference
     tapes tf_propagation_lind (propagation.py:551-585) under the same GradientTape (optimizers/optimizer.py:206-216).
-    `U_bar` [B,D^2,D^2] is the cotangent of the superoperators (d loss = Re sum conj(U_bar) dU); returns f64 [B,K,N]."""
+    `U_bar` [B,D^2,D^2] is the cotangent of the superoperators (d loss = Re sum conj(U_bar) dU); returns f64 [B,K,N].
+
+    `want_model_grads`: (grad_signals, grad_h0 [B,D,D], grad_hks [B,K,D,D], grad_col_ops [B,C,D,D]) through
+    c3p_pwc_lindblad_model_vjp -- per sample (sum over B for operators the batch shares), d loss = Re sum conj(grad) d(operator),
+    every operator entry an independent complex number (nothing assumed Hermitian).  D <= 6."""
     if recheck_operators:
         forget_operators(h0, hks)
     call = _Call(h0, hks, signals, U_bar, fr_phase, col_ops)
@@ -541,6 +545,16 @@ def propagate_batch_lindblad_vjp(h0, hks, signals, dt: float, col_ops, U_bar, *,
         grad = call.torch.empty((B, K, N), dtype=call.torch.float64, device=call.dev)
     else:
         grad = np.empty((B, K, N), dtype=np.float64)
+    if want_model_grads:
+        C = int(col.shape[0])
+        g0, gk, gc = call.empty((B, D, D)), call.empty((B, K, D, D)), call.empty((B, C, D, D))
+        _lib.check(
+            _lib.load().c3p_pwc_lindblad_model_vjp(
+                _ptr(h0), h0_bs, _ptr(hks), hk_bs, _ptr(signals), _ptr(col), C, float(dt), B, K, N, D, call.flags,
+                _ptr(fr_phase), _ptr(U_bar), _ptr(grad), _ptr(g0), _ptr(gk), _ptr(gc), call.stream
+            )
+        )
+        return grad, g0, gk, gc
     _lib.check(
         _lib.load().c3p_pwc_lindblad_vjp(
             _ptr(h0), h0_bs, _ptr(hks), hk_bs, _ptr(signals), _ptr(col), int(col.shape[0]), float(dt), B, K, N, D,

@@ -279,6 +279,22 @@ int c3p_pwc_lindblad_vjp(const void* h0, int64_t h0_bstride, const void* hks, in
                          const double* signals, const void* col_ops, int C, double dt, int B, int K, int N, int D,
                          int flags, const double* fr_phase, const void* U_bar, double* grad_signals, void* stream);
 
+/* The Lindblad vector-Jacobian product WITH the cotangents of the model operators, for open-system model learning (T1, T2* and
+ * temperature enter through col_ops only; the reference tapes tf_propagation_lind, c3/libraries/propagation.py:551-585, under
+ * c3/optimizers/optimizer.py:206-216).  Arguments and C3P_HOST_PTRS staging as c3p_pwc_lindblad_vjp, and
+ *   grad_signals f64 [B,K,N] or NULL (not wanted); the same arithmetic as c3p_pwc_lindblad_vjp on the VALU sweep (bitwise equal);
+ *   grad_h0 c128 [B,D,D], grad_hks c128 [B,K,D,D], grad_col_ops c128 [B,C,D,D]: PER SAMPLE (operators shared by the batch: the
+ *     caller sums over b, as with grad_h0 of c3p_pwc_unitary_vjp's gen_bar_out), d loss = Re sum conj(grad) d(operator), every
+ *     operator entry an independent complex number, nothing assumed Hermitian (the dissipator is not holomorphic in col_ops).
+ * The backward sweep of c3p_grad.hip (general-generator form, VALU) keeps the generator cotangent Z_n of every slice, contracts
+ * it to D x D per slice (the adjoint of H -> -i (H (x) 1 - 1 (x) H^T)) and adds up sum_n Z_n for the dissipator; a second kernel
+ * adds the segment partials in segment order (bitwise reproducible) and applies the adjoint of the dissipator map.
+ * Served for D <= 6 (superoperators up to 36 x 36); a larger D is an error, never a fallback. */
+int c3p_pwc_lindblad_model_vjp(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
+                               const void* col_ops, int C, double dt, int B, int K, int N, int D, int flags,
+                               const double* fr_phase, const void* U_bar, double* grad_signals, void* grad_h0, void* grad_hks,
+                               void* grad_col_ops, void* stream);
+
 /* Open-system optimiser evaluation from ONE forward pass (D = 7, 8, 9: 49 x 49 .. 81 x 81 superoperators, Hermitian Hamiltonians;
  * D = 2, 3: 4 x 4 / 9 x 9 superoperators on the small-D kernels, any Hamiltonian, up to 8 control lines -- there the tape holds
  * the generator tables, the segment products and the slice propagators; D = 4 (two qubits) with C3P_HERMITIAN_H in `flags` of
