@@ -874,7 +874,8 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
   lp.idx16 = lp.r * 4 + lp.c;
   const int K = A.K;
   double* tab = c3p_sd_lds;  // (1+K) images + scalars (table modes only; shared by the waves of a workgroup)
-  const int SG = (K * A.Lmax) | 1;
+  // (core + border real loop: one more row per chain, the weight of the drift table -- see the per-segment weights below)
+  const int SG = ((K + ((SPLIT && K > 0) ? 1 : 0)) * A.Lmax) | 1;
   double* img = tab + ((GIVEN || XG) ? 0 : (1 + K) * (MAT + 4)) + wv * (4 * IMG + 4 * SG);  // this wave's 4 chain images
   double* sg = img + 4 * IMG;  // 4 chains x K x Lmax signals, odd chain stride (bank spread)
   double* part = tab + (1 + K) * (MAT + 4) + nwv * (4 * IMG + 4 * SG);  // MW: the waves' partial products [nwv][D][D][2]
@@ -1117,39 +1118,65 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
         // chosen per segment OUTSIDE the slice loop (the loop is instantiated twice) so that neither form's registers burden the
         // other's schedule.
         const bool deg6 = __builtin_amdgcn_readfirstlane((int)(nrm * rscale <= C3P_MM6_THETA)) != 0;
-        auto split_loop = [&](auto deg6_tag) {
+        // Per-segment weights: the amplitudes of the segment are rewritten ONCE as a_k(t) = -rscale c_k(t), with one more row
+        // a_0(t) = -rscale on the segment's slices and 0 on the padded slots of a wave's shorter chains (Y = 0, E = I), so that a
+        // slice is Y = a_0 T_0 + sum_k a_k T_k: one multiply and K multiply-adds per value, no factors and no masks in the loop.
+        // The trace shift of the segment, sum_n mu_i(n) = len mu_0 + sum_k mu_k sum_t c_k(t) (mu_r = 0 for every table of a real
+        // Hamiltonian: build_tables), needs the amplitudes alone and is formed here as well, reduced as the loops reduce it.
+        {
+          double ph = 0.0;
+          for (int k = 0; k < K; ++k) {
+            const double mk = tab[(k + 1) * (MAT + 4) + MAT + 1];
+            for (int t = lp.idx16; t < A.Lmax; t += 16) {
+              const double c0 = sg[lp.b * SG + k * A.Lmax + t];  // zero past the segment's end
+              ph = c3p_phase_add(ph, c0 * mk);
+              sg[lp.b * SG + k * A.Lmax + t] = -rscale * c0;
+            }
+          }
+          if (K > 0)
+            for (int t = lp.idx16; t < A.Lmax; t += 16) sg[lp.b * SG + K * A.Lmax + t] = (valid && t < len) ? -rscale : 0.0;
+          ph = c3p_phase_add(ph, __shfl_xor(ph, 1));
+          ph = c3p_phase_add(ph, __shfl_xor(ph, 2));
+          ph = c3p_phase_add(ph, __shfl_xor(ph, 16));
+          ph = c3p_phase_add(ph, __shfl_xor(ph, 32));
+          mus_i = c3p_phase_add(ph, (double)(valid ? len : 0) * c3p_phase_add(0.0, tab[MAT + 1]));
+          wave_sync();
+        }
+        auto split_loop = [&](auto deg6_tag, auto k_tag) {
           constexpr bool DEG6 = decltype(deg6_tag)::value;  // true = the degree-6 pair, false = the degree-8 pair
+          constexpr int KC = decltype(k_tag)::value;        // K at compile time (0 .. 2); -1 = the run-time loop over the tables
+          const double* ap = sg + lp.b * SG;
           for (int t = 0; t < tmax; ++t) {
-            const bool act = valid && t < len;
-            const double sc = act ? rscale : 0.0;
-            const double muw = act ? 1.0 : 0.0;
-            double mu_r = muw * tab[MAT + 0], mu_i = muw * tab[MAT + 1];
             SM Y;
             {
-              const double f = -sc;
+              // (K = 0 has no amplitude rows: the drift weight comes from the slot's mask)
+              const double a0 = KC == 0 ? ((valid && t < len) ? -rscale : 0.0) : ap[K * A.Lmax + t];
 #pragma unroll
               for (int I = 0; I < NC; ++I) {
 #pragma unroll
-                for (int J = 0; J < NC; ++J) Y.m[I][J] = f * lds_ld(tab + so[I] + J * 4);
-                Y.vr[I] = f * lds_ld(tab + sro[I]);
-                Y.vc[I] = f * lds_ld(tab + sco[I]);
+                for (int J = 0; J < NC; ++J) Y.m[I][J] = a0 * lds_ld(tab + so[I] + J * 4);
+                Y.vr[I] = a0 * lds_ld(tab + sro[I]);
+                Y.vc[I] = a0 * lds_ld(tab + sco[I]);
               }
-              Y.s = f * lds_ld(tab + sso);
+              Y.s = a0 * lds_ld(tab + sso);
             }
-            for (int k = 0; k < K; ++k) {
-              const double c0 = sg[lp.b * SG + k * A.Lmax + t];
-              const double f = -sc * c0;
+            auto add_table = [&](int k) {
+              const double ak = ap[k * A.Lmax + t];
               const double* tk = tab + (k + 1) * (MAT + 4);
-              mu_r = fma(c0, tk[MAT + 0], mu_r);
-              mu_i = fma(c0, tk[MAT + 1], mu_i);
 #pragma unroll
               for (int I = 0; I < NC; ++I) {
 #pragma unroll
-                for (int J = 0; J < NC; ++J) Y.m[I][J] = fma(f, lds_ld(tk + so[I] + J * 4), Y.m[I][J]);
-                Y.vr[I] = fma(f, lds_ld(tk + sro[I]), Y.vr[I]);
-                Y.vc[I] = fma(f, lds_ld(tk + sco[I]), Y.vc[I]);
+                for (int J = 0; J < NC; ++J) Y.m[I][J] = fma(ak, lds_ld(tk + so[I] + J * 4), Y.m[I][J]);
+                Y.vr[I] = fma(ak, lds_ld(tk + sro[I]), Y.vr[I]);
+                Y.vc[I] = fma(ak, lds_ld(tk + sco[I]), Y.vc[I]);
               }
-              Y.s = fma(f, lds_ld(tk + sso), Y.s);
+              Y.s = fma(ak, lds_ld(tk + sso), Y.s);
+            };
+            if constexpr (KC >= 0) {
+#pragma unroll
+              for (int k = 0; k < KC; ++k) add_table(k);
+            } else {
+              for (int k = 0; k < K; ++k) add_table(k);
             }
             SM W1, W2, W3, Cm, Sp, acc, acs;
             s8_zero(W1), s8_zero(W2), s8_zero(W3);
@@ -1257,19 +1284,26 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
               }
               Gr.s = Cm.s;
               Gi.s = -acc.s;
-              mus_r = mu_r;
-              mus_i = c3p_phase_add(0.0, mu_i);
             } else {
               chain_step8(Cm, acc, Gr, Gi, lp, tail_lane, row0_lane);
-              mus_r += mu_r;
-              mus_i = c3p_phase_add(mus_i, mu_i);
             }
           }
         };
+        // (both choices are made per segment OUTSIDE the slice loop; K > 2 keeps the run-time loop over the tables)
+        auto split_loop_k = [&](auto deg6_tag) {
+          if (K == 2)
+            split_loop(deg6_tag, std::integral_constant<int, 2>{});
+          else if (K == 1)
+            split_loop(deg6_tag, std::integral_constant<int, 1>{});
+          else if (K == 0)
+            split_loop(deg6_tag, std::integral_constant<int, 0>{});
+          else
+            split_loop(deg6_tag, std::integral_constant<int, -1>{});
+        };
         if (deg6)
-          split_loop(std::true_type{});
+          split_loop_k(std::true_type{});
         else
-          split_loop(std::false_type{});
+          split_loop_k(std::false_type{});
         // back to the complex half-image layout of the epilogue (once per segment, through the chain's image)
         wave_sync();
         for (int e = lp.idx16; e < 4 * NBI * W; e += 16) img[lp.b * IMG + e] = 0.0;
@@ -1968,6 +2002,9 @@ hipError_t launch_chain_t(const SmallArgs& A, hipStream_t st) {
     lds = (size_t)(4 * C::IMG) * sizeof(double);
   else
     lds = (size_t)((1 + A.K) * (C::MAT + 4) + 4 * C::IMG + 4 * ((A.K * A.Lmax) | 1)) * sizeof(double);
+  // the core + border real loop (D = 5, 9) keeps one more amplitude row per chain: the weights of the drift table
+  const bool split81 = (D == 9 || D == 5) && !c3p_opt_on(C3P_OPT_no_split81);
+  const int krows = A.K + ((split81 && A.K > 0) ? 1 : 0);
   if (lds > 60 * 1024) return hipErrorInvalidValue;
   if (A.mode == C3P_MODE_EXPM) {
     if (A.dUs_out)
@@ -1982,7 +2019,7 @@ hipError_t launch_chain_t(const SmallArgs& A, hipStream_t st) {
     // one workgroup per sample (MW) when the S / 4 waves of a sample fit a CU together with enough other samples for all
     // B workgroups to be resident at once (8 waves per CU at two per SIMD): B = 256, S = 32 -> 256 workgroups of 8 waves
     const int nW = A.S >> 2;
-    const size_t wstride = (size_t)(4 * C::IMG + 4 * ((A.K * A.Lmax) | 1));
+    const size_t wstride = (size_t)(4 * C::IMG + 4 * ((krows * A.Lmax) | 1));
     const size_t lds_mw = (size_t)((1 + A.K) * (C::MAT + 4) + nW * wstride + (size_t)nW * D * D * 2) * sizeof(double);
     const bool mw = A.fuse && (A.S & 3) == 0 && (nW == 2 || nW == 4 || nW == 8) && (long)A.B * nW <= 2048 &&
                     lds_mw * (8 / nW) <= (size_t)156 * 1024 && !c3p_opt_on(C3P_OPT_no_mw);
@@ -2016,7 +2053,7 @@ hipError_t launch_chain_t(const SmallArgs& A, hipStream_t st) {
           A2.Lmax = lmax;
         }
       }
-      const size_t wstride2 = (size_t)(4 * C::IMG + 4 * ((A2.K * A2.Lmax) | 1));
+      const size_t wstride2 = (size_t)(4 * C::IMG + 4 * ((krows * A2.Lmax) | 1));
       const size_t lds_mw2 = (size_t)((1 + A2.K) * (C::MAT + 4) + nW * wstride2 + (size_t)nW * D * D * 2) * sizeof(double);
       if (lds_mw2 > (size_t)156 * 1024) A2 = A;  // (the longer segments need more LDS for their control amplitudes)
       const size_t lds_use = A2.seg_long > 0 ? lds_mw2 : lds_mw;
@@ -2035,7 +2072,9 @@ hipError_t launch_chain_t(const SmallArgs& A, hipStream_t st) {
       if constexpr (D == 9 || D == 5) {
         if (!c3p_opt_on(C3P_OPT_no_split81)) kern1 = smalld_chain_kernel<D, false, false, false, false, true>;
       }
-      C3P_LAUNCH(kern1, dim3(grid), dim3(64), lds, st, A);
+      const size_t lds1 = (size_t)((1 + A.K) * (C::MAT + 4) + 4 * C::IMG + 4 * ((krows * A.Lmax) | 1)) * sizeof(double);
+      if (lds1 > 60 * 1024) return hipErrorInvalidValue;
+      C3P_LAUNCH(kern1, dim3(grid), dim3(64), lds1, st, A);
     }
   }
   return hipGetLastError();
