@@ -199,6 +199,23 @@ int ws_get(DeviceWs* w, Slot s, size_t bytes, void** out) {
   return 0;
 }
 
+// the timing event pair of c3p_last_kernel_ms around a call's main kernel(s); armed by c3p_set_profiling
+int record_start(DeviceWs* w, hipStream_t st) {
+  if (!w->profiling || g_dry) return 0;
+  if (!w->ev0) {
+    HIP_TRY(hipEventCreate(&w->ev0));
+    HIP_TRY(hipEventCreate(&w->ev1));
+  }
+  HIP_TRY(hipEventRecord(w->ev0, st));
+  return 0;
+}
+int record_stop(DeviceWs* w, hipStream_t st) {
+  if (!w->profiling || g_dry) return 0;
+  HIP_TRY(hipEventRecord(w->ev1, st));
+  w->ev_valid = true;
+  return 0;
+}
+
 struct ChainPlan {
   int S, seg_len;
   bool global_scratch;
@@ -231,7 +248,6 @@ ChainPlan plan_generic(int B, int N, int Dm) {
 // `profile` = false keeps the timing event pair (and c3p_last_kernel) on the caller's main kernel.
 int run_chain_generic(DeviceWs* w, ChainArgs base, cplx* U_out, hipStream_t st, bool profile = true) {
   const int Dm = base.Dm;
-  profile = profile && w->profiling && !g_dry;
   // GIVEN mode callers may hand over matrices that live in one of the two segment slots (the segment products of the
   // big-D kernels): this launch must not write its own segment products into the buffer it is reading (and ws_get
   // must not re-allocate it), so it starts on the OTHER slot.
@@ -259,18 +275,9 @@ int run_chain_generic(DeviceWs* w, ChainArgs base, cplx* U_out, hipStream_t st, 
     base.scratch = (cplx*)v;
   }
   g_last_kernel = p.global_scratch ? C3P_KERNEL_GENERIC_GLOBAL : C3P_KERNEL_GENERIC_LDS;
-  if (profile) {
-    if (!w->ev0) {
-      HIP_TRY(hipEventCreate(&w->ev0));
-      HIP_TRY(hipEventCreate(&w->ev1));
-    }
-    HIP_TRY(hipEventRecord(w->ev0, st));
-  }
+  if (profile && record_start(w, st)) return -1;
   LAUNCH_TRY(c3p_launch_chain_generic(base, p.global_scratch, st));
-  if (profile) {
-    HIP_TRY(hipEventRecord(w->ev1, st));
-    w->ev_valid = true;
-  }
+  if (profile && record_stop(w, st)) return -1;
   // ordered combine of the S segment products: groups of 8 until <= 16 remain
   int count = p.S;
   cplx* cur = seg;
@@ -335,29 +342,114 @@ static inline bool tiled_unitary_grad(int D, int B) {
   return valu > tiled;
 }
 
-int record_start(DeviceWs* w, hipStream_t st) {
-  if (!w->profiling || g_dry) return 0;
-  if (!w->ev0) {
-    HIP_TRY(hipEventCreate(&w->ev0));
-    HIP_TRY(hipEventCreate(&w->ev1));
+// One piecewise-constant call after staging: device pointers and sizes.  A batch stride of 0 means one operator set shared
+// by all samples.  Every runner below takes this record; the sample chunks of the gradient entry points are cut here only.
+struct PwcProblem {
+  const cplx* h0;
+  long h0_bs;
+  const cplx* hks;
+  long hk_bs;
+  const double* signals;  // [B,K,N]
+  const cplx* clp;        // Lindblad dissipator [Dm,Dm] or null
+  double dt;
+  int B, K, N, D, Dm, lindblad;
+  const double* fr_phase;  // [B,Dm] or null
+  bool per_sample() const { return h0_bs != 0 || hk_bs != 0; }
+  int nsamp() const { return per_sample() ? B : 1; }  // operator sets (tables) of the call
+  // the problem of samples [b0, b0 + nb)
+  PwcProblem chunk(long b0, int nb) const {
+    PwcProblem c = *this;
+    c.h0 += b0 * h0_bs;
+    c.hks += b0 * hk_bs;
+    c.signals += b0 * K * N;
+    if (fr_phase) c.fr_phase += b0 * Dm;
+    c.B = nb;
+    return c;
   }
-  HIP_TRY(hipEventRecord(w->ev0, st));
-  return 0;
+};
+// the per-sample cotangents and results of a gradient call at sample b0: U_bar [B,Dm,Dm], grad_signals [B,K,N] and the model-operator
+// cotangents of the Lindblad path
+const cplx* ubar_at(const PwcProblem& P, const cplx* U_bar, long b0) { return U_bar + b0 * (long)P.Dm * P.Dm; }
+double* grad_at(const PwcProblem& P, double* grad_signals, long b0) { return grad_signals + b0 * P.K * P.N; }
+struct LindModelOut {
+  const cplx* col;  // [C,D,D]
+  int C;
+  cplx *g_h0, *g_hks, *g_col;  // [nb,D,D], [nb,K,D,D], [nb,C,D,D]
+  LindModelOut at(const PwcProblem& P, long b0) const {
+    const long dd = (long)P.D * P.D;
+    return {col, C, g_h0 + b0 * dd, g_hks + b0 * P.K * dd, g_col + b0 * C * dd};
+  }
+};
+// elements of a batched operand as staged from the host: `one` per sample, `stride` apart (0 = shared: one copy)
+size_t staged_elems(int B, int64_t stride, size_t one) { return (size_t)(B - 1) * (size_t)stride + one; }
+
+// The table-build arguments of the three kernel families, from the record; a site adds what is its own (tables, conjT, counters).
+PrepArgs prep_args(const PwcProblem& P) {
+  PrepArgs p = {};
+  p.h0 = P.h0;
+  p.h0_bstride = P.h0_bs;
+  p.hks = P.hks;
+  p.hks_bstride = P.hk_bs;
+  p.clp = P.clp;
+  p.dt = P.dt;
+  p.K = P.K;
+  p.Dh = P.D;
+  p.lindblad = P.lindblad;
+  return p;
 }
-int record_stop(DeviceWs* w, hipStream_t st) {
-  if (!w->profiling || g_dry) return 0;
-  HIP_TRY(hipEventRecord(w->ev1, st));
-  w->ev_valid = true;
-  return 0;
+MidPrepArgs mid_prep_args(const PwcProblem& P, int nig, int wd) {
+  MidPrepArgs p = {};
+  p.h0 = P.h0;
+  p.h0_bstride = P.h0_bs;
+  p.hks = P.hks;
+  p.hks_bstride = P.hk_bs;
+  p.clp = P.clp;
+  p.dt = P.dt;
+  p.K = P.K;
+  p.Dh = P.D;
+  p.Dm = P.Dm;
+  p.lindblad = P.lindblad;
+  p.rows = 16 * nig;
+  p.W = wd;
+  return p;
+}
+RegdPrepArgs regd_prep_args(const PwcProblem& P) {
+  RegdPrepArgs p = {};
+  p.h0 = P.h0;
+  p.h0_bstride = P.h0_bs;
+  p.hks = P.hks;
+  p.hks_bstride = P.hk_bs;
+  p.clp = P.clp;
+  p.dt = P.dt;
+  p.K = P.K;
+  p.Dh = P.D;
+  p.Dm = P.Dm;
+  p.lindblad = P.lindblad;
+  return p;
+}
+// What every table-driven chain and sweep launch takes from the record, on S segments.  Nothing else: mode, no_t18, no_t18n and
+// no_real are set by some sites and left zero by others.
+template <class Args>
+void fill_chain(Args& a, const PwcProblem& P, long S) {
+  a.tab_per_sample = P.per_sample() ? 1 : 0;
+  a.signals = P.signals;
+  a.B = P.B;
+  a.K = P.K;
+  a.N = P.N;
+  a.Dm = P.Dm;
+  a.S = (int)S;
+  a.Lmax = (int)((P.N + S - 1) / S);
 }
 
-// ordered combine of `count` matrices per sample (cur: [B,count,Dm,Dm]) into U_out
-int combine_smalld(DeviceWs* w, const cplx* cur, int B, int count, int Dm, int right_order,
-                   const double* fr_phase, cplx* U_out, hipStream_t st) {
+// ordered combine of `count` matrices per sample (cur: [B,count,Dm,Dm]) into U_out on the supplied-matrix mode of a chain kernel
+// (launch: c3p_launch_smalld_chain at Dm <= 12, c3p_launch_midd_chain at 13 <= Dm <= 40)
+template <class Args>
+int combine_chain(hipError_t (*launch)(const Args&, hipStream_t), DeviceWs* w, const cplx* cur, int B, int count, int Dm, int right_order,
+                  const double* fr_phase, cplx* U_out, hipStream_t st) {
   const size_t msz = (size_t)Dm * Dm * sizeof(cplx);
   Slot next_slot = SL_SEG_B;
   while (true) {
-    SmallArgs c = {};
+    Args c = {};
     c.mode = C3P_MODE_GIVEN;
     c.mats = cur;
     c.B = B;
@@ -375,7 +467,7 @@ int combine_smalld(DeviceWs* w, const cplx* cur, int B, int count, int Dm, int r
       c.seg_out = (cplx*)v;
     }
     c.Lmax = (count + c.S - 1) / c.S;
-    LAUNCH_TRY(c3p_launch_smalld_chain(c, st));
+    LAUNCH_TRY(launch(c, st));
     if (c.seg_out == U_out) break;
     cur = c.seg_out;
     count = c.S;
@@ -423,7 +515,6 @@ int pick_segments(int B, int N, int K, int Dm, bool need_mult4, long slots = 819
 // in the Hermitian basis on the small-D tile layout (c3p_smallr.hip).  Real generator tables -> segment products (turned back
 // into the reference's vectorisation by the chain that formed them) -> ordered product with the frame phases (the
 // supplied-matrix mode of the complex small-D chain kernel).  Returns 1 when not applicable.
-int combine_midd(DeviceWs* w, const cplx* cur, int B, int count, int Dm, int right_order, const double* fr_phase, cplx* U_out, hipStream_t st);
 // segments of the real Hermitian-basis kernels at Dm = 16 (two qubits; one wavefront = four chains, one wavefront per SIMD:
 // 4096 chain slots): the S that minimises rounds x segment length within the LDS of both kernels; -1 = none
 int pick_segments_r(int B, int N, int K, int Dm, bool need_mult4, bool with_grad) {
@@ -449,14 +540,14 @@ int pick_segments_r(int B, int N, int K, int Dm, bool need_mult4, bool with_grad
   }
   return (int)best;
 }
-int run_pwc_smallr(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs, const double* signals, const cplx* clp, double dt,
-                   int B, int K, int N, int D, int Dm, const double* fr_phase, cplx* U_out, hipStream_t st) {
-  const bool per_sample = (h0_bs != 0) || (hk_bs != 0);
+int run_pwc_smallr(DeviceWs* w, const PwcProblem& P, cplx* U_out, hipStream_t st) {
+  const int B = P.B, K = P.K, N = P.N, Dm = P.Dm;
+  const bool per_sample = P.per_sample();
   int S = Dm > 12 ? pick_segments_r(B, N, K, Dm, per_sample, false) : pick_segments(B, N, K, Dm, per_sample);
   if (S < 0) return 1;
   while (S < N && c3p_smallr_lds_bytes(Dm, K, (N + S - 1) / S) > (size_t)60 * 1024) S += per_sample ? 4 : 1;
   if (c3p_smallr_lds_bytes(Dm, K, (N + S - 1) / S) > (size_t)60 * 1024) return 1;
-  const int nsamp = per_sample ? B : 1;
+  const int nsamp = P.nsamp();
   const size_t tdoubles = (size_t)nsamp * c3p_smallr_table_doubles(Dm, K);
   const size_t fl_off = (tdoubles * sizeof(double) + 255) & ~(size_t)255;
   void *tv, *sv;
@@ -464,29 +555,11 @@ int run_pwc_smallr(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, lon
   if (ws_get(w, SL_SEG_A, (size_t)B * S * Dm * Dm * sizeof(cplx), &sv)) return -1;
   double* tabs = (double*)tv;
   int* flags = reinterpret_cast<int*>(static_cast<char*>(tv) + fl_off);
-  RegdPrepArgs p = {};
-  p.h0 = h0;
-  p.h0_bstride = h0_bs;
-  p.hks = hks;
-  p.hks_bstride = hk_bs;
-  p.clp = clp;
-  p.dt = dt;
-  p.K = K;
-  p.Dh = D;
-  p.Dm = Dm;
-  p.lindblad = 1;
-  LAUNCH_TRY(c3p_launch_smallr_prep(p, nsamp, tabs, flags, st));
+  LAUNCH_TRY(c3p_launch_smallr_prep(regd_prep_args(P), nsamp, tabs, flags, st));
   SmallRArgs a = {};
   a.no_t18n = opt_no_t18n();
   a.tables = tabs;
-  a.tab_per_sample = per_sample ? 1 : 0;
-  a.signals = signals;
-  a.B = B;
-  a.K = K;
-  a.N = N;
-  a.Dm = Dm;
-  a.S = S;
-  a.Lmax = (N + S - 1) / S;
+  fill_chain(a, P, S);
   a.seg_out = (cplx*)sv;
   g_last_kernel = C3P_KERNEL_SMALLD;
   if (record_start(w, st)) return -1;
@@ -494,23 +567,19 @@ int run_pwc_smallr(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, lon
   if (record_stop(w, st)) return -1;
   if (Dm > 12) {
     g_last_kernel = C3P_KERNEL_MFMA;
-    const int keep = g_last_kernel;
-    const int rc = combine_midd(w, (const cplx*)sv, B, S, Dm, 0, fr_phase, U_out, st);
-    g_last_kernel = keep;
-    return rc ? -1 : 0;
+    return combine_chain(c3p_launch_midd_chain, w, (const cplx*)sv, B, S, Dm, 0, P.fr_phase, U_out, st) ? -1 : 0;
   }
-  return combine_smalld(w, (const cplx*)sv, B, S, Dm, 0, fr_phase, U_out, st) ? -1 : 0;
+  return combine_chain(c3p_launch_smalld_chain, w, (const cplx*)sv, B, S, Dm, 0, P.fr_phase, U_out, st) ? -1 : 0;
 }
 
-int run_pwc_smalld(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs,
-                   const double* signals, const cplx* clp, double dt, int B, int K, int N, int D, int Dm,
-                   const double* fr_phase, cplx* U_out, cplx* dUs_out, hipStream_t st) {
-  const bool per_sample = (h0_bs != 0) || (hk_bs != 0);
-  const int S = pick_segments(B, N, K, Dm, per_sample);
+int run_pwc_smalld(DeviceWs* w, const PwcProblem& P, cplx* U_out, cplx* dUs_out, hipStream_t st) {
+  const int B = P.B, K = P.K, N = P.N, Dm = P.Dm;
+  const double* fr_phase = P.fr_phase;
+  const int S = pick_segments(B, N, K, Dm, P.per_sample());
   if (S < 0) return 1;  // not applicable -> caller falls back to the generic kernel
-  const int nsamp = per_sample ? B : 1;
+  const int nsamp = P.nsamp();
   const bool fuse = (S > 1) && (S % 4 == 0) && !c3p_opt_on(C3P_OPT_no_fuse);
-  const bool inline_tables = !lindblad && !c3p_opt_on(C3P_OPT_prep_kernel);
+  const bool inline_tables = !P.lindblad && !c3p_opt_on(C3P_OPT_prep_kernel);
   int* counters = nullptr;
   if (fuse) {
     void* cv;
@@ -522,37 +591,21 @@ int run_pwc_smalld(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const 
   if (inline_tables) {
     // unitary mode: the chain kernel builds its tables itself (no dependent launch in front of it)
     a.inline_tables = 1;
-    a.h0 = h0;
-    a.h0_bstride = h0_bs;
-    a.hks = hks;
-    a.hks_bstride = hk_bs;
-    a.dt = dt;
+    a.h0 = P.h0;
+    a.h0_bstride = P.h0_bs;
+    a.hks = P.hks;
+    a.hks_bstride = P.hk_bs;
+    a.dt = P.dt;
   } else {
     void* v;
     if (ws_get(w, SL_TABLES, (size_t)nsamp * c3p_smalld_table_doubles(Dm, K) * sizeof(double), &v)) return -1;
-    PrepArgs p = {};
-    p.h0 = h0;
-    p.h0_bstride = h0_bs;
-    p.hks = hks;
-    p.hks_bstride = hk_bs;
-    p.clp = clp;
-    p.dt = dt;
-    p.K = K;
-    p.Dh = D;
-    p.lindblad = lindblad;
+    PrepArgs p = prep_args(P);
     p.tables = (double*)v;
     LAUNCH_TRY(c3p_launch_smalld_prep(p, Dm, nsamp, st));
     a.tables = (const double*)v;
   }
-  a.tab_per_sample = per_sample ? 1 : 0;
-  a.signals = signals;
-  a.B = B;
-  a.K = K;
-  a.N = N;
-  a.Dm = Dm;
-  a.S = S;
-  a.Lmax = (N + S - 1) / S;
-  a.mode = lindblad ? C3P_MODE_LINDBLAD : C3P_MODE_UNITARY;
+  fill_chain(a, P, S);
+  a.mode = P.lindblad ? C3P_MODE_LINDBLAD : C3P_MODE_UNITARY;
   a.dUs_out = dUs_out;
   if (S == 1) {
     a.seg_out = U_out;
@@ -572,12 +625,9 @@ int run_pwc_smalld(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const 
   if (record_start(w, st)) return -1;
   LAUNCH_TRY(c3p_launch_smalld_chain(a, st));
   if (record_stop(w, st)) return -1;
-  if (S > 1 && !fuse) return combine_smalld(w, a.seg_out, B, S, Dm, 0, fr_phase, U_out, st);
+  if (S > 1 && !fuse) return combine_chain(c3p_launch_smalld_chain, w, a.seg_out, B, S, Dm, 0, fr_phase, U_out, st);
   return 0;
 }
-
-int combine_midd(DeviceWs* w, const cplx* cur, int B, int count, int Dm, int right_order, const double* fr_phase,
-                 cplx* U_out, hipStream_t st);
 
 // Gradient on the mid-D MFMA kernels (13 <= D <= 40): tables, forward segment products (chain kernel, no
 // combine), the per-sample scan of c3p_grad.hip, then the pair-T18 backward sweep.  1 = not applicable.
@@ -738,7 +788,7 @@ int run_xg_midd(DeviceWs* w, const cplx* hs, long hs_bstride, double coef_r, dou
   if (record_start(w, st)) return -1;
   LAUNCH_TRY(c3p_launch_midd_chain(a, st));
   if (record_stop(w, st)) return -1;
-  if (S > 1) return combine_midd(w, a.seg_out, B, (int)S, D, 0, fr_phase, U_out, st);
+  if (S > 1) return combine_chain(c3p_launch_midd_chain, w, a.seg_out, B, (int)S, D, 0, fr_phase, U_out, st);
   return 0;
 }
 
@@ -787,7 +837,7 @@ int run_xg_smalld(DeviceWs* w, const cplx* hs, long hs_bstride, double coef_r, d
   if (record_start(w, st)) return -1;
   LAUNCH_TRY(c3p_launch_smalld_chain(a, st));
   if (record_stop(w, st)) return -1;
-  if (S > 1 && !fuse) return combine_smalld(w, a.seg_out, B, S, D, 0, fr_phase, U_out, st);
+  if (S > 1 && !fuse) return combine_chain(c3p_launch_smalld_chain, w, a.seg_out, B, S, D, 0, fr_phase, U_out, st);
   return 0;
 }
 
@@ -919,21 +969,11 @@ int lind_small_segments(int B, int K, int N, int Dm, bool need_mult4) {
     return -1;
   return S;
 }
-int lind_small_forward(DeviceWs* w, const LindSmallBufs& bf, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs, const double* signals,
-                       const cplx* clp, double dt, int B, int K, int N, int D, int Dm, int S, bool hermitian, hipStream_t st) {
-  const bool per_sample = (h0_bs != 0) || (hk_bs != 0);
-  const int nsamp = per_sample ? B : 1;
+int lind_small_forward(DeviceWs* w, const LindSmallBufs& bf, const PwcProblem& P, int S, bool hermitian, hipStream_t st) {
+  const int K = P.K, N = P.N, D = P.D, Dm = P.Dm;
+  const int nsamp = P.nsamp();
   const size_t tdoubles = (size_t)nsamp * c3p_smalld_table_doubles(Dm, K);
-  PrepArgs p = {};
-  p.h0 = h0;
-  p.h0_bstride = h0_bs;
-  p.hks = hks;
-  p.hks_bstride = hk_bs;
-  p.clp = clp;
-  p.dt = dt;
-  p.K = K;
-  p.Dh = D;
-  p.lindblad = 1;
+  PrepArgs p = prep_args(P);
   p.tables = bf.tabs;
   LAUNCH_TRY(c3p_launch_smalld_prep(p, Dm, nsamp, st));
   p.conjT = 1;
@@ -947,29 +987,11 @@ int lind_small_forward(DeviceWs* w, const LindSmallBufs& bf, const cplx* h0, lon
     const size_t fl_off = (rdoubles * sizeof(double) + 255) & ~(size_t)255;
     void* tv;
     if (ws_get(w, SL_TABLES, fl_off + (size_t)nsamp * (1 + K) * sizeof(int), &tv)) return -1;
-    RegdPrepArgs rp = {};
-    rp.h0 = h0;
-    rp.h0_bstride = h0_bs;
-    rp.hks = hks;
-    rp.hks_bstride = hk_bs;
-    rp.clp = clp;
-    rp.dt = dt;
-    rp.K = K;
-    rp.Dh = D;
-    rp.Dm = Dm;
-    rp.lindblad = 1;
-    LAUNCH_TRY(c3p_launch_smallr_prep(rp, nsamp, (double*)tv, reinterpret_cast<int*>(static_cast<char*>(tv) + fl_off), st));
+    LAUNCH_TRY(c3p_launch_smallr_prep(regd_prep_args(P), nsamp, (double*)tv, reinterpret_cast<int*>(static_cast<char*>(tv) + fl_off), st));
     SmallRArgs ra = {};
     ra.no_t18n = opt_no_t18n();
     ra.tables = (const double*)tv;
-    ra.tab_per_sample = per_sample ? 1 : 0;
-    ra.signals = signals;
-    ra.B = B;
-    ra.K = K;
-    ra.N = N;
-    ra.Dm = Dm;
-    ra.S = S;
-    ra.Lmax = (N + S - 1) / S;
+    fill_chain(ra, P, S);
     ra.seg_out = bf.seg;
     ra.dUs_out = bf.dus;
     LAUNCH_TRY(c3p_launch_smallr_chain(ra, st));
@@ -978,23 +1000,17 @@ int lind_small_forward(DeviceWs* w, const LindSmallBufs& bf, const cplx* h0, lon
   SmallArgs a = {};
   a.no_t18n = opt_no_t18n();
   a.tables = bf.tabs;
-  a.tab_per_sample = per_sample ? 1 : 0;
-  a.signals = signals;
-  a.B = B;
-  a.K = K;
-  a.N = N;
-  a.Dm = Dm;
-  a.S = S;
-  a.Lmax = (N + S - 1) / S;
+  fill_chain(a, P, S);
   a.mode = C3P_MODE_LINDBLAD;
   a.seg_out = bf.seg;
   a.dUs_out = bf.dus;
   LAUNCH_TRY(c3p_launch_smalld_chain(a, st));
   return 0;
 }
-int lind_small_backward(DeviceWs* w, const LindSmallBufs& bf, bool per_sample, const double* signals, int B, int K, int N, int Dm, int S,
-                        const double* fr_phase, const cplx* Ubar, double* grad, hipStream_t st) {
-  const int nsamp = per_sample ? B : 1;
+// (the backward halves read the sizes, the signals, the frame phases and per_sample() of the record: the operators are in the tables)
+int lind_small_backward(DeviceWs* w, const LindSmallBufs& bf, const PwcProblem& P, int S, const cplx* Ubar, double* grad, hipStream_t st) {
+  const int B = P.B, K = P.K, N = P.N, Dm = P.Dm;
+  const int nsamp = P.nsamp();
   const size_t tdoubles = (size_t)nsamp * c3p_smalld_table_doubles(Dm, K);
   const size_t msz = (size_t)Dm * Dm * sizeof(cplx);
   void *mv, *bv;
@@ -1004,7 +1020,7 @@ int lind_small_backward(DeviceWs* w, const LindSmallBufs& bf, bool per_sample, c
   cplx* pstore = pre + (size_t)B * S * Dm * Dm;
   GradArgs G = {};
   G.Ubar = Ubar;
-  G.fr_phase = fr_phase;
+  G.fr_phase = P.fr_phase;
   G.B = B;
   G.K = K;
   G.N = N;
@@ -1019,19 +1035,12 @@ int lind_small_backward(DeviceWs* w, const LindSmallBufs& bf, bool per_sample, c
   SmallGradArgs g = {};
   g.tables = bf.tabs;
   g.tables_h = bf.tabs + tdoubles;
-  g.tab_per_sample = per_sample ? 1 : 0;
-  g.signals = signals;
+  fill_chain(g, P, S);
   g.Mb = G.Mb;
   g.pre = pre;
   g.dUs = bf.dus;
   g.pstore = pstore;
   g.grad = grad;
-  g.B = B;
-  g.K = K;
-  g.N = N;
-  g.Dm = Dm;
-  g.S = S;
-  g.Lmax = (N + S - 1) / S;
   LAUNCH_TRY(c3p_launch_smalld_grad_general(g, st));
   return 0;
 }
@@ -1039,13 +1048,9 @@ int lind_small_backward(DeviceWs* w, const LindSmallBufs& bf, bool per_sample, c
 // real tables of G' and G'^T, real segment products and slice propagators from the forward half; the cotangent in the basis
 // (hb_ubar), the real segment scan and the real pair-evaluation sweep in the backward half.  The block is laid out inside
 // the memory the complex halves would use (it is smaller in every part).
-struct LindSmallRSizes {
-  size_t tabs, seg, dus;
-  size_t total() const { return tabs + seg + dus; }
-};
-LindSmallRSizes lind_smallr_sizes(int B, int K, int N, int Dm, int S, int nsamp) {
+LindSmallSizes lind_smallr_sizes(int B, int K, int N, int Dm, int S, int nsamp) {  // tables with their flags, real segment products and slice propagators
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  LindSmallRSizes z;
+  LindSmallSizes z;
   z.tabs = up(2 * (size_t)nsamp * c3p_smallr_table_doubles(Dm, K) * sizeof(double)) + up((size_t)nsamp * (1 + K) * sizeof(int));
   z.seg = up((size_t)B * S * Dm * Dm * sizeof(double));
   z.dus = up((size_t)B * N * Dm * Dm * sizeof(double));
@@ -1056,7 +1061,7 @@ struct LindSmallRBufs {
   int* flags;
   double *seg, *dus;
 };
-LindSmallRBufs lind_smallr_carve(void* base, const LindSmallRSizes& z, int nsamp, int Dm, int K) {
+LindSmallRBufs lind_smallr_carve(void* base, const LindSmallSizes& z, int nsamp, int Dm, int K) {
   char* p = static_cast<char*>(base);
   const size_t td = (size_t)nsamp * c3p_smallr_table_doubles(Dm, K);
   LindSmallRBufs b;
@@ -1072,149 +1077,84 @@ bool lind_smallr_ok(bool hermitian, int D, int Dm, int K, int N, int S) {
          c3p_smallr_lds_bytes(Dm, K, (N + S - 1) / S) <= (size_t)60 * 1024 && c3p_smallr_grad_lds_bytes(Dm, K, (N + S - 1) / S) <= (size_t)60 * 1024;
 }
 // forward half; seg_complex (workspace, [B,S,Dm,Dm]) receives the segment products in the reference's vectorisation for U
-int lind_smallr_forward(const LindSmallRBufs& bf, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs, const double* signals, const cplx* clp,
-                        double dt, int B, int K, int N, int D, int Dm, int S, cplx* seg_complex, hipStream_t st) {
-  const bool per_sample = (h0_bs != 0) || (hk_bs != 0);
-  const int nsamp = per_sample ? B : 1;
-  RegdPrepArgs rp = {};
-  rp.h0 = h0;
-  rp.h0_bstride = h0_bs;
-  rp.hks = hks;
-  rp.hks_bstride = hk_bs;
-  rp.clp = clp;
-  rp.dt = dt;
-  rp.K = K;
-  rp.Dh = D;
-  rp.Dm = Dm;
-  rp.lindblad = 1;
-  LAUNCH_TRY(c3p_launch_smallr_prep_pair(rp, nsamp, bf.tabs, bf.tabs_t, bf.flags, st));
+int lind_smallr_forward(const LindSmallRBufs& bf, const PwcProblem& P, int S, cplx* seg_complex, hipStream_t st) {
+  LAUNCH_TRY(c3p_launch_smallr_prep_pair(regd_prep_args(P), P.nsamp(), bf.tabs, bf.tabs_t, bf.flags, st));
   SmallRArgs ra = {};
   ra.no_t18n = opt_no_t18n();
   ra.tables = bf.tabs;
-  ra.tab_per_sample = per_sample ? 1 : 0;
-  ra.signals = signals;
-  ra.B = B;
-  ra.K = K;
-  ra.N = N;
-  ra.Dm = Dm;
-  ra.S = S;
-  ra.Lmax = (N + S - 1) / S;
+  fill_chain(ra, P, S);
   ra.seg_out = seg_complex;
   ra.seg_real = bf.seg;
   ra.dus_real = bf.dus;
   LAUNCH_TRY(c3p_launch_smallr_chain(ra, st));
   return 0;
 }
-int lind_smallr_backward(DeviceWs* w, const LindSmallRBufs& bf, bool per_sample, const double* signals, int B, int K, int N, int D, int Dm, int S,
-                         const double* fr_phase, const cplx* Ubar, double* grad, hipStream_t st) {
+int lind_smallr_backward(DeviceWs* w, const LindSmallRBufs& bf, const PwcProblem& P, int S, const cplx* Ubar, double* grad, hipStream_t st) {
+  const int B = P.B, Dm = P.Dm;
   const size_t m8 = (size_t)Dm * Dm * sizeof(double);
   void *uv, *pv, *sv;
   if (ws_get(w, SL_SCRATCH, (size_t)B * m8, &uv)) return -1;
   if (ws_get(w, SL_SEG_A, (size_t)B * S * m8, &pv)) return -1;
   if (ws_get(w, SL_SEG_B, (size_t)B * S * m8, &sv)) return -1;
-  LAUNCH_TRY(c3p_launch_hb_ubar(Ubar, fr_phase, B, D, (double*)uv, st));
+  LAUNCH_TRY(c3p_launch_hb_ubar(Ubar, P.fr_phase, B, P.D, (double*)uv, st));
   LAUNCH_TRY(c3p_launch_smallr_scan(bf.seg, (const double*)uv, B, S, Dm, (double*)pv, (double*)sv, st));
   SmallRGradArgs g = {};
   g.no_t18n = opt_no_t18n();
   g.tables = bf.tabs;
   g.tables_t = bf.tabs_t;
-  g.tab_per_sample = per_sample ? 1 : 0;
-  g.signals = signals;
+  fill_chain(g, P, S);
   g.pre = (const double*)pv;
   g.suf = (const double*)sv;
   g.dus = bf.dus;
   g.grad = grad;
-  g.B = B;
-  g.K = K;
-  g.N = N;
-  g.Dm = Dm;
-  g.S = S;
-  g.Lmax = (N + S - 1) / S;
   LAUNCH_TRY(c3p_launch_smallr_grad(g, st));
   return 0;
 }
 
 // two qubits (16 x 16 superoperators), declared Hermitian: both halves on the real kernels; 1 = not applicable
-int run_vjp_lind_smallr16(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs, const double* signals, const cplx* clp,
-                          double dt, int B, int K, int N, int D, int Dm, const double* fr_phase, const cplx* Ubar, double* grad, hipStream_t st) {
-  const bool per_sample = (h0_bs != 0) || (hk_bs != 0);
-  const int S = pick_segments_r(B, N, K, Dm, per_sample, true);
+int run_vjp_lind_smallr16(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double* grad, hipStream_t st) {
+  const int B = P.B, K = P.K, N = P.N, D = P.D, Dm = P.Dm;
+  const int S = pick_segments_r(B, N, K, Dm, P.per_sample(), true);
   if (S < 0 || !lind_smallr_ok(true, D, Dm, K, N, S)) return 1;
-  const int nsamp = per_sample ? B : 1;
-  const LindSmallRSizes zr = lind_smallr_sizes(B, K, N, Dm, S, nsamp);
+  const int nsamp = P.nsamp();
+  const LindSmallSizes zr = lind_smallr_sizes(B, K, N, Dm, S, nsamp);
   void *blk, *sc;
   if (ws_get(w, SL_OUT1, zr.total(), &blk)) return -1;
   if (ws_get(w, SL_OUT2, (size_t)B * S * Dm * Dm * sizeof(cplx), &sc)) return -1;
   const LindSmallRBufs rb = lind_smallr_carve(blk, zr, nsamp, Dm, K);
-  if (lind_smallr_forward(rb, h0, h0_bs, hks, hk_bs, signals, clp, dt, B, K, N, D, Dm, S, (cplx*)sc, st)) return -1;
-  return lind_smallr_backward(w, rb, per_sample, signals, B, K, N, D, Dm, S, fr_phase, Ubar, grad, st) ? -1 : 0;
+  if (lind_smallr_forward(rb, P, S, (cplx*)sc, st)) return -1;
+  return lind_smallr_backward(w, rb, P, S, Ubar, grad, st) ? -1 : 0;
 }
 
 // Returns 1 when not applicable.
-int run_vjp_lind_smalld(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs, const double* signals, const cplx* clp,
-                        double dt, int B, int K, int N, int D, int Dm, const double* fr_phase, const cplx* Ubar, double* grad,
-                        bool hermitian, hipStream_t st) {
-  const bool per_sample = (h0_bs != 0) || (hk_bs != 0);
-  const int S = lind_small_segments(B, K, N, Dm, per_sample);
+int run_vjp_lind_smalld(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double* grad, bool hermitian, hipStream_t st) {
+  const int B = P.B, K = P.K, N = P.N, D = P.D, Dm = P.Dm;
+  const int nsamp = P.nsamp();
+  const int S = lind_small_segments(B, K, N, Dm, P.per_sample());
   if (S < 0) return 1;
-  const LindSmallSizes z = lind_small_sizes(B, K, N, Dm, S, per_sample ? B : 1);
+  const LindSmallSizes z = lind_small_sizes(B, K, N, Dm, S, nsamp);
   void* blk;
   if (ws_get(w, SL_OUT1, z.total(), &blk)) return -1;
   if (lind_smallr_ok(hermitian, D, Dm, K, N, S)) {
-    const int nsamp = per_sample ? B : 1;
-    const LindSmallRSizes zr = lind_smallr_sizes(B, K, N, Dm, S, nsamp);
+    const LindSmallSizes zr = lind_smallr_sizes(B, K, N, Dm, S, nsamp);
     const LindSmallRBufs rb = lind_smallr_carve(blk, zr, nsamp, Dm, K);
     void* sc;
     if (ws_get(w, SL_OUT2, (size_t)B * S * Dm * Dm * sizeof(cplx), &sc)) return -1;  // (the complex segment products: not needed here)
-    if (lind_smallr_forward(rb, h0, h0_bs, hks, hk_bs, signals, clp, dt, B, K, N, D, Dm, S, (cplx*)sc, st)) return -1;
-    return lind_smallr_backward(w, rb, per_sample, signals, B, K, N, D, Dm, S, fr_phase, Ubar, grad, st) ? -1 : 0;
+    if (lind_smallr_forward(rb, P, S, (cplx*)sc, st)) return -1;
+    return lind_smallr_backward(w, rb, P, S, Ubar, grad, st) ? -1 : 0;
   }
   const LindSmallBufs bf = lind_small_carve(blk, z);
-  if (lind_small_forward(w, bf, h0, h0_bs, hks, hk_bs, signals, clp, dt, B, K, N, D, Dm, S, hermitian, st)) return -1;
-  return lind_small_backward(w, bf, per_sample, signals, B, K, N, Dm, S, fr_phase, Ubar, grad, st) ? -1 : 0;
+  if (lind_small_forward(w, bf, P, S, hermitian, st)) return -1;
+  return lind_small_backward(w, bf, P, S, Ubar, grad, st) ? -1 : 0;
 }
 
 // ---------------------------------------------------------------------------
 // Mid-D MFMA path (13 <= Dm <= 40): one 4-wave workgroup per chain, matrices as LDS images
 // ---------------------------------------------------------------------------
-int combine_midd(DeviceWs* w, const cplx* cur, int B, int count, int Dm, int right_order,
-                 const double* fr_phase, cplx* U_out, hipStream_t st) {
-  const size_t msz = (size_t)Dm * Dm * sizeof(cplx);
-  Slot next_slot = SL_SEG_B;
-  while (true) {
-    MidArgs c = {};
-    c.mode = C3P_MODE_GIVEN;
-    c.mats = cur;
-    c.B = B;
-    c.N = count;
-    c.Dm = Dm;
-    c.right_order = right_order;
-    if (count <= 8) {
-      c.S = 1;
-      c.seg_out = U_out;
-      c.fr_phase = fr_phase;
-    } else {
-      c.S = (count + 3) / 4;
-      void* v;
-      if (ws_get(w, next_slot, (size_t)B * c.S * msz, &v)) return -1;
-      c.seg_out = (cplx*)v;
-    }
-    c.Lmax = (count + c.S - 1) / c.S;
-    LAUNCH_TRY(c3p_launch_midd_chain(c, st));
-    if (c.seg_out == U_out) break;
-    cur = c.seg_out;
-    count = c.S;
-    next_slot = (next_slot == SL_SEG_B) ? SL_SEG_A : SL_SEG_B;
-  }
-  return 0;
-}
-
-int run_pwc_midd(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs,
-                 const double* signals, const cplx* clp, double dt, int B, int K, int N, int D, int Dm,
-                 const double* fr_phase, cplx* U_out, cplx* dUs_out, hipStream_t st) {
+int run_pwc_midd(DeviceWs* w, const PwcProblem& P, cplx* U_out, cplx* dUs_out, hipStream_t st) {
+  const int B = P.B, K = P.K, N = P.N, Dm = P.Dm;
   int nig, nj, wd;
   if (!c3p_midd_geometry(Dm, &nig, &nj, &wd)) return 1;
-  const bool per_sample = (h0_bs != 0) || (hk_bs != 0);
   // workgroups resident at once are LDS-limited (three images per workgroup); aim at two rounds
   const size_t lds0 = c3p_midd_lds_bytes(Dm, K, 0);
   int wg_per_cu = (int)((156 * 1024) / (lds0 + 4096));
@@ -1223,42 +1163,23 @@ int run_pwc_midd(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cp
   const long smax = N / 8 > 1 ? N / 8 : 1;
   const long S = pick_segments_rounds(B, N, 256L * wg_per_cu, smax, Dm <= 16 ? 400 : 100);
   if (lds0 > 158 * 1024) return 1;
-  const int nsamp = per_sample ? B : 1;
+  const int nsamp = P.nsamp();
   void* v;
   if (ws_get(w, SL_TABLES, (size_t)nsamp * c3p_midd_table_doubles(Dm, K) * sizeof(double), &v)) return -1;
-  MidPrepArgs p = {};
-  p.h0 = h0;
-  p.h0_bstride = h0_bs;
-  p.hks = hks;
-  p.hks_bstride = hk_bs;
-  p.clp = clp;
-  p.dt = dt;
-  p.K = K;
-  p.Dh = D;
-  p.Dm = Dm;
-  p.lindblad = lindblad;
-  p.rows = 16 * nig;
-  p.W = wd;
+  MidPrepArgs p = mid_prep_args(P, nig, wd);
   p.tables = (double*)v;
   LAUNCH_TRY(c3p_launch_midd_prep(p, nsamp, st));
   MidArgs a = {};
   a.tables = (const double*)v;
-  a.tab_per_sample = per_sample ? 1 : 0;
-  a.signals = signals;
-  a.B = B;
-  a.K = K;
-  a.N = N;
-  a.Dm = Dm;
-  a.S = (int)S;
-  a.Lmax = (int)((N + S - 1) / S);
-  a.mode = lindblad ? C3P_MODE_LINDBLAD : C3P_MODE_UNITARY;
+  fill_chain(a, P, S);
+  a.mode = P.lindblad ? C3P_MODE_LINDBLAD : C3P_MODE_UNITARY;
   a.dUs_out = dUs_out;
   a.no_t18 = c3p_opt_on(C3P_OPT_no_t18) ? 1 : 0;
   a.no_t18n = opt_no_t18n();
   a.no_real = c3p_opt_on(C3P_OPT_no_real) ? 1 : 0;
   if (S == 1) {
     a.seg_out = U_out;
-    a.fr_phase = fr_phase;
+    a.fr_phase = P.fr_phase;
   } else {
     void* sv;
     if (ws_get(w, SL_SEG_A, (size_t)B * S * Dm * Dm * sizeof(cplx), &sv)) return -1;
@@ -1268,15 +1189,14 @@ int run_pwc_midd(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cp
   if (record_start(w, st)) return -1;
   LAUNCH_TRY(c3p_launch_midd_chain(a, st));
   if (record_stop(w, st)) return -1;
-  if (S > 1) return combine_midd(w, a.seg_out, B, (int)S, Dm, 0, fr_phase, U_out, st);
+  if (S > 1) return combine_chain(c3p_launch_midd_chain, w, a.seg_out, B, (int)S, Dm, 0, P.fr_phase, U_out, st);
   return 0;
 }
 
 // Lindblad gradient on the mid-D MFMA kernels (16 x 16, 25 x 25, 36 x 36 superoperators: D = 4, 5, 6), general-generator
 // form; see run_vjp_lind_smalld.  Returns 1 when not applicable.
-int run_vjp_lind_midd(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs, const double* signals, const cplx* clp,
-                      double dt, int B, int K, int N, int D, int Dm, const double* fr_phase, const cplx* Ubar, double* grad,
-                      hipStream_t st) {
+int run_vjp_lind_midd(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double* grad, hipStream_t st) {
+  const int B = P.B, K = P.K, N = P.N, Dm = P.Dm;
   int nig, nj, wd;
   if (!c3p_midd_geometry(Dm, &nig, &nj, &wd) || K > 16) return 1;
   if (!((nig == 2 && nj == 4) || (nig == 4 && nj == 7) || (nig == 5 && nj == 9))) return 1;
@@ -1287,25 +1207,12 @@ int run_vjp_lind_midd(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, 
   auto lds_need = [&](long s) { return c3p_midd_grad_image_bytes(Dm) + (size_t)K * ((N + s - 1) / s) * sizeof(double); };
   while (lds_need(S) > (size_t)150 * 1024 && S < N) ++S;
   if (lds_need(S) > (size_t)150 * 1024) return 1;
-  const bool per_sample = (h0_bs != 0) || (hk_bs != 0);
-  const int nsamp = per_sample ? B : 1;
+  const int nsamp = P.nsamp();
   const size_t tdoubles = (size_t)nsamp * c3p_midd_table_doubles(Dm, K);
   void* v;
   if (ws_get(w, SL_TABLES, 2 * tdoubles * sizeof(double), &v)) return -1;
   double* tabs = (double*)v;
-  MidPrepArgs p = {};
-  p.h0 = h0;
-  p.h0_bstride = h0_bs;
-  p.hks = hks;
-  p.hks_bstride = hk_bs;
-  p.clp = clp;
-  p.dt = dt;
-  p.K = K;
-  p.Dh = D;
-  p.Dm = Dm;
-  p.lindblad = 1;
-  p.rows = 16 * nig;
-  p.W = wd;
+  MidPrepArgs p = mid_prep_args(P, nig, wd);
   p.tables = tabs;
   LAUNCH_TRY(c3p_launch_midd_prep(p, nsamp, st));
   p.conjT = 1;
@@ -1321,14 +1228,7 @@ int run_vjp_lind_midd(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, 
   cplx* pstore = dUs + (size_t)B * N * Dm * Dm;
   MidArgs a = {};
   a.tables = tabs;
-  a.tab_per_sample = per_sample ? 1 : 0;
-  a.signals = signals;
-  a.B = B;
-  a.K = K;
-  a.N = N;
-  a.Dm = Dm;
-  a.S = (int)S;
-  a.Lmax = (int)((N + S - 1) / S);
+  fill_chain(a, P, S);
   a.mode = C3P_MODE_LINDBLAD;
   a.seg_out = (cplx*)sv;
   a.dUs_out = dUs;
@@ -1338,7 +1238,7 @@ int run_vjp_lind_midd(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, 
   LAUNCH_TRY(c3p_launch_midd_chain(a, st));
   GradArgs G = {};
   G.Ubar = Ubar;
-  G.fr_phase = fr_phase;
+  G.fr_phase = P.fr_phase;
   G.B = B;
   G.K = K;
   G.N = N;
@@ -1353,19 +1253,12 @@ int run_vjp_lind_midd(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, 
   MidGradArgs g = {};
   g.tables = tabs;
   g.tables_h = tabs + tdoubles;
-  g.tab_per_sample = a.tab_per_sample;
-  g.signals = signals;
+  fill_chain(g, P, S);
   g.Mb = G.Mb;
   g.pre = pre;
   g.dUs = dUs;
   g.pstore = pstore;
   g.grad = grad;
-  g.B = B;
-  g.K = K;
-  g.N = N;
-  g.Dm = Dm;
-  g.S = (int)S;
-  g.Lmax = a.Lmax;
   LAUNCH_TRY(c3p_launch_midd_grad_general(g, st));
   return 0;
 }
@@ -1494,34 +1387,21 @@ int run_vjp_xg_general(DeviceWs* w, const cplx* hs, long hs_bstride, double coef
 // ---------------------------------------------------------------------------
 // Big-D MFMA path (81 x 81 Lindblad superoperators): 8-wave workgroup per chain, global arena
 // ---------------------------------------------------------------------------
-int run_pwc_bigd(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs,
-                 const double* signals, const cplx* clp, double dt, int B, int K, int N, int D, int Dm,
-                 const double* fr_phase, cplx* U_out, cplx* dUs_out, hipStream_t st) {
+int run_pwc_bigd(DeviceWs* w, const PwcProblem& P, cplx* U_out, cplx* dUs_out, hipStream_t st) {
+  const int B = P.B, K = P.K, N = P.N, D = P.D, Dm = P.Dm;
+  const double* fr_phase = P.fr_phase;
   int nig, nj, wd;
   if (!c3p_bigd_geometry(Dm, &nig, &nj, &wd)) return 1;
-  const bool per_sample = (h0_bs != 0) || (hk_bs != 0);
   long S = (C3P_BIGD_MAX_WGS + B - 1) / B;
   const long smax = N / 8 > 1 ? N / 8 : 1;
   if (S > smax) S = smax;
   if (S < 1) S = 1;
   while (c3p_bigd_lds_bytes(Dm, K, (int)((N + S - 1) / S)) > 150 * 1024 && S < N) ++S;
   if (c3p_bigd_lds_bytes(Dm, K, (int)((N + S - 1) / S)) > 150 * 1024) return 1;
-  const int nsamp = per_sample ? B : 1;
+  const int nsamp = P.nsamp();
   void* v;
   if (ws_get(w, SL_TABLES, (size_t)nsamp * c3p_bigd_table_doubles(Dm, K) * sizeof(double), &v)) return -1;
-  MidPrepArgs p = {};
-  p.h0 = h0;
-  p.h0_bstride = h0_bs;
-  p.hks = hks;
-  p.hks_bstride = hk_bs;
-  p.clp = clp;
-  p.dt = dt;
-  p.K = K;
-  p.Dh = D;
-  p.Dm = Dm;
-  p.lindblad = lindblad;
-  p.rows = 16 * nig;
-  p.W = wd;
+  MidPrepArgs p = mid_prep_args(P, nig, wd);
   p.tile_nig = nig;
   p.tile_nj = nj;
   p.tables = (double*)v;
@@ -1530,15 +1410,8 @@ int run_pwc_bigd(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cp
   if (ws_get(w, SL_SCRATCH, c3p_bigd_arena_doubles(Dm) * sizeof(double), &av)) return -1;
   MidArgs a = {};
   a.tables = (const double*)v;
-  a.tab_per_sample = per_sample ? 1 : 0;
-  a.signals = signals;
-  a.B = B;
-  a.K = K;
-  a.N = N;
-  a.Dm = Dm;
-  a.S = (int)S;
-  a.Lmax = (int)((N + S - 1) / S);
-  a.mode = lindblad ? C3P_MODE_LINDBLAD : C3P_MODE_UNITARY;
+  fill_chain(a, P, S);
+  a.mode = P.lindblad ? C3P_MODE_LINDBLAD : C3P_MODE_UNITARY;
   a.dUs_out = dUs_out;
   cplx* seg = U_out;
   if (S > 1) {
@@ -1574,16 +1447,16 @@ int run_pwc_bigd(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cp
 // Register-resident MFMA path (Dm = 49, 65, 81; the 81 x 81 Lindblad superoperators of cfg4): 4-wave workgroup
 // per chain, right operands / accumulators in registers, three-real-product complex arithmetic (c3p_regd.hip)
 // ---------------------------------------------------------------------------
-int run_pwc_regd(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs,
-                 const double* signals, const cplx* clp, double dt, int B, int K, int N, int D, int Dm,
-                 const double* fr_phase, cplx* U_out, cplx* dUs_out, hipStream_t st) {
+int run_pwc_regd(DeviceWs* w, const PwcProblem& P, cplx* U_out, cplx* dUs_out, hipStream_t st) {
+  const int B = P.B, K = P.K, N = P.N, D = P.D, Dm = P.Dm, lindblad = P.lindblad;
+  const double* fr_phase = P.fr_phase;
   if (!c3p_regd_supported(Dm) || K > 16) return 1;
-  const bool per_sample = (h0_bs != 0) || (hk_bs != 0);
+  const bool per_sample = P.per_sample();
   long S = (C3P_REGD_MAX_WGS + B - 1) / B;
   const long smax = N / 8 > 1 ? N / 8 : 1;
   if (S > smax) S = smax;
   if (S < 1) S = 1;
-  const int nsamp = per_sample ? B : 1;
+  const int nsamp = P.nsamp();
   // Lindblad superoperators of Hermitian Hamiltonians: the whole chain in real arithmetic in the Hermitian basis
   // (c3p_regr.hip); the complex kernel keeps the samples whose tables are not real there
   const bool hb = lindblad && c3p_regr_supported(D, Dm) && !c3p_opt_on(C3P_OPT_no_hermitian_basis);
@@ -1592,17 +1465,7 @@ int run_pwc_regd(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cp
   const size_t ftab = hb ? (size_t)nsamp * (1 + K) * sizeof(int) : 0;
   void* v;
   if (ws_get(w, SL_TABLES, ctab + rtab + ftab, &v)) return -1;
-  RegdPrepArgs p = {};
-  p.h0 = h0;
-  p.h0_bstride = h0_bs;
-  p.hks = hks;
-  p.hks_bstride = hk_bs;
-  p.clp = clp;
-  p.dt = dt;
-  p.K = K;
-  p.Dh = D;
-  p.Dm = Dm;
-  p.lindblad = lindblad;
+  RegdPrepArgs p = regd_prep_args(P);
   p.tables = (double*)v;
   LAUNCH_TRY(c3p_launch_regd_prep(p, nsamp, st));
   double* rtables = reinterpret_cast<double*>(static_cast<char*>(v) + ctab);
@@ -1612,14 +1475,7 @@ int run_pwc_regd(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cp
   if (ws_get(w, SL_SCRATCH, std::max(c3p_regd_arena_bytes(Dm), hb ? c3p_regr_arena_bytes(Dm) : (size_t)0), &av)) return -1;
   MidArgs a = {};
   a.tables = (const double*)v;
-  a.tab_per_sample = per_sample ? 1 : 0;
-  a.signals = signals;
-  a.B = B;
-  a.K = K;
-  a.N = N;
-  a.Dm = Dm;
-  a.S = (int)S;
-  a.Lmax = (int)((N + S - 1) / S);
+  fill_chain(a, P, S);
   a.mode = lindblad ? C3P_MODE_LINDBLAD : C3P_MODE_UNITARY;
   a.dUs_out = dUs_out;
   if (hb) {
@@ -1715,6 +1571,22 @@ static size_t grad_store_budget(DeviceWs* w, Slot slot) {
   if (budget < ((size_t)64 << 20)) budget = (size_t)64 << 20;
   return budget;
 }
+// Samples per chunk of a sweep that keeps `bytes_per_sample` of forward intermediates in SL_OUT1: what fits the budget, at least
+// one; the grad_chunk option (C3P_GRAD_CHUNK) overrides it.
+static long grad_chunk_samples(DeviceWs* w, size_t bytes_per_sample) {
+  long Bc = (long)(grad_store_budget(w, SL_OUT1) / (bytes_per_sample + 1));
+  if (c3p_opt(C3P_OPT_grad_chunk) > 0) Bc = c3p_opt(C3P_OPT_grad_chunk);
+  return Bc < 1 ? 1 : Bc;
+}
+// run(b0, nb) on chunks of at most Bc of the B samples, until one does not return 0 (1 = not applicable, -1 = error)
+template <class Run>
+int in_chunks(long B, long Bc, Run&& run) {
+  for (long b0 = 0; b0 < B; b0 += Bc) {
+    const int rc = run(b0, (int)(B - b0 < Bc ? B - b0 : Bc));
+    if (rc != 0) return rc;
+  }
+  return 0;
+}
 
 // ---------------------------------------------------------------------------
 // Lindblad control gradient at D = 7, 8, 9 (49 x 49 .. 81 x 81 superoperators, cfg4) in the Hermitian basis: forward chain
@@ -1772,21 +1644,10 @@ static LindRegrBufs lind_regr_carve(void* base, const LindRegrSizes& z) {
   return b;
 }
 // tables of G' and G'^T, Hermiticity flags (read back: one synchronisation per call), forward chain with Q^T
-int lind_regr_forward(DeviceWs* w, const LindRegrBufs& bf, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs, const double* signals,
-                      const cplx* clp, double dt, int B, int K, int N, int D, int Dm, long S, hipStream_t st) {
-  const bool per_sample = (h0_bs != 0) || (hk_bs != 0);
-  const int nsamp = per_sample ? B : 1;
-  RegdPrepArgs p = {};
-  p.h0 = h0;
-  p.h0_bstride = h0_bs;
-  p.hks = hks;
-  p.hks_bstride = hk_bs;
-  p.clp = clp;
-  p.dt = dt;
-  p.K = K;
-  p.Dh = D;
-  p.Dm = Dm;
-  p.lindblad = 1;
+int lind_regr_forward(DeviceWs* w, const LindRegrBufs& bf, const PwcProblem& P, long S, hipStream_t st) {
+  const int K = P.K, Dm = P.Dm;
+  const int nsamp = P.nsamp();
+  const RegdPrepArgs p = regd_prep_args(P);
   LAUNCH_TRY(c3p_launch_regr_prep_t(p, nsamp, bf.tab_f, bf.flag_f, 0, st));
   LAUNCH_TRY(c3p_launch_regr_prep_t(p, nsamp, bf.tab_t, bf.flag_t, 1, st));
   {
@@ -1799,14 +1660,7 @@ int lind_regr_forward(DeviceWs* w, const LindRegrBufs& bf, const cplx* h0, long 
   void* av;
   if (ws_get(w, SL_SCRATCH, std::max(c3p_regr_grad_arena_bytes(Dm), c3p_regr_arena_bytes(Dm)), &av)) return -1;
   MidArgs a = {};
-  a.tab_per_sample = per_sample ? 1 : 0;
-  a.signals = signals;
-  a.B = B;
-  a.K = K;
-  a.N = N;
-  a.Dm = Dm;
-  a.S = (int)S;
-  a.Lmax = (int)((N + S - 1) / S);
+  fill_chain(a, P, S);
   a.mode = C3P_MODE_LINDBLAD;
   a.hb_tables = bf.tab_f;
   a.hb_tabflag = bf.flag_f;
@@ -1817,8 +1671,8 @@ int lind_regr_forward(DeviceWs* w, const LindRegrBufs& bf, const cplx* h0, long 
   return 0;
 }
 // cotangent in the Hermitian basis, segment scan, backward sweep (scratch from the workspace)
-int lind_regr_backward(DeviceWs* w, const LindRegrBufs& bf, bool per_sample, const double* signals, int B, int K, int N, int D, int Dm,
-                       long S, const double* fr_phase, const cplx* Ubar, double* grad, hipStream_t st) {
+int lind_regr_backward(DeviceWs* w, const LindRegrBufs& bf, const PwcProblem& P, long S, const cplx* Ubar, double* grad, hipStream_t st) {
+  const int B = P.B, Dm = P.Dm;
   const size_t msz = (size_t)Dm * Dm;
   void *bv, *av;
   if (ws_get(w, SL_SEG_B, ((size_t)3 * B * S + B) * msz * sizeof(double) + (size_t)B * sizeof(double), &bv)) return -1;
@@ -1828,34 +1682,32 @@ int lind_regr_backward(DeviceWs* w, const LindRegrBufs& bf, bool per_sample, con
   double* lam = suf + (size_t)B * S * msz;
   double* ubr = lam + (size_t)B * S * msz;
   double* tau = ubr + (size_t)B * msz;
-  LAUNCH_TRY(c3p_launch_hb_ubar(Ubar, fr_phase, B, D, ubr, st));
+  LAUNCH_TRY(c3p_launch_hb_ubar(Ubar, P.fr_phase, B, P.D, ubr, st));
   LAUNCH_TRY(c3p_launch_regr_scan(bf.seg, ubr, B, (int)S, Dm, pre, suf, lam, tau, st));
   RegrGradArgs g = {};
   g.tables = bf.tab_f;
   g.tables_t = bf.tab_t;
-  g.tab_per_sample = per_sample ? 1 : 0;
-  g.signals = signals;
+  g.tab_per_sample = P.per_sample() ? 1 : 0;
+  g.signals = P.signals;
   g.qT = bf.qT;
   g.lam = lam;
   g.tau = tau;
   g.grad = grad;
   g.arena = (double*)av;
   g.B = B;
-  g.K = K;
-  g.N = N;
+  g.K = P.K;
+  g.N = P.N;
   g.Dm = Dm;
   g.S = (int)S;
   g.degree = c3p_opt(C3P_OPT_regr_grad_degree) > 0 ? (int)c3p_opt(C3P_OPT_regr_grad_degree) : 0;
   LAUNCH_TRY(c3p_launch_regr_grad(g, st));
   return 0;
 }
-int run_vjp_lind_regr(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs, const double* signals, const cplx* clp,
-                      double dt, int B, int K, int N, int D, int Dm, const double* fr_phase, const cplx* Ubar, double* grad,
-                      hipStream_t st) {
-  if (!lind_regr_grad_ok(D, Dm) || K > 16 || K < 1) return 1;
-  const bool per_sample = (h0_bs != 0) || (hk_bs != 0);
+int run_vjp_lind_regr(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double* grad, hipStream_t st) {
+  const int B = P.B, K = P.K, N = P.N, Dm = P.Dm;
+  if (!lind_regr_grad_ok(P.D, Dm) || K > 16 || K < 1) return 1;
   const long S = lind_regr_segments(B, N);
-  const LindRegrSizes z = lind_regr_sizes(B, K, N, Dm, S, per_sample ? B : 1);
+  const LindRegrSizes z = lind_regr_sizes(B, K, N, Dm, S, P.nsamp());
   void *tv, *sv, *qv;
   if (ws_get(w, SL_TABLES, 2 * z.tab1 + 2 * z.ftab, &tv)) return -1;
   if (ws_get(w, SL_SEG_A, z.seg, &sv)) return -1;
@@ -1863,35 +1715,35 @@ int run_vjp_lind_regr(DeviceWs* w, const cplx* h0, long h0_bs, const cplx* hks, 
   LindRegrBufs bf = lind_regr_carve(tv, z);
   bf.seg = (cplx*)sv;
   bf.qT = (double*)qv;
-  const int rc = lind_regr_forward(w, bf, h0, h0_bs, hks, hk_bs, signals, clp, dt, B, K, N, D, Dm, S, st);
+  const int rc = lind_regr_forward(w, bf, P, S, st);
   if (rc != 0) return rc;
-  return lind_regr_backward(w, bf, per_sample, signals, B, K, N, D, Dm, S, fr_phase, Ubar, grad, st);
+  return lind_regr_backward(w, bf, P, S, Ubar, grad, st);
 }
 
-int run_vjp_tiled(DeviceWs* w, int lindblad, const cplx* h0, long h0_bs, const cplx* hks, long hk_bs, const double* signals,
-                  const cplx* clp, double dt, int B, int K, int N, int D, int Dm, const double* fr_phase, const cplx* U_bar,
-                  double* grad, hipStream_t st, bool per_slice = false, cplx* zout = nullptr) {
-  const bool per_sample = !per_slice && ((h0_bs != 0) || (hk_bs != 0));
+int run_vjp_tiled(DeviceWs* w, const PwcProblem& P, const cplx* U_bar, double* grad, hipStream_t st, bool per_slice = false,
+                  cplx* zout = nullptr) {
+  const int B = P.B, K = P.K, N = P.N, Dm = P.Dm;
+  const bool per_sample = !per_slice && P.per_sample();
   const int Bc = c3p_tiled_vjp_chunk(Dm, K, N, B, per_sample, grad_store_budget(w, SL_SCRATCH));
   void* v;
   if (ws_get(w, SL_SCRATCH, c3p_tiled_vjp_ws_bytes(Dm, K, N, Bc, per_sample), &v)) return -1;
   if (g_dry) return 0;
   TiledArgs t = {};
-  t.lindblad = lindblad;
+  t.lindblad = P.lindblad;
   t.per_slice = per_slice ? 1 : 0;
-  t.h0 = h0;
-  t.h0_bstride = h0_bs;
-  t.hks = hks;
-  t.hks_bstride = hk_bs;
-  t.signals = signals;
-  t.clp = clp;
-  t.dt = dt;
+  t.h0 = P.h0;
+  t.h0_bstride = P.h0_bs;
+  t.hks = P.hks;
+  t.hks_bstride = P.hk_bs;
+  t.signals = P.signals;
+  t.clp = P.clp;
+  t.dt = P.dt;
   t.B = B;
   t.K = K;
   t.N = N;
-  t.D = D;
+  t.D = P.D;
   t.Dm = Dm;
-  t.fr_phase = fr_phase;
+  t.fr_phase = P.fr_phase;
   // the per-slice launch sequences are replayed as hipGraphs, which the legacy default stream cannot capture
   hipStream_t run = st;
   if (!run) {
@@ -1968,12 +1820,8 @@ int pwc_common(int lindblad, const void* h0, int64_t h0_bstride, const void* hks
   const void *d_h0 = h0, *d_hks = hks, *d_sig = signals, *d_col = col_ops, *d_ph = fr_phase;
   void *d_U = U_out, *d_dUs = dUs_out;
   if (flags & C3P_HOST_PTRS) {
-    const size_t h0_one = (size_t)(per_slice ? N : 1) * D * D;
-    const size_t h0_elems = h0_bstride ? (size_t)(B - 1) * h0_bstride + h0_one : h0_one;
-    const size_t hk_one = (size_t)K * D * D;
-    const size_t hk_elems = hks_bstride ? (size_t)(B - 1) * hks_bstride + hk_one : hk_one;
-    if (sg.in(h0, h0_elems * cs, &d_h0)) return -1;
-    if (sg.in(hks, K ? hk_elems * cs : 0, &d_hks)) return -1;
+    if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)(per_slice ? N : 1) * D * D) * cs, &d_h0)) return -1;
+    if (sg.in(hks, K ? staged_elems(B, hks_bstride, (size_t)K * D * D) * cs : 0, &d_hks)) return -1;
     if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
     if (sg.in(col_ops, lindblad ? (size_t)C * D * D * cs : 0, &d_col)) return -1;
     if (sg.in(fr_phase, fr_phase ? (size_t)B * Dm * sizeof(double) : 0, &d_ph)) return -1;
@@ -2002,6 +1850,7 @@ int pwc_common(int lindblad, const void* h0, int64_t h0_bstride, const void* hks
     LAUNCH_TRY(c3p_launch_clp((const cplx*)d_col, C, D, (cplx*)v, st));
     a.clp = (const cplx*)v;
   }
+  const PwcProblem P = {a.h0, a.h0_bstride, a.hks, a.hks_bstride, a.signals, a.clp, dt, B, K, N, D, Dm, lindblad, a.fr_phase};
   bool done = false;
   if (!(flags & C3P_FORCE_GENERIC) && per_slice && !lindblad && K == 0 && D <= kSmallDLimit && c3p_smalld_supported(D)) {
     // branch B (propagation.py:295-308): X_n = -i dt H_n
@@ -2030,31 +1879,27 @@ int pwc_common(int lindblad, const void* h0, int64_t h0_bstride, const void* hks
   }
   if (!done && !(flags & C3P_FORCE_GENERIC) && !per_slice && lindblad && (flags & C3P_HERMITIAN_H) && !a.dUs_out &&
       c3p_smallr_supported(D, Dm, K) && !c3p_opt_on(C3P_OPT_no_smallr)) {
-    const int rc = run_pwc_smallr(w, a.h0, a.h0_bstride, a.hks, a.hks_bstride, a.signals, a.clp, dt, B, K, N, D, Dm, a.fr_phase, (cplx*)d_U, st);
+    const int rc = run_pwc_smallr(w, P, (cplx*)d_U, st);
     if (rc < 0) return -1;
     done = (rc == 0);
   }
   if (!done && !(flags & C3P_FORCE_GENERIC) && !per_slice && Dm <= kSmallDLimit && c3p_smalld_supported(Dm) && K <= 8) {
-    const int rc = run_pwc_smalld(w, lindblad, a.h0, a.h0_bstride, a.hks, a.hks_bstride, a.signals, a.clp, dt,
-                                  B, K, N, D, Dm, a.fr_phase, (cplx*)d_U, a.dUs_out, st);
+    const int rc = run_pwc_smalld(w, P, (cplx*)d_U, a.dUs_out, st);
     if (rc < 0) return -1;
     done = (rc == 0);
   }
   if (!done && !(flags & C3P_FORCE_GENERIC) && !per_slice && Dm >= 13 && Dm <= 40 && K <= 16) {
-    const int rc = run_pwc_midd(w, lindblad, a.h0, a.h0_bstride, a.hks, a.hks_bstride, a.signals, a.clp, dt, B,
-                                K, N, D, Dm, a.fr_phase, (cplx*)d_U, a.dUs_out, st);
+    const int rc = run_pwc_midd(w, P, (cplx*)d_U, a.dUs_out, st);
     if (rc < 0) return -1;
     done = (rc == 0);
   }
   if (!done && !(flags & C3P_FORCE_GENERIC) && !per_slice && c3p_regd_supported(Dm) && K <= 16 && !c3p_opt_on(C3P_OPT_no_regd)) {
-    const int rc = run_pwc_regd(w, lindblad, a.h0, a.h0_bstride, a.hks, a.hks_bstride, a.signals, a.clp, dt, B,
-                                K, N, D, Dm, a.fr_phase, (cplx*)d_U, a.dUs_out, st);
+    const int rc = run_pwc_regd(w, P, (cplx*)d_U, a.dUs_out, st);
     if (rc < 0) return -1;
     done = (rc == 0);
   }
   if (!done && !(flags & C3P_FORCE_GENERIC) && !per_slice && K <= 16) {
-    const int rc = run_pwc_bigd(w, lindblad, a.h0, a.h0_bstride, a.hks, a.hks_bstride, a.signals, a.clp, dt, B,
-                                K, N, D, Dm, a.fr_phase, (cplx*)d_U, a.dUs_out, st);
+    const int rc = run_pwc_bigd(w, P, (cplx*)d_U, a.dUs_out, st);
     if (rc < 0) return -1;
     done = (rc == 0);
   }
@@ -2327,10 +2172,10 @@ int c3p_matmul_chain(const void* M, int B, int N, int D, int flags, void* out, v
   a.right_order = (flags & C3P_ORDER_RIGHT) ? 1 : 0;
   if (!(flags & C3P_FORCE_GENERIC) && D <= kSmallDLimit && c3p_smalld_supported(D)) {
     g_last_kernel = C3P_KERNEL_SMALLD;
-    if (combine_smalld(w, (const cplx*)d_M, B, N, D, a.right_order, nullptr, (cplx*)d_out, st)) return -1;
+    if (combine_chain(c3p_launch_smalld_chain, w, (const cplx*)d_M, B, N, D, a.right_order, nullptr, (cplx*)d_out, st)) return -1;
   } else if (!(flags & C3P_FORCE_GENERIC) && D >= 13 && D <= 40) {
     g_last_kernel = C3P_KERNEL_MFMA;
-    if (combine_midd(w, (const cplx*)d_M, B, N, D, a.right_order, nullptr, (cplx*)d_out, st)) return -1;
+    if (combine_chain(c3p_launch_midd_chain, w, (const cplx*)d_M, B, N, D, a.right_order, nullptr, (cplx*)d_out, st)) return -1;
   } else if (run_chain_generic(w, a, (cplx*)d_out, st)) {
     return -1;
   }
@@ -2397,10 +2242,10 @@ int ode_segmented(DeviceWs* w, OdeArgs a, int nseg, const cplx* init, long init_
     // mid-D chain kernel
     a.step = C3P_STEP_PROPAGATOR_ID;
     LAUNCH_TRY(c3p_launch_ode_rhoq(a, st));
-    if (combine_midd(w, (const cplx*)v_maps, B, nseg, D, 0, nullptr, (cplx*)v_U, st)) return -1;
+    if (combine_chain(c3p_launch_midd_chain, w, (const cplx*)v_maps, B, nseg, D, 0, nullptr, (cplx*)v_U, st)) return -1;
   } else {
     LAUNCH_TRY(c3p_launch_ode_row(a, nullptr, st));
-    if (combine_smalld(w, (const cplx*)v_maps, B, nseg, D, 0, nullptr, (cplx*)v_U, st)) return -1;
+    if (combine_chain(c3p_launch_smalld_chain, w, (const cplx*)v_maps, B, nseg, D, 0, nullptr, (cplx*)v_U, st)) return -1;
   }
   if (psi_out) HIP_TRY(c3p_launch_ode_apply((const cplx*)v_U, init, init_bstride, psi_out, B, D, st));
   return 0;
@@ -2915,31 +2760,25 @@ int c3p_gate_overlap(const void* U, int B, int D, const int32_t* comp_rows, int 
 }
 
 // The general-generator sweep in three VALU kernels on dense generator tables (c3p_grad.hip, general form), D^2 <= 36, one chunk
-// of nb samples.  `mo` set: the sweep also accumulates the model-operator cotangents, and the reduce kernel writes them.
-struct LindModelOut {
-  const cplx* col;  // [C,D,D]
-  int C;
-  cplx *g_h0, *g_hks, *g_col;  // [nb,D,D], [nb,K,D,D], [nb,C,D,D]
-};
-static int run_vjp_lind_valu(DeviceWs* w, const cplx* h0, int64_t h0_bstride, const cplx* hks, int64_t hks_bstride, const double* sig,
-                             const cplx* clp, double dt, int nb, int K, int N, int D, const double* ph, const cplx* ub, double* grad,
-                             const LindModelOut* mo, bool* global_out, hipStream_t st) {
+// of samples.  `mo` set: the sweep also accumulates the model-operator cotangents, and the reduce kernel writes them.
+static int run_vjp_lind_valu(DeviceWs* w, const PwcProblem& P, const cplx* ub, double* grad, const LindModelOut* mo, bool* global_out,
+                             hipStream_t st) {
   const size_t cs = sizeof(cplx);
-  const int Dm = D * D;
+  const int nb = P.B, K = P.K, N = P.N, D = P.D, Dm = P.Dm;
   const long gsz = (long)Dm * Dm;
-  const int nt = (h0_bstride || hks_bstride) ? nb : 1;
+  const int nt = P.nsamp();
   void* tab;
   if (ws_get(w, SL_TABLES, (size_t)nt * (K + 1) * gsz * cs, &tab)) return -1;
-  LAUNCH_TRY(c3p_launch_lind_generators(h0, h0_bstride, hks, hks_bstride, clp, nt, K, D, (cplx*)tab, st));
+  LAUNCH_TRY(c3p_launch_lind_generators(P.h0, P.h0_bs, P.hks, P.hk_bs, P.clp, nt, K, D, (cplx*)tab, st));
   GradArgs A = {};
   A.h0 = (const cplx*)tab;
   A.h0_bstride = nt > 1 ? (long)(K + 1) * gsz : 0;
   A.hks = (const cplx*)tab + gsz;
   A.hks_bstride = A.h0_bstride;
-  A.signals = sig;
-  A.fr_phase = ph;
+  A.signals = P.signals;
+  A.fr_phase = P.fr_phase;
   A.Ubar = ub;
-  A.dt = dt;
+  A.dt = P.dt;
   A.B = nb;
   A.K = K;
   A.N = N;
@@ -2978,7 +2817,7 @@ static int run_vjp_lind_valu(DeviceWs* w, const cplx* h0, int64_t h0_bstride, co
     return 0;
   }
   LAUNCH_TRY(c3p_launch_grad_bwd_general_model(A, global, st));
-  LAUNCH_TRY(c3p_launch_lind_model_reduce(A.mpart, mo->col, mo->C, nb, A.S, K, D, dt, mo->g_h0, mo->g_hks, mo->g_col, st));
+  LAUNCH_TRY(c3p_launch_lind_model_reduce(A.mpart, mo->col, mo->C, nb, A.S, K, D, P.dt, mo->g_h0, mo->g_hks, mo->g_col, st));
   return 0;
 }
 
@@ -3001,8 +2840,8 @@ int c3p_pwc_lindblad_vjp(const void* h0, int64_t h0_bstride, const void* hks, in
   const void *d_h0 = h0, *d_hks = hks, *d_sig = signals, *d_ph = fr_phase, *d_ub = U_bar, *d_col = col_ops;
   void* d_grad = grad_signals;
   if (flags & C3P_HOST_PTRS) {
-    if (sg.in(h0, ((size_t)(B - 1) * (size_t)h0_bstride + (size_t)D * D) * cs, &d_h0)) return -1;
-    if (sg.in(hks, ((size_t)(B - 1) * (size_t)hks_bstride + (size_t)K * D * D) * cs, &d_hks)) return -1;
+    if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)D * D) * cs, &d_h0)) return -1;
+    if (sg.in(hks, staged_elems(B, hks_bstride, (size_t)K * D * D) * cs, &d_hks)) return -1;
     if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
     if (sg.in(col_ops, (size_t)C * D * D * cs, &d_col)) return -1;
     if (sg.in(U_bar, (size_t)B * Dm * Dm * cs, &d_ub)) return -1;
@@ -3012,79 +2851,52 @@ int c3p_pwc_lindblad_vjp(const void* h0, int64_t h0_bstride, const void* hks, in
   void* clp;
   if (ws_get(w, SL_CLP, (size_t)Dm * Dm * cs, &clp)) return -1;
   LAUNCH_TRY(c3p_launch_clp((const cplx*)d_col, C, D, (cplx*)clp, st));
-  // The general-generator sweeps keep the slice propagators and the prefix of every slice: 2 N D^4 complex per sample.  Large
-  // batches are processed in chunks of samples that keep that below 24 GB (C3P_GRAD_CHUNK overrides the chunk size).
-  auto in_chunks = [&](auto&& run) -> int {  // run(b0, nb) -> 0 done, 1 not applicable, -1 error
-    long Bc = (long)(grad_store_budget(w, SL_OUT1) / (2 * (size_t)N * Dm * Dm * cs + 1));
-    if (c3p_opt(C3P_OPT_grad_chunk) > 0) Bc = c3p_opt(C3P_OPT_grad_chunk);
-    if (Bc < 1) Bc = 1;
-    for (long b0 = 0; b0 < B; b0 += Bc) {
-      const int rc = run(b0, (int)(B - b0 < Bc ? B - b0 : Bc));
-      if (rc != 0) return rc;
-    }
-    return 0;
-  };
-  const cplx* p_h0 = (const cplx*)d_h0;
-  const cplx* p_hk = (const cplx*)d_hks;
-  const double* p_sig = (const double*)d_sig;
-  const double* p_ph = (const double*)d_ph;
+  const PwcProblem P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, (const cplx*)clp, dt, B, K, N, D, Dm,
+                        1, (const double*)d_ph};
   const cplx* p_ub = (const cplx*)d_ub;
   double* p_grad = (double*)d_grad;
-  const long gsz = (long)Dm * Dm;
-  auto phase_at = [&](long b0) { return p_ph ? p_ph + b0 * Dm : nullptr; };
+  // The general-generator sweeps keep the slice propagators and the prefix of every slice: 2 N D^4 complex per sample.  Large
+  // batches are processed in chunks of samples that keep that below 24 GB (C3P_GRAD_CHUNK overrides the chunk size).
+  const size_t general_store = 2 * (size_t)N * Dm * Dm * cs;
+  // a family that served the call: the kernel it reports, the end of the timed span, the staged results back
+  auto served = [&](int kernel) -> int {
+    g_last_kernel = kernel;
+    if (record_stop(w, st)) return -1;
+    if (flags & C3P_HOST_PTRS) return sg.finish();
+    return 0;
+  };
   if (Dm <= kSmallDLimit && c3p_smalld_supported(Dm) && K <= 8 && !(flags & C3P_FORCE_GENERIC) && !c3p_opt_on(C3P_OPT_tiled_grad) &&
       !c3p_opt_on(C3P_OPT_valu_grad)) {
     // superoperators up to 12 x 12 (D <= 3): the general-generator sweep on the small-D matrix-core kernels
     if (record_start(w, st)) return -1;
-    const int rc = in_chunks([&](long b0, int nb) {
-      return run_vjp_lind_smalld(w, p_h0 + b0 * h0_bstride, h0_bstride, p_hk + b0 * hks_bstride, hks_bstride, p_sig + b0 * K * N,
-                                 (const cplx*)clp, dt, nb, K, N, D, Dm, phase_at(b0), p_ub + b0 * gsz, p_grad + b0 * K * N,
-                                 (flags & C3P_HERMITIAN_H) != 0, st);
+    const int rc = in_chunks(B, grad_chunk_samples(w, general_store), [&](long b0, int nb) {
+      return run_vjp_lind_smalld(w, P.chunk(b0, nb), ubar_at(P, p_ub, b0), grad_at(P, p_grad, b0), (flags & C3P_HERMITIAN_H) != 0, st);
     });
     if (rc < 0) return -1;
-    if (rc == 0) {
-      g_last_kernel = C3P_KERNEL_SMALLD;
-      if (record_stop(w, st)) return -1;
-      if (flags & C3P_HOST_PTRS) return sg.finish();
-      return 0;
-    }
+    if (rc == 0) return served(C3P_KERNEL_SMALLD);
   }
   if (D == 4 && (flags & C3P_HERMITIAN_H) && K <= 8 && !(flags & C3P_FORCE_GENERIC) && !c3p_opt_on(C3P_OPT_no_smallr) &&
       !c3p_opt_on(C3P_OPT_tiled_grad) && !c3p_opt_on(C3P_OPT_valu_grad)) {
     // two qubits with declared Hermitian Hamiltonians: the real Hermitian-basis kernels of c3p_smallr.hip, both halves
     if (record_start(w, st)) return -1;
-    const int rc = in_chunks([&](long b0, int nb) {
-      return run_vjp_lind_smallr16(w, p_h0 + b0 * h0_bstride, h0_bstride, p_hk + b0 * hks_bstride, hks_bstride, p_sig + b0 * K * N,
-                                   (const cplx*)clp, dt, nb, K, N, D, Dm, phase_at(b0), p_ub + b0 * gsz, p_grad + b0 * K * N, st);
+    const int rc = in_chunks(B, grad_chunk_samples(w, general_store), [&](long b0, int nb) {
+      return run_vjp_lind_smallr16(w, P.chunk(b0, nb), ubar_at(P, p_ub, b0), grad_at(P, p_grad, b0), st);
     });
     if (rc < 0) return -1;
-    if (rc == 0) {
-      g_last_kernel = C3P_KERNEL_MFMA;
-      if (record_stop(w, st)) return -1;
-      if (flags & C3P_HOST_PTRS) return sg.finish();
-      return 0;
-    }
+    if (rc == 0) return served(C3P_KERNEL_MFMA);
   }
   // 49 x 49 .. 81 x 81 superoperators (D = 7, 8, 9; cfg4) and, zero padded in the 49 class, 36 x 36 (D = 6): on-chip backward sweep in
   // the Hermitian basis, real arithmetic; the transposed local prefix of every slice (N D^4 doubles per sample) is kept in HBM:
   // chunks of samples below the budget.  1 = a Hamiltonian is not Hermitian (the caller goes on to the complex sweeps).
   auto try_regr = [&]() -> int {
     if (record_start(w, st)) return -1;
-    long Bc = (long)(grad_store_budget(w, SL_OUT1) / ((size_t)N * Dm * Dm * sizeof(double) + 1));
-    if (c3p_opt(C3P_OPT_grad_chunk) > 0) Bc = c3p_opt(C3P_OPT_grad_chunk);
-    if (Bc < 1) Bc = 1;
-    int rc = 0;
-    for (long b0 = 0; b0 < B && rc == 0; b0 += Bc) {
-      const int nb = (int)(B - b0 < Bc ? B - b0 : Bc);
-      rc = run_vjp_lind_regr(w, p_h0 + b0 * h0_bstride, h0_bstride, p_hk + b0 * hks_bstride, hks_bstride, p_sig + b0 * K * N,
-                             (const cplx*)clp, dt, nb, K, N, D, Dm, phase_at(b0), p_ub + b0 * gsz, p_grad + b0 * K * N, st);
+    const int rc = in_chunks(B, grad_chunk_samples(w, (size_t)N * Dm * Dm * sizeof(double)), [&](long b0, int nb) {
+      const int rc = run_vjp_lind_regr(w, P.chunk(b0, nb), ubar_at(P, p_ub, b0), grad_at(P, p_grad, b0), st);
       if (rc == 1 && b0 > 0) return fail("internal: the Hermitian-basis sweep declined a later chunk");
-    }
+      return rc;
+    });
     if (rc != 0) return rc;
-    g_last_kernel = C3P_KERNEL_MFMA;
-    if (record_stop(w, st)) return -1;
-    if (flags & C3P_HOST_PTRS) return sg.finish() ? -1 : 0;
-    return 0;
+    return served(C3P_KERNEL_MFMA);
   };
   const bool regr_ok = lind_regr_grad_ok(D, Dm) && !(flags & C3P_FORCE_GENERIC) && !c3p_opt_on(C3P_OPT_tiled_grad) &&
                        !c3p_opt_on(C3P_OPT_valu_grad) && !c3p_opt_on(C3P_OPT_no_hermitian_basis);
@@ -3095,44 +2907,29 @@ int c3p_pwc_lindblad_vjp(const void* h0, int64_t h0_bstride, const void* hks, in
   if (Dm >= 13 && Dm <= 36 && !(flags & C3P_FORCE_GENERIC) && !c3p_opt_on(C3P_OPT_tiled_grad) && !c3p_opt_on(C3P_OPT_valu_grad)) {
     // 16 x 16 .. 36 x 36 superoperators (D = 4, 5, 6): the same sweep on the mid-D matrix-core kernels
     if (record_start(w, st)) return -1;
-    const int rc = in_chunks([&](long b0, int nb) {
-      return run_vjp_lind_midd(w, p_h0 + b0 * h0_bstride, h0_bstride, p_hk + b0 * hks_bstride, hks_bstride, p_sig + b0 * K * N,
-                               (const cplx*)clp, dt, nb, K, N, D, Dm, phase_at(b0), p_ub + b0 * gsz, p_grad + b0 * K * N, st);
+    const int rc = in_chunks(B, grad_chunk_samples(w, general_store), [&](long b0, int nb) {
+      return run_vjp_lind_midd(w, P.chunk(b0, nb), ubar_at(P, p_ub, b0), grad_at(P, p_grad, b0), st);
     });
     if (rc < 0) return -1;
-    if (rc == 0) {
-      g_last_kernel = C3P_KERNEL_MFMA;
-      if (record_stop(w, st)) return -1;
-      if (flags & C3P_HOST_PTRS) return sg.finish();
-      return 0;
-    }
+    if (rc == 0) return served(C3P_KERNEL_MFMA);
   }
   if (Dm <= 36 && !c3p_opt_on(C3P_OPT_tiled_grad)) {
     // the same sweep in three VALU kernels on dense generator tables (c3p_grad.hip, general form): fallback and second opinion
     bool global = false;
-    auto run_valu = [&](long b0, int nb) -> int {
-      return run_vjp_lind_valu(w, p_h0 + b0 * h0_bstride, h0_bstride, p_hk + b0 * hks_bstride, hks_bstride, p_sig + b0 * K * N,
-                               (const cplx*)clp, dt, nb, K, N, D, phase_at(b0), p_ub + b0 * gsz, p_grad + b0 * K * N, nullptr, &global, st);
-    };
     if (record_start(w, st)) return -1;
-    if (in_chunks(run_valu) != 0) return -1;
-    g_last_kernel = global ? C3P_KERNEL_GENERIC_GLOBAL : C3P_KERNEL_GENERIC_LDS;
-    if (record_stop(w, st)) return -1;
-    if (flags & C3P_HOST_PTRS) return sg.finish();
-    return 0;
+    const int rc = in_chunks(B, grad_chunk_samples(w, general_store), [&](long b0, int nb) {
+      return run_vjp_lind_valu(w, P.chunk(b0, nb), ubar_at(P, p_ub, b0), grad_at(P, p_grad, b0), nullptr, &global, st);
+    });
+    if (rc != 0) return -1;
+    return served(global ? C3P_KERNEL_GENERIC_GLOBAL : C3P_KERNEL_GENERIC_LDS);
   }
   if (regr_ok && D != 6) {
     const int rc = try_regr();
     if (rc <= 0) return rc;
   }
-  g_last_kernel = C3P_KERNEL_MFMA;
   if (record_start(w, st)) return -1;
-  if (run_vjp_tiled(w, 1, (const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, (const cplx*)clp, dt, B,
-                    K, N, D, Dm, (const double*)d_ph, (const cplx*)d_ub, (double*)d_grad, st))
-    return -1;
-  if (record_stop(w, st)) return -1;
-  if (flags & C3P_HOST_PTRS) return sg.finish();
-  return 0;
+  if (run_vjp_tiled(w, P, p_ub, p_grad, st)) return -1;
+  return served(C3P_KERNEL_MFMA);
 }
 
 int c3p_pwc_lindblad_model_vjp(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
@@ -3158,8 +2955,8 @@ int c3p_pwc_lindblad_model_vjp(const void* h0, int64_t h0_bstride, const void* h
   void* d_grad = grad_signals;
   cplx *g_h0 = (cplx*)grad_h0, *g_hks = (cplx*)grad_hks, *g_col = (cplx*)grad_col_ops;
   if (flags & C3P_HOST_PTRS) {
-    if (sg.in(h0, ((size_t)(B - 1) * (size_t)h0_bstride + (size_t)D * D) * cs, &d_h0)) return -1;
-    if (sg.in(hks, ((size_t)(B - 1) * (size_t)hks_bstride + (size_t)K * D * D) * cs, &d_hks)) return -1;
+    if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)D * D) * cs, &d_h0)) return -1;
+    if (sg.in(hks, staged_elems(B, hks_bstride, (size_t)K * D * D) * cs, &d_hks)) return -1;
     if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
     if (sg.in(col_ops, (size_t)C * D * D * cs, &d_col)) return -1;
     if (sg.in(U_bar, (size_t)B * Dm * Dm * cs, &d_ub)) return -1;
@@ -3180,20 +2977,17 @@ int c3p_pwc_lindblad_model_vjp(const void* h0, int64_t h0_bstride, const void* h
   void* clp;
   if (ws_get(w, SL_CLP, (size_t)Dm * Dm * cs, &clp)) return -1;
   LAUNCH_TRY(c3p_launch_clp((const cplx*)d_col, C, D, (cplx*)clp, st));
-  // chunks of samples as in c3p_pwc_lindblad_vjp: the sweep keeps 2 N D^4 complex per sample
-  long Bc = (long)(grad_store_budget(w, SL_OUT1) / (2 * (size_t)N * Dm * Dm * cs + 1));
-  if (c3p_opt(C3P_OPT_grad_chunk) > 0) Bc = c3p_opt(C3P_OPT_grad_chunk);
-  if (Bc < 1) Bc = 1;
+  const PwcProblem P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, (const cplx*)clp, dt, B, K, N, D, Dm,
+                        1, (const double*)d_ph};
+  const LindModelOut mo = {(const cplx*)d_col, C, g_h0, g_hks, g_col};
   bool global = false;
   if (record_start(w, st)) return -1;
-  for (long b0 = 0; b0 < B; b0 += Bc) {
-    const int nb = (int)(B - b0 < Bc ? B - b0 : Bc);
-    const LindModelOut mo = {(const cplx*)d_col, C, g_h0 + b0 * Dm, g_hks + b0 * K * Dm, g_col + b0 * C * Dm};
-    if (run_vjp_lind_valu(w, (const cplx*)d_h0 + b0 * h0_bstride, h0_bstride, (const cplx*)d_hks + b0 * hks_bstride, hks_bstride,
-                          (const double*)d_sig + b0 * K * N, (const cplx*)clp, dt, nb, K, N, D, d_ph ? (const double*)d_ph + b0 * Dm : nullptr,
-                          (const cplx*)d_ub + b0 * (long)Dm * Dm, (double*)d_grad + b0 * K * N, &mo, &global, st))
-      return -1;
-  }
+  // chunks of samples as in c3p_pwc_lindblad_vjp: the sweep keeps 2 N D^4 complex per sample
+  const int rc = in_chunks(B, grad_chunk_samples(w, 2 * (size_t)N * Dm * Dm * cs), [&](long b0, int nb) {
+    const LindModelOut mc = mo.at(P, b0);
+    return run_vjp_lind_valu(w, P.chunk(b0, nb), ubar_at(P, (const cplx*)d_ub, b0), grad_at(P, (double*)d_grad, b0), &mc, &global, st);
+  });
+  if (rc != 0) return -1;
   g_last_kernel = global ? C3P_KERNEL_GENERIC_GLOBAL : C3P_KERNEL_GENERIC_LDS;
   if (record_stop(w, st)) return -1;
   if (flags & C3P_HOST_PTRS) return sg.finish();
@@ -3233,6 +3027,7 @@ int c3p_pwc_lindblad_taped(const void* h0, int64_t h0_bstride, const void* hks, 
   if (!h0 || !hks || !signals || !col_ops || C <= 0 || !U_out || !tape) return fail("NULL pointer argument");
   if (h0_bstride < 0 || hks_bstride < 0) return fail("negative batch stride");
   if (segments < 1 || segments > N) return fail("bad segment count %d", segments);
+  PwcProblem P = {(const cplx*)h0, h0_bstride, (const cplx*)hks, hks_bstride, signals, nullptr, dt, B, K, N, D, Dm, 1, fr_phase};  // (clp: below)
   if (D <= 4) {
     // small-D kernels: the forward half of run_vjp_lind_smalld writes into the tape, U = the ordered product of its segments
     int seg_chk = 0;
@@ -3247,32 +3042,26 @@ int c3p_pwc_lindblad_taped(const void* h0, int64_t h0_bstride, const void* hks, 
     void* clp;
     if (ws_get(w, SL_CLP, (size_t)Dm * Dm * sizeof(cplx), &clp)) return -1;
     LAUNCH_TRY(c3p_launch_clp((const cplx*)col_ops, C, D, (cplx*)clp, st));
+    P.clp = (const cplx*)clp;
     if (lind_smallr_ok((flags & C3P_HERMITIAN_H) != 0, D, Dm, K, N, segments)) {
       // declared Hermitian: the tape holds the REAL tables, segment products and slice propagators (c3p_pwc_lindblad_vjp_taped
       // must be given the same flag); U from the complex copies of the segment products
-      const bool ps = (h0_bstride != 0) || (hks_bstride != 0);
-      const int nsamp = ps ? B : 1;
+      const int nsamp = P.nsamp();
       const LindSmallRBufs rb = lind_smallr_carve(tape, lind_smallr_sizes(B, K, N, Dm, segments, nsamp), nsamp, Dm, K);
       void* sc;
       if (ws_get(w, SL_OUT2, (size_t)B * segments * Dm * Dm * sizeof(cplx), &sc)) return -1;
       if (record_start(w, st)) return -1;
-      if (lind_smallr_forward(rb, (const cplx*)h0, h0_bstride, (const cplx*)hks, hks_bstride, signals, (const cplx*)clp, dt, B, K, N, D, Dm, segments,
-                              (cplx*)sc, st))
-        return -1;
+      if (lind_smallr_forward(rb, P, segments, (cplx*)sc, st)) return -1;
       if (record_stop(w, st)) return -1;
       g_last_kernel = Dm > 12 ? C3P_KERNEL_MFMA : C3P_KERNEL_SMALLD;
-      const int keep = g_last_kernel;
-      const int rc = Dm > 12 ? combine_midd(w, (const cplx*)sc, B, segments, Dm, 0, fr_phase, (cplx*)U_out, st)
-                             : combine_smalld(w, (const cplx*)sc, B, segments, Dm, 0, fr_phase, (cplx*)U_out, st);
-      g_last_kernel = keep;
+      const int rc = Dm > 12 ? combine_chain(c3p_launch_midd_chain, w, (const cplx*)sc, B, segments, Dm, 0, fr_phase, (cplx*)U_out, st)
+                             : combine_chain(c3p_launch_smalld_chain, w, (const cplx*)sc, B, segments, Dm, 0, fr_phase, (cplx*)U_out, st);
       return rc ? -1 : 0;
     }
     if (D == 4) return fail("the taped Lindblad evaluation at D = 4 runs in the Hermitian basis: declare the Hamiltonians Hermitian (C3P_HERMITIAN_H) or use the untaped pair");
     const LindSmallBufs bf = lind_small_carve(tape, lind_small_sizes(B, K, N, Dm, segments, B));
     if (record_start(w, st)) return -1;
-    if (lind_small_forward(w, bf, (const cplx*)h0, h0_bstride, (const cplx*)hks, hks_bstride, signals, (const cplx*)clp, dt, B, K, N, D, Dm, segments,
-                           (flags & C3P_HERMITIAN_H) != 0, st))
-      return -1;
+    if (lind_small_forward(w, bf, P, segments, (flags & C3P_HERMITIAN_H) != 0, st)) return -1;
     if (record_stop(w, st)) return -1;
     g_last_kernel = C3P_KERNEL_SMALLD;
     if (segments == 1) {
@@ -3280,7 +3069,7 @@ int c3p_pwc_lindblad_taped(const void* h0, int64_t h0_bstride, const void* hks, 
       if (fr_phase) LAUNCH_TRY(c3p_launch_rowphase((cplx*)U_out, fr_phase, B, Dm, st));
       return 0;
     }
-    return combine_smalld(w, bf.seg, B, segments, Dm, 0, fr_phase, (cplx*)U_out, st) ? -1 : 0;
+    return combine_chain(c3p_launch_smalld_chain, w, bf.seg, B, segments, Dm, 0, fr_phase, (cplx*)U_out, st) ? -1 : 0;
   }
   if (!c3p_regr_supported(D, Dm)) return fail("the taped Lindblad evaluation serves D = 2, 3, 4 (small-D tile kernels) and D = 7, 8, 9 (Hermitian-basis kernels), got D=%d", D);
   {
@@ -3301,16 +3090,16 @@ int c3p_pwc_lindblad_taped(const void* h0, int64_t h0_bstride, const void* hks, 
   void* clp;
   if (ws_get(w, SL_CLP, (size_t)Dm * Dm * cs, &clp)) return -1;
   LAUNCH_TRY(c3p_launch_clp((const cplx*)col_ops, C, D, (cplx*)clp, st));
+  P.clp = (const cplx*)clp;
   const LindRegrBufs bf = lind_regr_carve(tape, z);
   if (record_start(w, st)) return -1;
-  const int rc = lind_regr_forward(w, bf, (const cplx*)h0, h0_bstride, (const cplx*)hks, hks_bstride, signals, (const cplx*)clp, dt, B, K, N, D,
-                                   Dm, segments, st);
+  const int rc = lind_regr_forward(w, bf, P, segments, st);
   if (rc < 0) return -1;
   if (rc == 1) return fail("a Hamiltonian is not Hermitian: its Lindblad generator is complex in the Hermitian basis (use c3p_pwc_lindblad and c3p_pwc_lindblad_vjp)");
   if (record_stop(w, st)) return -1;
   g_last_kernel = C3P_KERNEL_MFMA;
   // U: the segment products back in the reference's vectorisation (a copy: the tape keeps the real ones), ordered combine
-  const bool per_sample = (h0_bstride != 0) || (hks_bstride != 0);
+  const bool per_sample = P.per_sample();
   const long S = segments;
   cplx* segc = (cplx*)U_out;
   if (S > 1) {
@@ -3346,6 +3135,8 @@ int c3p_pwc_lindblad_vjp_taped(const void* tape, size_t tape_bytes, int segments
   const int Dm = D * D;
   if (!tape || !signals || !U_bar || !grad_signals) return fail("NULL pointer argument");
   if (segments < 1 || segments > N) return fail("bad segment count %d", segments);
+  // the operators are in the tape: of them the backward halves read only whether the tables are per sample (a nonzero stride)
+  const PwcProblem P = {nullptr, per_sample_operators ? 1 : 0, nullptr, 0, signals, nullptr, 0.0, B, K, N, D, Dm, 1, fr_phase};
   if (D <= 4) {
     int seg_chk = 0;
     const size_t need = c3p_pwc_lindblad_tape_bytes(B, K, N, D, &seg_chk);
@@ -3357,11 +3148,10 @@ int c3p_pwc_lindblad_vjp_taped(const void* tape, size_t tape_bytes, int segments
     if (!w) return fail("no HIP device");
     if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
     if (lind_smallr_ok((flags & C3P_HERMITIAN_H) != 0, D, Dm, K, N, segments)) {
-      const int nsamp = per_sample_operators ? B : 1;
+      const int nsamp = P.nsamp();
       const LindSmallRBufs rb = lind_smallr_carve(const_cast<void*>(tape), lind_smallr_sizes(B, K, N, Dm, segments, nsamp), nsamp, Dm, K);
       if (record_start(w, st)) return -1;
-      if (lind_smallr_backward(w, rb, per_sample_operators != 0, signals, B, K, N, D, Dm, segments, fr_phase, (const cplx*)U_bar, grad_signals, st))
-        return -1;
+      if (lind_smallr_backward(w, rb, P, segments, (const cplx*)U_bar, grad_signals, st)) return -1;
       if (record_stop(w, st)) return -1;
       g_last_kernel = Dm > 12 ? C3P_KERNEL_MFMA : C3P_KERNEL_SMALLD;
       return 0;
@@ -3369,7 +3159,7 @@ int c3p_pwc_lindblad_vjp_taped(const void* tape, size_t tape_bytes, int segments
     if (D == 4) return fail("the taped Lindblad evaluation at D = 4 needs C3P_HERMITIAN_H, as given to c3p_pwc_lindblad_taped");
     const LindSmallBufs bf = lind_small_carve(const_cast<void*>(tape), lind_small_sizes(B, K, N, Dm, segments, B));
     if (record_start(w, st)) return -1;
-    if (lind_small_backward(w, bf, per_sample_operators != 0, signals, B, K, N, Dm, segments, fr_phase, (const cplx*)U_bar, grad_signals, st)) return -1;
+    if (lind_small_backward(w, bf, P, segments, (const cplx*)U_bar, grad_signals, st)) return -1;
     if (record_stop(w, st)) return -1;
     g_last_kernel = C3P_KERNEL_SMALLD;
     return 0;
@@ -3391,7 +3181,7 @@ int c3p_pwc_lindblad_vjp_taped(const void* tape, size_t tape_bytes, int segments
   if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
   const LindRegrBufs bf = lind_regr_carve(const_cast<void*>(tape), z);
   if (record_start(w, st)) return -1;
-  if (lind_regr_backward(w, bf, per_sample_operators != 0, signals, B, K, N, D, Dm, segments, fr_phase, (const cplx*)U_bar, grad_signals, st)) return -1;
+  if (lind_regr_backward(w, bf, P, segments, (const cplx*)U_bar, grad_signals, st)) return -1;
   if (record_stop(w, st)) return -1;
   g_last_kernel = C3P_KERNEL_MFMA;
   return 0;
@@ -3670,88 +3460,6 @@ struct GoalSpec {
 };
 static int unitary_vjp_branch_a(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
                                 double dt, int B, int K, int N, int D, int flags, const double* fr_phase, const void* U_bar,
-                                double* grad_signals, void* gen_bar_out, void* stream, const GoalSpec* goal);
-
-int c3p_pwc_unitary_vjp(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride,
-                        const double* signals, double dt, int B, int K, int N, int D, int flags,
-                        const double* fr_phase, const void* U_bar, double* grad_signals, void* gen_bar_out,
-                        void* stream) {
-  if (flags & C3P_ORDER_RIGHT) return fail("c3p_pwc_unitary_vjp: unsupported flag");
-  if (flags & C3P_PER_SLICE_H) {
-    // branch B of pwc (propagation.py:295-308): the Hamiltonians are handed over per slice, so the result is the cotangent of
-    // every slice GENERATOR G_n = -i dt H_n (gen_bar_out) -- what the tape propagates on into model.get_Hamiltonian
-    if (B < 0 || N <= 0 || D <= 0) return fail("bad sizes B=%d N=%d D=%d", B, N, D);
-    if (B == 0) return 0;
-    if (!h0 || !U_bar || !gen_bar_out) return fail("per-slice gradient: h0 (the Hamiltonians), U_bar and gen_bar_out are required");
-    const size_t cs = sizeof(cplx);
-    hipStream_t st = (hipStream_t)stream;
-    WsLock lk(st);
-    DeviceWs* w = lk.w;
-    if (!w) return fail("no HIP device");
-    if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-    Stage sg{w, st};
-    const void *d_h = h0, *d_ph = fr_phase, *d_ub = U_bar;
-    void* d_z = gen_bar_out;
-    if (flags & C3P_HOST_PTRS) {
-      if (sg.in(h0, (size_t)(h0_bstride ? B : 1) * N * D * D * cs, &d_h)) return -1;
-      if (sg.in(U_bar, (size_t)B * D * D * cs, &d_ub)) return -1;
-      if (fr_phase && sg.in(fr_phase, (size_t)B * D * sizeof(double), &d_ph)) return -1;
-      if (sg.out(gen_bar_out, (size_t)B * N * D * D * cs, &d_z)) return -1;
-    }
-    if (D <= 40 && !(flags & C3P_FORCE_GENERIC) && !c3p_opt_on(C3P_OPT_tiled_grad)) {
-      // on-chip general-generator sweeps (nothing assumed about the slice Hamiltonians), in chunks of samples that keep the
-      // slice propagators + prefixes (2 N D^2 complex per sample) below 24 GB
-      long Bc = (long)(grad_store_budget(w, SL_OUT1) / (2 * (size_t)N * D * D * cs + 1));
-      if (c3p_opt(C3P_OPT_grad_chunk) > 0) Bc = c3p_opt(C3P_OPT_grad_chunk);
-      if (Bc < 1) Bc = 1;
-      int rc = 0;
-      for (long b0 = 0; b0 < B && rc == 0; b0 += Bc) {
-        const int nb = (int)(B - b0 < Bc ? B - b0 : Bc);
-        rc = run_vjp_xg_general(w, (const cplx*)d_h + b0 * h0_bstride, h0_bstride, 0.0, -dt, nb, N, D,
-                                d_ph ? (const double*)d_ph + b0 * D : nullptr, (const cplx*)d_ub + b0 * D * D,
-                                (cplx*)d_z + b0 * (long)N * D * D, st);
-      }
-      if (rc < 0) return -1;
-      if (rc == 0) {
-        g_last_kernel = D <= kSmallDLimit ? C3P_KERNEL_SMALLD : C3P_KERNEL_MFMA;
-        if (flags & C3P_HOST_PTRS) return sg.finish();
-        return 0;
-      }
-    }
-    g_last_kernel = C3P_KERNEL_MFMA;
-    if (run_vjp_tiled(w, 0, (const cplx*)d_h, h0_bstride, nullptr, 0, nullptr, nullptr, dt, B, 0, N, D, D, (const double*)d_ph,
-                      (const cplx*)d_ub, nullptr, st, true, (cplx*)d_z))
-      return -1;
-    if (flags & C3P_HOST_PTRS) return sg.finish();
-    return 0;
-  }
-  if (!U_bar) return fail("NULL pointer argument");
-  return unitary_vjp_branch_a(h0, h0_bstride, hks, hks_bstride, signals, dt, B, K, N, D, flags, fr_phase, U_bar, grad_signals,
-                              gen_bar_out, stream, nullptr);
-}
-
-int c3p_pwc_unitary_goal_vjp(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
-                             double dt, int B, int K, int N, int D, int flags, const double* fr_phase, const int32_t* comp_rows,
-                             int L, const void* ideal, int kind, double* infid_out, double* grad_signals, double* grad_fr_phase,
-                             void* U_out, void* stream) {
-  if (flags & (C3P_ORDER_RIGHT | C3P_PER_SLICE_H)) return fail("c3p_pwc_unitary_goal_vjp: unsupported flag");
-  if (L <= 0 || L > D || L > C3P_GOAL_LMAX) return fail("bad computational subspace size L=%d (D=%d, at most %d)", L, D, C3P_GOAL_LMAX);
-  if (kind != 0 && kind != 1) return fail("unknown infidelity kind %d", kind);
-  if (!comp_rows || !ideal || !infid_out) return fail("NULL pointer argument");
-  if (grad_fr_phase && !fr_phase) return fail("grad_fr_phase needs fr_phase");
-  if (D > 64 || (D > 40 && (B >= 384 || c3p_opt_on(C3P_OPT_tiled_grad))))
-    return fail("the fused goal runs on the on-chip and VALU backward sweeps (D <= 40, or D <= 64 below 384 samples): use "
-                "c3p_pwc_unitary, c3p_gate_overlap and c3p_pwc_unitary_vjp for D=%d B=%d", D, B);
-  if (flags & C3P_HOST_PTRS)
-    for (int a = 0; a < L; ++a)
-      if (comp_rows[a] < 0 || comp_rows[a] >= D) return fail("comp_rows[%d]=%d outside [0,%d)", a, comp_rows[a], D);
-  GoalSpec g = {comp_rows, L, ideal, kind, infid_out, grad_fr_phase, U_out};
-  return unitary_vjp_branch_a(h0, h0_bstride, hks, hks_bstride, signals, dt, B, K, N, D, flags, fr_phase, nullptr, grad_signals,
-                              nullptr, stream, &g);
-}
-
-static int unitary_vjp_branch_a(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
-                                double dt, int B, int K, int N, int D, int flags, const double* fr_phase, const void* U_bar,
                                 double* grad_signals, void* gen_bar_out, void* stream, const GoalSpec* goal) {
   if (B < 0 || K <= 0 || N <= 0 || D <= 0) return fail("bad sizes B=%d K=%d N=%d D=%d", B, K, N, D);
   if (D > 64 && gen_bar_out) return fail("gen_bar_out (per-slice generator cotangents) is available for D <= 64, got %d", D);
@@ -3783,8 +3491,8 @@ static int unitary_vjp_branch_a(const void* h0, int64_t h0_bstride, const void* 
           }
         if (dev > 1e-9 * mag) return fail("c3p_pwc_unitary_vjp needs Hermitian Hamiltonians (deviation %.3g)", dev);
       }
-    if (sg.in(h0, ((size_t)(B - 1) * (size_t)h0_bstride + (size_t)D * D) * cs, &d_h0)) return -1;
-    if (sg.in(hks, ((size_t)(B - 1) * (size_t)hks_bstride + (size_t)K * D * D) * cs, &d_hks)) return -1;
+    if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)D * D) * cs, &d_h0)) return -1;
+    if (sg.in(hks, staged_elems(B, hks_bstride, (size_t)K * D * D) * cs, &d_hks)) return -1;
     if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
     if (U_bar && sg.in(U_bar, (size_t)B * D * D * cs, &d_ub)) return -1;
     if (fr_phase && sg.in(fr_phase, (size_t)B * D * sizeof(double), &d_ph)) return -1;
@@ -3858,8 +3566,8 @@ static int unitary_vjp_branch_a(const void* h0, int64_t h0_bstride, const void* 
   // (the fused goal entry has no tiled form: it stays on the VALU sweep in its whole domain)
   const bool tiled_grad = goal ? false : tiled_unitary_grad(D, B);
   if (!done && !(flags & C3P_FORCE_GENERIC) && tiled_grad && !gen_bar_out) {
-    if (run_vjp_tiled(w, 0, A.h0, h0_bstride, A.hks, hks_bstride, A.signals, nullptr, dt, B, K, N, D, D, A.fr_phase, A.Ubar, A.grad, st))
-      return -1;
+    const PwcProblem P = {A.h0, h0_bstride, A.hks, hks_bstride, A.signals, nullptr, dt, B, K, N, D, D, 0, A.fr_phase};
+    if (run_vjp_tiled(w, P, A.Ubar, A.grad, st)) return -1;
     done = true;
     g_last_kernel = C3P_KERNEL_MFMA;
   }
@@ -3888,6 +3596,78 @@ static int unitary_vjp_branch_a(const void* h0, int64_t h0_bstride, const void* 
   if (record_stop(w, st)) return -1;
   if (flags & C3P_HOST_PTRS) return sg.finish();
   return 0;
+}
+
+int c3p_pwc_unitary_vjp(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride,
+                        const double* signals, double dt, int B, int K, int N, int D, int flags,
+                        const double* fr_phase, const void* U_bar, double* grad_signals, void* gen_bar_out,
+                        void* stream) {
+  if (flags & C3P_ORDER_RIGHT) return fail("c3p_pwc_unitary_vjp: unsupported flag");
+  if (flags & C3P_PER_SLICE_H) {
+    // branch B of pwc (propagation.py:295-308): the Hamiltonians are handed over per slice, so the result is the cotangent of
+    // every slice GENERATOR G_n = -i dt H_n (gen_bar_out) -- what the tape propagates on into model.get_Hamiltonian
+    if (B < 0 || N <= 0 || D <= 0) return fail("bad sizes B=%d N=%d D=%d", B, N, D);
+    if (B == 0) return 0;
+    if (!h0 || !U_bar || !gen_bar_out) return fail("per-slice gradient: h0 (the Hamiltonians), U_bar and gen_bar_out are required");
+    const size_t cs = sizeof(cplx);
+    hipStream_t st = (hipStream_t)stream;
+    WsLock lk(st);
+    DeviceWs* w = lk.w;
+    if (!w) return fail("no HIP device");
+    if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+    Stage sg{w, st};
+    const void *d_h = h0, *d_ph = fr_phase, *d_ub = U_bar;
+    void* d_z = gen_bar_out;
+    if (flags & C3P_HOST_PTRS) {
+      if (sg.in(h0, (size_t)(h0_bstride ? B : 1) * N * D * D * cs, &d_h)) return -1;
+      if (sg.in(U_bar, (size_t)B * D * D * cs, &d_ub)) return -1;
+      if (fr_phase && sg.in(fr_phase, (size_t)B * D * sizeof(double), &d_ph)) return -1;
+      if (sg.out(gen_bar_out, (size_t)B * N * D * D * cs, &d_z)) return -1;
+    }
+    // the slice Hamiltonians as the record's h0: no control operators, no signals (K = 0)
+    const PwcProblem P = {(const cplx*)d_h, h0_bstride, nullptr, 0, nullptr, nullptr, dt, B, 0, N, D, D, 0, (const double*)d_ph};
+    auto served = [&](int kernel) -> int {  // (this branch has no timed span)
+      g_last_kernel = kernel;
+      if (flags & C3P_HOST_PTRS) return sg.finish();
+      return 0;
+    };
+    if (D <= 40 && !(flags & C3P_FORCE_GENERIC) && !c3p_opt_on(C3P_OPT_tiled_grad)) {
+      // on-chip general-generator sweeps (nothing assumed about the slice Hamiltonians), in chunks of samples that keep the
+      // slice propagators + prefixes (2 N D^2 complex per sample) below 24 GB
+      const int rc = in_chunks(B, grad_chunk_samples(w, 2 * (size_t)N * D * D * cs), [&](long b0, int nb) {
+        const PwcProblem c = P.chunk(b0, nb);
+        return run_vjp_xg_general(w, c.h0, h0_bstride, 0.0, -dt, nb, N, D, c.fr_phase, ubar_at(P, (const cplx*)d_ub, b0),
+                                  (cplx*)d_z + b0 * (long)N * D * D, st);
+      });
+      if (rc < 0) return -1;
+      if (rc == 0) return served(D <= kSmallDLimit ? C3P_KERNEL_SMALLD : C3P_KERNEL_MFMA);
+    }
+    if (run_vjp_tiled(w, P, (const cplx*)d_ub, nullptr, st, true, (cplx*)d_z)) return -1;
+    return served(C3P_KERNEL_MFMA);
+  }
+  if (!U_bar) return fail("NULL pointer argument");
+  return unitary_vjp_branch_a(h0, h0_bstride, hks, hks_bstride, signals, dt, B, K, N, D, flags, fr_phase, U_bar, grad_signals,
+                              gen_bar_out, stream, nullptr);
+}
+
+int c3p_pwc_unitary_goal_vjp(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
+                             double dt, int B, int K, int N, int D, int flags, const double* fr_phase, const int32_t* comp_rows,
+                             int L, const void* ideal, int kind, double* infid_out, double* grad_signals, double* grad_fr_phase,
+                             void* U_out, void* stream) {
+  if (flags & (C3P_ORDER_RIGHT | C3P_PER_SLICE_H)) return fail("c3p_pwc_unitary_goal_vjp: unsupported flag");
+  if (L <= 0 || L > D || L > C3P_GOAL_LMAX) return fail("bad computational subspace size L=%d (D=%d, at most %d)", L, D, C3P_GOAL_LMAX);
+  if (kind != 0 && kind != 1) return fail("unknown infidelity kind %d", kind);
+  if (!comp_rows || !ideal || !infid_out) return fail("NULL pointer argument");
+  if (grad_fr_phase && !fr_phase) return fail("grad_fr_phase needs fr_phase");
+  if (D > 64 || (D > 40 && (B >= 384 || c3p_opt_on(C3P_OPT_tiled_grad))))
+    return fail("the fused goal runs on the on-chip and VALU backward sweeps (D <= 40, or D <= 64 below 384 samples): use "
+                "c3p_pwc_unitary, c3p_gate_overlap and c3p_pwc_unitary_vjp for D=%d B=%d", D, B);
+  if (flags & C3P_HOST_PTRS)
+    for (int a = 0; a < L; ++a)
+      if (comp_rows[a] < 0 || comp_rows[a] >= D) return fail("comp_rows[%d]=%d outside [0,%d)", a, comp_rows[a], D);
+  GoalSpec g = {comp_rows, L, ideal, kind, infid_out, grad_fr_phase, U_out};
+  return unitary_vjp_branch_a(h0, h0_bstride, hks, hks_bstride, signals, dt, B, K, N, D, flags, fr_phase, nullptr, grad_signals,
+                              nullptr, stream, &g);
 }
 
 int c3p_synth_signals_vjp(const double* env_params, const int32_t* env_shapes, const double* carrier,

@@ -270,6 +270,24 @@ def test_lindblad_tape_layout_is_host_arithmetic(lib):
     assert lib.c3p_pwc_lindblad_tape_bytes(4, 17, 100, 9, None) == 0  # more control lines than the kernels hold
 
 
+def test_lindblad_tape_plan_is_pinned(lib):
+    """Bytes and segment count of c3p_pwc_lindblad_tape_bytes on 420 shapes (308 of them served), recorded in
+    tests/golden/lindblad_tape_plan.json from the library before the host layer took one problem record: the segment planners of the
+    small-D, two-qubit and Hermitian-basis sweeps and the three tape layouts, all host arithmetic (no device, no option set)."""
+    import ctypes
+    import itertools
+    import json
+
+    plan = json.load(open(os.path.join(ROOT, "tests", "golden", "lindblad_tape_plan.json")))
+    shapes = list(itertools.product(plan["D"], plan["B"], plan["K"], plan["N"]))
+    assert len(shapes) == len(plan["bytes"]) == len(plan["segments"]) == 420
+    assert sum(1 for n in plan["bytes"] if n > 0) == 308
+    for (D, B, K, N), nbytes, segments in zip(shapes, plan["bytes"], plan["segments"]):
+        seg = ctypes.c_int(-1)
+        got = lib.c3p_pwc_lindblad_tape_bytes(B, K, N, D, ctypes.byref(seg))
+        assert (got, seg.value) == (nbytes, segments), (D, B, K, N)
+
+
 def _build_abi_client(tmp_path):
     import shutil
     import subprocess

@@ -384,16 +384,31 @@ def test_lindblad_vjp_small_superoperators_general_sweep(prop, D, N, B, C, per_s
         assert np.abs(g[b] - want).max() < 1e-10 * np.abs(want).max()
 
 
+# (D, Hermitian h0 / hks, per-sample operators): the real small-D sweeps (the first two), then the complex small-D sweep, the mid-D
+# sweep, the Hermitian-basis sweep at 49 x 49, and one set of operators shared by all samples (batch strides 0)
+_CHUNK_CASES = [pytest.param(2, True, True, id="2"), pytest.param(4, True, True, id="4")] + [
+    pytest.param(D, herm, True, id=f"{D}-{'hermitian' if herm else 'general'}")
+    for D, herm in [(3, True), (2, False), (3, False), (4, False), (5, True), (6, True), (7, True)]
+] + [pytest.param(3, True, False, id="3-hermitian-shared")]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("D", [2, 4])
-def test_lindblad_vjp_sample_chunks(prop, D):
+@pytest.mark.parametrize("D,hermitian,per_sample", _CHUNK_CASES)
+def test_lindblad_vjp_sample_chunks(prop, D, hermitian, per_sample):
     """Large batches run the general-generator sweep in chunks of samples (its workspace is 2 N D^4 complex per sample):
-    C3P_GRAD_CHUNK=2 on five samples with per-sample operators and frame phases must reproduce the single-chunk result."""
+    C3P_GRAD_CHUNK=2 on five samples with per-sample operators and frame phases must reproduce the single-chunk result.
+    Every kernel family of the entry point cuts its chunks from the same record of the call, so each is run once."""
     rng = np.random.default_rng(D)
-    herm = lambda s: (lambda a: s * (a + a.conj().T) / 2)(rng.normal(size=(D, D)) + 1j * rng.normal(size=(D, D)))
+    if hermitian:
+        op = lambda s: (lambda a: s * (a + a.conj().T) / 2)(rng.normal(size=(D, D)) + 1j * rng.normal(size=(D, D)))
+    else:
+        op = lambda s: s * (rng.normal(size=(D, D)) + 1j * rng.normal(size=(D, D))) / 2
     B, K, N, Dm = 5, 2, 24, D * D
-    h0 = np.stack([herm(0.8) for _ in range(B)])
-    hks = np.stack([np.stack([herm(0.5) for _ in range(K)]) for _ in range(B)])
+    if per_sample:
+        h0 = np.stack([op(0.8) for _ in range(B)])
+        hks = np.stack([np.stack([op(0.5) for _ in range(K)]) for _ in range(B)])
+    else:
+        h0, hks = op(0.8), np.stack([op(0.5) for _ in range(K)])
     col = np.stack([0.25 * (rng.normal(size=(D, D)) + 1j * rng.normal(size=(D, D)))])
     sig = rng.uniform(-1, 1, size=(B, K, N))
     Ubar = rng.normal(size=(B, Dm, Dm)) + 1j * rng.normal(size=(B, Dm, Dm))
@@ -402,14 +417,16 @@ def test_lindblad_vjp_sample_chunks(prop, D):
     _lib.set_option("grad_chunk", "2")
     try:
         many = np.asarray(prop.propagate_batch_lindblad_vjp(h0, hks, sig, 0.3, col, Ubar, fr_phase=ph))
-        _lib.set_option("valu_grad", "1")
-        valu = np.asarray(prop.propagate_batch_lindblad_vjp(h0, hks, sig, 0.3, col, Ubar, fr_phase=ph))
+        if Dm <= 36:
+            _lib.set_option("valu_grad", "1")
+            valu = np.asarray(prop.propagate_batch_lindblad_vjp(h0, hks, sig, 0.3, col, Ubar, fr_phase=ph))
     finally:
         _lib.set_option("grad_chunk", None)
         _lib.set_option("valu_grad", None)
     assert np.abs(one - many).max() < 1e-12 * np.abs(one).max()
-    assert np.abs(one - valu).max() < 1e-10 * np.abs(one).max()
-    want = o.pwc_lindblad_signal_gradient(h0[4], hks[4], col, sig[4], 0.3, Ubar[4], ph[4])
+    if Dm <= 36:  # (beyond 36 x 36 there is no VALU sweep to compare with)
+        assert np.abs(one - valu).max() < 1e-10 * np.abs(one).max()
+    want = o.pwc_lindblad_signal_gradient(h0[4] if per_sample else h0, hks[4] if per_sample else hks, col, sig[4], 0.3, Ubar[4], ph[4])
     assert np.abs(many[4] - want).max() < 1e-10 * np.abs(want).max()
 
 
