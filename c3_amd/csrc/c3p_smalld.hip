@@ -710,40 +710,63 @@ __device__ __forceinline__ void row_phase_factors(const double* row_phase, const
   }
 }
 
+// out = zh with the lane's rows times the complex factors pr[I] + i pi[I], in D-layout.  r even: mine = Re, other = Im; r odd:
+// mine = Im, other = Re -- the partner's halves come from lane ^ 16, all exchanges in flight together (behind the predicated
+// stores of store_plain each one was a round trip of its own: 15 in a row in the final store of cfg2).
+template <int D>
+__device__ __forceinline__ void scale_rows(const double (&zh)[SD<D>::NBI][SD<D>::NJ], const double (&pr)[SD<D>::NBI],
+                                           const double (&pi)[SD<D>::NBI], const LanePos& lp,
+                                           double (&out)[SD<D>::NBI][SD<D>::NJ]) {
+  using C = SD<D>;
+  double oth[C::NBI][C::NJ];
+#pragma unroll
+  for (int I = 0; I < C::NBI; ++I)
+#pragma unroll
+    for (int J = 0; J < C::NJ; ++J) oth[I][J] = __shfl_xor(zh[I][J], 16);
+#pragma unroll
+  for (int I = 0; I < C::NBI; ++I)
+#pragma unroll
+    for (int J = 0; J < C::NJ; ++J)
+      out[I][J] = (lp.r & 1) ? fma(pr[I], zh[I][J], pi[I] * oth[I][J]) : fma(pr[I], zh[I][J], -pi[I] * oth[I][J]);
+}
+
 template <int D, bool WRITE_THROUGH = false>
 __device__ __forceinline__ void store_plain(const double (&zh)[SD<D>::NBI][SD<D>::NJ], double* dst,
                                             double sr, double si, const double* row_phase,
                                             const LanePos& lp, bool active, const double* pre_c = nullptr,
                                             const double* pre_s = nullptr) {
   using C = SD<D>;
+  double pr[C::NBI], pi[C::NBI];
 #pragma unroll
   for (int I = 0; I < C::NBI; ++I) {
     const int row = 2 * I + (lp.r >> 1);
-    double pr = sr, pi = si;
+    pr[I] = sr, pi[I] = si;
     if (pre_c != nullptr) {
-      pr = sr * pre_c[I] - si * pre_s[I];
-      pi = sr * pre_s[I] + si * pre_c[I];
+      pr[I] = sr * pre_c[I] - si * pre_s[I];
+      pi[I] = sr * pre_s[I] + si * pre_c[I];
     } else if (row_phase != nullptr && row < D) {
       double sn, cs;
       sincos(row_phase[row], &sn, &cs);
-      pr = sr * cs - si * sn;
-      pi = sr * sn + si * cs;
+      pr[I] = sr * cs - si * sn;
+      pi[I] = sr * sn + si * cs;
     }
+  }
+  double outv[C::NBI][C::NJ];
+  scale_rows<D>(zh, pr, pi, lp, outv);
+#pragma unroll
+  for (int I = 0; I < C::NBI; ++I) {
+    const int row = 2 * I + (lp.r >> 1);
 #pragma unroll
     for (int J = 0; J < C::NJ; ++J) {
-      const double mine = zh[I][J];
-      const double other = __shfl_xor(mine, 16);
-      // r even: mine = Re, other = Im ; r odd: mine = Im, other = Re
-      const double outv = (lp.r & 1) ? fma(pr, mine, pi * other) : fma(pr, mine, -pi * other);
       const int col = 4 * J + lp.c;
       if (active && row < D && col < D) {
         double* p = dst + (row * D + col) * 2 + (lp.r & 1);
         if constexpr (WRITE_THROUGH) {
           // sc1 (write-through) store: visible to other CUs/XCDs without a release fence
-          __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(outv),
+          __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(outv[I][J]),
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
-          *p = outv;
+          *p = outv[I][J];
         }
       }
     }
@@ -862,7 +885,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
   const int wv = MW ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
   const int nwv = MW ? (int)(blockDim.x >> 6) : 1;
 #ifdef C3P_SD_TIMING
-  long long tk0 = wall_clock64(), tk1 = 0, tk2 = 0, tk3 = 0, tk4 = 0, tk5 = 0, tk6 = 0, tk7 = 0, tk8 = 0, tk9 = 0;
+  long long tk0 = wall_clock64(), tk1 = 0, tk2 = 0, tk3 = 0, tk4 = 0, tk5 = 0, tk6 = 0, tk7 = 0, tk8 = 0, tk9 = 0, tkl = 0, tka = 0, tkb = 0;
 #define SD_TICK(v) v = wall_clock64()
 #else
 #define SD_TICK(v)
@@ -878,7 +901,6 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
   const int SG = ((K + ((SPLIT && K > 0) ? 1 : 0)) * A.Lmax) | 1;
   double* img = tab + ((GIVEN || XG) ? 0 : (1 + K) * (MAT + 4)) + wv * (4 * IMG + 4 * SG);  // this wave's 4 chain images
   double* sg = img + 4 * IMG;  // 4 chains x K x Lmax signals, odd chain stride (bank spread)
-  double* part = tab + (1 + K) * (MAT + 4) + nwv * (4 * IMG + 4 * SG);  // MW: the waves' partial products [nwv][D][D][2]
 
   // XCD-aware block order: workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  Logical block
   // (bid % 8) * (nb / 8) + bid / 8 keeps consecutive logical blocks -- the waves of one sample, which exchange their
@@ -927,6 +949,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
 
   double U[NBI][NJ];
   double mus_r = 0.0, mus_i = 0.0;
+  bool img_holds_U = false;      // the chains' images hold U (the real loops leave it there on their way back to the half-image layout)
 
   if constexpr (GIVEN) {
     // ---- ordered product of supplied matrices ----
@@ -1304,10 +1327,12 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
           split_loop_k(std::true_type{});
         else
           split_loop_k(std::false_type{});
-        // back to the complex half-image layout of the epilogue (once per segment, through the chain's image)
+        SD_TICK(tkl);
+        // back to the complex half-image layout of the epilogue (once per segment, through the chain's image, which stays behind
+        // as the left operand of the fold's first product).  Only the padding is zeroed: rows 2 D, 2 D + 1 and columns D .. 4 NJ - 1.
         wave_sync();
-        for (int e = lp.idx16; e < 4 * NBI * W; e += 16) img[lp.b * IMG + e] = 0.0;
-        wave_sync();
+        if (lp.idx16 < 4 * NJ) img[lp.b * IMG + 2 * D * W + lp.idx16] = img[lp.b * IMG + (2 * D + 1) * W + lp.idx16] = 0.0;
+        for (int e = lp.idx16; e < 2 * D * (4 * NJ - D); e += 16) img[lp.b * IMG + (e / (4 * NJ - D)) * W + D + e % (4 * NJ - D)] = 0.0;
 #pragma unroll
         for (int I = 0; I < NC; ++I) {
           const int i = 4 * I + lp.r;
@@ -1335,6 +1360,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
 #pragma unroll
           for (int J = 0; J < NJ; ++J) U[I][J] = img[woff + I * 4 * W + J * 4];
         wave_sync();
+        img_holds_U = true;
       } else {
       for (int t = 0; t < tmax; ++t) {
         // (Two waves share a SIMD and the arbiter serves the OLDER one first: wave w finishes its segment at ~64 % of the
@@ -1508,6 +1534,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
 #pragma unroll
         for (int J = 0; J < NJ; ++J) U[I][J] = img[woff + I * 4 * W + J * 4];
       wave_sync();
+      img_holds_U = true;
       }  // !SPLIT
     } else {
     // the slice loop is instantiated per plan (T18 / Paterson-Stockmeyer) with the branch outside, as on the real path
@@ -1763,7 +1790,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
   // ---- segment result ----
   SD_TICK(tk2);
 #ifdef C3P_SD_TIMING
-  if (MW && blockIdx.x == 7 && lane == 0) printf("sd wave %d: loop ends at %lld (100 MHz ticks after the wave's start), prologue %lld, slices %d\n", wv, tk2 - tk0, tk1 - tk0, tmax);
+  if (tkl == 0) tkl = tk2;
 #endif
   if constexpr (!GIVEN) {
     if (A.fuse) {
@@ -1777,60 +1804,113 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
       const int roff1 = ((lp.b + 1) & 3) * IMG + rrest;  // A fragments of the NEXT chain's image
       const int roff2 = ((lp.b + 2) & 3) * IMG + rrest;
       double V[NBI][NJ], Wt[NBI][NJ];
+      // Wt (slot 0) = M3 M2 M1 M0 of the four slots' matrices; `in_image`: the chains' images hold M already
+      auto fold_slots = [&](const double (&M)[NBI][NJ], bool in_image) {
 #pragma unroll
-      for (int I = 0; I < NBI; ++I)
+        for (int I = 0; I < NBI; ++I)
 #pragma unroll
-        for (int J = 0; J < NJ; ++J) V[I][J] = Wt[I][J] = 0.0;
-      write_image<D>(U, img, woff);
-      mm_img<D>(img, roff1, negmask, U, V);  // slots 0, 2: U_{b+1} U_b
-      write_image<D>(V, img, woff);
-      mm_img<D>(img, roff2, negmask, V, Wt);  // slot 0: (U3 U2)(U1 U0)
+          for (int J = 0; J < NJ; ++J) V[I][J] = Wt[I][J] = 0.0;
+        if (!in_image) write_image<D>(M, img, woff);
+        mm_img<D>(img, roff1, negmask, M, V);  // slots 0, 2: M_{b+1} M_b
+        write_image<D>(V, img, woff);
+        mm_img<D>(img, roff2, negmask, V, Wt);  // slot 0: (M3 M2)(M1 M0)
+      };
+      fold_slots(U, img_holds_U);
+      SD_TICK(tka);
       const int nW = A.S >> 2;
       const int wq = seg >> 2;
+      const double* ph = A.fr_phase ? A.fr_phase + (long)sample * D : nullptr;
+      double* dst = reinterpret_cast<double*>(A.final_out) + (long)sample * D * D * 2;
+      const int lo = (lp.b * nW) >> 2, hi = ((lp.b + 1) * nW) >> 2;
+      const int cnt = hi - lo;
+      const int cmax = (nW + 3) >> 2;
       double sn, cs;
       sincos(ti, &sn, &cs);
       // (Hermitian Hamiltonians: the trace shifts are imaginary, tr = 0 exactly -- skip the double-precision exp of the fold)
       double er = 1.0;
       if (__ballot(tr != 0.0) != 0) er = exp(tr);
-      const double* ph = A.fr_phase ? A.fr_phase + (long)sample * D : nullptr;
-      if (nW == 1) {
-        double* dst = reinterpret_cast<double*>(A.final_out) + (long)sample * D * D * 2;
-        store_plain<D>(Wt, dst, er * cs, er * sn, ph, lp, valid && lp.b == 0);
-        return;
-      }
-      const int lo = (lp.b * nW) >> 2, hi = ((lp.b + 1) * nW) >> 2;
-      const int cnt = hi - lo;
-      const int cmax = (nW + 3) >> 2;
-      const double* base;
-      double phc[NBI], phs[NBI];
+      SD_TICK(tkb);
       if constexpr (MW) {
-        // (2) the waves of the sample are the waves of this workgroup: partials through LDS, wave 0 folds them
-        store_plain<D>(Wt, part + (long)wq * D * D * 2, er * cs, er * sn, nullptr, lp, lp.b == 0);
+        // (2) the waves of the sample are the waves of this workgroup and wave 0 folds their partials behind a barrier.  A partial
+        // is handed over in the layout its consumer reads: scaled by the wave's e^{tr + i ti} in registers (scale_rows, the
+        // arithmetic of store_plain: with equal segments this mode is bit for bit the one-wave mode, tests/test_gpu_round2.py) and
+        // written as the image of the wave's chain 0 (the wave's other three images take the unused slots of Wt), from which wave 0
+        // reads right operands in register order and streams left operands as they are.
+        {
+          double pr[NBI], pi[NBI];
+#pragma unroll
+          for (int I = 0; I < NBI; ++I) pr[I] = er * cs, pi[I] = er * sn;
+          scale_rows<D>(Wt, pr, pi, lp, V);
+        }
+        write_image<D>(V, img, woff);
         SD_TICK(tk3);
         // (wave 0 -- the older wave of its SIMD, through its loop first -- evaluates the row phases of the final store
         // while it waits for the others: five double-precision sincos, 1.5 us otherwise spent after the barrier)
+        double phc[NBI], phs[NBI];
         if (wv == 0) row_phase_factors<D>(ph, lp, phc, phs);
         __syncthreads();
+#ifdef C3P_SD_TIMING
+        if (blockIdx.x == 7 && lane == 0)
+          printf("sd wave %d: slices %d, prologue to the table barrier %lld, behind it %lld, loop ends at %lld (100 MHz ticks after the wave's start); "
+                 "layout %lld products %lld phase %lld partial store %lld\n", wv, tmax, tk9 - tk0, tk1 - tk9, tkl - tk0, tk2 - tkl, tka - tk2, tkb - tka, tk3 - tkb);
+#endif
         if (wv != 0) return;
         SD_TICK(tk5);
-        base = part + (long)lo * D * D * 2;
-      } else {
-        {
-          double* dst = reinterpret_cast<double*>(A.seg_out) + ((long)sample * nW + wq) * D * D * 2;
-          store_plain<D, true>(Wt, dst, er * cs, er * sn, nullptr, lp, valid && lp.b == 0);
+        // slot b takes a contiguous quarter of the nW partials (none: the identity); partial p is image 0 of wave p
+        const int pstride = 4 * IMG + 4 * SG;
+        const int woff0 = woff - lp.b * IMG;
+#pragma unroll
+        for (int I = 0; I < NBI; ++I)
+#pragma unroll
+          for (int J = 0; J < NJ; ++J) {
+            const int row = 2 * I + (lp.r >> 1), col = 4 * J + lp.c;
+            const double idv = (row < D && row == col && (lp.r & 1) == 0) ? 1.0 : 0.0;
+            U[I][J] = cnt > 0 ? img[lo * pstride + woff0 + I * 4 * W + J * 4] : idv;
+          }
+        for (int t = 1; t < cmax; ++t) {
+          const bool act = t < cnt;
+          double acc[NBI][NJ];
+#pragma unroll
+          for (int I = 0; I < NBI; ++I)
+#pragma unroll
+            for (int J = 0; J < NJ; ++J) acc[I][J] = 0.0;
+          mm_img<D>(img, (act ? lo + t : 0) * pstride + rrest, negmask, U, acc);
+#pragma unroll
+          for (int I = 0; I < NBI; ++I)
+#pragma unroll
+            for (int J = 0; J < NJ; ++J) U[I][J] = act ? acc[I][J] : U[I][J];
         }
-        // (2) publish and arrive (cdna guide G16, form R1: write-through payload, drain, relaxed ticket)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        int old = 0;
-        if (lane == 0)
-          old = __hip_atomic_fetch_add(A.counters + sample, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        old = __builtin_amdgcn_readfirstlane(old);
-        if (old != nW - 1) return;
-        if (lane == 0) A.counters[sample] = 0;  // self-resetting: the next launch finds it zero
-        // (3) last arriver of this sample: fold the nW partials (slot b takes a contiguous quarter)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        base = reinterpret_cast<const double*>(A.seg_out) + ((long)sample * nW + lo) * D * D * 2;
+        SD_TICK(tk6);
+        fold_slots(U, false);
+        SD_TICK(tk7);
+        store_plain<D>(Wt, dst, 1.0, 0.0, ph, lp, lp.b == 0, phc, phs);
+#ifdef C3P_SD_TIMING
+        SD_TICK(tk4);
+        if (blockIdx.x == 0 && threadIdx.x == 0)
+          printf("sd timing (100 MHz ticks): tables %lld signals %lld prologue %lld loop %lld fold4+store %lld barrier %lld level1 %lld fold2 %lld store %lld total %lld\n", tk8 - tk0, tk9 - tk8, tk1 - tk0, tk2 - tk1, tk3 - tk2, tk5 - tk3, tk6 - tk5, tk7 - tk6, tk4 - tk7, tk4 - tk0);
+#endif
+        return;
       }
+      // one-wave workgroups: the partials meet in global memory behind a ticket, as plain complex arrays
+      if (nW == 1) {
+        store_plain<D>(Wt, dst, er * cs, er * sn, ph, lp, valid && lp.b == 0);
+        return;
+      }
+      {
+        double* pdst = reinterpret_cast<double*>(A.seg_out) + ((long)sample * nW + wq) * D * D * 2;
+        store_plain<D, true>(Wt, pdst, er * cs, er * sn, nullptr, lp, valid && lp.b == 0);
+      }
+      // (2) publish and arrive (cdna guide G16, form R1: write-through payload, drain, relaxed ticket)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      int old = 0;
+      if (lane == 0)
+        old = __hip_atomic_fetch_add(A.counters + sample, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      old = __builtin_amdgcn_readfirstlane(old);
+      if (old != nW - 1) return;
+      if (lane == 0) A.counters[sample] = 0;  // self-resetting: the next launch finds it zero
+      // (3) last arriver of this sample: fold the nW partials (slot b takes a contiguous quarter)
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      const double* base = reinterpret_cast<const double*>(A.seg_out) + ((long)sample * nW + lo) * D * D * 2;
       // the next partial of the slot is always in flight while the current product runs, and the first two are
       // fetched together: ONE cross-CU memory round trip for S <= 32
       double Pn[NBI][NJ];
@@ -1870,26 +1950,8 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
             for (int J = 0; J < NJ; ++J) U[I][J] = acc[I][J];
         }
       }
-      SD_TICK(tk6);
-#pragma unroll
-      for (int I = 0; I < NBI; ++I)
-#pragma unroll
-        for (int J = 0; J < NJ; ++J) V[I][J] = Wt[I][J] = 0.0;
-      write_image<D>(U, img, woff);
-      mm_img<D>(img, roff1, negmask, U, V);
-      write_image<D>(V, img, woff);
-      mm_img<D>(img, roff2, negmask, V, Wt);
-      SD_TICK(tk7);
-      double* dst = reinterpret_cast<double*>(A.final_out) + (long)sample * D * D * 2;
-      if constexpr (MW)
-        store_plain<D>(Wt, dst, 1.0, 0.0, ph, lp, lp.b == 0, phc, phs);
-      else
-        store_plain<D>(Wt, dst, 1.0, 0.0, ph, lp, lp.b == 0);
-#ifdef C3P_SD_TIMING
-      SD_TICK(tk4);
-      if (MW && blockIdx.x == 0 && threadIdx.x == 0)
-        printf("sd timing (100 MHz ticks): tables %lld signals %lld prologue %lld loop %lld fold4+store %lld barrier %lld level1 %lld fold2 %lld store %lld total %lld\n", tk8 - tk0, tk9 - tk8, tk1 - tk0, tk2 - tk1, tk3 - tk2, tk5 - tk3, tk6 - tk5, tk7 - tk6, tk4 - tk7, tk4 - tk0);
-#endif
+      fold_slots(U, false);
+      store_plain<D>(Wt, dst, 1.0, 0.0, ph, lp, lp.b == 0);
       return;
     }
   }
@@ -2020,6 +2082,8 @@ hipError_t launch_chain_t(const SmallArgs& A, hipStream_t st) {
     // B workgroups to be resident at once (8 waves per CU at two per SIMD): B = 256, S = 32 -> 256 workgroups of 8 waves
     const int nW = A.S >> 2;
     const size_t wstride = (size_t)(4 * C::IMG + 4 * ((krows * A.Lmax) | 1));
+    // (the last term held the waves' partial products as plain arrays; they now stay in the waves' images.  It is kept in both sizes
+    // below on purpose: it counts toward the gates that choose this mode and its split, and no shape is to change path here)
     const size_t lds_mw = (size_t)((1 + A.K) * (C::MAT + 4) + nW * wstride + (size_t)nW * D * D * 2) * sizeof(double);
     const bool mw = A.fuse && (A.S & 3) == 0 && (nW == 2 || nW == 4 || nW == 8) && (long)A.B * nW <= 2048 &&
                     lds_mw * (8 / nW) <= (size_t)156 * 1024 && !c3p_opt_on(C3P_OPT_no_mw);
