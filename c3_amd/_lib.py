@@ -59,6 +59,7 @@ SIGNATURES = {
     "c3p_pwc_unitary_goal_vjp": (_i, [_vp, _i64, _vp, _i64, _vp, _d, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "c3p_pwc_lindblad_vjp": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _d, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "c3p_pwc_lindblad_model_vjp": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _d, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c3p_pwc_lindblad_model_vjp_hb": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _d, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c3p_pwc_lindblad_tape_bytes": (C.c_size_t, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     "c3p_pwc_lindblad_taped": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _d, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.c_size_t, _i, _vp]),
     "c3p_pwc_lindblad_vjp_taped": (_i, [_vp, C.c_size_t, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -1670,8 +1670,10 @@ int lind_regr_forward(DeviceWs* w, const LindRegrBufs& bf, const PwcProblem& P, 
   LAUNCH_TRY(c3p_launch_regr_chain(a, av, st));
   return 0;
 }
-// cotangent in the Hermitian basis, segment scan, backward sweep (scratch from the workspace)
-int lind_regr_backward(DeviceWs* w, const LindRegrBufs& bf, const PwcProblem& P, long S, const cplx* Ubar, double* grad, hipStream_t st) {
+// cotangent in the Hermitian basis, segment scan, backward sweep (scratch from the workspace).  `mo` set: the sweep also keeps the
+// sums of the generator cotangents per chain, and the reduce kernel writes the model-operator cotangents from them.
+int lind_regr_backward(DeviceWs* w, const LindRegrBufs& bf, const PwcProblem& P, long S, const cplx* Ubar, double* grad, hipStream_t st,
+                       const LindModelOut* mo = nullptr) {
   const int B = P.B, Dm = P.Dm;
   const size_t msz = (size_t)Dm * Dm;
   void *bv, *av;
@@ -1700,10 +1702,18 @@ int lind_regr_backward(DeviceWs* w, const LindRegrBufs& bf, const PwcProblem& P,
   g.Dm = Dm;
   g.S = (int)S;
   g.degree = c3p_opt(C3P_OPT_regr_grad_degree) > 0 ? (int)c3p_opt(C3P_OPT_regr_grad_degree) : 0;
+  if (mo) {
+    void* mv;
+    if (ws_get(w, SL_LMODEL_PART, (size_t)B * S * c3p_regr_model_part_doubles(Dm, P.K) * sizeof(double), &mv)) return -1;
+    g.mpart = (double*)mv;
+  }
   LAUNCH_TRY(c3p_launch_regr_grad(g, st));
+  if (mo)
+    LAUNCH_TRY(c3p_launch_regr_model_reduce(g.mpart, tau, P.signals, mo->col, mo->C, B, (int)S, P.K, P.N, P.D, P.dt, mo->g_h0, mo->g_hks,
+                                            mo->g_col, st));
   return 0;
 }
-int run_vjp_lind_regr(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double* grad, hipStream_t st) {
+int run_vjp_lind_regr(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double* grad, hipStream_t st, const LindModelOut* mo = nullptr) {
   const int B = P.B, K = P.K, N = P.N, Dm = P.Dm;
   if (!lind_regr_grad_ok(P.D, Dm) || K > 16 || K < 1) return 1;
   const long S = lind_regr_segments(B, N);
@@ -1717,7 +1727,7 @@ int run_vjp_lind_regr(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double
   bf.qT = (double*)qv;
   const int rc = lind_regr_forward(w, bf, P, S, st);
   if (rc != 0) return rc;
-  return lind_regr_backward(w, bf, P, S, Ubar, grad, st);
+  return lind_regr_backward(w, bf, P, S, Ubar, grad, st, mo);
 }
 
 int run_vjp_tiled(DeviceWs* w, const PwcProblem& P, const cplx* U_bar, double* grad, hipStream_t st, bool per_slice = false,
@@ -2939,7 +2949,7 @@ int c3p_pwc_lindblad_model_vjp(const void* h0, int64_t h0_bstride, const void* h
   if (flags & (C3P_PER_SLICE_H | C3P_ORDER_RIGHT)) return fail("c3p_pwc_lindblad_model_vjp: unsupported flag");
   if (D > 6)
     return fail("c3p_pwc_lindblad_model_vjp: D=%d, the model-operator cotangents of the Lindblad path are served for D <= 6 "
-                "(superoperators up to 36 x 36)", D);
+                "(superoperators up to 36 x 36); c3p_pwc_lindblad_model_vjp_hb serves D = 7, 8, 9 for Hermitian Hamiltonians", D);
   if (B == 0) return 0;
   if (!h0 || !hks || !signals || !col_ops || !U_bar || !grad_h0 || !grad_hks || !grad_col_ops) return fail("NULL pointer argument");
   if (h0_bstride < 0 || hks_bstride < 0) return fail("negative batch stride");
@@ -2989,6 +2999,76 @@ int c3p_pwc_lindblad_model_vjp(const void* h0, int64_t h0_bstride, const void* h
   });
   if (rc != 0) return -1;
   g_last_kernel = global ? C3P_KERNEL_GENERIC_GLOBAL : C3P_KERNEL_GENERIC_LDS;
+  if (record_stop(w, st)) return -1;
+  if (flags & C3P_HOST_PTRS) return sg.finish();
+  return 0;
+}
+
+// The model-operator cotangents at D = 7, 8, 9 (and D = 6 under regr_grad_d6) from the Hermitian-basis sweep: the sweep of
+// c3p_pwc_lindblad_vjp with the sums of the real generator cotangents kept per chain (c3p_regrg.hip).
+int c3p_pwc_lindblad_model_vjp_hb(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
+                                  const void* col_ops, int C, double dt, int B, int K, int N, int D, int flags, const double* fr_phase,
+                                  const void* U_bar, double* grad_signals, void* grad_h0, void* grad_hks, void* grad_col_ops,
+                                  void* stream) {
+  if (B < 0 || K <= 0 || N <= 0 || D <= 0 || C <= 0) return fail("bad sizes B=%d K=%d N=%d D=%d C=%d", B, K, N, D, C);
+  if (flags & (C3P_PER_SLICE_H | C3P_ORDER_RIGHT | C3P_FORCE_GENERIC)) return fail("c3p_pwc_lindblad_model_vjp_hb: unsupported flag");
+  const int Dm = D * D;
+  if (!lind_regr_grad_ok(D, Dm))
+    return fail("c3p_pwc_lindblad_model_vjp_hb: D=%d, the Hermitian-basis sweep serves D = 7, 8, 9 (D = 6 under regr_grad_d6); "
+                "c3p_pwc_lindblad_model_vjp serves D <= 6", D);
+  if (K > 16) return fail("c3p_pwc_lindblad_model_vjp_hb: K=%d, the Hermitian-basis sweep serves 1 <= K <= 16", K);
+  if (B == 0) return 0;
+  if (!h0 || !hks || !signals || !col_ops || !U_bar || !grad_h0 || !grad_hks || !grad_col_ops) return fail("NULL pointer argument");
+  if (h0_bstride < 0 || hks_bstride < 0) return fail("negative batch stride");
+  const size_t cs = sizeof(cplx);
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  DeviceWs* w = lk.w;
+  if (!w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  Stage sg{w, st};
+  const void *d_h0 = h0, *d_hks = hks, *d_sig = signals, *d_ph = fr_phase, *d_ub = U_bar, *d_col = col_ops;
+  void* d_grad = grad_signals;
+  cplx *g_h0 = (cplx*)grad_h0, *g_hks = (cplx*)grad_hks, *g_col = (cplx*)grad_col_ops;
+  if (flags & C3P_HOST_PTRS) {
+    if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)D * D) * cs, &d_h0)) return -1;
+    if (sg.in(hks, staged_elems(B, hks_bstride, (size_t)K * D * D) * cs, &d_hks)) return -1;
+    if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
+    if (sg.in(col_ops, (size_t)C * D * D * cs, &d_col)) return -1;
+    if (sg.in(U_bar, (size_t)B * Dm * Dm * cs, &d_ub)) return -1;
+    if (fr_phase && sg.in(fr_phase, (size_t)B * Dm * sizeof(double), &d_ph)) return -1;
+    if (grad_signals && sg.out(grad_signals, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
+    // the three operator cotangents are staged in one block of their own
+    void* blk;
+    const size_t n0 = (size_t)B * D * D, nk = (size_t)B * K * D * D, nc = (size_t)B * C * D * D;
+    if (ws_get(w, SL_LMODEL_OUT, (n0 + nk + nc) * cs, &blk)) return -1;
+    g_h0 = (cplx*)blk, g_hks = g_h0 + n0, g_col = g_hks + nk;
+    sg.backs.push_back({grad_h0, g_h0, n0 * cs});
+    sg.backs.push_back({grad_hks, g_hks, nk * cs});
+    sg.backs.push_back({grad_col_ops, g_col, nc * cs});
+  }
+  if (!d_grad) {  // grad_signals not wanted: the sweep still writes it
+    if (ws_get(w, SL_OUT0, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
+  }
+  void* clp;
+  if (ws_get(w, SL_CLP, (size_t)Dm * Dm * cs, &clp)) return -1;
+  LAUNCH_TRY(c3p_launch_clp((const cplx*)d_col, C, D, (cplx*)clp, st));
+  const PwcProblem P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, (const cplx*)clp, dt, B, K, N, D, Dm,
+                        1, (const double*)d_ph};
+  const LindModelOut mo = {(const cplx*)d_col, C, g_h0, g_hks, g_col};
+  if (record_start(w, st)) return -1;
+  // chunks of samples as in c3p_pwc_lindblad_vjp: the transposed prefixes (N D^4 doubles per sample) and the sums of the generator
+  // cotangents (S (1 + K) D^4 doubles per sample, S <= 32)
+  const size_t per_sample = ((size_t)N + (size_t)32 * (1 + K)) * Dm * Dm * sizeof(double);
+  const int rc = in_chunks(B, grad_chunk_samples(w, per_sample), [&](long b0, int nb) {
+    const LindModelOut mc = mo.at(P, b0);
+    const int rc = run_vjp_lind_regr(w, P.chunk(b0, nb), ubar_at(P, (const cplx*)d_ub, b0), grad_at(P, (double*)d_grad, b0), st, &mc);
+    if (rc == 1)
+      return fail("c3p_pwc_lindblad_model_vjp_hb: h0 / hks must be Hermitian (the generator is not real in the Hermitian basis)");
+    return rc;
+  });
+  if (rc != 0) return -1;
+  g_last_kernel = C3P_KERNEL_MFMA;
   if (record_stop(w, st)) return -1;
   if (flags & C3P_HOST_PTRS) return sg.finish();
   return 0;

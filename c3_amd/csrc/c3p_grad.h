@@ -65,3 +65,54 @@ hipError_t c3p_launch_lind_model_reduce(const cplx* mpart, const cplx* col, int 
 hipError_t c3p_launch_lind_slice_generators(const cplx* hs, long hs_bstride, const cplx* clp, int B, int N, int D, cplx* out, hipStream_t st);
 hipError_t c3p_launch_lind_generators(const cplx* h0, long h0_bstride, const cplx* hks, long hks_bstride, const cplx* clp, int nb,
                                       int K, int D, cplx* out, hipStream_t st);
+
+// ---- the adjoint maps of the Lindblad generator (lind_gen_kernel, clp_kernel), shared by the reduce kernels of the model-operator
+// cotangents: lind_model_reduce_kernel (c3p_grad.hip) and regr_model_reduce_kernel (c3p_regrg.hip) ----
+// Z: the cotangent of the generator [Ds^2 x Ds^2], row (i,j), column (k,l); z(row, col) loads one element.
+// tau(Z)[a,c] = i (sum_j Z[(a,j),(c,j)] - sum_i Z[(i,c),(i,a)]), the adjoint of H -> -i (H (x) 1 - 1 (x) H^T): this returns the
+// bracket, c3p_lind_times_i the factor (a caller may scale in between)
+template <class Ld>
+__device__ __forceinline__ cplx c3p_lind_tau_sum(Ld&& z, int a, int c, int Ds) {
+  cplx sum = cmake(0, 0);
+  for (int j = 0; j < Ds; ++j) {
+    const cplx p = z(a * Ds + j, c * Ds + j);
+    const cplx m = z(j * Ds + c, j * Ds + a);
+    sum.x += p.x - m.x;
+    sum.y += p.y - m.y;
+  }
+  return sum;
+}
+__device__ __forceinline__ cplx c3p_lind_times_i(cplx v) { return cmake(-v.y, v.x); }
+// The adjoint of the dissipator map  clp = sum_c C (x) C* - 1/2 (C^+C) (x) 1 - 1/2 1 (x) (C^+C)^T  (propagation.py:570-581) applied to
+// W [Ds^2 x Ds^2, row-major, LDS], the cotangent of clp.  With d loss = Re sum conj(grad) d(operator), every operator entry an
+// independent complex number:
+//   R[p,q]      = sum_j W[(p,j),(q,j)] + sum_i W[(i,q),(i,p)]                       (the cotangent of C^+C is -R / 2)
+//   grad_C[a,b] = sum_jl W[(a,j),(b,l)] C[j,l] + sum_ik conj(W[(i,a),(k,b)]) C[i,k] - 1/2 (C (R + R^+))[a,b]
+// All threads of the workgroup; R: Ds^2 elements of LDS scratch; col [C,Ds,Ds]; g_col: the [C,Ds,Ds] block of this sample.  W is
+// complete and visible on entry.
+__device__ __forceinline__ void c3p_lind_dissipator_adjoint(const cplx* W, cplx* R, const cplx* col, int C, int Ds, cplx* g_col) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int Dm = Ds * Ds;
+  for (int e = tid; e < Dm; e += nt) {
+    const int p = e / Ds, q = e - p * Ds;
+    cplx r = cmake(0, 0);
+    for (int j = 0; j < Ds; ++j) r = cadd(r, cadd(W[(p * Ds + j) * Dm + (q * Ds + j)], W[(j * Ds + q) * Dm + (j * Ds + p)]));
+    R[e] = r;
+  }
+  __syncthreads();
+  for (int e = tid; e < C * Dm; e += nt) {
+    const int c = e / Dm, ab = e - c * Dm, a = ab / Ds, bb = ab - a * Ds;
+    const cplx* Cc = col + (long)c * Dm;
+    cplx g = cmake(0, 0);
+    for (int j = 0; j < Ds; ++j)
+      for (int l = 0; l < Ds; ++l) {
+        cfma(g, W[(a * Ds + j) * Dm + (bb * Ds + l)], Cc[j * Ds + l]);
+        cfma(g, cconj(W[(j * Ds + a) * Dm + (l * Ds + bb)]), Cc[j * Ds + l]);
+      }
+    cplx h = cmake(0, 0);
+    for (int p = 0; p < Ds; ++p) cfma(h, Cc[a * Ds + p], cadd(R[p * Ds + bb], cconj(R[bb * Ds + p])));
+    g.x = fma(-0.5, h.x, g.x);
+    g.y = fma(-0.5, h.y, g.y);
+    g_col[(long)c * Dm + ab] = g;
+  }
+}

@@ -683,15 +683,8 @@ __global__ void __launch_bounds__(256) grad_bwd_general_kernel(GradArgs A) {
       const int Ds = A.Dsys;
       if (tid < Ds * Ds) {
         const int a = tid / Ds, c = tid - a * Ds;
-        cplx sum = cmake(0, 0);
-        for (int j = 0; j < Ds; ++j) {
-          const cplx p = M.ld(q.dT + (a * Ds + j) * ld + (c * Ds + j));
-          const cplx m = M.ld(q.dT + (j * Ds + c) * ld + (j * Ds + a));
-          sum.x += p.x - m.x;
-          sum.y += p.y - m.y;
-        }
-        sum = cmul(ph, sum);
-        const cplx tau = cmake(-sum.y, sum.x);
+        const cplx sum = cmul(ph, c3p_lind_tau_sum([&](int row, int col) { return M.ld(q.dT + row * ld + col); }, a, c, Ds));
+        const cplx tau = c3p_lind_times_i(sum);
         cplx* tp = A.mpart + (long)wg * ((long)D * D + (long)(A.K + 1) * Ds * Ds) + (long)D * D + tid;
         const double* sig = A.signals + (long)b * A.K * A.N + n;
         const bool first = n == n1 - 1;
@@ -726,9 +719,7 @@ __global__ void __launch_bounds__(256) grad_bwd_general_kernel(GradArgs A) {
 // Model-operator cotangents of the Lindblad path from the partial blocks of grad_bwd_general_kernel<., true>: one workgroup
 // per sample adds the S segment partials in segment order (the same bits on every run) and applies dt, then the adjoint of the
 // dissipator map of clp_kernel (propagation.py:570-581),  clp = sum_c C (x) C* - 1/2 (C^+C) (x) 1 - 1/2 1 (x) (C^+C)^T,
-// to W = dt W0.  With d loss = Re sum conj(grad) d(operator), every operator entry an independent complex number:
-//   R[p,q]      = sum_j W[(p,j),(q,j)] + sum_i W[(i,q),(i,p)]                       (the cotangent of C^+C is -R / 2)
-//   grad_C[a,b] = sum_jl W[(a,j),(b,l)] C[j,l] + sum_ik conj(W[(i,a),(k,b)]) C[i,k] - 1/2 (C (R + R^+))[a,b]
+// to W = dt W0 (c3p_lind_dissipator_adjoint, c3p_grad.h).
 __global__ void __launch_bounds__(256) lind_model_reduce_kernel(const cplx* mpart, const cplx* col, int C, int S, int K, int Ds, double dt,
                                                                 cplx* g_h0, cplx* g_hks, cplx* g_col) {
   __shared__ cplx W[C3P_MODEL_DM_MAX * C3P_MODEL_DM_MAX];
@@ -750,28 +741,7 @@ __global__ void __launch_bounds__(256) lind_model_reduce_kernel(const cplx* mpar
       g_hks[(long)b * K * Dm + (e - nw - Dm)] = acc;
   }
   __syncthreads();
-  for (int e = tid; e < Dm; e += nt) {
-    const int p = e / Ds, q = e - p * Ds;
-    cplx r = cmake(0, 0);
-    for (int j = 0; j < Ds; ++j) r = cadd(r, cadd(W[(p * Ds + j) * Dm + (q * Ds + j)], W[(j * Ds + q) * Dm + (j * Ds + p)]));
-    R[e] = r;
-  }
-  __syncthreads();
-  for (int e = tid; e < C * Dm; e += nt) {
-    const int c = e / Dm, ab = e - c * Dm, a = ab / Ds, bb = ab - a * Ds;
-    const cplx* Cc = col + (long)c * Dm;
-    cplx g = cmake(0, 0);
-    for (int j = 0; j < Ds; ++j)
-      for (int l = 0; l < Ds; ++l) {
-        cfma(g, W[(a * Ds + j) * Dm + (bb * Ds + l)], Cc[j * Ds + l]);
-        cfma(g, cconj(W[(j * Ds + a) * Dm + (l * Ds + bb)]), Cc[j * Ds + l]);
-      }
-    cplx h = cmake(0, 0);
-    for (int p = 0; p < Ds; ++p) cfma(h, Cc[a * Ds + p], cadd(R[p * Ds + bb], cconj(R[bb * Ds + p])));
-    g.x = fma(-0.5, h.x, g.x);
-    g.y = fma(-0.5, h.y, g.y);
-    g_col[((long)b * C + c) * Dm + ab] = g;
-  }
+  c3p_lind_dissipator_adjoint(W, R, col, C, Ds, g_col + (long)b * C * Dm);
 }
 
 // row r = (i,j), column c = (k,l) of -i (H (x) 1 - 1 (x) H^T) [+ clp]: -i (H[i,k] d_jl - d_ik H[l,j])

@@ -96,9 +96,18 @@ struct RegrGradArgs {
   double* arena;           // C3P_REGD_MAX_WGS tile sets
   int B, K, N, Dm, S;
   int degree;              // 0: chosen per segment; 8, 12, 16, 20: forced (A/B)
+  // set: the sweep also keeps the generator cotangent e^mu dT of every slice, summed over the slices of a chain with the
+  // weights 1, c_1(n) .. c_K(n): [B,S,1+K] tile sets with their border slot (c3p_regr_model_part_doubles per chain)
+  double* mpart;
 };
 size_t c3p_regr_grad_arena_bytes(int Dm);
 hipError_t c3p_launch_regr_grad(const RegrGradArgs& A, hipStream_t st);
+// model-operator cotangents from the sweep's partial sums (A.mpart): one workgroup per sample adds the S segments in order,
+// leaves the Hermitian basis and applies the adjoint maps of the Lindblad generator (c3p_grad.h).  tau [B] and signals [B,K,N]
+// as in RegrGradArgs, col [C,Dh,Dh]; grad_h0 [B,Dh,Dh], grad_hks [B,K,Dh,Dh], grad_col [B,C,Dh,Dh]
+size_t c3p_regr_model_part_doubles(int Dm, int K);  // per chain
+hipError_t c3p_launch_regr_model_reduce(const double* mpart, const double* tau, const double* signals, const cplx* col, int C, int B, int S,
+                                        int K, int N, int Dh, double dt, cplx* g_h0, cplx* g_hks, cplx* g_col, hipStream_t st);
 // U_bar'[b] = Re(T diag(e^{-i phi_b}) U_bar[b] T^+): the cotangent of the real chain product in the Hermitian basis
 hipError_t c3p_launch_hb_ubar(const cplx* Ubar, const double* fr_phase, int B, int Dh, double* out, hipStream_t st);
 // segment scan, real Dm x Dm matrices: seg_slots = the complex slots of the real chain kernel (real matrix in the second

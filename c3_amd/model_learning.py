@@ -269,11 +269,14 @@ def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets
       "grad_signals" {gate: [P,K,N]}; "grad_fr_phase" {gate: [P,D]} or None.
     With `device` everything up to the populations stays there (gradients are tensors on it).
 
-    With `col_ops` [C,D,D] the system is open (D <= 6), as in `goal_run_batched`: the populations are LINEAR in the sequence
+    With `col_ops` [C,D,D] the system is open (D <= 9), as in `goal_run_batched`: the populations are LINEAR in the sequence
     state x = S_seq vec(rho0), so x_bar is pop_bar on its diagonal entries n D + n; step 3 is
     `propagate_batch_lindblad_vjp(..., want_model_grads=True)`, and the result also holds "grad_col_ops" [P,C,D,D], the cotangent
     of the collapse operators (through which T1, T2* and the temperature of the bath act), `grad_fr_phase[gate]` is [P,D^2].
     The initial state is a constant: no gradient flows through a thermal rho0.
+    D = 7, 8, 9 (two coupled qutrits) take the Hermitian-basis sweep (`hermitian_basis=True`): h0 / hks must be Hermitian, and
+    "grad_h0" / "grad_hks" are then Hermitian matrices, the Hermitian part of the general cotangent -- exact in
+    `model_param_grads` for every Hermitian dh0 / dhks, which is what a model parameter moves.
     """
     P = len(data_sets)
     if col_ops is not None:
@@ -371,7 +374,8 @@ def _goal_run_open_with_grad(h0, hks, gate_signals, dt, data_sets, psi_init, lab
     grad_signals, grad_ph = {}, ({} if fr_phase is not None else None)
     for gate in gate_signals:
         a = args[gate]
-        g_sig, g0, gk, gc = propagation.propagate_batch_lindblad_vjp(a[0], a[1], a[2], dt, col, U_bar[gate], fr_phase=a[3], want_model_grads=True)
+        g_sig, g0, gk, gc = propagation.propagate_batch_lindblad_vjp(a[0], a[1], a[2], dt, col, U_bar[gate], fr_phase=a[3], want_model_grads=True,
+                                                                     hermitian_basis=D >= 7)
         grad_signals[gate] = g_sig
         grad_h0 = g0 if grad_h0 is None else grad_h0 + g0
         grad_hks = gk if grad_hks is None else grad_hks + gk
@@ -386,7 +390,9 @@ def model_param_grads(grad_h0, grad_hks, dh0, dhks=None, grad_col_ops=None, dcol
     """Gradient w.r.t. T model parameters theta from the operator cotangents of `goal_run_batched_with_grad`:
     Re sum conj(grad_h0) dh0/dtheta (+ Re sum conj(grad_hks) dhks/dtheta).  `dh0` [T,D,D] (a model shared by the P sets:
     result [T], summed over the sets) or [P,T,D,D] (per set: result [P,T]); `dhks` [T,K,D,D] or [P,T,K,D,D], or None.
-    Open systems: `grad_col_ops` [P,C,D,D] with `dcol_ops` [T,C,D,D] or [P,T,C,D,D] adds Re sum conj(grad_col_ops) dcol_ops/dtheta."""
+    Open systems: `grad_col_ops` [P,C,D,D] with `dcol_ops` [T,C,D,D] or [P,T,C,D,D] adds Re sum conj(grad_col_ops) dcol_ops/dtheta.
+    Open systems at D = 7, 8, 9 return Hermitian grad_h0 / grad_hks (the Hermitian part of the general cotangent): the result is exact
+    for Hermitian `dh0` / `dhks`; the anti-Hermitian part of a direction does not enter."""
     tonp = lambda a: a.detach().cpu().numpy() if propagation._is_torch(a) else np.asarray(a)
     g0, gk = tonp(grad_h0), tonp(grad_hks)
     dh0 = np.asarray(tonp(dh0), dtype=np.complex128)

@@ -508,14 +508,21 @@ def propagate_per_slice_vjp(hs, dt: float, U_bar, *, fr_phase=None):
     return (1j * dt) * Z
 
 
-def propagate_batch_lindblad_vjp(h0, hks, signals, dt: float, col_ops, U_bar, *, fr_phase=None, recheck_operators: bool = False, want_model_grads: bool = False):
+def propagate_batch_lindblad_vjp(h0, hks, signals, dt: float, col_ops, U_bar, *, fr_phase=None, recheck_operators: bool = False, want_model_grads: bool = False, hermitian_basis: bool = False):
     """Vector-Jacobian product of `propagate_batch(..., lindbladian=True)` w.r.t. the control samples: the reference
     tapes tf_propagation_lind (propagation.py:551-585) under the same GradientTape (optimizers/optimizer.py:206-216).
     `U_bar` [B,D^2,D^2] is the cotangent of the superoperators (d loss = Re sum conj(U_bar) dU); returns f64 [B,K,N].
 
     `want_model_grads`: (grad_signals, grad_h0 [B,D,D], grad_hks [B,K,D,D], grad_col_ops [B,C,D,D]) through
     c3p_pwc_lindblad_model_vjp -- per sample (sum over B for operators the batch shares), d loss = Re sum conj(grad) d(operator),
-    every operator entry an independent complex number (nothing assumed Hermitian).  D <= 6."""
+    every operator entry an independent complex number (nothing assumed Hermitian).  D <= 6.
+
+    `hermitian_basis` (with `want_model_grads`): the same four results for D = 7, 8, 9 through c3p_pwc_lindblad_model_vjp_hb, the
+    real Hermitian-basis sweep.  h0 / hks must be Hermitian (an error otherwise, never a fallback).  grad_col_ops is the full
+    cotangent; grad_h0 / grad_hks are HERMITIAN matrices, the Hermitian part (g + g^+) / 2 of the general cotangent: a real
+    generator only sees Hermitian perturbations of H, and Re sum conj(grad) dH is exact for every Hermitian dH."""
+    if hermitian_basis and not want_model_grads:
+        raise C3PropError("C3:Error: hermitian_basis selects the model-cotangent entry of the Hermitian-basis sweep: it needs want_model_grads=True")
     if recheck_operators:
         forget_operators(h0, hks)
     call = _Call(h0, hks, signals, U_bar, fr_phase, col_ops)
@@ -548,8 +555,9 @@ def propagate_batch_lindblad_vjp(h0, hks, signals, dt: float, col_ops, U_bar, *,
     if want_model_grads:
         C = int(col.shape[0])
         g0, gk, gc = call.empty((B, D, D)), call.empty((B, K, D, D)), call.empty((B, C, D, D))
+        entry = _lib.load().c3p_pwc_lindblad_model_vjp_hb if hermitian_basis else _lib.load().c3p_pwc_lindblad_model_vjp
         _lib.check(
-            _lib.load().c3p_pwc_lindblad_model_vjp(
+            entry(
                 _ptr(h0), h0_bs, _ptr(hks), hk_bs, _ptr(signals), _ptr(col), C, float(dt), B, K, N, D, call.flags,
                 _ptr(fr_phase), _ptr(U_bar), _ptr(grad), _ptr(g0), _ptr(gk), _ptr(gc), call.stream
             )

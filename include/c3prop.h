@@ -289,11 +289,36 @@ int c3p_pwc_lindblad_vjp(const void* h0, int64_t h0_bstride, const void* hks, in
  * The backward sweep of c3p_grad.hip (general-generator form, VALU) keeps the generator cotangent Z_n of every slice, contracts
  * it to D x D per slice (the adjoint of H -> -i (H (x) 1 - 1 (x) H^T)) and adds up sum_n Z_n for the dissipator; a second kernel
  * adds the segment partials in segment order (bitwise reproducible) and applies the adjoint of the dissipator map.
- * Served for D <= 6 (superoperators up to 36 x 36); a larger D is an error, never a fallback. */
+ * Served for D <= 6 (superoperators up to 36 x 36); a larger D is an error, never a fallback (D = 7, 8, 9 with Hermitian
+ * Hamiltonians: c3p_pwc_lindblad_model_vjp_hb below). */
 int c3p_pwc_lindblad_model_vjp(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
                                const void* col_ops, int C, double dt, int B, int K, int N, int D, int flags,
                                const double* fr_phase, const void* U_bar, double* grad_signals, void* grad_h0, void* grad_hks,
                                void* grad_col_ops, void* stream);
+
+/* The same cotangents at D = 7, 8, 9 (49 x 49 .. 81 x 81 superoperators; two coupled qutrits, cfg4) from the Hermitian-basis sweep
+ * of c3p_pwc_lindblad_vjp (c3p_regrg.hip), arguments and C3P_HOST_PTRS staging as c3p_pwc_lindblad_model_vjp.  At the end of every
+ * slice the sweep holds the REAL generator cotangent of that slice in registers; it is summed over the slices of every chain with
+ * the weights 1, c_1(n) .. c_K(n) (one owner thread per element, sweep order, no atomics), and a second kernel adds the segments in
+ * ascending order, leaves the Hermitian basis and applies the adjoints of H -> -i (H (x) 1 - 1 (x) H^T) and of the dissipator map.
+ *   Shapes: D = 7, 8, 9 (D = 6 under the regr_grad_d6 option), 1 <= K <= 16; any other D is an error that names
+ *     c3p_pwc_lindblad_model_vjp.
+ *   h0 / hks must be Hermitian: the call reads the flags of the table build back (one synchronisation of the stream, as the control
+ *     sweep does); a non-Hermitian Hamiltonian is an error ("... must be Hermitian"), never a fallback.
+ *   grad_col_ops c128 [B,C,D,D] is the FULL cotangent, every entry an independent complex number: the dissipator preserves
+ *     Hermiticity for every C, so nothing is lost in the real basis.
+ *   grad_h0 c128 [B,D,D], grad_hks c128 [B,K,D,D] are HERMITIAN matrices: the Hermitian part (g + g^+) / 2 of what the general sweep
+ *     returns.  A real generator only sees Hermitian perturbations of H; Re sum conj(grad) dH is exact for every Hermitian dH.
+ *   grad_signals f64 [B,K,N] or NULL: bitwise what c3p_pwc_lindblad_vjp returns on the Hermitian-basis sweep under the same options
+ *     (same segment count).
+ *   All outputs are per sample and bitwise reproducible, and bitwise independent of the sample chunks (grad_chunk) at a fixed
+ *     segment count.  The per-sample budget of a chunk counts the partial sums, S (1 + K) D^4 doubles, beside the N D^4 doubles of
+ *     transposed prefixes.  c3p_last_kernel reports C3P_KERNEL_MFMA.
+ * Not served: D >= 10, non-Hermitian Hamiltonians at D = 7 .. 9, the caller-owned tape (c3p_pwc_lindblad_vjp_taped). */
+int c3p_pwc_lindblad_model_vjp_hb(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
+                                  const void* col_ops, int C, double dt, int B, int K, int N, int D, int flags,
+                                  const double* fr_phase, const void* U_bar, double* grad_signals, void* grad_h0, void* grad_hks,
+                                  void* grad_col_ops, void* stream);
 
 /* Open-system optimiser evaluation from ONE forward pass (D = 7, 8, 9: 49 x 49 .. 81 x 81 superoperators, Hermitian Hamiltonians;
  * D = 2, 3: 4 x 4 / 9 x 9 superoperators on the small-D kernels, any Hamiltonian, up to 8 control lines -- there the tape holds
