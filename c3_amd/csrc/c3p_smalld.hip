@@ -1567,12 +1567,26 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
       const bool act = valid && t < len;
       // ---- X = scale (G0 + sum_k c_k G_k) in D-layout; trace shift mu ----
       // chains past their segment end (lengths differ by at most one slice) take X = 0, E = I
-      const double sc = act ? scale : 0.0;
+      double sc = act ? scale : 0.0;
       const double muw = act ? 1.0 : 0.0;
       double mu_r, mu_i;
       double X[NBI][NJ];
+      int my_s = ps;  // squarings of THIS chain's matrix (supplied generators only)
       if constexpr (XG) {
         const long m = (long)sample * A.N + n0 + (act ? t : 0);
+        // The polynomial and the loop count `ps` are the wave's (largest norm of its four chains); scaling and squaring are
+        // the chain's own: a matrix of small norm next to a large one must not be scaled down further and squared more often
+        // than its norm asks for -- every squaring doubles the rounding error of exp(X) = 1 + small (2^ps u instead of u).
+        // my_s = the smallest count that brings this matrix inside the scaled norm the wave's plan was made for.
+        {
+          const double lim = nrm * scale;
+          double scaled = A.meta[m * 4 + 2] * scale;
+          while (my_s > 0 && 2.0 * scaled <= lim) {
+            scaled *= 2.0;
+            --my_s;
+          }
+          sc = act ? ldexp(1.0, -my_s) : 0.0;
+        }
         mu_r = muw * A.meta[m * 4 + 0];
         mu_i = muw * A.meta[m * 4 + 1];
         const double2* src = reinterpret_cast<const double2*>(A.hs) + (long)sample * A.hs_bstride + (long)(n0 + (act ? t : 0)) * D * D;
@@ -1741,10 +1755,11 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
 #pragma unroll
           for (int J = 0; J < NJ; ++J) acc[I][J] = 0.0;
         mm_img<D>(img, roff, negmask, P, acc);
+        const bool sq = !XG || it < my_s;  // (XG: a chain that needs fewer squarings than the wave keeps its result)
 #pragma unroll
         for (int I = 0; I < NBI; ++I)
 #pragma unroll
-          for (int J = 0; J < NJ; ++J) P[I][J] = acc[I][J];
+          for (int J = 0; J < NJ; ++J) P[I][J] = sq ? acc[I][J] : P[I][J];
       }
       // ---- partial propagator write-out ----
       if constexpr (DUS) {
