@@ -784,11 +784,60 @@ __device__ __forceinline__ double wave_max64(double v) {
   return v;
 }
 
+// Column sums of |G|, the block the segment's norm bound is formed from (c3p_sd_segment_norm below): SD_CSW doubles per table,
+// cs_k[j] = sum_i |G_k[i][j]| in slot j < D and zeros behind.  The sums are taken from the half-image table in LDS, in this one
+// place and in one order, so that every kernel and every table mode (built in the kernel, copied from the prep kernel's buffer)
+// forms the same bits from the same table.  Plain sqrt(a^2 + b^2) on unrolled, independent LDS reads (round 6: the elements
+// are dt x Hamiltonian entries, no overflow to guard, and the table build sits on the critical path of every workgroup's prologue).
+constexpr int SD_CSW = 16;  // = the lanes of a chain: lane idx16 = j takes column j (D <= 12)
+
+template <int D>
+__device__ __forceinline__ double sd_colsum(const double* g, int j) {
+  constexpr int W = SD<D>::W;
+  double cs = 0.0;
+  if (j < D) {
+    double ar[D], ai[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) ar[i] = g[(2 * i) * W + j], ai[i] = g[(2 * i + 1) * W + j];
+#pragma unroll
+    for (int i = 0; i < D; ++i) cs += sqrt(fma(ar[i], ar[i], ai[i] * ai[i]));
+  }
+  return cs;
+}
+
+// the block of tables that are already in LDS (copied from global memory; the grad kernels): table first + step q goes to
+// lanes 16 q .. 16 q + 15 of the wave, four tables per pass.  The caller synchronises before (tables) and behind (block).
+template <int D>
+__device__ __forceinline__ void sd_colsums(const double* tab, int K, double* csb, int lane, int first = 0, int step = 1) {
+  constexpr int MAT = SD<D>::MAT;
+  for (int t0 = first; t0 <= K; t0 += 4 * step) {
+    const int ti = t0 + (lane >> 4) * step;
+    if (ti <= K) csb[ti * SD_CSW + (lane & 15)] = sd_colsum<D>(tab + ti * (MAT + 4), lane & 15);
+  }
+}
+
+// Segment-wide bound on ||X(t)||_1, X(t) = G_0 + sum_k c_k(t) G_k, for one chain (16 lanes, lane idx16 = column):
+//   ||X(t)||_1 = max_j sum_i |X_ij(t)|  <=  max_j ( cs_0[j] + sum_k max_t |c_k(t)| cs_k[j] ),
+// never larger than the sum of norms ||G_0||_1 + sum_k max_t |c_k| ||G_k||_1 (max_j (a_j + b_j) <= max a + max b), which lets
+// every table's widest column meet in one column it does not have.  One fma chain per column in the order of the tables, then
+// the maximum over the chain's lanes: every kernel that decides on this bound gets the same bits.  `maxk(k)` is the chain's
+// max_t |c_k(t)| on the segment, uniform over the chain's lanes.
+template <class F>
+__device__ __forceinline__ double c3p_sd_segment_norm(const double* csb, int K, int idx16, F&& maxk) {
+  double v = csb[idx16];
+  for (int k = 0; k < K; ++k) v = fma(maxk(k), csb[(k + 1) * SD_CSW + idx16], v);
+  v = fmax(v, __shfl_xor(v, 1));
+  v = fmax(v, __shfl_xor(v, 2));
+  v = fmax(v, __shfl_xor(v, 16));
+  v = fmax(v, __shfl_xor(v, 32));
+  return v;
+}
+
 // The wave builds its own tables in LDS (unitary mode): G = -i dt (h - tr h / D) as half images plus
 // {Re mu, Im mu, ||G||_1, max |Re G|} -- what smalld_prep_kernel writes, without a dependent launch in
 // front of the chain kernel (~12 us of a 250 us batch).
 template <int D>
-__device__ __forceinline__ void build_tables(const SmallArgs& A, int sample, double* tab, int lane, int first = 0, int step = 1) {
+__device__ __forceinline__ void build_tables(const SmallArgs& A, int sample, double* tab, double* csb, int lane, int first = 0, int step = 1) {
   using C = SD<D>;
   constexpr int MAT = C::MAT, W = C::W;
   constexpr int NE = (D * D + 63) / 64;
@@ -829,18 +878,10 @@ __device__ __forceinline__ void build_tables(const SmallArgs& A, int sample, dou
         remax = fmax(remax, fabs(gr[q]));
       }
     }
-    // column sums of |G| (the 1-norm).  Round 6: plain sqrt(a^2 + b^2) on unrolled, independent LDS reads instead of D
-    // dependent hypot() calls (the elements are dt x Hamiltonian entries: no overflow to guard) -- this function sits on the
-    // critical path of every workgroup's prologue
+    // column sums of |G|: kept for the segment's bound, their maximum is the 1-norm
     wave_sync();
-    double cs = 0.0;
-    if (lane < D) {
-      double ar[D], ai[D];
-#pragma unroll
-      for (int i = 0; i < D; ++i) ar[i] = out[(2 * i) * W + lane], ai[i] = out[(2 * i + 1) * W + lane];
-#pragma unroll
-      for (int i = 0; i < D; ++i) cs += sqrt(fma(ar[i], ar[i], ai[i] * ai[i]));
-    }
+    const double cs = sd_colsum<D>(out, lane);
+    if (lane < SD_CSW) csb[ti * SD_CSW + lane] = cs;
     const double nrm = wave_max64(cs);
     // the real fast path also needs Y = -Im G symmetric (Hermitian input).  Dressed operators V^T H V are
     // symmetric only to rounding (measured 5e-16 relative), so asymmetry below 1e-14 ||G|| counts as none;
@@ -901,6 +942,11 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
   const int SG = ((K + ((SPLIT && K > 0) ? 1 : 0)) * A.Lmax) | 1;
   double* img = tab + ((GIVEN || XG) ? 0 : (1 + K) * (MAT + 4)) + wv * (4 * IMG + 4 * SG);  // this wave's 4 chain images
   double* sg = img + 4 * IMG;  // 4 chains x K x Lmax signals, odd chain stride (bank spread)
+  // column sums of the tables, a block of its own (the table records and every offset into them stay).  Workgroup per sample:
+  // behind the waves' images.  One wave: in the wave's images, which nothing touches before the slice loop (the bound is taken in
+  // the prologue) -- a launch of this mode fills the LDS of a CU with eight workgroups at the segment length pick_segments allows,
+  // and must not grow; behind the images only where the block does not fit in them (D = 2, 3 with more than ten tables)
+  double* csb = (!MW && (1 + K) * SD_CSW <= 4 * IMG) ? img : tab + (1 + K) * (MAT + 4) + nwv * (4 * IMG + 4 * SG);
 
   // XCD-aware block order: workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  Logical block
   // (bid % 8) * (nb / 8) + bid / 8 keeps consecutive logical blocks -- the waves of one sample, which exchange their
@@ -1019,13 +1065,17 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
         }
     }
     if (A.inline_tables) {
-      build_tables<D>(A, __builtin_amdgcn_readfirstlane(sample), tab, lane, wv, nwv);
+      build_tables<D>(A, __builtin_amdgcn_readfirstlane(sample), tab, csb, lane, wv, nwv);
     } else {
       const double* gt0 = A.tables + (long)(A.tab_per_sample ? sample : 0) * (1 + K) * (MAT + 4);
       for (int e = (MW ? (int)threadIdx.x : lane); e < (1 + K) * (MAT + 4); e += 64 * nwv) tab[e] = gt0[e];
+      // tables of the prep kernel: their column sums are formed here, from the copy in LDS and dealt to the waves as a table
+      // build is (the barriers below publish the block)
+      __syncthreads();
+      sd_colsums<D>(tab, K, csb, lane, wv, nwv);
     }
     if constexpr (!MW) __syncthreads();
-    // segment-wide bound on ||X||_1 <= ||G0|| + sum_k max_t |c_k(t)| ||G_k||  -> one plan per segment
+    // segment-wide bound on ||X||_1, column by column (c3p_sd_segment_norm)  -> one plan per segment
     // (MW: the amplitudes are fetched while wave 0 builds the tables, their maxima taken from LDS after the barrier)
     auto seg_max = [&](int k, bool from_lds) {
       const double* s = A.signals + ((long)sample * K + k) * A.N + n0;
@@ -1074,8 +1124,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
         }
       }
     }
-    nrm = tab[MAT + 2];
-    for (int k = 0; k < K; ++k) nrm = fma(seg_max(k, MW), tab[(k + 1) * (MAT + 4) + MAT + 2], nrm);
+    nrm = c3p_sd_segment_norm(csb, K, lp.idx16, [&](int k) { return seg_max(k, MW); });
     }
     nrm = fmax(nrm, __shfl_xor(nrm, 4));
     nrm = fmax(nrm, __shfl_xor(nrm, 8));
@@ -2075,10 +2124,12 @@ hipError_t launch_chain_t(const SmallArgs& A, hipStream_t st) {
   const long nchains = (long)A.B * A.S;
   const unsigned grid = (unsigned)((nchains + 3) / 4);
   size_t lds = 0;
+  // the tables' column sums (SD_CSW doubles per table) of the one-wave kernels live in the wave's images; behind them where they do not fit
+  const size_t cs_tail1 = (1 + A.K) * SD_CSW <= 4 * C::IMG ? 0 : (size_t)(1 + A.K) * SD_CSW;
   if (A.mode == C3P_MODE_GIVEN || A.mode == C3P_MODE_EXPM)
     lds = (size_t)(4 * C::IMG) * sizeof(double);
   else
-    lds = (size_t)((1 + A.K) * (C::MAT + 4) + 4 * C::IMG + 4 * ((A.K * A.Lmax) | 1)) * sizeof(double);
+    lds = (size_t)((1 + A.K) * (C::MAT + 4) + 4 * C::IMG + 4 * ((A.K * A.Lmax) | 1) + cs_tail1) * sizeof(double);
   // the core + border real loop (D = 5, 9) keeps one more amplitude row per chain: the weights of the drift table
   const bool split81 = (D == 9 || D == 5) && !c3p_opt_on(C3P_OPT_no_split81);
   const int krows = A.K + ((split81 && A.K > 0) ? 1 : 0);
@@ -2097,9 +2148,12 @@ hipError_t launch_chain_t(const SmallArgs& A, hipStream_t st) {
     // B workgroups to be resident at once (8 waves per CU at two per SIMD): B = 256, S = 32 -> 256 workgroups of 8 waves
     const int nW = A.S >> 2;
     const size_t wstride = (size_t)(4 * C::IMG + 4 * ((krows * A.Lmax) | 1));
-    // (the last term held the waves' partial products as plain arrays; they now stay in the waves' images.  It is kept in both sizes
-    // below on purpose: it counts toward the gates that choose this mode and its split, and no shape is to change path here)
-    const size_t lds_mw = (size_t)((1 + A.K) * (C::MAT + 4) + nW * wstride + (size_t)nW * D * D * 2) * sizeof(double);
+    // (the last term held the waves' partial products as plain arrays; they now stay in the waves' images, and the tables' column
+    // sums -- SD_CSW doubles per table -- stand at its start.  It keeps its former size in both sizes below on purpose wherever
+    // the column sums fit in it (all but D = 2, 3 with several tables): it counts toward the gates that choose this mode and its
+    // split, and no shape is to change path here)
+    const size_t tail_mw = std::max((size_t)nW * D * D * 2, (size_t)(1 + A.K) * SD_CSW);
+    const size_t lds_mw = (size_t)((1 + A.K) * (C::MAT + 4) + nW * wstride + tail_mw) * sizeof(double);
     const bool mw = A.fuse && (A.S & 3) == 0 && (nW == 2 || nW == 4 || nW == 8) && (long)A.B * nW <= 2048 &&
                     lds_mw * (8 / nW) <= (size_t)156 * 1024 && !c3p_opt_on(C3P_OPT_no_mw);
     if (mw) {
@@ -2113,7 +2167,9 @@ hipError_t launch_chain_t(const SmallArgs& A, hipStream_t st) {
         // matrix cores -- round 6: tools/sweep_split81.py, profiles/r06/sweep_skew.txt; one slice of the long segments moves the
         // two waves of a SIMD by 7 us against each other, so the optimum is sharp)
         // (the complex loop of the same kernel keeps 640: profiles/r06/sweep_skew_complex.txt -- its samples re-split on the device)
-        int skew = ((D == 9 || D == 5) && !c3p_opt_on(C3P_OPT_no_split81)) ? 700 : 640, skew_c = 640;
+        // (D = 9 with the column-wise norm bound -- no workgroup of cfg2 on the seven-product loop any more: 704, long segments of
+        // 44 slices instead of 43, 0.6 us faster than 700 in every run of profiles/r09/sweep_skew.json; D = 5 was not re-swept)
+        int skew = ((D == 9 || D == 5) && !c3p_opt_on(C3P_OPT_no_split81)) ? (D == 9 ? 704 : 700) : 640, skew_c = 640;
         if (c3p_opt(C3P_OPT_mw_skew) >= 0) skew = skew_c = (int)c3p_opt(C3P_OPT_mw_skew);
         if (skew > 500 && skew < 900) {
           const int h = A.S / 2;
@@ -2133,7 +2189,7 @@ hipError_t launch_chain_t(const SmallArgs& A, hipStream_t st) {
         }
       }
       const size_t wstride2 = (size_t)(4 * C::IMG + 4 * ((krows * A2.Lmax) | 1));
-      const size_t lds_mw2 = (size_t)((1 + A2.K) * (C::MAT + 4) + nW * wstride2 + (size_t)nW * D * D * 2) * sizeof(double);
+      const size_t lds_mw2 = (size_t)((1 + A2.K) * (C::MAT + 4) + nW * wstride2 + tail_mw) * sizeof(double);
       if (lds_mw2 > (size_t)156 * 1024) A2 = A;  // (the longer segments need more LDS for their control amplitudes)
       const size_t lds_use = A2.seg_long > 0 ? lds_mw2 : lds_mw;
       auto kern = smalld_chain_kernel<D, false, false, false, true>;
@@ -2151,7 +2207,7 @@ hipError_t launch_chain_t(const SmallArgs& A, hipStream_t st) {
       if constexpr (D == 9 || D == 5) {
         if (!c3p_opt_on(C3P_OPT_no_split81)) kern1 = smalld_chain_kernel<D, false, false, false, false, true>;
       }
-      const size_t lds1 = (size_t)((1 + A.K) * (C::MAT + 4) + 4 * C::IMG + 4 * ((krows * A.Lmax) | 1)) * sizeof(double);
+      const size_t lds1 = (size_t)((1 + A.K) * (C::MAT + 4) + 4 * C::IMG + 4 * ((krows * A.Lmax) | 1) + cs_tail1) * sizeof(double);
       if (lds1 > 60 * 1024) return hipErrorInvalidValue;
       C3P_LAUNCH(kern1, dim3(grid), dim3(64), lds1, st, A);
     }
@@ -2255,7 +2311,24 @@ __global__ void __launch_bounds__(64, 1) smalld_grad_kernel(SmallGradArgs A) {
   if (A.skip_real) {  // the real-Hamiltonian sweep has taken this wave's chains (same tables, same norm bound: same decision)
     bool realH = true;
     for (int k = 0; k <= K; ++k) realH = realH && (tab[k * (MAT + 4) + MAT + 3] == 0.0);
-    if (__builtin_amdgcn_readfirstlane((int)realH) != 0 && __builtin_amdgcn_readfirstlane(c3p_squarings(nrm, C3P_MM8_THETA)) <= SDG_MAXS)
+    // its bound is the column-wise one (c3p_sd_segment_norm), formed here as it forms it; the plan of this kernel's own sweep
+    // stays on the sum of norms above
+    double* csb = sg + 4 * K * A.Lmax;
+    sd_colsums<D>(tab, K, csb, lane);
+    __syncthreads();
+    double nrm_r = c3p_sd_segment_norm(csb, K, lp.idx16, [&](int k) {
+      double cmax = 0.0;
+      for (int t = lp.idx16; t < A.Lmax; t += 16) cmax = fmax(cmax, fabs(sg[(lp.b * K + k) * A.Lmax + t]));
+      cmax = fmax(cmax, __shfl_xor(cmax, 1));
+      cmax = fmax(cmax, __shfl_xor(cmax, 2));
+      cmax = fmax(cmax, __shfl_xor(cmax, 16));
+      cmax = fmax(cmax, __shfl_xor(cmax, 32));
+      return cmax;
+    });
+    nrm_r = fmax(nrm_r, __shfl_xor(nrm_r, 4));
+    nrm_r = fmax(nrm_r, __shfl_xor(nrm_r, 8));
+    nrm_r = readfirstlane_f64(nrm_r);
+    if (__builtin_amdgcn_readfirstlane((int)realH) != 0 && __builtin_amdgcn_readfirstlane(c3p_squarings(nrm_r, C3P_MM8_THETA)) <= SDG_MAXS)
       return;
   }
   const double scale = ldexp(1.0, -ps);
@@ -2767,6 +2840,7 @@ __global__ void __launch_bounds__(64, 1) smalld_grad_real_kernel(SmallGradArgs A
   double* tab = c3p_sd_lds;
   double* rimg = tab + (1 + K) * (MAT + 4);  // per chain: Re R, Im R as real row-major images (row stride WR)
   double* sg = rimg + 4 * 2 * RIMG;
+  double* csb = sg + 4 * K * A.Lmax;  // column sums of the tables (the segment's norm bound)
 
   const long chain = (long)blockIdx.x * 4 + lp.b;
   const long nchains = (long)A.B * A.S;
@@ -2781,8 +2855,10 @@ __global__ void __launch_bounds__(64, 1) smalld_grad_real_kernel(SmallGradArgs A
   const double* gt0 = A.tables + (long)(A.tab_per_sample ? sample : 0) * (1 + K) * (MAT + 4);
   for (int e = lane; e < (1 + K) * (MAT + 4); e += 64) tab[e] = gt0[e];
   __syncthreads();
-  double nrm = tab[MAT + 2];
-  for (int k = 0; k < K; ++k) {
+  // the forward kernel's bound (column by column: c3p_sd_segment_norm), from the same tables
+  sd_colsums<D>(tab, K, csb, lane);
+  __syncthreads();
+  double nrm = c3p_sd_segment_norm(csb, K, lp.idx16, [&](int k) {
     const double* s = A.signals + ((long)sample * K + k) * A.N + n0;
     double cmax = 0.0;
     for (int t = lp.idx16; t < A.Lmax; t += 16) {
@@ -2794,8 +2870,8 @@ __global__ void __launch_bounds__(64, 1) smalld_grad_real_kernel(SmallGradArgs A
     cmax = fmax(cmax, __shfl_xor(cmax, 2));
     cmax = fmax(cmax, __shfl_xor(cmax, 16));
     cmax = fmax(cmax, __shfl_xor(cmax, 32));
-    nrm = fma(cmax, tab[(k + 1) * (MAT + 4) + MAT + 2], nrm);
-  }
+    return cmax;
+  });
   nrm = fmax(nrm, __shfl_xor(nrm, 4));
   nrm = fmax(nrm, __shfl_xor(nrm, 8));
   nrm = readfirstlane_f64(nrm);
@@ -3161,7 +3237,7 @@ hipError_t launch_grad_real_t(const SmallGradArgs& A, hipStream_t st) {
   constexpr int NB = RD<D>::NB, RIMG = 4 * NB * (4 * NB + 1);
   const long nchains = (long)A.B * A.S;
   const unsigned grid = (unsigned)((nchains + 3) / 4);
-  const size_t lds = (size_t)((1 + A.K) * (C::MAT + 4) + 8 * RIMG + 4 * A.K * A.Lmax) * sizeof(double);
+  const size_t lds = (size_t)((1 + A.K) * (C::MAT + 4 + SD_CSW) + 8 * RIMG + 4 * A.K * A.Lmax) * sizeof(double);
   if (lds > 60 * 1024) return hipErrorInvalidValue;
   C3P_LAUNCH(smalld_grad_real_kernel<D>, dim3(grid), dim3(64), lds, st, A);
   return hipGetLastError();
@@ -3172,7 +3248,7 @@ hipError_t launch_grad_t(const SmallGradArgs& A, hipStream_t st) {
   using C = SD<D>;
   const long nchains = (long)A.B * A.S;
   const unsigned grid = (unsigned)((nchains + 3) / 4);
-  const size_t lds = (size_t)((1 + A.K) * (C::MAT + 4) + 8 * C::MAT + 4 * A.K * A.Lmax) * sizeof(double);
+  const size_t lds = (size_t)((1 + A.K) * (C::MAT + 4 + SD_CSW) + 8 * C::MAT + 4 * A.K * A.Lmax) * sizeof(double);
   if (lds > 60 * 1024) return hipErrorInvalidValue;
   C3P_LAUNCH(smalld_grad_kernel<D>, dim3(grid), dim3(64), lds, st, A);
   return hipGetLastError();
