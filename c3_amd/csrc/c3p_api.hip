@@ -351,16 +351,18 @@ struct PwcProblem {
   long hk_bs;
   const double* signals;  // [B,K,N]
   const cplx* clp;        // Lindblad dissipator [Dm,Dm] or null
+  long clp_bs;            // elements between the samples' dissipators (C3P_COL_PER_SAMPLE: Dm*Dm), 0 = shared
   double dt;
   int B, K, N, D, Dm, lindblad;
   const double* fr_phase;  // [B,Dm] or null
-  bool per_sample() const { return h0_bs != 0 || hk_bs != 0; }
+  bool per_sample() const { return h0_bs != 0 || hk_bs != 0 || clp_bs != 0; }
   int nsamp() const { return per_sample() ? B : 1; }  // operator sets (tables) of the call
   // the problem of samples [b0, b0 + nb)
   PwcProblem chunk(long b0, int nb) const {
     PwcProblem c = *this;
     c.h0 += b0 * h0_bs;
     c.hks += b0 * hk_bs;
+    if (clp) c.clp += b0 * clp_bs;
     c.signals += b0 * K * N;
     if (fr_phase) c.fr_phase += b0 * Dm;
     c.B = nb;
@@ -372,14 +374,18 @@ struct PwcProblem {
 const cplx* ubar_at(const PwcProblem& P, const cplx* U_bar, long b0) { return U_bar + b0 * (long)P.Dm * P.Dm; }
 double* grad_at(const PwcProblem& P, double* grad_signals, long b0) { return grad_signals + b0 * P.K * P.N; }
 struct LindModelOut {
-  const cplx* col;  // [C,D,D]
+  const cplx* col;  // [C,D,D], or [B,C,D,D] col_bs apart
+  long col_bs;
   int C;
   cplx *g_h0, *g_hks, *g_col;  // [nb,D,D], [nb,K,D,D], [nb,C,D,D]
   LindModelOut at(const PwcProblem& P, long b0) const {
     const long dd = (long)P.D * P.D;
-    return {col, C, g_h0 + b0 * dd, g_hks + b0 * P.K * dd, g_col + b0 * C * dd};
+    return {col + b0 * col_bs, col_bs, C, g_h0 + b0 * dd, g_hks + b0 * P.K * dd, g_col + b0 * C * dd};
   }
 };
+// Collapse operators of a Lindblad call: [C,D,D], or [B,C,D,D] under C3P_COL_PER_SAMPLE
+long col_bstride(int flags, int C, int D) { return (flags & C3P_COL_PER_SAMPLE) ? (long)C * D * D : 0; }
+size_t col_elems(int flags, int B, int C, int D) { return (size_t)((flags & C3P_COL_PER_SAMPLE) ? B : 1) * C * D * D; }
 // elements of a batched operand as staged from the host: `one` per sample, `stride` apart (0 = shared: one copy)
 size_t staged_elems(int B, int64_t stride, size_t one) { return (size_t)(B - 1) * (size_t)stride + one; }
 
@@ -391,6 +397,7 @@ PrepArgs prep_args(const PwcProblem& P) {
   p.hks = P.hks;
   p.hks_bstride = P.hk_bs;
   p.clp = P.clp;
+  p.clp_bstride = P.clp_bs;
   p.dt = P.dt;
   p.K = P.K;
   p.Dh = P.D;
@@ -404,6 +411,7 @@ MidPrepArgs mid_prep_args(const PwcProblem& P, int nig, int wd) {
   p.hks = P.hks;
   p.hks_bstride = P.hk_bs;
   p.clp = P.clp;
+  p.clp_bstride = P.clp_bs;
   p.dt = P.dt;
   p.K = P.K;
   p.Dh = P.D;
@@ -420,6 +428,7 @@ RegdPrepArgs regd_prep_args(const PwcProblem& P) {
   p.hks = P.hks;
   p.hks_bstride = P.hk_bs;
   p.clp = P.clp;
+  p.clp_bstride = P.clp_bs;
   p.dt = P.dt;
   p.K = P.K;
   p.Dh = P.D;
@@ -1524,7 +1533,7 @@ int run_pwc_regd(DeviceWs* w, const PwcProblem& P, cplx* U_out, cplx* dUs_out, h
 // ---------------------------------------------------------------------------
 int run_pwc_tiled(DeviceWs* w, const ChainArgs& a, bool per_slice, cplx* U_out, hipStream_t st) {
   const bool lindblad = a.mode == C3P_MODE_LINDBLAD;
-  const bool per_sample = !per_slice && (a.h0_bstride != 0 || a.hks_bstride != 0);
+  const bool per_sample = !per_slice && (a.h0_bstride != 0 || a.hks_bstride != 0 || a.clp_bstride != 0);
   const int K = per_slice ? 0 : a.K;
   const int Bc = c3p_tiled_chunk(a.Dm, K, a.B, per_sample, (size_t)24 << 30);
   void* v;
@@ -1538,6 +1547,7 @@ int run_pwc_tiled(DeviceWs* w, const ChainArgs& a, bool per_slice, cplx* U_out, 
   t.hks_bstride = a.hks_bstride;
   t.signals = a.signals;
   t.clp = a.clp;
+  t.clp_bstride = a.clp_bstride;
   t.dt = a.dt;
   t.B = a.B;
   t.K = K;
@@ -1709,7 +1719,7 @@ int lind_regr_backward(DeviceWs* w, const LindRegrBufs& bf, const PwcProblem& P,
   }
   LAUNCH_TRY(c3p_launch_regr_grad(g, st));
   if (mo)
-    LAUNCH_TRY(c3p_launch_regr_model_reduce(g.mpart, tau, P.signals, mo->col, mo->C, B, (int)S, P.K, P.N, P.D, P.dt, mo->g_h0, mo->g_hks,
+    LAUNCH_TRY(c3p_launch_regr_model_reduce(g.mpart, tau, P.signals, mo->col, mo->col_bs, mo->C, B, (int)S, P.K, P.N, P.D, P.dt, mo->g_h0, mo->g_hks,
                                             mo->g_col, st));
   return 0;
 }
@@ -1747,6 +1757,7 @@ int run_vjp_tiled(DeviceWs* w, const PwcProblem& P, const cplx* U_bar, double* g
   t.hks_bstride = P.hk_bs;
   t.signals = P.signals;
   t.clp = P.clp;
+  t.clp_bstride = P.clp_bs;
   t.dt = P.dt;
   t.B = B;
   t.K = K;
@@ -1808,6 +1819,19 @@ struct Stage {
   }
 };
 
+// The dissipator(s) of a Lindblad call into SL_CLP: one [Dm,Dm] for the batch, or one per sample under C3P_COL_PER_SAMPLE
+// (*bs = elements between them, 0 = shared).
+int build_clp(DeviceWs* w, const void* d_col, int C, int D, int B, int flags, const cplx** clp, long* bs, hipStream_t st) {
+  const long gsz = (long)D * D * D * D;
+  const int nb = (flags & C3P_COL_PER_SAMPLE) ? B : 1;
+  void* v;
+  if (ws_get(w, SL_CLP, (size_t)nb * gsz * sizeof(cplx), &v)) return -1;
+  LAUNCH_TRY(c3p_launch_clp((const cplx*)d_col, C, D, nb, (cplx*)v, st));
+  *clp = (const cplx*)v;
+  *bs = (flags & C3P_COL_PER_SAMPLE) ? gsz : 0;
+  return 0;
+}
+
 int pwc_common(int lindblad, const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride,
                const double* signals, const void* col_ops, int C, double dt, int B, int K, int N, int D,
                int flags, const double* fr_phase, void* U_out, void* dUs_out, void* stream) {
@@ -1818,6 +1842,7 @@ int pwc_common(int lindblad, const void* h0, int64_t h0_bstride, const void* hks
   if (!h0) return fail("h0 is NULL");
   if (K > 0 && (!hks || !signals)) return fail("K > 0 but hks/signals missing");
   if (lindblad && (!col_ops || C <= 0)) return fail("lindblad propagation needs col_ops");
+  if (!lindblad && (flags & C3P_COL_PER_SAMPLE)) return fail("c3p_pwc_unitary: C3P_COL_PER_SAMPLE needs collapse operators (c3p_pwc_lindblad)");
   const bool per_slice = (flags & C3P_PER_SLICE_H) != 0;
   const int Dm = lindblad ? D * D : D;
   const size_t cs = sizeof(cplx);
@@ -1833,7 +1858,7 @@ int pwc_common(int lindblad, const void* h0, int64_t h0_bstride, const void* hks
     if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)(per_slice ? N : 1) * D * D) * cs, &d_h0)) return -1;
     if (sg.in(hks, K ? staged_elems(B, hks_bstride, (size_t)K * D * D) * cs : 0, &d_hks)) return -1;
     if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
-    if (sg.in(col_ops, lindblad ? (size_t)C * D * D * cs : 0, &d_col)) return -1;
+    if (sg.in(col_ops, lindblad ? col_elems(flags, B, C, D) * cs : 0, &d_col)) return -1;
     if (sg.in(fr_phase, fr_phase ? (size_t)B * Dm * sizeof(double) : 0, &d_ph)) return -1;
     if (sg.out(U_out, (size_t)B * Dm * Dm * cs, &d_U)) return -1;
     if (sg.out(dUs_out, dUs_out ? (size_t)B * N * Dm * Dm * cs : 0, &d_dUs)) return -1;
@@ -1854,13 +1879,8 @@ int pwc_common(int lindblad, const void* h0, int64_t h0_bstride, const void* hks
   a.Dm = Dm;
   a.mode = lindblad ? C3P_MODE_LINDBLAD : C3P_MODE_UNITARY;
   a.dUs_out = (cplx*)d_dUs;
-  if (lindblad) {
-    void* v;
-    if (ws_get(w, SL_CLP, (size_t)Dm * Dm * cs, &v)) return -1;
-    LAUNCH_TRY(c3p_launch_clp((const cplx*)d_col, C, D, (cplx*)v, st));
-    a.clp = (const cplx*)v;
-  }
-  const PwcProblem P = {a.h0, a.h0_bstride, a.hks, a.hks_bstride, a.signals, a.clp, dt, B, K, N, D, Dm, lindblad, a.fr_phase};
+  if (lindblad && build_clp(w, d_col, C, D, B, flags, &a.clp, &a.clp_bstride, st)) return -1;
+  const PwcProblem P = {a.h0, a.h0_bstride, a.hks, a.hks_bstride, a.signals, a.clp, a.clp_bstride, dt, B, K, N, D, Dm, lindblad, a.fr_phase};
   bool done = false;
   if (!(flags & C3P_FORCE_GENERIC) && per_slice && !lindblad && K == 0 && D <= kSmallDLimit && c3p_smalld_supported(D)) {
     // branch B (propagation.py:295-308): X_n = -i dt H_n
@@ -1879,7 +1899,7 @@ int pwc_common(int lindblad, const void* h0, int64_t h0_bstride, const void* hks
     // then the supplied-generator mode of the matrix-core chain kernels with X_n = dt L_n
     void* gv;
     if (ws_get(w, SL_SCRATCH, (size_t)B * N * Dm * Dm * cs, &gv)) return -1;
-    LAUNCH_TRY(c3p_launch_lind_slice_generators(a.h0, a.h0_bstride, a.clp, B, N, D, (cplx*)gv, st));
+    LAUNCH_TRY(c3p_launch_lind_slice_generators(a.h0, a.h0_bstride, a.clp, a.clp_bstride, B, N, D, (cplx*)gv, st));
     const long gbs = (long)N * Dm * Dm;
     const int rc = (Dm <= kSmallDLimit && c3p_smalld_supported(Dm))
                        ? run_xg_smalld(w, (const cplx*)gv, gbs, dt, 0.0, B, N, Dm, a.fr_phase, (cplx*)d_U, a.dUs_out, st)
@@ -2347,6 +2367,7 @@ int c3p_ode_solve(const void* h0, const void* hks, const double* signals, const 
   if (B < 0 || N < 0 || D <= 0 || K < 0 || K > 32) return fail("bad sizes B=%d K=%d N=%d D=%d", B, K, N, D);
   if (solver < 0 || solver > 3) return fail("unknown solver id %d", solver);
   if (step < 0 || step > 2) return fail("unknown step function id %d", step);
+  if (flags & C3P_COL_PER_SAMPLE) return fail("c3p_ode_solve: C3P_COL_PER_SAMPLE is not served (one col_ops [C,D,D] for the batch)");
   if (B == 0) return 0;
   if (N < 2) return fail("the ODE solver needs at least two time samples (N=%d)", N);
   if (!h0 || !init || !states) return fail("NULL pointer argument");
@@ -2520,6 +2541,7 @@ int c3p_ode_solve_vjp(const void* h0, const void* hks, const double* signals, co
   if (B < 0 || N < 0 || D <= 0 || K < 0 || K > 32) return fail("bad sizes B=%d K=%d N=%d D=%d", B, K, N, D);
   if (solver < 0 || solver > 3) return fail("unknown solver id %d", solver);
   if (step < 0 || step > 2) return fail("unknown step function id %d", step);
+  if (flags & C3P_COL_PER_SAMPLE) return fail("c3p_ode_solve_vjp: C3P_COL_PER_SAMPLE is not served (one col_ops [C,D,D] for the batch)");
   if (B == 0) return 0;
   if ((states_bar != nullptr) == (target != nullptr)) return fail("exactly one of states_bar and target must be given");
   if (target && bar_all) return fail("bar_all needs states_bar");
@@ -2779,7 +2801,7 @@ static int run_vjp_lind_valu(DeviceWs* w, const PwcProblem& P, const cplx* ub, d
   const int nt = P.nsamp();
   void* tab;
   if (ws_get(w, SL_TABLES, (size_t)nt * (K + 1) * gsz * cs, &tab)) return -1;
-  LAUNCH_TRY(c3p_launch_lind_generators(P.h0, P.h0_bs, P.hks, P.hk_bs, P.clp, nt, K, D, (cplx*)tab, st));
+  LAUNCH_TRY(c3p_launch_lind_generators(P.h0, P.h0_bs, P.hks, P.hk_bs, P.clp, P.clp_bs, nt, K, D, (cplx*)tab, st));
   GradArgs A = {};
   A.h0 = (const cplx*)tab;
   A.h0_bstride = nt > 1 ? (long)(K + 1) * gsz : 0;
@@ -2827,7 +2849,7 @@ static int run_vjp_lind_valu(DeviceWs* w, const PwcProblem& P, const cplx* ub, d
     return 0;
   }
   LAUNCH_TRY(c3p_launch_grad_bwd_general_model(A, global, st));
-  LAUNCH_TRY(c3p_launch_lind_model_reduce(A.mpart, mo->col, mo->C, nb, A.S, K, D, P.dt, mo->g_h0, mo->g_hks, mo->g_col, st));
+  LAUNCH_TRY(c3p_launch_lind_model_reduce(A.mpart, mo->col, mo->col_bs, mo->C, nb, A.S, K, D, P.dt, mo->g_h0, mo->g_hks, mo->g_col, st));
   return 0;
 }
 
@@ -2853,15 +2875,15 @@ int c3p_pwc_lindblad_vjp(const void* h0, int64_t h0_bstride, const void* hks, in
     if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)D * D) * cs, &d_h0)) return -1;
     if (sg.in(hks, staged_elems(B, hks_bstride, (size_t)K * D * D) * cs, &d_hks)) return -1;
     if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
-    if (sg.in(col_ops, (size_t)C * D * D * cs, &d_col)) return -1;
+    if (sg.in(col_ops, col_elems(flags, B, C, D) * cs, &d_col)) return -1;
     if (sg.in(U_bar, (size_t)B * Dm * Dm * cs, &d_ub)) return -1;
     if (fr_phase && sg.in(fr_phase, (size_t)B * Dm * sizeof(double), &d_ph)) return -1;
     if (sg.out(grad_signals, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
   }
-  void* clp;
-  if (ws_get(w, SL_CLP, (size_t)Dm * Dm * cs, &clp)) return -1;
-  LAUNCH_TRY(c3p_launch_clp((const cplx*)d_col, C, D, (cplx*)clp, st));
-  const PwcProblem P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, (const cplx*)clp, dt, B, K, N, D, Dm,
+  const cplx* clp;
+  long clp_bs;
+  if (build_clp(w, d_col, C, D, B, flags, &clp, &clp_bs, st)) return -1;
+  const PwcProblem P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, clp, clp_bs, dt, B, K, N, D, Dm,
                         1, (const double*)d_ph};
   const cplx* p_ub = (const cplx*)d_ub;
   double* p_grad = (double*)d_grad;
@@ -2968,7 +2990,7 @@ int c3p_pwc_lindblad_model_vjp(const void* h0, int64_t h0_bstride, const void* h
     if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)D * D) * cs, &d_h0)) return -1;
     if (sg.in(hks, staged_elems(B, hks_bstride, (size_t)K * D * D) * cs, &d_hks)) return -1;
     if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
-    if (sg.in(col_ops, (size_t)C * D * D * cs, &d_col)) return -1;
+    if (sg.in(col_ops, col_elems(flags, B, C, D) * cs, &d_col)) return -1;
     if (sg.in(U_bar, (size_t)B * Dm * Dm * cs, &d_ub)) return -1;
     if (fr_phase && sg.in(fr_phase, (size_t)B * Dm * sizeof(double), &d_ph)) return -1;
     if (sg.out(grad_signals, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;  // SL_OUT0 (SL_OUT1 is the sweep's store)
@@ -2984,12 +3006,12 @@ int c3p_pwc_lindblad_model_vjp(const void* h0, int64_t h0_bstride, const void* h
   if (!d_grad) {  // grad_signals not wanted: the sweep still writes it
     if (ws_get(w, SL_OUT0, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
   }
-  void* clp;
-  if (ws_get(w, SL_CLP, (size_t)Dm * Dm * cs, &clp)) return -1;
-  LAUNCH_TRY(c3p_launch_clp((const cplx*)d_col, C, D, (cplx*)clp, st));
-  const PwcProblem P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, (const cplx*)clp, dt, B, K, N, D, Dm,
+  const cplx* clp;
+  long clp_bs;
+  if (build_clp(w, d_col, C, D, B, flags, &clp, &clp_bs, st)) return -1;
+  const PwcProblem P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, clp, clp_bs, dt, B, K, N, D, Dm,
                         1, (const double*)d_ph};
-  const LindModelOut mo = {(const cplx*)d_col, C, g_h0, g_hks, g_col};
+  const LindModelOut mo = {(const cplx*)d_col, col_bstride(flags, C, D), C, g_h0, g_hks, g_col};
   bool global = false;
   if (record_start(w, st)) return -1;
   // chunks of samples as in c3p_pwc_lindblad_vjp: the sweep keeps 2 N D^4 complex per sample
@@ -3034,7 +3056,7 @@ int c3p_pwc_lindblad_model_vjp_hb(const void* h0, int64_t h0_bstride, const void
     if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)D * D) * cs, &d_h0)) return -1;
     if (sg.in(hks, staged_elems(B, hks_bstride, (size_t)K * D * D) * cs, &d_hks)) return -1;
     if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
-    if (sg.in(col_ops, (size_t)C * D * D * cs, &d_col)) return -1;
+    if (sg.in(col_ops, col_elems(flags, B, C, D) * cs, &d_col)) return -1;
     if (sg.in(U_bar, (size_t)B * Dm * Dm * cs, &d_ub)) return -1;
     if (fr_phase && sg.in(fr_phase, (size_t)B * Dm * sizeof(double), &d_ph)) return -1;
     if (grad_signals && sg.out(grad_signals, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
@@ -3050,12 +3072,12 @@ int c3p_pwc_lindblad_model_vjp_hb(const void* h0, int64_t h0_bstride, const void
   if (!d_grad) {  // grad_signals not wanted: the sweep still writes it
     if (ws_get(w, SL_OUT0, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
   }
-  void* clp;
-  if (ws_get(w, SL_CLP, (size_t)Dm * Dm * cs, &clp)) return -1;
-  LAUNCH_TRY(c3p_launch_clp((const cplx*)d_col, C, D, (cplx*)clp, st));
-  const PwcProblem P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, (const cplx*)clp, dt, B, K, N, D, Dm,
+  const cplx* clp;
+  long clp_bs;
+  if (build_clp(w, d_col, C, D, B, flags, &clp, &clp_bs, st)) return -1;
+  const PwcProblem P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, clp, clp_bs, dt, B, K, N, D, Dm,
                         1, (const double*)d_ph};
-  const LindModelOut mo = {(const cplx*)d_col, C, g_h0, g_hks, g_col};
+  const LindModelOut mo = {(const cplx*)d_col, col_bstride(flags, C, D), C, g_h0, g_hks, g_col};
   if (record_start(w, st)) return -1;
   // chunks of samples as in c3p_pwc_lindblad_vjp: the transposed prefixes (N D^4 doubles per sample) and the sums of the generator
   // cotangents (S (1 + K) D^4 doubles per sample, S <= 32)
@@ -3101,13 +3123,16 @@ size_t c3p_pwc_lindblad_tape_bytes(int B, int K, int N, int D, int* segments_out
 int c3p_pwc_lindblad_taped(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
                            const void* col_ops, int C, double dt, int B, int K, int N, int D, int flags, const double* fr_phase,
                            void* U_out, void* tape, size_t tape_bytes, int segments, void* stream) {
+  if (flags & C3P_COL_PER_SAMPLE)
+    return fail("c3p_pwc_lindblad_taped: C3P_COL_PER_SAMPLE is not served (one col_ops [C,D,D] for the batch; c3p_pwc_lindblad and "
+                "c3p_pwc_lindblad_vjp take it)");
   if (flags & ~C3P_HERMITIAN_H) return fail("c3p_pwc_lindblad_taped takes device pointers and no flags but C3P_HERMITIAN_H");
   if (B <= 0 || K < 1 || K > 16 || N <= 0 || D <= 0) return fail("bad sizes B=%d K=%d N=%d D=%d", B, K, N, D);
   const int Dm = D * D;
   if (!h0 || !hks || !signals || !col_ops || C <= 0 || !U_out || !tape) return fail("NULL pointer argument");
   if (h0_bstride < 0 || hks_bstride < 0) return fail("negative batch stride");
   if (segments < 1 || segments > N) return fail("bad segment count %d", segments);
-  PwcProblem P = {(const cplx*)h0, h0_bstride, (const cplx*)hks, hks_bstride, signals, nullptr, dt, B, K, N, D, Dm, 1, fr_phase};  // (clp: below)
+  PwcProblem P = {(const cplx*)h0, h0_bstride, (const cplx*)hks, hks_bstride, signals, nullptr, 0, dt, B, K, N, D, Dm, 1, fr_phase};  // (clp: below)
   if (D <= 4) {
     // small-D kernels: the forward half of run_vjp_lind_smalld writes into the tape, U = the ordered product of its segments
     int seg_chk = 0;
@@ -3121,7 +3146,7 @@ int c3p_pwc_lindblad_taped(const void* h0, int64_t h0_bstride, const void* hks, 
     if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
     void* clp;
     if (ws_get(w, SL_CLP, (size_t)Dm * Dm * sizeof(cplx), &clp)) return -1;
-    LAUNCH_TRY(c3p_launch_clp((const cplx*)col_ops, C, D, (cplx*)clp, st));
+    LAUNCH_TRY(c3p_launch_clp((const cplx*)col_ops, C, D, 1, (cplx*)clp, st));
     P.clp = (const cplx*)clp;
     if (lind_smallr_ok((flags & C3P_HERMITIAN_H) != 0, D, Dm, K, N, segments)) {
       // declared Hermitian: the tape holds the REAL tables, segment products and slice propagators (c3p_pwc_lindblad_vjp_taped
@@ -3169,7 +3194,7 @@ int c3p_pwc_lindblad_taped(const void* h0, int64_t h0_bstride, const void* hks, 
   const size_t cs = sizeof(cplx);
   void* clp;
   if (ws_get(w, SL_CLP, (size_t)Dm * Dm * cs, &clp)) return -1;
-  LAUNCH_TRY(c3p_launch_clp((const cplx*)col_ops, C, D, (cplx*)clp, st));
+  LAUNCH_TRY(c3p_launch_clp((const cplx*)col_ops, C, D, 1, (cplx*)clp, st));
   P.clp = (const cplx*)clp;
   const LindRegrBufs bf = lind_regr_carve(tape, z);
   if (record_start(w, st)) return -1;
@@ -3210,13 +3235,14 @@ int c3p_pwc_lindblad_taped(const void* h0, int64_t h0_bstride, const void* hks, 
 int c3p_pwc_lindblad_vjp_taped(const void* tape, size_t tape_bytes, int segments, int per_sample_operators, const double* signals, int B,
                                int K, int N, int D, int flags, const double* fr_phase, const void* U_bar, double* grad_signals,
                                void* stream) {
+  if (flags & C3P_COL_PER_SAMPLE) return fail("c3p_pwc_lindblad_vjp_taped: C3P_COL_PER_SAMPLE is not served (c3p_pwc_lindblad_vjp takes it)");
   if (flags & ~C3P_HERMITIAN_H) return fail("c3p_pwc_lindblad_vjp_taped takes device pointers and no flags but C3P_HERMITIAN_H (as given to c3p_pwc_lindblad_taped)");
   if (B <= 0 || K < 1 || K > 16 || N <= 0 || D <= 0) return fail("bad sizes B=%d K=%d N=%d D=%d", B, K, N, D);
   const int Dm = D * D;
   if (!tape || !signals || !U_bar || !grad_signals) return fail("NULL pointer argument");
   if (segments < 1 || segments > N) return fail("bad segment count %d", segments);
   // the operators are in the tape: of them the backward halves read only whether the tables are per sample (a nonzero stride)
-  const PwcProblem P = {nullptr, per_sample_operators ? 1 : 0, nullptr, 0, signals, nullptr, 0.0, B, K, N, D, Dm, 1, fr_phase};
+  const PwcProblem P = {nullptr, per_sample_operators ? 1 : 0, nullptr, 0, signals, nullptr, 0, 0.0, B, K, N, D, Dm, 1, fr_phase};
   if (D <= 4) {
     int seg_chk = 0;
     const size_t need = c3p_pwc_lindblad_tape_bytes(B, K, N, D, &seg_chk);
@@ -3313,6 +3339,8 @@ int c3p_seq_chain(const void* G, int64_t G_bstride, int n_gates, int M, int P, c
   if (P == 0 || S == 0) return 0;
   if (!lengths || !out) return fail("NULL lengths / output pointer");
   if (mode == C3P_SEQ_STATE && !psi0) return fail("state mode needs psi0");
+  if ((flags & C3P_SEQ_PSI0_PER_SAMPLE) && mode != C3P_SEQ_STATE) return fail("C3P_SEQ_PSI0_PER_SAMPLE needs the state mode (C3P_SEQ_STATE)");
+  const long psi0_bs = (flags & C3P_SEQ_PSI0_PER_SAMPLE) ? M : 0;
   if (Lmax > 0 && !seqs) return fail("seqs is NULL but Lmax=%d", Lmax);
   if (n_gates > 0 && !G) return fail("gate table is NULL");
   const size_t cs = sizeof(cplx);
@@ -3342,7 +3370,7 @@ int c3p_seq_chain(const void* G, int64_t G_bstride, int n_gates, int M, int P, c
     if (sg.in(G, g_elems * cs, &d_G)) return -1;
     if (sg.in(seqs, (size_t)S * Lmax * sizeof(int32_t), &d_seqs)) return -1;
     if (sg.in(lengths, (size_t)S * sizeof(int32_t), &d_len)) return -1;
-    if (sg.in(mode == C3P_SEQ_STATE ? psi0 : nullptr, (size_t)M * cs, &d_psi)) return -1;
+    if (sg.in(mode == C3P_SEQ_STATE ? psi0 : nullptr, (size_t)(psi0_bs ? P : 1) * M * cs, &d_psi)) return -1;
     if (sg.out(out, out_bytes, &d_out)) return -1;
   }
   void* flag;
@@ -3361,6 +3389,7 @@ int c3p_seq_chain(const void* G, int64_t G_bstride, int n_gates, int M, int P, c
   a.mode = mode;
   a.superop = (flags & C3P_SEQ_SUPEROP) ? 1 : 0;
   a.psi0 = (const cplx*)d_psi;
+  a.psi0_bstride = psi0_bs;
   a.out = d_out;
   a.bad = (int*)flag;
   g_last_kernel = C3P_KERNEL_SEQ;
@@ -3377,15 +3406,21 @@ int c3p_seq_chain(const void* G, int64_t G_bstride, int n_gates, int M, int P, c
   return 0;
 }
 
-int c3p_seq_chain_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
-                      const int32_t* lengths, int mode, const void* psi0, const void* out_bar, int flags, void* G_bar, void* out,
-                      void* stream) {
+}  // extern "C"
+
+namespace {
+// c3p_seq_chain_vjp and c3p_seq_state_vjp: psi0 [M] (psi0_bstride 0) or one per sample; psi0_bar [P,M] or null (state mode only)
+int seq_vjp_common(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
+                   const int32_t* lengths, int mode, const void* psi0, int64_t psi0_bstride, const void* out_bar, int flags, void* G_bar,
+                   void* psi0_bar, void* out, void* stream) {
   if (P < 0 || S < 0 || n_gates < 0 || Lmax < 0 || M <= 0 || M > C3P_SEQ_MAX_M || G_bstride < 0)
     return fail("bad sizes P=%d S=%d n_gates=%d M=%d Lmax=%d G_bstride=%lld (M <= %d)", P, S, n_gates, M, Lmax,
                 (long long)G_bstride, C3P_SEQ_MAX_M);
   if (mode != C3P_SEQ_PRODUCT && mode != C3P_SEQ_STATE && mode != C3P_SEQ_POPULATION)
     return fail("unknown sequence output mode %d (0 = product, 1 = state, 2 = population)", mode);
   if (P > 65535) return fail("P=%d parameter samples: at most 65535 per call", P);
+  if (psi0_bstride < 0) return fail("negative psi0_bstride");
+  if ((psi0_bstride != 0 || psi0_bar) && mode != C3P_SEQ_STATE) return fail("a per-sample psi0 and psi0_bar need the state mode (C3P_SEQ_STATE)");
   if (P == 0) return 0;
   // an empty table (n_gates = 0) still runs the chains: lengths and indices are checked and `out` is written
   if (n_gates > 0 && !G_bar) return fail("G_bar is NULL");
@@ -3404,7 +3439,8 @@ int c3p_seq_chain_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int 
   if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
   Stage sg{w, st};
   const void *d_G = G, *d_seqs = seqs, *d_len = lengths, *d_psi = psi0, *d_ob = out_bar;
-  void *d_gbar = G_bar, *d_out = out;
+  void *d_gbar = G_bar, *d_out = out, *d_pbar = psi0_bar;
+  const size_t pbar_bytes = psi0_bar ? (size_t)P * M * cs : 0;
   const size_t out_bytes = mode == C3P_SEQ_PRODUCT ? (size_t)P * S * M * M * cs
                            : mode == C3P_SEQ_STATE ? (size_t)P * S * M * cs
                                                    : (size_t)P * S * sizeof(double);
@@ -3423,19 +3459,21 @@ int c3p_seq_chain_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int 
     if (S > 0) {
       if (sg.in(seqs, (size_t)S * Lmax * sizeof(int32_t), &d_seqs)) return -1;
       if (sg.in(lengths, (size_t)S * sizeof(int32_t), &d_len)) return -1;
-      if (sg.in(mode == C3P_SEQ_STATE ? psi0 : nullptr, (size_t)M * cs, &d_psi)) return -1;
+      if (sg.in(mode == C3P_SEQ_STATE ? psi0 : nullptr, ((size_t)(P - 1) * psi0_bstride + M) * cs, &d_psi)) return -1;
       if (sg.in(out_bar, out_bytes, &d_ob)) return -1;
       if (sg.out(out, out ? out_bytes : 0, &d_out)) return -1;
     }
     if (sg.out(G_bar, gbar_bytes, &d_gbar)) return -1;
+    if (sg.out(psi0_bar, pbar_bytes, &d_pbar)) return -1;
   }
   g_last_kernel = C3P_KERNEL_SEQ_VJP;
   if (S == 0) {  // no sequence: a zero gradient
     if (gbar_bytes) HIP_TRY(hipMemsetAsync(d_gbar, 0, gbar_bytes, st));
+    if (pbar_bytes) HIP_TRY(hipMemsetAsync(d_pbar, 0, pbar_bytes, st));
     if (flags & C3P_HOST_PTRS) return sg.finish();
     return 0;
   }
-  const SeqVjpPlan pl = c3p_seq_vjp_plan(n_gates, M, P, S, Lmax, mode);
+  const SeqVjpPlan pl = c3p_seq_vjp_plan(n_gates, M, P, S, Lmax, mode, psi0_bar != nullptr);
   void *flag, *ws, *slab;
   if (ws_get(w, SL_SEQ_FLAG, sizeof(int), &flag)) return -1;
   if (ws_get(w, SL_SEQ_VJP_WS, pl.ws_elems * cs, &ws)) return -1;
@@ -3454,6 +3492,7 @@ int c3p_seq_chain_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int 
   a.f.mode = mode;
   a.f.superop = (flags & C3P_SEQ_SUPEROP) ? 1 : 0;
   a.f.psi0 = (const cplx*)d_psi;
+  a.f.psi0_bstride = (long)psi0_bstride;
   a.f.out = d_out;
   a.f.bad = (int*)flag;
   a.out_bar = d_ob;
@@ -3464,6 +3503,7 @@ int c3p_seq_chain_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int 
   a.slab = (cplx*)slab;
   a.G_bar = (cplx*)d_gbar;
   a.shared = shared;
+  a.psi0_bar = (cplx*)d_pbar;
   g_note_plan = "checkpoint interval C=" + std::to_string(pl.C) + " nblk=" + std::to_string(pl.nblk);
   HIP_TRY(c3p_launch_seq_vjp(a, pl, st));
   int bad = 0;
@@ -3475,6 +3515,26 @@ int c3p_seq_chain_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int 
   }
   if (bad) return fail("a sequence has a length outside [0, %d] or a gate index outside [0, %d): the gradient is not valid", Lmax, n_gates);
   return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int c3p_seq_chain_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
+                      const int32_t* lengths, int mode, const void* psi0, const void* out_bar, int flags, void* G_bar, void* out,
+                      void* stream) {
+  if ((flags & C3P_SEQ_PSI0_PER_SAMPLE) && mode != C3P_SEQ_STATE) return fail("C3P_SEQ_PSI0_PER_SAMPLE needs the state mode (C3P_SEQ_STATE)");
+  return seq_vjp_common(G, G_bstride, n_gates, M, P, seqs, S, Lmax, lengths, mode, psi0, (flags & C3P_SEQ_PSI0_PER_SAMPLE) ? M : 0, out_bar,
+                        flags, G_bar, nullptr, out, stream);
+}
+
+int c3p_seq_state_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
+                      const int32_t* lengths, const void* psi0, int64_t psi0_bstride, const void* out_bar, int flags, void* G_bar,
+                      void* psi0_bar, void* out, void* stream) {
+  if (!psi0_bar) return fail("c3p_seq_state_vjp: psi0_bar is NULL (c3p_seq_chain_vjp serves calls that do not want it)");
+  if (flags & C3P_SEQ_PSI0_PER_SAMPLE) return fail("c3p_seq_state_vjp takes psi0_bstride, not C3P_SEQ_PSI0_PER_SAMPLE");
+  return seq_vjp_common(G, G_bstride, n_gates, M, P, seqs, S, Lmax, lengths, C3P_SEQ_STATE, psi0, psi0_bstride, out_bar, flags, G_bar,
+                        psi0_bar, out, stream);
 }
 
 int c3p_synth_signals(const double* env_params, const int32_t* env_shapes, const double* carrier,
@@ -3646,7 +3706,7 @@ static int unitary_vjp_branch_a(const void* h0, int64_t h0_bstride, const void* 
   // (the fused goal entry has no tiled form: it stays on the VALU sweep in its whole domain)
   const bool tiled_grad = goal ? false : tiled_unitary_grad(D, B);
   if (!done && !(flags & C3P_FORCE_GENERIC) && tiled_grad && !gen_bar_out) {
-    const PwcProblem P = {A.h0, h0_bstride, A.hks, hks_bstride, A.signals, nullptr, dt, B, K, N, D, D, 0, A.fr_phase};
+    const PwcProblem P = {A.h0, h0_bstride, A.hks, hks_bstride, A.signals, nullptr, 0, dt, B, K, N, D, D, 0, A.fr_phase};
     if (run_vjp_tiled(w, P, A.Ubar, A.grad, st)) return -1;
     done = true;
     g_last_kernel = C3P_KERNEL_MFMA;
@@ -3705,7 +3765,7 @@ int c3p_pwc_unitary_vjp(const void* h0, int64_t h0_bstride, const void* hks, int
       if (sg.out(gen_bar_out, (size_t)B * N * D * D * cs, &d_z)) return -1;
     }
     // the slice Hamiltonians as the record's h0: no control operators, no signals (K = 0)
-    const PwcProblem P = {(const cplx*)d_h, h0_bstride, nullptr, 0, nullptr, nullptr, dt, B, 0, N, D, D, 0, (const double*)d_ph};
+    const PwcProblem P = {(const cplx*)d_h, h0_bstride, nullptr, 0, nullptr, nullptr, 0, dt, B, 0, N, D, D, 0, (const double*)d_ph};
     auto served = [&](int kernel) -> int {  // (this branch has no timed span)
       g_last_kernel = kernel;
       if (flags & C3P_HOST_PTRS) return sg.finish();

@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(256) chain_kernel(ChainArgs A) {
         for (int e = tid; e < nel; e += nt) {
           const int r = e / Dm, c = e - r * Dm;
           const int i = r / D, j = r - i * D, k = c / D, l = c - k * D;
-          cplx v = A.clp[e];
+          cplx v = A.clp[(long)b * A.clp_bstride + e];
           if (j == l) {
             const cplx h = h_elem(A, h0b, hkb, sig, n, i, k);
             v.x += h.y;
@@ -272,11 +272,13 @@ __global__ void __launch_bounds__(256) chain_kernel(ChainArgs A) {
 }
 
 // clp[(i,j),(k,l)] = sum_c C[i,k] conj(C[j,l]) - 1/2 (C^+C)[i,k] d_jl - 1/2 d_ik sum_m C[m,j] conj(C[m,l])
-// (the slice-independent dissipator, propagation.py:570-581)
-__global__ void clp_kernel(const cplx* col, int C, int D, cplx* clp) {
+// (the slice-independent dissipator, propagation.py:570-581); blockIdx.y = operator set: col [nb,C,D,D] -> clp [nb,Dm,Dm]
+__global__ void clp_kernel(const cplx* col_all, int C, int D, cplx* clp_all) {
   const int Dm = D * D;
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (long)Dm * Dm) return;
+  const cplx* col = col_all + (long)blockIdx.y * C * D * D;
+  cplx* clp = clp_all + (long)blockIdx.y * Dm * Dm;
   const int r = e / Dm, c = e - (long)r * Dm;
   const int i = r / D, j = r - i * D, k = c / D, l = c - k * D;
   cplx v = cmake(0, 0);
@@ -558,9 +560,9 @@ hipError_t c3p_launch_chain_generic(const ChainArgs& A, bool global_scratch, hip
   return hipGetLastError();
 }
 
-hipError_t c3p_launch_clp(const cplx* col, int C, int D, cplx* clp, hipStream_t st) {
+hipError_t c3p_launch_clp(const cplx* col, int C, int D, int nb, cplx* clp, hipStream_t st) {
   const long total = (long)D * D * D * D;
-  C3P_LAUNCH(clp_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, col, C, D,
+  C3P_LAUNCH(clp_kernel, dim3((unsigned)((total + 255) / 256), (unsigned)nb), dim3(256), 0, st, col, C, D,
                      clp);
   return hipGetLastError();
 }

@@ -53,18 +53,18 @@ hipError_t c3p_launch_grad_scan_general(const GradArgs& A, bool global_scratch, 
 hipError_t c3p_launch_grad_bwd_general(const GradArgs& A, bool global_scratch, hipStream_t st);
 // the same sweep, which also leaves the partial sums of the model-operator cotangents in A.mpart (D = Dsys^2 <= C3P_MODEL_DM_MAX),
 // and the kernel that adds them in segment order and applies the adjoint of the dissipator map: grad_h0 [B,D,D],
-// grad_hks [B,K,D,D], grad_col [B,C,D,D] of the system dimension D, col [C,D,D]
+// grad_hks [B,K,D,D], grad_col [B,C,D,D] of the system dimension D, col [C,D,D] (col_bstride 0) or [B,C,D,D]
 #define C3P_MODEL_DM_MAX 36
 #define C3P_MODEL_NW 6  // 36 * 36 elements of W0 on 256 threads
 hipError_t c3p_launch_grad_bwd_general_model(const GradArgs& A, bool global_scratch, hipStream_t st);
-hipError_t c3p_launch_lind_model_reduce(const cplx* mpart, const cplx* col, int C, int B, int S, int K, int D, double dt, cplx* g_h0,
+hipError_t c3p_launch_lind_model_reduce(const cplx* mpart, const cplx* col, long col_bstride, int C, int B, int S, int K, int D, double dt, cplx* g_h0,
                                         cplx* g_hks, cplx* g_col, hipStream_t st);
 // dense Lindblad generators [nb][(K+1)][D^2 x D^2]: G_0 = -i (spre(h0) - spost(h0)) + clp, G_k = -i (spre(hk) - spost(hk))
-// (propagation.py:551-582); nb = B when an operator stride is non-zero, else 1
+// (propagation.py:551-582); nb = B when an operator stride is non-zero, else 1; clp [Dm,Dm] (clp_bstride 0) or one per sample
 // per-slice variant: out[b,n] = -i (spre(hs[b,n]) - spost(hs[b,n])) + clp for every slice Hamiltonian (branch B + lindbladian)
-hipError_t c3p_launch_lind_slice_generators(const cplx* hs, long hs_bstride, const cplx* clp, int B, int N, int D, cplx* out, hipStream_t st);
-hipError_t c3p_launch_lind_generators(const cplx* h0, long h0_bstride, const cplx* hks, long hks_bstride, const cplx* clp, int nb,
-                                      int K, int D, cplx* out, hipStream_t st);
+hipError_t c3p_launch_lind_slice_generators(const cplx* hs, long hs_bstride, const cplx* clp, long clp_bstride, int B, int N, int D, cplx* out, hipStream_t st);
+hipError_t c3p_launch_lind_generators(const cplx* h0, long h0_bstride, const cplx* hks, long hks_bstride, const cplx* clp,
+                                      long clp_bstride, int nb, int K, int D, cplx* out, hipStream_t st);
 
 // ---- the adjoint maps of the Lindblad generator (lind_gen_kernel, clp_kernel), shared by the reduce kernels of the model-operator
 // cotangents: lind_model_reduce_kernel (c3p_grad.hip) and regr_model_reduce_kernel (c3p_regrg.hip) ----

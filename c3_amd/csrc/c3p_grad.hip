@@ -720,7 +720,7 @@ __global__ void __launch_bounds__(256) grad_bwd_general_kernel(GradArgs A) {
 // per sample adds the S segment partials in segment order (the same bits on every run) and applies dt, then the adjoint of the
 // dissipator map of clp_kernel (propagation.py:570-581),  clp = sum_c C (x) C* - 1/2 (C^+C) (x) 1 - 1/2 1 (x) (C^+C)^T,
 // to W = dt W0 (c3p_lind_dissipator_adjoint, c3p_grad.h).
-__global__ void __launch_bounds__(256) lind_model_reduce_kernel(const cplx* mpart, const cplx* col, int C, int S, int K, int Ds, double dt,
+__global__ void __launch_bounds__(256) lind_model_reduce_kernel(const cplx* mpart, const cplx* col, long col_bs, int C, int S, int K, int Ds, double dt,
                                                                 cplx* g_h0, cplx* g_hks, cplx* g_col) {
   __shared__ cplx W[C3P_MODEL_DM_MAX * C3P_MODEL_DM_MAX];
   __shared__ cplx R[C3P_MODEL_DM_MAX];
@@ -741,11 +741,11 @@ __global__ void __launch_bounds__(256) lind_model_reduce_kernel(const cplx* mpar
       g_hks[(long)b * K * Dm + (e - nw - Dm)] = acc;
   }
   __syncthreads();
-  c3p_lind_dissipator_adjoint(W, R, col, C, Ds, g_col + (long)b * C * Dm);
+  c3p_lind_dissipator_adjoint(W, R, col + (long)b * col_bs, C, Ds, g_col + (long)b * C * Dm);
 }
 
 // row r = (i,j), column c = (k,l) of -i (H (x) 1 - 1 (x) H^T) [+ clp]: -i (H[i,k] d_jl - d_ik H[l,j])
-__global__ void lind_gen_kernel(const cplx* h0, long h0_bs, const cplx* hks, long hk_bs, const cplx* clp, int K, int D, cplx* out) {
+__global__ void lind_gen_kernel(const cplx* h0, long h0_bs, const cplx* hks, long hk_bs, const cplx* clp, long clp_bs, int K, int D, cplx* out) {
   const int Dm = D * D;
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (long)Dm * Dm) return;
@@ -753,7 +753,7 @@ __global__ void lind_gen_kernel(const cplx* h0, long h0_bs, const cplx* hks, lon
   const cplx* H = which == 0 ? h0 + (long)b * h0_bs : hks + (long)b * hk_bs + (long)(which - 1) * D * D;
   const int r = (int)(e / Dm), c = (int)(e - (long)r * Dm);
   const int i = r / D, j = r - i * D, k = c / D, l = c - k * D;
-  cplx v = which == 0 ? clp[e] : cmake(0, 0);
+  cplx v = which == 0 ? clp[(long)b * clp_bs + e] : cmake(0, 0);
   if (j == l) {
     const cplx h = H[i * D + k];
     v.x += h.y;
@@ -768,7 +768,7 @@ __global__ void lind_gen_kernel(const cplx* h0, long h0_bs, const cplx* hks, lon
 }
 
 // dense superoperator generator of every slice Hamiltonian (no dt): row (i,j), column (k,l)
-__global__ void lind_slice_gen_kernel(const cplx* hs, long hs_bs, const cplx* clp, int N, int D, cplx* out) {
+__global__ void lind_slice_gen_kernel(const cplx* hs, long hs_bs, const cplx* clp, long clp_bs, int N, int D, cplx* out) {
   const int Dm = D * D;
   const long e = (long)blockIdx.y * blockDim.x + threadIdx.x;
   if (e >= (long)Dm * Dm) return;
@@ -777,7 +777,7 @@ __global__ void lind_slice_gen_kernel(const cplx* hs, long hs_bs, const cplx* cl
   const cplx* H = hs + b * hs_bs + n * (long)D * D;
   const int r = (int)(e / Dm), c = (int)(e - (long)r * Dm);
   const int i = r / D, j = r - i * D, k = c / D, l = c - k * D;
-  cplx v = clp[e];
+  cplx v = clp[b * clp_bs + e];
   if (j == l) {
     const cplx h = H[i * D + k];
     v.x += h.y;
@@ -878,23 +878,25 @@ hipError_t c3p_launch_grad_bwd_general_model(const GradArgs& A, bool global_scra
   return global_scratch ? launch_general(grad_bwd_general_kernel<true, true>, (unsigned)(A.B * A.S), A, true, st)
                         : launch_general(grad_bwd_general_kernel<false, true>, (unsigned)(A.B * A.S), A, false, st);
 }
-hipError_t c3p_launch_lind_model_reduce(const cplx* mpart, const cplx* col, int C, int B, int S, int K, int D, double dt, cplx* g_h0,
+hipError_t c3p_launch_lind_model_reduce(const cplx* mpart, const cplx* col, long col_bstride, int C, int B, int S, int K, int D, double dt, cplx* g_h0,
                                         cplx* g_hks, cplx* g_col, hipStream_t st) {
   if (D * D > C3P_MODEL_DM_MAX) return hipErrorInvalidValue;
-  C3P_LAUNCH(lind_model_reduce_kernel, dim3((unsigned)B), dim3(256), 0, st, mpart, col, C, S, K, D, dt, g_h0, g_hks, g_col);
+  C3P_LAUNCH(lind_model_reduce_kernel, dim3((unsigned)B), dim3(256), 0, st, mpart, col, col_bstride, C, S, K, D, dt, g_h0, g_hks,
+             g_col);
   return hipGetLastError();
 }
-hipError_t c3p_launch_lind_generators(const cplx* h0, long h0_bstride, const cplx* hks, long hks_bstride, const cplx* clp, int nb,
-                                      int K, int D, cplx* out, hipStream_t st) {
+hipError_t c3p_launch_lind_generators(const cplx* h0, long h0_bstride, const cplx* hks, long hks_bstride, const cplx* clp,
+                                      long clp_bstride, int nb, int K, int D, cplx* out, hipStream_t st) {
   const long nel = (long)D * D * D * D;
   C3P_LAUNCH(lind_gen_kernel, dim3((unsigned)((nel + 255) / 256), (unsigned)nb, (unsigned)(K + 1)), dim3(256), 0, st, h0, h0_bstride,
-                     hks, hks_bstride, clp, K, D, out);
+                     hks, hks_bstride, clp, clp_bstride, K, D, out);
   return hipGetLastError();
 }
 
-hipError_t c3p_launch_lind_slice_generators(const cplx* hs, long hs_bstride, const cplx* clp, int B, int N, int D, cplx* out, hipStream_t st) {
+hipError_t c3p_launch_lind_slice_generators(const cplx* hs, long hs_bstride, const cplx* clp, long clp_bstride, int B, int N, int D, cplx* out, hipStream_t st) {
   const long nel = (long)D * D * D * D;
-  C3P_LAUNCH(lind_slice_gen_kernel, dim3((unsigned)((long)B * N), (unsigned)((nel + 255) / 256)), dim3(256), 0, st, hs, hs_bstride, clp, N,
+  C3P_LAUNCH(lind_slice_gen_kernel, dim3((unsigned)((long)B * N), (unsigned)((nel + 255) / 256)), dim3(256), 0, st, hs, hs_bstride, clp,
+             clp_bstride, N,
                      D, out);
   return hipGetLastError();
 }

@@ -67,6 +67,7 @@ struct ChainArgs {
   long hks_bstride;
   const double* signals;   // [B,K,N]
   const cplx* clp;         // [Dm*Dm] Lindblad dissipator
+  long clp_bstride;        // elements between samples (0 = shared)
   const cplx* mats;        // [B,N,Dm,Dm] for MODE_EXPM / MODE_GIVEN
   const double* fr_phase;  // [B,Dm] or null: row phases applied when writing seg_out
   double dt;
@@ -83,7 +84,8 @@ struct ChainArgs {
 size_t c3p_generic_lds_bytes(int Dm);
 int c3p_generic_threads(int Dm);
 hipError_t c3p_launch_chain_generic(const ChainArgs& A, bool global_scratch, hipStream_t st);
-hipError_t c3p_launch_clp(const cplx* col, int C, int D, cplx* clp, hipStream_t st);
+// col [nb,C,D,D] -> clp [nb,Dm,Dm]
+hipError_t c3p_launch_clp(const cplx* col, int C, int D, int nb, cplx* clp, hipStream_t st);
 hipError_t c3p_launch_kron(const cplx* A, const cplx* Bm, int n, int Da, int Db, int which, cplx* out,
                            hipStream_t st);
 int c3p_infid_blocks(int B);

@@ -59,6 +59,7 @@ struct MidPrepArgs {
   const cplx* hks;
   long hks_bstride;
   const cplx* clp;
+  long clp_bstride;  // elements between samples (0 = shared)
   double dt;
   int K, Dh, Dm, lindblad;
   int conjT;  // tables of G^H instead of G (backward sweep of general generators)

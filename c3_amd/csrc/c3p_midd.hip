@@ -1480,7 +1480,7 @@ __global__ void __launch_bounds__(256) midd_prep_kernel(MidPrepArgs P) {
       v = cmake(x.y * P.dt, -x.x * P.dt);
     } else {
       const int i = row / Dh, j = row - i * Dh, k = col / Dh, l = col - k * Dh;
-      v = (ti == 0) ? P.clp[(long)row * D + col] : cmake(0, 0);
+      v = (ti == 0) ? P.clp[(long)sample * P.clp_bstride + (long)row * D + col] : cmake(0, 0);
       if (j == l) {
         const cplx x = h[i * Dh + k];
         v.x += x.y;

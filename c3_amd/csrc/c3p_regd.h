@@ -13,6 +13,7 @@ struct RegdPrepArgs {
   const cplx* hks;
   long hks_bstride;
   const cplx* clp;
+  long clp_bstride;  // elements between samples (0 = shared)
   double dt;
   int K, Dh, Dm, lindblad;
   double* tables;
@@ -106,8 +107,8 @@ hipError_t c3p_launch_regr_grad(const RegrGradArgs& A, hipStream_t st);
 // leaves the Hermitian basis and applies the adjoint maps of the Lindblad generator (c3p_grad.h).  tau [B] and signals [B,K,N]
 // as in RegrGradArgs, col [C,Dh,Dh]; grad_h0 [B,Dh,Dh], grad_hks [B,K,Dh,Dh], grad_col [B,C,Dh,Dh]
 size_t c3p_regr_model_part_doubles(int Dm, int K);  // per chain
-hipError_t c3p_launch_regr_model_reduce(const double* mpart, const double* tau, const double* signals, const cplx* col, int C, int B, int S,
-                                        int K, int N, int Dh, double dt, cplx* g_h0, cplx* g_hks, cplx* g_col, hipStream_t st);
+hipError_t c3p_launch_regr_model_reduce(const double* mpart, const double* tau, const double* signals, const cplx* col, long col_bstride, int C,
+                                        int B, int S, int K, int N, int Dh, double dt, cplx* g_h0, cplx* g_hks, cplx* g_col, hipStream_t st);
 // U_bar'[b] = Re(T diag(e^{-i phi_b}) U_bar[b] T^+): the cotangent of the real chain product in the Hermitian basis
 hipError_t c3p_launch_hb_ubar(const cplx* Ubar, const double* fr_phase, int B, int Dh, double* out, hipStream_t st);
 // segment scan, real Dm x Dm matrices: seg_slots = the complex slots of the real chain kernel (real matrix in the second

@@ -681,7 +681,7 @@ __global__ void __launch_bounds__(256) regr_prep_kernel(RegdPrepArgs P, double* 
   const cplx* h = (ti == 0) ? P.h0 + (long)sample * P.h0_bstride : P.hks + (long)sample * P.hks_bstride + (long)(ti - 1) * Dh * Dh;
   auto gelem = [&](int row, int col) -> cplx {
     const int i = row / Dh, j = row - i * Dh, k = col / Dh, l = col - k * Dh;
-    cplx v = (ti == 0) ? P.clp[(long)row * D + col] : cmake(0, 0);
+    cplx v = (ti == 0) ? P.clp[(long)sample * P.clp_bstride + (long)row * D + col] : cmake(0, 0);
     if (j == l) {
       const cplx x = h[i * Dh + k];
       v.x += x.y;

@@ -193,7 +193,7 @@ __global__ void __launch_bounds__(256) regr_scan_fold_kernel(const double* pre, 
 // (the Hermitian part of the general sweep's), grad_col complete -- the dissipator preserves Hermiticity for every C.
 // Fixed owners and order everywhere: the same bits on every run.
 __global__ void __launch_bounds__(256) regr_model_reduce_kernel(const double* mpart, const double* tau, const double* signals, const cplx* col,
-                                                                int C, int S, int K, int N, int Dh, double dt, cplx* g_h0, cplx* g_hks,
+                                                                long col_bs, int C, int S, int K, int N, int Dh, double dt, cplx* g_h0, cplx* g_hks,
                                                                 cplx* g_col) {
   __shared__ double red[256];
   __shared__ double shift_s;
@@ -265,7 +265,7 @@ __global__ void __launch_bounds__(256) regr_model_reduce_kernel(const double* mp
       const int a = e / Dh, c = e - a * Dh;
       gh[e] = c3p_lind_times_i(c3p_lind_tau_sum([&](int row, int cl) { return W[row * Dm + cl]; }, a, c, Dh));
     }
-    if (k1 == 0) c3p_lind_dissipator_adjoint(W, R, col, C, Dh, g_col + bidx * C * Dm);
+    if (k1 == 0) c3p_lind_dissipator_adjoint(W, R, col + bidx * col_bs, C, Dh, g_col + bidx * C * Dm);
     __syncthreads();
   }
 }
@@ -310,14 +310,15 @@ size_t c3p_regr_model_part_doubles(int Dm, int K) {
   return (size_t)(1 + K) * ((size_t)n * n * 256 + 2 * cls);
 }
 
-hipError_t c3p_launch_regr_model_reduce(const double* mpart, const double* tau, const double* signals, const cplx* col, int C, int B, int S,
-                                        int K, int N, int Dh, double dt, cplx* g_h0, cplx* g_hks, cplx* g_col, hipStream_t st) {
+hipError_t c3p_launch_regr_model_reduce(const double* mpart, const double* tau, const double* signals, const cplx* col, long col_bstride, int C,
+                                        int B, int S, int K, int N, int Dh, double dt, cplx* g_h0, cplx* g_hks, cplx* g_col, hipStream_t st) {
   const int Dm = Dh * Dh;
   if (!mpart || !tau || !signals || !col || C < 1 || Dm > 81) return hipErrorInvalidValue;
   const size_t lds = ((size_t)2 * (Dm * Dm + Dm) + (size_t)Dm * Dm) * sizeof(double);
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(regr_model_reduce_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  C3P_LAUNCH(regr_model_reduce_kernel, dim3((unsigned)B), dim3(256), lds, st, mpart, tau, signals, col, C, S, K, N, Dh, dt, g_h0, g_hks, g_col);
+  C3P_LAUNCH(regr_model_reduce_kernel, dim3((unsigned)B), dim3(256), lds, st, mpart, tau, signals, col, col_bstride, C, S, K, N, Dh, dt,
+             g_h0, g_hks, g_col);
   return hipGetLastError();
 }
 

@@ -17,7 +17,8 @@ struct SeqArgs {
   int S, Lmax;
   int mode;            // C3P_SEQ_PRODUCT / _STATE / _POPULATION
   int superop;         // population = |x_0| (vectorised density matrix) instead of |x_0|^2
-  const cplx* psi0;    // [M] (mode STATE)
+  const cplx* psi0;    // [M], or [P,M] psi0_bstride elements apart (mode STATE)
+  long psi0_bstride;   // 0 = one start vector for every sample
   void* out;           // c128 [P,S,M,M] / c128 [P,S,M] / f64 [P,S]
   int* bad;            // set to 1 by any chain with a negative / too long length or an out-of-range gate index
 };

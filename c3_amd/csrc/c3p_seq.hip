@@ -5,7 +5,7 @@
 // as L matrix-vector products (first gate applied first, as evaluate_sequences / tf_matmul_left).  The three output
 // modes are the same chain with different start vectors and epilogues:
 //   PRODUCT     x_0 = e_c for every column c: M chains per sequence, column c of U_seq
-//   STATE       x_0 = psi0
+//   STATE       x_0 = psi0, or psi0[p] of the chain's sample (psi0_bstride != 0)
 //   POPULATION  x_0 = e_0, output |x_L[0]|^2 (or |x_L[0]| for a superoperator on vec(|0><0|))
 // No factor is ever gathered or copied, and no matrix product is formed in the vector modes: a chain reads its gate
 // index, then the gate, from the table.  One launch per call whatever the mix of lengths.
@@ -43,9 +43,10 @@ __global__ __launch_bounds__(64) void seq_lane_kernel(SeqArgs a) {
   const long item = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (item >= (long)a.S * C) return;
   const int s = (int)(item / C), col = (int)(item % C);
+  const cplx* psi = a.mode == C3P_SEQ_STATE ? a.psi0 + (long)p * a.psi0_bstride : nullptr;
   cplx v[M];
 #pragma unroll
-  for (int i = 0; i < M; ++i) v[i] = a.mode == C3P_SEQ_STATE ? a.psi0[i] : cmake(i == col ? 1.0 : 0.0, 0.0);
+  for (int i = 0; i < M; ++i) v[i] = a.mode == C3P_SEQ_STATE ? psi[i] : cmake(i == col ? 1.0 : 0.0, 0.0);
   int len = a.lengths[s];
   bool ok = len >= 0 && len <= a.Lmax;
   if (!ok) len = 0;
@@ -114,7 +115,8 @@ __global__ __launch_bounds__(64) void seq_wave_kernel(SeqArgs a) {
     }
   }
   const cplx* T = LDS ? tab : Gp;
-  for (int i = lane; i < M; i += 64) vb[i] = a.mode == C3P_SEQ_STATE ? a.psi0[i] : cmake(i == col ? 1.0 : 0.0, 0.0);
+  const cplx* psi = a.mode == C3P_SEQ_STATE ? a.psi0 + (long)p * a.psi0_bstride : nullptr;
+  for (int i = lane; i < M; i += 64) vb[i] = a.mode == C3P_SEQ_STATE ? psi[i] : cmake(i == col ? 1.0 : 0.0, 0.0);
   __syncthreads();
   int len = a.lengths[s];  // the same for the whole workgroup: every branch below is uniform
   bool ok = len >= 0 && len <= a.Lmax;

@@ -20,6 +20,10 @@
 // A workgroup walks several chains one after another (nblk workgroups per sample), so the checkpoint workspace is per
 // lane / per workgroup in flight, not per chain.  A second kernel sums the slab over the workgroups (and, for a shared
 // table, over the samples) in a fixed order: two identical calls give identical bits.
+// The cotangent of the start vector (state mode, psi0_bar) is what the sweep of a chain ends on, xbar_0.  A lane (lane kernel) or
+// the owner of a row (wave kernel) adds the xbar_0 of the chains it walks in the order it walks them; the lane kernel then adds
+// its 64 lanes in a butterfly of fixed shape; the workgroup's sum goes to its row behind the G_bar rows of the slab, and the same
+// reduce launch adds the nblk rows of a sample in order.  No atomics: the same bits on every run.
 // Every pass checks the length and each index before it reads through them; a bad chain raises the flag and adds nothing.
 #include "c3p_seq_vjp.h"
 
@@ -61,11 +65,15 @@ __global__ __launch_bounds__(64) void seq_vjp_lane_kernel(SeqVjpArgs a) {
   cplx* ck = a.ws + q;                          // ck[(k M + i) NQ]: coalesced over the lanes
   cplx* sg = a.ws + (long)a.nck * M * NQ + q;  // sg[(u M + i) NQ]
   const int C = a.C;
+  const cplx* psi = f.mode == C3P_SEQ_STATE ? f.psi0 + (long)p * f.psi0_bstride : nullptr;
+  cplx pbar[M];  // this lane's sum of xbar_0 over its chains
+#pragma unroll
+  for (int i = 0; i < M; ++i) pbar[i] = cmake(0.0, 0.0);
   for (long item = (long)blk * 64 + lane; item < items; item += (long)a.nblk * 64) {
     const int s = (int)(item / Cm), col = (int)(item % Cm);
     cplx v[M];
 #pragma unroll
-    for (int i = 0; i < M; ++i) v[i] = f.mode == C3P_SEQ_STATE ? f.psi0[i] : cmake(i == col ? 1.0 : 0.0, 0.0);
+    for (int i = 0; i < M; ++i) v[i] = f.mode == C3P_SEQ_STATE ? psi[i] : cmake(i == col ? 1.0 : 0.0, 0.0);
     int len = f.lengths[s];
     bool ok = len >= 0 && len <= f.Lmax;
     if (!ok) len = 0;
@@ -187,9 +195,26 @@ __global__ __launch_bounds__(64) void seq_vjp_lane_kernel(SeqVjpArgs a) {
         for (int j = 0; j < M; ++j) b[j] = w[j];
       }
     }
-    if (!ok) atomicOr(f.bad, 1);
+    if (!ok) {
+      atomicOr(f.bad, 1);
+      continue;
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) pbar[i] = cadd(pbar[i], b[i]);
   }
   __syncthreads();
+  if (a.psi0_bar) {  // (uniform) the 64 lanes' sums, a butterfly of fixed shape: every lane ends with the same total
+    cplx* po = a.slab + (long)f.P * a.nblk * nMM + ((long)p * a.nblk + blk) * M;
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      double re = pbar[i].x, im = pbar[i].y;
+      for (int o = 1; o < 64; o <<= 1) {
+        re += __shfl_xor(re, o);
+        im += __shfl_xor(im, o);
+      }
+      if (lane == 0) po[i] = cmake(re, im);
+    }
+  }
   // the workgroup's sum of its 64 copies; entry e starts at lane copy (e mod 64) (spreads the reads over the banks),
   // always the same order for the same entry
   cplx* out = a.slab + ((long)p * a.nblk + blk) * nMM;
@@ -221,6 +246,11 @@ __global__ __launch_bounds__(64) void seq_vjp_wave_kernel(SeqVjpArgs a) {
       tab[gr * ld + c] = Gp[e];
     }
   for (long e = lane; e < nMM; e += 64) pgall[e] = cmake(0.0, 0.0);
+  // the workgroup's partial psi0_bar lives in its slab row; entry r is owned by the lane that computes row r of every product
+  cplx* pbar = a.psi0_bar ? a.slab + (long)f.P * a.nblk * nMM + q * M : nullptr;
+  if (pbar)
+    for (int r = lane; r < M; r += 64) pbar[r] = cmake(0.0, 0.0);
+  const cplx* psi = f.mode == C3P_SEQ_STATE ? f.psi0 + (long)p * f.psi0_bstride : nullptr;
   const cplx* T = TAB_LDS ? tab : Gp;
   cplx* ck = a.ws + q * (long)(a.nck + a.C) * M;  // ck[k M + r], then the segment states sg[u M + r]
   cplx* sg = ck + (long)a.nck * M;
@@ -235,7 +265,7 @@ __global__ __launch_bounds__(64) void seq_vjp_wave_kernel(SeqVjpArgs a) {
     bool ok = len >= 0 && len <= f.Lmax;
     if (!ok) len = 0;
     const int* row = f.seqs + (long)s * f.Lmax;
-    for (int r = lane; r < M; r += 64) xb[r] = f.mode == C3P_SEQ_STATE ? f.psi0[r] : cmake(r == col ? 1.0 : 0.0, 0.0);
+    for (int r = lane; r < M; r += 64) xb[r] = f.mode == C3P_SEQ_STATE ? psi[r] : cmake(r == col ? 1.0 : 0.0, 0.0);
     __syncthreads();
     int t = 0;
     int g = len > 0 ? __builtin_amdgcn_readfirstlane(row[0]) : 0;
@@ -345,6 +375,9 @@ __global__ __launch_bounds__(64) void seq_vjp_wave_kernel(SeqVjpArgs a) {
       }
     }
     if (!ok && lane == 0) atomicOr(f.bad, 1);
+    // xbar_0 is in bb[0 .. M), row r written by this lane (the last step of the sweep, or the load of out_bar when len = 0)
+    if (ok && pbar)
+      for (int r = lane; r < M; r += 64) pbar[r] = cadd(pbar[r], bb[r]);
     __syncthreads();
   }
   if (PART_LDS) {
@@ -353,11 +386,22 @@ __global__ __launch_bounds__(64) void seq_vjp_wave_kernel(SeqVjpArgs a) {
   }
 }
 
-// Gbar[po] = sum of the slab rows of sample po (all samples for a shared table), in a fixed order
-__global__ __launch_bounds__(256) void seq_vjp_reduce_kernel(const cplx* slab, int P, int nblk, long nMM, int shared, cplx* G_bar) {
+// Gbar[po] = sum of the slab rows of sample po (all samples for a shared table), in a fixed order; entries nMM .. nMM + M of
+// the grid (psi0_bar set): psi0_bar[po] = sum of the nblk partial rows of sample po, always per sample
+__global__ __launch_bounds__(256) void seq_vjp_reduce_kernel(const cplx* slab, int P, int nblk, long nMM, int shared, cplx* G_bar, int M,
+                                                             cplx* psi0_bar) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int po = blockIdx.y;
-  if (e >= nMM) return;
+  if (e >= nMM) {
+    const long r = e - nMM;
+    if (!psi0_bar || r >= M) return;
+    const cplx* ps = slab + (long)P * nblk * nMM + (long)po * nblk * M;
+    cplx acc = cmake(0.0, 0.0);
+    for (int b = 0; b < nblk; ++b) acc = cadd(acc, ps[(long)b * M + r]);
+    psi0_bar[(long)po * M + r] = acc;
+    return;
+  }
+  if (shared && po > 0) return;  // (the grid spans the samples only for psi0_bar)
   cplx acc = cmake(0.0, 0.0);
   const int p0 = shared ? 0 : po, p1 = shared ? P : po + 1;
   for (int p = p0; p < p1; ++p)
@@ -377,7 +421,7 @@ hipError_t launch_lane(const SeqVjpArgs& a, const SeqVjpPlan& pl, hipStream_t st
 
 }  // namespace
 
-SeqVjpPlan c3p_seq_vjp_plan(int n_gates, int M, int P, int S, int Lmax, int mode) {
+SeqVjpPlan c3p_seq_vjp_plan(int n_gates, int M, int P, int S, int Lmax, int mode, bool want_psi0_bar) {
   SeqVjpPlan pl = {};
   const size_t cs = sizeof(cplx);
   const size_t nMM = (size_t)n_gates * M * M;
@@ -405,7 +449,7 @@ SeqVjpPlan c3p_seq_vjp_plan(int n_gates, int M, int P, int S, int Lmax, int mode
   const long by_slab = (long)std::max<size_t>(1, kVjpSlabBytes / std::max<size_t>(1, (size_t)P * nMM * cs));
   pl.nblk = (int)std::max<long>(1, std::min(std::min(want, by_ws), std::min(by_slab, 65535L)));
   pl.ws_elems = (size_t)P * pl.nblk * units_per_wg * (pl.nck + pl.C) * M;
-  pl.slab_elems = (size_t)P * pl.nblk * nMM;
+  pl.slab_elems = (size_t)P * pl.nblk * (nMM + (want_psi0_bar ? (size_t)M : 0));
   return pl;
 }
 
@@ -437,8 +481,9 @@ hipError_t c3p_launch_seq_vjp(const SeqVjpArgs& a, const SeqVjpPlan& pl, hipStre
       C3P_LAUNCH((seq_vjp_wave_kernel<false, false>), grid, dim3(64), pl.lds, st, a);
     e = hipGetLastError();
   }
-  if (e != hipSuccess || nMM == 0) return e;
-  const dim3 rgrid((unsigned)((nMM + 255) / 256), (unsigned)(a.shared ? 1 : P));
-  C3P_LAUNCH(seq_vjp_reduce_kernel, rgrid, dim3(256), 0, st, a.slab, P, pl.nblk, nMM, a.shared, a.G_bar);
+  const long nred = nMM + (a.psi0_bar ? a.f.M : 0);
+  if (e != hipSuccess || nred == 0) return e;
+  const dim3 rgrid((unsigned)((nred + 255) / 256), (unsigned)(a.shared && !a.psi0_bar ? 1 : P));
+  C3P_LAUNCH(seq_vjp_reduce_kernel, rgrid, dim3(256), 0, st, a.slab, P, pl.nblk, nMM, a.shared, a.G_bar, a.f.M, a.psi0_bar);
   return hipGetLastError();
 }

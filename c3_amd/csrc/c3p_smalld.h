@@ -71,6 +71,7 @@ struct PrepArgs {
   const cplx* hks;
   long hks_bstride;
   const cplx* clp;  // Lindblad dissipator [Dm*Dm] or null
+  long clp_bstride;  // elements between samples (0 = shared)
   double dt;
   int K, Dh, lindblad;
   int conjT;  // tables of G^H instead of G (backward sweep of general generators)

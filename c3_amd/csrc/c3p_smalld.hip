@@ -2053,7 +2053,7 @@ __global__ void __launch_bounds__(64) smalld_prep_kernel(PrepArgs P) {
       v = cmake(x.y * P.dt, -x.x * P.dt);  // -i dt h
     } else {
       const int i = row / Dh, j = row - i * Dh, k = col / Dh, l = col - k * Dh;
-      v = (ti == 0) ? P.clp[e] : cmake(0, 0);
+      v = (ti == 0) ? P.clp[(long)sample * P.clp_bstride + e] : cmake(0, 0);
       if (j == l) {
         const cplx x = h[i * Dh + k];
         v.x += x.y;

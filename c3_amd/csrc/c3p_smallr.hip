@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(64) smallr_prep_kernel(RegdPrepArgs P, double*
   // element (row, col) of L0 = dt (clp - i (H0 (x) I - I (x) H0^T)) / Lk = -i dt (Hk (x) I - I (x) Hk^T) (propagation.py:565-582)
   auto gelem = [&](int row, int col) -> cplx {
     const int i = row / Dh, j = row - i * Dh, k = col / Dh, l = col - k * Dh;
-    cplx v = (ti == 0) ? P.clp[(long)row * D + col] : cmake(0, 0);
+    cplx v = (ti == 0) ? P.clp[(long)sample * P.clp_bstride + (long)row * D + col] : cmake(0, 0);
     if (j == l) {
       const cplx x = h[i * Dh + k];
       v.x += x.y;

@@ -16,6 +16,7 @@ struct TiledArgs {
   long hks_bstride;
   const double* signals;   // [B,K,N]
   const cplx* clp;         // [Dm*Dm] Lindblad dissipator or null
+  long clp_bstride;        // complex elements between samples (0 = shared)
   double dt;
   int B, K, N, D, Dm;
   const double* fr_phase;  // [B,Dm] or null

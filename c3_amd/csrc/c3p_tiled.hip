@@ -340,6 +340,7 @@ struct TabArgs {
   const cplx* hks;
   long hks_bstride;
   const cplx* clp;
+  long clp_bstride;
   double dt;
   int K, Dh, Dm, lindblad;
   int b0;          // first sample of the chunk (per-sample tables)
@@ -347,6 +348,8 @@ struct TabArgs {
   double* meta;    // [nsamp][1+K][4] = {mu_r, mu_i, ||G - mu||_1, 0}
 };
 
+// the dissipator of table set s (b0 counts samples only when the tables are per sample, as for h0 / hks)
+__device__ __forceinline__ const cplx* tg_table_clp(const TabArgs& P, int s) { return P.clp + (long)(P.b0 + s) * P.clp_bstride; }
 __device__ __forceinline__ const cplx* tg_table_src(const TabArgs& P, int ti, int s) {
   return ti == 0 ? P.h0 + (long)(P.b0 + s) * P.h0_bstride : P.hks + (long)(P.b0 + s) * P.hks_bstride + (long)(ti - 1) * P.Dh * P.Dh;
 }
@@ -356,9 +359,10 @@ __global__ void __launch_bounds__(256) tg_meta_kernel(TabArgs P) {
   __shared__ double r1[256], r2[256];
   const int ti = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
   const cplx* h = tg_table_src(P, ti, s);
+  const cplx* clp = tg_table_clp(P, s);
   double tr = 0.0, tim = 0.0;
   for (int i = tid; i < P.Dm; i += 256) {
-    const cplx v = tg_gelem(h, P.clp, P.lindblad, P.Dh, P.Dm, P.dt, ti == 0, i, i);
+    const cplx v = tg_gelem(h, clp, P.lindblad, P.Dh, P.Dm, P.dt, ti == 0, i, i);
     tr += v.x;
     tim += v.y;
   }
@@ -378,7 +382,7 @@ __global__ void __launch_bounds__(256) tg_meta_kernel(TabArgs P) {
   for (int j = tid; j < P.Dm; j += 256) {
     double sum = 0.0;
     for (int i = 0; i < P.Dm; ++i) {
-      cplx v = tg_gelem(h, P.clp, P.lindblad, P.Dh, P.Dm, P.dt, ti == 0, i, j);
+      cplx v = tg_gelem(h, clp, P.lindblad, P.Dh, P.Dm, P.dt, ti == 0, i, j);
       if (i == j) {
         v.x -= mur;
         v.y -= mui;
@@ -412,7 +416,7 @@ __global__ void __launch_bounds__(256) tg_table_kernel(TabArgs P, int DPR, int D
   double out = 0.0;
   if (i < P.Dm && c < P.Dm) {
     const cplx* h = tg_table_src(P, ti, s);
-    cplx g = tg_gelem(h, P.clp, P.lindblad, P.Dh, P.Dm, P.dt, ti == 0, i, c);
+    cplx g = tg_gelem(h, tg_table_clp(P, s), P.lindblad, P.Dh, P.Dm, P.dt, ti == 0, i, c);
     if (i == c) {
       const double* m = P.meta + ((long)s * (1 + P.K) + ti) * 4;
       g.x -= m[0];
@@ -477,6 +481,7 @@ struct AsmArgs {
   const cplx* hs;
   long hs_bstride;
   const cplx* clp;
+  long clp_bstride;
   int lindblad, Dh, Dm;
   double dt;
   double scale;
@@ -501,7 +506,7 @@ __global__ void __launch_bounds__(256) tg_assemble_kernel(AsmArgs P, int DPR, in
       double out = 0.0;
       if (i < P.Dm && c < P.Dm) {
         const cplx* h = P.hs + (long)(P.b0 + b) * P.hs_bstride + (long)P.n * P.Dh * P.Dh;
-        const cplx g = tg_gelem(h, P.clp, P.lindblad, P.Dh, P.Dm, P.dt, true, i, c);
+        const cplx g = tg_gelem(h, P.clp + (long)(P.b0 + b) * P.clp_bstride, P.lindblad, P.Dh, P.Dm, P.dt, true, i, c);
         out = P.scale * (p ? g.y : g.x);
       }
       X[e] = out;
@@ -545,8 +550,9 @@ __global__ void __launch_bounds__(256) tg_assemble_slots_kernel(AsmArgs P, int n
       double out = 0.0;
       if (i < P.Dm && c < P.Dm) {
         const cplx* h = P.hs + (long)(P.b0 + b) * P.hs_bstride + (long)n * P.Dh * P.Dh;
-        const cplx g = P.adjoint ? cconj(tg_gelem(h, P.clp, P.lindblad, P.Dh, P.Dm, P.dt, true, c, i))
-                                 : tg_gelem(h, P.clp, P.lindblad, P.Dh, P.Dm, P.dt, true, i, c);
+        const cplx* clp = P.clp + (long)(P.b0 + b) * P.clp_bstride;
+        const cplx g = P.adjoint ? cconj(tg_gelem(h, clp, P.lindblad, P.Dh, P.Dm, P.dt, true, c, i))
+                                 : tg_gelem(h, clp, P.lindblad, P.Dh, P.Dm, P.dt, true, i, c);
         out = P.scale * (p ? g.y : g.x);
       }
       X[e] = out;
@@ -813,7 +819,7 @@ int c3p_tiled_chunk(int Dm, int K, int B, bool per_sample_tables, size_t budget_
 int c3p_tiled_run(const TiledArgs& A, void* ws, int Bc, hipStream_t st, std::string& err) {
   const TG g(A.Dm);
   const long MS = g.MS;
-  const bool per_sample = !A.per_slice && (A.h0_bstride != 0 || A.hks_bstride != 0);
+  const bool per_sample = !A.per_slice && (A.h0_bstride != 0 || A.hks_bstride != 0 || A.clp_bstride != 0);
   const int K = A.per_slice ? 0 : A.K;
   const size_t nt = per_sample ? (size_t)Bc : 1;
   double* mats = reinterpret_cast<double*>(ws);
@@ -838,6 +844,7 @@ int c3p_tiled_run(const TiledArgs& A, void* ws, int Bc, hipStream_t st, std::str
       T.hks = A.hks;
       T.hks_bstride = A.hks_bstride;
       T.clp = A.clp;
+      T.clp_bstride = A.clp_bstride;
       T.dt = A.dt;
       T.K = K;
       T.Dh = A.D;
@@ -869,7 +876,9 @@ int c3p_tiled_run(const TiledArgs& A, void* ws, int Bc, hipStream_t st, std::str
       const long nmat = (long)nb * A.N;
       C3P_LAUNCH(tg_hnorm_kernel, dim3((unsigned)nmat), dim3(64), 0, st, A.h0 + (long)b0 * A.h0_bstride, A.h0_bstride, A.N,
                          A.D, red);
-      if (A.lindblad) C3P_LAUNCH(tg_hnorm_kernel, dim3(1), dim3(64), 0, st, A.clp, 0L, 1, A.Dm, red + 2);
+      if (A.lindblad)  // ||clp||_1: the maximum over the chunk's dissipators when they are per sample
+        C3P_LAUNCH(tg_hnorm_kernel, dim3(A.clp_bstride ? (unsigned)nb : 1u), dim3(64), 0, st, A.clp + (long)b0 * A.clp_bstride, A.clp_bstride, 1,
+                   A.Dm, red + 2);
       TG_TRY(hipGetLastError());
       std::vector<unsigned long long> hr(64);
       TG_TRY(hipMemcpyAsync(hr.data(), red, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -913,6 +922,7 @@ int c3p_tiled_run(const TiledArgs& A, void* ws, int Bc, hipStream_t st, std::str
         P.hs_bstride = A.h0_bstride;
       }
       P.clp = A.clp;
+      P.clp_bstride = A.clp_bstride;
       P.lindblad = A.lindblad;
       P.Dh = A.D;
       P.Dm = A.Dm;
@@ -1006,7 +1016,7 @@ int c3p_tiled_vjp_run(const TiledArgs& A, const cplx* U_bar, double* grad, cplx*
   const TG g(A.Dm);
   const long MS = g.MS;
   const bool per_slice = A.per_slice != 0;  // branch B: h0 = per-slice Hamiltonians, result = generator cotangents (zout)
-  const bool per_sample = !per_slice && (A.h0_bstride != 0 || A.hks_bstride != 0);
+  const bool per_sample = !per_slice && (A.h0_bstride != 0 || A.hks_bstride != 0 || A.clp_bstride != 0);
   const int K = per_slice ? 0 : A.K, N = A.N;
   const size_t nt = per_sample ? (size_t)Bc : 1;
   double* mats = reinterpret_cast<double*>(ws);
@@ -1049,6 +1059,7 @@ int c3p_tiled_vjp_run(const TiledArgs& A, const cplx* U_bar, double* grad, cplx*
       T.hks = A.hks;
       T.hks_bstride = A.hks_bstride;
       T.clp = A.clp;
+      T.clp_bstride = A.clp_bstride;
       T.dt = A.dt;
       T.K = K;
       T.Dh = A.D;
@@ -1081,7 +1092,9 @@ int c3p_tiled_vjp_run(const TiledArgs& A, const cplx* U_bar, double* grad, cplx*
     } else {
       const long nmat = (long)nb * N;
       C3P_LAUNCH(tg_hnorm_kernel, dim3((unsigned)nmat), dim3(64), 0, st, A.h0 + (long)b0 * A.h0_bstride, A.h0_bstride, N, A.D, red);
-      if (A.lindblad) C3P_LAUNCH(tg_hnorm_kernel, dim3(1), dim3(64), 0, st, A.clp, 0L, 1, A.Dm, red + 2);
+      if (A.lindblad)  // ||clp||_1: the maximum over the chunk's dissipators when they are per sample
+        C3P_LAUNCH(tg_hnorm_kernel, dim3(A.clp_bstride ? (unsigned)nb : 1u), dim3(64), 0, st, A.clp + (long)b0 * A.clp_bstride, A.clp_bstride, 1,
+                   A.Dm, red + 2);
       TG_TRY(hipGetLastError());
       std::vector<unsigned long long> hr(64);
       TG_TRY(hipMemcpyAsync(hr.data(), red, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -1124,6 +1137,7 @@ int c3p_tiled_vjp_run(const TiledArgs& A, const cplx* U_bar, double* grad, cplx*
       P.K = K;
       P.N = N;
       P.clp = A.clp;
+      P.clp_bstride = A.clp_bstride;
       P.lindblad = A.lindblad;
       P.Dh = A.D;
       P.Dm = A.Dm;

@@ -34,7 +34,8 @@ def thermal_initial_state(h0_diag_or_h0, init_temp, lindbladian: bool = True):
     Hamiltonian (a matrix, of which the diagonal is read, or that diagonal).  A finite temperature gives the Boltzmann weights
     exp(-hbar (E_i - E_0) / (kb T)), normalised, on the diagonal of a density matrix, returned as the density vector [D^2]
     (tf_dm_to_vec) -- this needs the Lindblad path, as in the reference; T = 0 gives the ground state, as vec(|0><0|) with
-    `lindbladian`, else as the ket [D].  Forward only: the temperature has no gradient through the initial state here."""
+    `lindbladian`, else as the ket [D].  `thermal_initial_state_vjp` is its derivative: with "grad_psi_init" of
+    `goal_run_batched_with_grad` it gives the gradient of a goal with respect to the temperature through rho0."""
     a = np.asarray(h0_diag_or_h0, dtype=np.complex128)
     diag = np.diagonal(a) if a.ndim == 2 else a.reshape(-1)
     dim = len(diag)
@@ -51,6 +52,44 @@ def thermal_initial_state(h0_diag_or_h0, init_temp, lindbladian: bool = True):
     if lindbladian:
         return np.outer(state, state).T.reshape(-1)
     return state
+
+
+def thermal_initial_state_vjp(h0_diag_or_h0, init_temp, rho0_bar):
+    """The exact derivative of `thermal_initial_state` at a finite temperature, in host numpy: from the cotangent `rho0_bar` [D^2] of
+    the density vector (d goal = Re sum conj(rho0_bar) d vec(rho0), "grad_psi_init"[p] of `goal_run_batched_with_grad`) returns
+    (grad_temp, grad_diag): d goal / d T and d goal / d E_k [D] for the diagonal energies E_k of the drift Hamiltonian (taken real).
+
+    With a_i = hbar (E_i - E_0) / (kb T), w_i = exp(-a_i) / Z and g_i = Re rho0_bar[i (D + 1)] (only the diagonal of rho0 moves):
+      d w_i / d T   = w_i (a_i - <a>) / T            grad_temp    = sum_i g_i w_i (a_i - <a>) / T
+      d w_i / d E_k = hbar / (kb T) w_i (w_k - d_ik)   grad_diag[k] = hbar / (kb T) w_k (<g> - g_k)
+    (<.> the mean under w; the shift by E_0 cancels).  At T = 0 the state is the ground state whatever the energies: both are zero."""
+    a = np.asarray(h0_diag_or_h0, dtype=np.complex128)
+    diag = (np.diagonal(a) if a.ndim == 2 else a.reshape(-1)).real
+    dim = len(diag)
+    bar = np.asarray(rho0_bar, dtype=np.complex128).reshape(-1)
+    if bar.size != dim * dim:
+        raise C3PropError(f"C3:Error: rho0_bar has {bar.size} entries, expected the cotangent of a density vector [{dim * dim}]")
+    if not abs(init_temp) > np.finfo(float).eps:
+        return 0.0, np.zeros(dim)
+    g = bar[:: dim + 1].real
+    c = HBAR / (KB * init_temp)
+    act = c * (diag - diag[0])
+    w = np.exp(-act)
+    w = w / np.sum(w)
+    grad_temp = float(np.sum(g * w * (act - np.sum(w * act))) / init_temp)
+    grad_diag = c * w * (np.sum(g * w) - g)
+    return grad_temp, grad_diag
+
+
+def _per_set_states(psi_init, D: int, P: int, sizes) -> Optional[np.ndarray]:
+    """psi_init as [P,n] with n in `sizes` when it holds one state per parameter set, else None (one state for every set: any shape
+    with n entries, or what the single-state code refuses -- so P kets [P,D] with P == D are read as ONE density vector [D^2]; pass density vectors [P,D^2] there)."""
+    psi = np.asarray(psi_init, dtype=np.complex128)
+    if psi.size in sizes:
+        return None
+    if psi.ndim == 2 and psi.shape[0] == P and psi.shape[1] in sizes:
+        return psi
+    return None  # (anything else is refused where a single state of that size is)
 
 
 def _density_vector(psi_init, D: int) -> np.ndarray:
@@ -78,7 +117,8 @@ def _open_system_states(h0, hks, gate_signals: Dict, dt: float, col_ops, P: int,
     from . import sequences as sq
 
     D = int(np.shape(h0)[-1])
-    rho0 = _density_vector(psi_init, D)
+    sets = _per_set_states(psi_init.detach().cpu().numpy() if propagation._is_torch(psi_init) else psi_init, D, P, (D, D * D))
+    rho0 = _density_vector(psi_init, D) if sets is None else np.stack([_density_vector(s, D) for s in sets])  # [D^2] or [P,D^2]
     for gate, sig in gate_signals.items():
         if int(sig.shape[0]) != P:
             raise C3PropError(f"C3:Error: gate {gate!r} has {int(sig.shape[0])} parameter sets, but there are {P} data sets")
@@ -199,13 +239,20 @@ def evaluate_sequences_batch(gate_Us: Dict, sequences: Sequence[Sequence[str]]):
 
 
 def populations_batch(U_seq, psi_init):
-    """|U_seq psi0|^2 [P,S,D]  (experiment.py:291-301,603-624, unitary case)."""
+    """|U_seq psi0|^2 [P,S,D]  (experiment.py:291-301,603-624, unitary case); psi_init one ket, or one per set [P,D]."""
+    P, D = int(U_seq.shape[0]), int(U_seq.shape[-1])
+    sets = _per_set_states(psi_init, D, P, (D,))
     if propagation._is_torch(U_seq):
         import torch
 
+        if sets is not None:
+            amp = torch.einsum("psij,pj->psi", U_seq, torch.as_tensor(sets, dtype=U_seq.dtype, device=U_seq.device))
+            return amp.real**2 + amp.imag**2
         psi = torch.as_tensor(np.asarray(psi_init).reshape(-1), dtype=U_seq.dtype, device=U_seq.device)
         amp = U_seq @ psi
         return amp.real**2 + amp.imag**2
+    if sets is not None:
+        return np.abs(np.einsum("psij,pj->psi", U_seq, sets)) ** 2
     amp = U_seq @ np.asarray(psi_init, dtype=np.complex128).reshape(-1)
     return np.abs(amp) ** 2
 
@@ -229,6 +276,10 @@ def goal_run_batched(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence
 
     With `col_ops` [C,D,D] the system is open: Lindblad superoperators, `psi_init` a ket [D] (taken as |psi><psi|) or a density
     vector [D^2] (`thermal_initial_state`), `fr_phase[gate]` [P,D^2], populations Re diag(vec_to_dm(S_seq vec(rho0))).
+
+    Per parameter set: `col_ops` [P,C,D,D] gives set p its own collapse operators (T1, T2*, bath temperature differ between the
+    sets), `psi_init` [P,D] or [P,D^2] (closed systems: [P,D]) its own initial state.  One state is recognised by its size, so P kets
+    with P == D are read as one density vector: pass [P,D^2] there.
     """
     P = len(data_sets)
     if col_ops is not None:
@@ -273,7 +324,10 @@ def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets
     state x = S_seq vec(rho0), so x_bar is pop_bar on its diagonal entries n D + n; step 3 is
     `propagate_batch_lindblad_vjp(..., want_model_grads=True)`, and the result also holds "grad_col_ops" [P,C,D,D], the cotangent
     of the collapse operators (through which T1, T2* and the temperature of the bath act), `grad_fr_phase[gate]` is [P,D^2].
-    The initial state is a constant: no gradient flows through a thermal rho0.
+    `col_ops` [P,C,D,D]: one set of collapse operators per parameter set; grad_col_ops[p] is then the cotangent of col_ops[p].
+    "grad_psi_init" is the cotangent of the initial state per set (also for a shared one: sum over p then): [P,D^2], that of
+    vec(rho0), for open systems (through `thermal_initial_state_vjp` the gradient of the temperature through rho0), [P,D], that of
+    the ket, for closed ones; `psi_init` may be one state or one per set, as in `goal_run_batched`.
     D = 7, 8, 9 (two coupled qutrits) take the Hermitian-basis sweep (`hermitian_basis=True`): h0 / hks must be Hermitian, and
     "grad_h0" / "grad_hks" are then Hermitian matrices, the Hermitian part of the general cotangent -- exact in
     `model_param_grads` for every Hermitian dh0 / dhks, which is what a model parameter moves.
@@ -292,7 +346,8 @@ def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets
     if int(first.shape[0]) != P:
         raise C3PropError("C3:Error: number of data sets and parameter sets differ")
     D = int(first.shape[-1])
-    psi = np.asarray(psi_init, dtype=np.complex128).reshape(-1)
+    sets = _per_set_states(psi_init, D, P, (D,))
+    psi = np.asarray(psi_init, dtype=np.complex128).reshape(-1) if sets is None else sets
     if device is not None:
         import torch
 
@@ -317,7 +372,7 @@ def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets
         np.add.at(rows, list(label_indices), 1.0)  # a label listed twice counts twice, as in process_batch
         pop_bar = sim_bar[..., None] * rows
     x_bar = 2.0 * (torch.as_tensor(pop_bar, device=device) if device is not None else pop_bar) * x
-    U_bar = sq.evaluate_sequences_indexed_vjp(Us, seqs, "state", x_bar, psi)
+    U_bar, psi_bar = sq.evaluate_sequences_indexed_vjp(Us, seqs, "state", x_bar, psi, want_psi0_bar=True)
     grad_h0 = grad_hks = None
     grad_signals, grad_ph = {}, ({} if fr_phase is not None else None)
     for gate, sig in gate_signals.items():
@@ -337,7 +392,7 @@ def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets
             # U = diag(e^{i phi}) P  =>  d loss / d phi_i = -Im sum_j conj(Ubar_ij) U_ij (optimal_control.goal_run_with_grad)
             grad_ph[gate] = None if ph is None else (-(Ub.conj() * Ug).sum(-1).imag)
     return {"goal": g_LL_prime_combined(goals, weights), "goals": goals, "sim_vals": sim_h, "grad_h0": grad_h0, "grad_hks": grad_hks,
-            "grad_signals": grad_signals, "grad_fr_phase": grad_ph}
+            "grad_signals": grad_signals, "grad_fr_phase": grad_ph, "grad_psi_init": psi_bar}
 
 
 def _goal_run_open_with_grad(h0, hks, gate_signals, dt, data_sets, psi_init, label_indices, fr_phase, device, col_ops) -> Dict:
@@ -369,7 +424,7 @@ def _goal_run_open_with_grad(h0, hks, gate_signals, dt, data_sets, psi_init, lab
         import torch
 
         x_bar = torch.as_tensor(x_bar, device=device)
-    U_bar = sq.evaluate_sequences_indexed_vjp(Us, seqs, "state", x_bar, rho0, superop=True)
+    U_bar, rho0_bar = sq.evaluate_sequences_indexed_vjp(Us, seqs, "state", x_bar, rho0, superop=True, want_psi0_bar=True)
     grad_h0 = grad_hks = grad_col = None
     grad_signals, grad_ph = {}, ({} if fr_phase is not None else None)
     for gate in gate_signals:
@@ -383,7 +438,7 @@ def _goal_run_open_with_grad(h0, hks, gate_signals, dt, data_sets, psi_init, lab
         if grad_ph is not None:
             grad_ph[gate] = None if a[3] is None else (-(U_bar[gate].conj() * Us[gate]).sum(-1).imag)
     return {"goal": g_LL_prime_combined(goals, weights), "goals": goals, "sim_vals": sim_h, "grad_h0": grad_h0, "grad_hks": grad_hks,
-            "grad_col_ops": grad_col, "grad_signals": grad_signals, "grad_fr_phase": grad_ph}
+            "grad_col_ops": grad_col, "grad_signals": grad_signals, "grad_fr_phase": grad_ph, "grad_psi_init": rho0_bar}
 
 
 def model_param_grads(grad_h0, grad_hks, dh0, dhks=None, grad_col_ops=None, dcol_ops=None):
@@ -409,14 +464,24 @@ def model_param_grads(grad_h0, grad_hks, dh0, dhks=None, grad_col_ops=None, dcol
     return out if per_set else out.sum(axis=0)
 
 
-def sensitivity_sweep(h0_of, hks_of, sweep_values: Sequence[float], gate_signals_one: Dict, dt: float, data_set: Dict, psi_init, label_indices, *, device=None) -> Dict:
+def sensitivity_sweep(h0_of, hks_of, sweep_values: Sequence[float], gate_signals_one: Dict, dt: float, data_set: Dict, psi_init, label_indices, *, device=None, col_ops_of=None,
+                      psi_init_of=None) -> Dict:
     """`Sensitivity.sensitivity` for one swept model parameter (sensitivity.py:100-124): the goal at every sweep
     point, all points in one batch.  `h0_of(v)` / `hks_of(v)` build the (dressed) operators at value v -- the
-    model update the reference performs per point (modellearning.py:227-232); the pulses are shared."""
+    model update the reference performs per point (modellearning.py:227-232); the pulses are shared.
+
+    `col_ops_of(v)` [C,D,D]: the sweep runs the open-system branch with the collapse operators of every point (a sweep over T1, T2* or
+    the bath temperature).  `psi_init_of(v)`: the initial state of every point (a ket [D] or a density vector [D^2], e.g.
+    `thermal_initial_state` at the swept temperature) instead of `psi_init`."""
     vals = list(sweep_values)
     P = len(vals)
     h0 = np.stack([np.asarray(h0_of(v), dtype=np.complex128) for v in vals])
     hks = np.stack([np.asarray(hks_of(v), dtype=np.complex128) for v in vals])
     sig = {g: np.broadcast_to(np.asarray(s, dtype=np.float64)[None], (P,) + tuple(np.shape(s))).copy() for g, s in gate_signals_one.items()}
-    r = goal_run_batched(h0, hks, sig, dt, [data_set] * P, psi_init, label_indices, device=device)
+    col = None if col_ops_of is None else np.stack([np.asarray(col_ops_of(v), dtype=np.complex128) for v in vals])  # [P,C,D,D]
+    if psi_init_of is not None:
+        psi_init = np.stack([np.asarray(psi_init_of(v), dtype=np.complex128).reshape(-1) for v in vals])  # [P,D] or [P,D^2]
+        if P == 1:  # (one point: a single state, which is what a size of D or D^2 is read as)
+            psi_init = psi_init[0]
+    r = goal_run_batched(h0, hks, sig, dt, [data_set] * P, psi_init, label_indices, device=device, col_ops=col)
     return {"values": np.asarray(vals), "goals": r["goals"], "sim_vals": r["sim_vals"]}

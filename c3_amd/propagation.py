@@ -127,6 +127,17 @@ def _bstride(arr, base_ndim: int, B: int, what: str) -> int:
     raise C3PropError(f"C3:Error: {what} has shape {tuple(arr.shape)}; expected {base_ndim} dims or a leading batch of {B}")
 
 
+def _col_per_sample(col, B: int):
+    """(C, flag) of collapse operators [C,D,D] (one set for the batch) or [B,C,D,D] (one per sample: C3P_COL_PER_SAMPLE)."""
+    return int(col.shape[-3]), (_lib.COL_PER_SAMPLE if _bstride(col, 3, B, "col_ops") else 0)
+
+
+def _shared_col_only(col_ops, what: str) -> None:
+    if col_ops is not None and not isinstance(col_ops, (list, tuple)) and getattr(col_ops, "ndim", 3) == 4:
+        raise C3PropError(f"C3:Error: {what} takes one col_ops [C,D,D] for the batch; per-sample col_ops [B,C,D,D] are served by "
+                          "propagate_batch(..., lindbladian=True) and propagate_batch_lindblad_vjp")
+
+
 # --------------------------------------------------------------------------
 # Batched entry point (the build's batch axis B; the reference loops in Python,
 # optimalcontrol_robust.py:54-63, modellearning.py:305-318)
@@ -152,6 +163,7 @@ def propagate_batch(
              [N,D,D] | [B,N,D,D]         per-slice Hamiltonians (branch B, propagation.py:295-308)
     hks      [K,D,D] | [B,K,D,D] | None
     signals  [B,K,N] real | None
+    col_ops  [C,D,D] | [B,C,D,D] (lindbladian): one set of collapse operators for the batch, or one per sample
     fr_phase [B,Dm] real or None; U <- diag(exp(i phase)) U   (experiment.py:482-509)
     Returns {"U": [B,Dm,Dm], "dUs": [B,N,Dm,Dm] or None}, Dm = D (unitary) or D*D (Lindblad).
 
@@ -196,14 +208,17 @@ def propagate_batch(
         if col_ops is None:
             raise C3PropError("C3:Error: lindbladian propagation needs collapse operators")
         col = call.c128(col_ops if _is_torch(col_ops) else np.asarray(col_ops))
+        C, col_flag = _col_per_sample(col, B)
+        flags |= col_flag
         if D in (2, 3, 4) and not (flags & _lib.PER_SLICE_H) and not want_dUs and _is_hermitian(call, h0) and (K == 0 or _is_hermitian(call, hks)):
             # one qubit / qutrit with Hermitian Hamiltonians: the generator is real in the Hermitian basis (c3p_smallr.hip)
             flags |= _lib.HERMITIAN_H
         rc = lib.c3p_pwc_lindblad(
-            _ptr(h0), h0_bs, _ptr(hks), hk_bs, _ptr(signals), _ptr(col), int(col.shape[0]), float(dt),
+            _ptr(h0), h0_bs, _ptr(hks), hk_bs, _ptr(signals), _ptr(col), C, float(dt),
             B, K, N, D, flags, _ptr(fr_phase), _ptr(U), _ptr(dUs), call.stream,
         )
     else:
+        _shared_col_only(col_ops, "the unitary propagation (lindbladian=False)")
         rc = lib.c3p_pwc_unitary(
             _ptr(h0), h0_bs, _ptr(hks), hk_bs, _ptr(signals), float(dt), B, K, N, D, flags,
             _ptr(fr_phase), _ptr(U), _ptr(dUs), call.stream,
@@ -436,6 +451,7 @@ def propagate_batch_lindblad_taped(h0, hks, signals, dt: float, col_ops, *, fr_p
 
     if recheck_operators:
         forget_operators(h0, hks)
+    _shared_col_only(col_ops, "the taped Lindblad evaluation")
     call = _Call(h0, hks, signals, col_ops, fr_phase)
     if not call.device:
         raise C3PropError("C3:Error: the taped Lindblad evaluation takes device tensors")
@@ -513,6 +529,8 @@ def propagate_batch_lindblad_vjp(h0, hks, signals, dt: float, col_ops, U_bar, *,
     tapes tf_propagation_lind (propagation.py:551-585) under the same GradientTape (optimizers/optimizer.py:206-216).
     `U_bar` [B,D^2,D^2] is the cotangent of the superoperators (d loss = Re sum conj(U_bar) dU); returns f64 [B,K,N].
 
+    `col_ops` is [C,D,D] or, one set per sample, [B,C,D,D] (grad_col_ops[b] is then the cotangent of col_ops[b]).
+
     `want_model_grads`: (grad_signals, grad_h0 [B,D,D], grad_hks [B,K,D,D], grad_col_ops [B,C,D,D]) through
     c3p_pwc_lindblad_model_vjp -- per sample (sum over B for operators the batch shares), d loss = Re sum conj(grad) d(operator),
     every operator entry an independent complex number (nothing assumed Hermitian).  D <= 6.
@@ -541,6 +559,7 @@ def propagate_batch_lindblad_vjp(h0, hks, signals, dt: float, col_ops, U_bar, *,
     if col_ops is None:
         raise C3PropError("C3:Error: lindbladian propagation needs collapse operators")
     col = call.c128(col_ops if _is_torch(col_ops) else np.asarray(col_ops))
+    C, col_flag = _col_per_sample(col, B)
     U_bar = call.c128(U_bar)
     if tuple(U_bar.shape) != (B, Dm, Dm):
         raise C3PropError(f"C3:Error: U_bar must be [{B},{Dm},{Dm}], got {tuple(U_bar.shape)}")
@@ -553,20 +572,19 @@ def propagate_batch_lindblad_vjp(h0, hks, signals, dt: float, col_ops, U_bar, *,
     else:
         grad = np.empty((B, K, N), dtype=np.float64)
     if want_model_grads:
-        C = int(col.shape[0])
         g0, gk, gc = call.empty((B, D, D)), call.empty((B, K, D, D)), call.empty((B, C, D, D))
         entry = _lib.load().c3p_pwc_lindblad_model_vjp_hb if hermitian_basis else _lib.load().c3p_pwc_lindblad_model_vjp
         _lib.check(
             entry(
-                _ptr(h0), h0_bs, _ptr(hks), hk_bs, _ptr(signals), _ptr(col), C, float(dt), B, K, N, D, call.flags,
+                _ptr(h0), h0_bs, _ptr(hks), hk_bs, _ptr(signals), _ptr(col), C, float(dt), B, K, N, D, call.flags | col_flag,
                 _ptr(fr_phase), _ptr(U_bar), _ptr(grad), _ptr(g0), _ptr(gk), _ptr(gc), call.stream
             )
         )
         return grad, g0, gk, gc
     _lib.check(
         _lib.load().c3p_pwc_lindblad_vjp(
-            _ptr(h0), h0_bs, _ptr(hks), hk_bs, _ptr(signals), _ptr(col), int(col.shape[0]), float(dt), B, K, N, D,
-            call.flags | (_lib.HERMITIAN_H if D in (2, 3, 4) and _is_hermitian(call, h0) and _is_hermitian(call, hks) else 0),
+            _ptr(h0), h0_bs, _ptr(hks), hk_bs, _ptr(signals), _ptr(col), C, float(dt), B, K, N, D,
+            call.flags | col_flag | (_lib.HERMITIAN_H if D in (2, 3, 4) and _is_hermitian(call, h0) and _is_hermitian(call, hks) else 0),
             _ptr(fr_phase), _ptr(U_bar), _ptr(grad), call.stream
         )
     )
@@ -863,6 +881,7 @@ def pwc(model, gen, instr, folding_stack: list, batch_size=None) -> Dict:
 
 def ode_solve_batch(h0, hks, signals, dt, init_state, solver="rk4", step_function="schrodinger", col_ops=None, final_only=False):
     """RK integration of B independent samples: signals [B,K,N]; init [D,M] or [B,D,M]."""
+    _shared_col_only(col_ops, "the ODE solver")
     call = _Call(h0, hks, signals, init_state, col_ops)
     lib = _lib.load()
     if solver not in solver_dict:
@@ -905,6 +924,7 @@ def ode_solve_batch(h0, hks, signals, dt, init_state, solver="rk4", step_functio
 
 
 def _ode_vjp_call(h0, hks, signals, dt, init_state, solver, step_function, col_ops, states_bar, target, want_states):
+    _shared_col_only(col_ops, "the ODE solver")
     call = _Call(h0, hks, signals, init_state, col_ops, states_bar, target)
     lib = _lib.load()
     if solver not in solver_dict:
@@ -1039,6 +1059,7 @@ class BatchPropagator:
         import torch
 
         self.torch = torch
+        _shared_col_only(col_ops, "BatchPropagator")
         _lib.require_gpu()
         self.lib = _lib.load()
         dev = signals.device

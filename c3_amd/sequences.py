@@ -202,12 +202,28 @@ def index_table(sequences: Sequence[Sequence], gate_index: Dict[str, int]):
     return seqs, lengths
 
 
+def _psi0_arg(call, psi0, Pn: int, M: int):
+    """(psi, per_sample): psi0 as [M] (any shape with M entries: one start vector for every sample) or [P,M] (one per sample)."""
+    if psi0 is None:
+        raise C3PropError("C3:Error: state mode needs psi0")
+    psi = call.c128(psi0)
+    n = 1
+    for s in psi.shape:
+        n *= int(s)
+    if n == M:
+        return psi.reshape(-1), False
+    if psi.ndim == 2 and tuple(int(s) for s in psi.shape) == (Pn, M):
+        return psi, True
+    raise C3PropError(f"C3:Error: psi0 has shape {tuple(psi.shape)}; expected {M} entries or one start vector per sample [{Pn},{M}]")
+
+
 def seq_chain(G, seqs, lengths, mode: str = "product", psi0=None, *, P: Optional[int] = None, superop: bool = False):
     """Direct binding of c3p_seq_chain.
 
     G [P, n_gates, M, M] (per-sample tables) or [n_gates, M, M] (one table for every sample; `P` then gives the number of
     samples, default 1); seqs int32 [S, Lmax]; lengths int32 [S].  numpy in -> numpy out (host pointers); CUDA tensors in
-    -> CUDA tensors out, on the current stream.  Returns [P,S,M,M] (product), [P,S,M] (state) or [P,S] f64 (population)."""
+    -> CUDA tensors out, on the current stream.  Returns [P,S,M,M] (product), [P,S,M] (state) or [P,S] f64 (population).
+    State mode: psi0 [M] starts every sample, psi0 [P,M] gives sample p its own start vector."""
     if mode not in MODES:
         raise C3PropError(f"C3:Error: unknown sequence mode {mode!r}; one of {sorted(MODES)}")
     call = _Call(G, psi0)
@@ -234,34 +250,35 @@ def seq_chain(G, seqs, lengths, mode: str = "product", psi0=None, *, P: Optional
     if sq.ndim != 2 or ln.ndim != 1 or int(ln.shape[0]) != int(sq.shape[0]):
         raise C3PropError(f"C3:Error: seqs must be [S,Lmax] and lengths [S], got {tuple(sq.shape)} and {tuple(ln.shape)}")
     S, Lmax = int(sq.shape[0]), int(sq.shape[1])
-    psi = None
+    psi, psi_per_sample = None, False
     if mode == "state":
-        if psi0 is None:
-            raise C3PropError("C3:Error: state mode needs psi0")
-        psi = call.c128(psi0).reshape(-1)
-        if int(psi.shape[0]) != M:
-            raise C3PropError(f"C3:Error: psi0 has {int(psi.shape[0])} entries, expected {M}")
+        psi, psi_per_sample = _psi0_arg(call, psi0, Pn, M)
     shape = {"product": (Pn, S, M, M), "state": (Pn, S, M), "population": (Pn, S)}[mode]
     if mode == "population":
         out = call.torch.empty(shape, dtype=call.torch.float64, device=call.dev) if call.device else np.empty(shape, dtype=np.float64)
     else:
         out = call.empty(shape)
-    flags = call.flags | (_lib.SEQ_SUPEROP if superop else 0)
+    flags = call.flags | (_lib.SEQ_SUPEROP if superop else 0) | (_lib.SEQ_PSI0_PER_SAMPLE if psi_per_sample else 0)
     _lib.check(
         _lib.load().c3p_seq_chain(_ptr(Gt), bstride, n, M, Pn, _ptr(sq), S, Lmax, _ptr(ln), MODES[mode], _ptr(psi), flags, _ptr(out), call.stream)
     )
     return out
 
 
-def seq_chain_vjp(G, seqs, lengths, mode: str, out_bar, psi0=None, *, P: Optional[int] = None, superop: bool = False, want_out: bool = False):
+def seq_chain_vjp(G, seqs, lengths, mode: str, out_bar, psi0=None, *, P: Optional[int] = None, superop: bool = False, want_out: bool = False, want_psi0_bar: bool = False):
     """Direct binding of c3p_seq_chain_vjp: the cotangent of the gate table G from the cotangent `out_bar` of what
     `seq_chain(G, seqs, lengths, mode, psi0, P=P, superop=superop)` returns (d loss = Re sum conj(out_bar) d out).
 
     Returns G_bar with G's layout: [P, n_gates, M, M] for per-sample tables, [n_gates, M, M] (summed over the samples)
     for a shared one; with `want_out`, (G_bar, out) where out is the forward output of the same pass.  numpy in -> numpy
-    out (host pointers); CUDA tensors in -> CUDA tensors out, on the current stream."""
+    out (host pointers); CUDA tensors in -> CUDA tensors out, on the current stream.
+
+    State mode: psi0 is [M] or, one per sample, [P,M].  `want_psi0_bar` (state mode, c3p_seq_state_vjp) appends psi0_bar [P,M] to
+    what is returned: the cotangent of the start vector per sample, also for a shared psi0 (sum over P then)."""
     if mode not in MODES:
         raise C3PropError(f"C3:Error: unknown sequence mode {mode!r}; one of {sorted(MODES)}")
+    if want_psi0_bar and mode != "state":
+        raise C3PropError("C3:Error: want_psi0_bar needs the state mode")
     call = _Call(G, psi0, out_bar)
     Gt = call.c128(G)
     if Gt.ndim == 3:
@@ -286,13 +303,9 @@ def seq_chain_vjp(G, seqs, lengths, mode: str, out_bar, psi0=None, *, P: Optiona
     if sq.ndim != 2 or ln.ndim != 1 or int(ln.shape[0]) != int(sq.shape[0]):
         raise C3PropError(f"C3:Error: seqs must be [S,Lmax] and lengths [S], got {tuple(sq.shape)} and {tuple(ln.shape)}")
     S, Lmax = int(sq.shape[0]), int(sq.shape[1])
-    psi = None
+    psi, psi_per_sample = None, False
     if mode == "state":
-        if psi0 is None:
-            raise C3PropError("C3:Error: state mode needs psi0")
-        psi = call.c128(psi0).reshape(-1)
-        if int(psi.shape[0]) != M:
-            raise C3PropError(f"C3:Error: psi0 has {int(psi.shape[0])} entries, expected {M}")
+        psi, psi_per_sample = _psi0_arg(call, psi0, Pn, M)
     shape = {"product": (Pn, S, M, M), "state": (Pn, S, M), "population": (Pn, S)}[mode]
     ob = call.f64(out_bar) if mode == "population" else call.c128(out_bar)
     if tuple(ob.shape) != shape:
@@ -305,6 +318,16 @@ def seq_chain_vjp(G, seqs, lengths, mode: str, out_bar, psi0=None, *, P: Optiona
             out = call.empty(shape)
     G_bar = call.empty((n, M, M) if bstride == 0 else (Pn, n, M, M))
     flags = call.flags | (_lib.SEQ_SUPEROP if superop else 0)
+    if want_psi0_bar:
+        psi_bar = call.empty((Pn, M))
+        _lib.check(
+            _lib.load().c3p_seq_state_vjp(
+                _ptr(Gt), bstride, n, M, Pn, _ptr(sq), S, Lmax, _ptr(ln), _ptr(psi), M if psi_per_sample else 0, _ptr(ob), flags, _ptr(G_bar),
+                _ptr(psi_bar), _ptr(out), call.stream
+            )
+        )
+        return (G_bar, out, psi_bar) if want_out else (G_bar, psi_bar)
+    flags |= _lib.SEQ_PSI0_PER_SAMPLE if psi_per_sample else 0
     _lib.check(
         _lib.load().c3p_seq_chain_vjp(
             _ptr(Gt), bstride, n, M, Pn, _ptr(sq), S, Lmax, _ptr(ln), MODES[mode], _ptr(psi), _ptr(ob), flags, _ptr(G_bar), _ptr(out), call.stream
@@ -331,25 +354,29 @@ def _gate_table(gate_Us: Dict):
 def evaluate_sequences_indexed(gate_Us: Dict, sequences: Sequence[Sequence[str]], mode: str = "product", psi0=None, *, superop: bool = False):
     """`model_learning.evaluate_sequences_batch` by index: the same {name: U [P,M,M]} dict and name lists, one
     c3p_seq_chain launch.  Returns U_seq [P,S,M,M] (product), U_seq psi0 [P,S,M] (state) or the population of state 0
-    [P,S] (|<0|U_seq|0>|^2; with `superop`, |(U_seq vec(|0><0|))[0]|).  Propagators given as [M,M] give P = 1."""
+    [P,S] (|<0|U_seq|0>|^2; with `superop`, |(U_seq vec(|0><0|))[0]|).  Propagators given as [M,M] give P = 1.
+    psi0 (state mode): [M], or [P,M] with one start vector per sample."""
     names, G = _gate_table(gate_Us)
     seqs, lengths = index_table(sequences, {k: i for i, k in enumerate(names)})
     return seq_chain(G, seqs, lengths, mode, psi0, superop=superop)
 
 
-def evaluate_sequences_indexed_vjp(gate_Us: Dict, sequences: Sequence[Sequence[str]], mode: str, out_bar, psi0=None, *, superop: bool = False, want_out: bool = False):
+def evaluate_sequences_indexed_vjp(gate_Us: Dict, sequences: Sequence[Sequence[str]], mode: str, out_bar, psi0=None, *, superop: bool = False, want_out: bool = False, want_psi0_bar: bool = False):
     """Vector-Jacobian product of `evaluate_sequences_indexed` (same dict, name lists, mode and psi0): {name: U_bar}
     with each propagator's shape ([P,M,M], or [M,M] for unbatched input), from the cotangent `out_bar` of its output.
-    One c3p_seq_chain_vjp launch.  With `want_out`: ({name: U_bar}, forward output)."""
+    One c3p_seq_chain_vjp launch.  With `want_out`: ({name: U_bar}, forward output).  psi0 (state mode) is [M] or [P,M];
+    `want_psi0_bar` appends psi0_bar [P,M], the cotangent of the start vector per sample, to what is returned."""
     names, G = _gate_table(gate_Us)
     seqs, lengths = index_table(sequences, {k: i for i, k in enumerate(names)})
     unbatched = G.ndim == 3
     if unbatched:  # a [M,M] propagator per name is one sample (P = 1) with its own table: G_bar keeps its shape
         G = G[None]
-    r = seq_chain_vjp(G, seqs, lengths, mode, out_bar, psi0, superop=superop, want_out=want_out)
-    G_bar = r[0] if want_out else r
+    r = seq_chain_vjp(G, seqs, lengths, mode, out_bar, psi0, superop=superop, want_out=want_out, want_psi0_bar=want_psi0_bar)
+    G_bar = r[0] if want_out or want_psi0_bar else r
     grads = {k: (G_bar[0, i] if unbatched else G_bar[:, i]) for i, k in enumerate(names)}
-    return (grads, r[1]) if want_out else grads
+    if want_out or want_psi0_bar:
+        return (grads,) + tuple(r[1:])
+    return grads
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

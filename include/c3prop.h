@@ -64,6 +64,12 @@ extern "C" {
                                  The reference makes no such distinction (propagation.py:551-585): c3_amd/propagation.py sets
                                  the flag after checking the arrays. */
 
+#define C3P_COL_PER_SAMPLE 0x40 /* Lindblad PWC entries: col_ops is [B,C,D,D], sample b uses col_ops[b] (one dissipator and one
+                                 table set per sample, as with a per-sample h0).  Honoured by c3p_pwc_lindblad (every route,
+                                 C3P_PER_SLICE_H and dUs_out included), c3p_pwc_lindblad_vjp, c3p_pwc_lindblad_model_vjp and
+                                 _model_vjp_hb (grad_col_ops[b] is then the cotangent of col_ops[b]) and c3p_reserve; an error
+                                 in c3p_pwc_unitary, c3p_pwc_lindblad_taped / _vjp_taped and c3p_ode_solve / _vjp. */
+
 /* kernels selected (returned by c3p_last_kernel, for tests/bench reporting) */
 #define C3P_KERNEL_NONE 0
 #define C3P_KERNEL_GENERIC_LDS 1
@@ -477,7 +483,8 @@ int c3p_gate_infid(const void* U, int B, int D, const int32_t* comp_rows, int L,
  *   seqs     int32 [S, Lmax] gate indices (row s uses its first lengths[s] entries); lengths int32 [S], 0 = identity.
  *            Shared by all P samples.
  *   mode     C3P_SEQ_PRODUCT:    out c128 [P,S,M,M] = U_seq
- *            C3P_SEQ_STATE:      out c128 [P,S,M]   = U_seq psi0, psi0 c128 [M]
+ *            C3P_SEQ_STATE:      out c128 [P,S,M]   = U_seq psi0, psi0 c128 [M]; with C3P_SEQ_PSI0_PER_SAMPLE in flags psi0 is
+ *                                c128 [P,M] and sample p starts from psi0[p] (the flag is an error in the other modes)
  *            C3P_SEQ_POPULATION: out f64  [P,S]     = |(U_seq e_0)[0]|^2, or with C3P_SEQ_SUPEROP in flags |(U_seq e_0)[0]|
  *                                (the Lindblad population of vec(|0><0|), fidelities.py:460-470)
  *            The state and population modes are matrix-vector chains: no matrix product is formed.
@@ -487,6 +494,7 @@ int c3p_gate_infid(const void* U, int B, int D, const int32_t* comp_rows, int L,
 #define C3P_SEQ_PRODUCT 0
 #define C3P_SEQ_STATE 1
 #define C3P_SEQ_POPULATION 2
+#define C3P_SEQ_PSI0_PER_SAMPLE 0x80 /* c3p_seq_chain, c3p_seq_chain_vjp, state mode: psi0 is [P,M], one start vector per sample */
 int c3p_seq_chain(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
                   const int32_t* lengths, int mode, const void* psi0, int flags, void* out, void* stream);
 
@@ -508,6 +516,18 @@ int c3p_seq_chain(const void* G, int64_t G_bstride, int n_gates, int M, int P, c
 int c3p_seq_chain_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
                       const int32_t* lengths, int mode, const void* psi0, const void* out_bar, int flags, void* G_bar,
                       void* out, void* stream);
+
+/* c3p_seq_chain_vjp in C3P_SEQ_STATE mode with the cotangent of the start vector as one more result.
+ *   psi0         c128 [M] (psi0_bstride 0: shared) or one per sample, psi0_bstride elements apart ([P,M]: M)
+ *   psi0_bar     c128 [P,M]: psi0_bar[p] = sum_s G[p,i_0]^H ... G[p,i_{L-1}]^H out_bar[p,s], the vector the reverse sweep of
+ *                every chain ends on; a sequence of length 0 contributes out_bar[p,s] itself.  Always per sample, also for
+ *                a shared psi0 (the caller sums over p, as with grad_h0).
+ *   G_bar, out   as c3p_seq_chain_vjp.
+ * The sum over the sequences follows G_bar's rule: one partial per workgroup, added by the reduce launch in a fixed order --
+ * bitwise reproducible, still two launches per call.  C3P_SEQ_PSI0_PER_SAMPLE is not taken here (psi0_bstride says it). */
+int c3p_seq_state_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
+                      const int32_t* lengths, const void* psi0, int64_t psi0_bstride, const void* out_bar, int flags, void* G_bar,
+                      void* psi0_bar, void* out, void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
