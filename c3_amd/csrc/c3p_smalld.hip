@@ -123,6 +123,128 @@ __device__ __forceinline__ void mm_img(const double* img, int roff, unsigned neg
   }
 }
 
+// ---- one half-image product dealt over the blocks of the instruction (the fold of the fused tail) ----
+// mm_img gives block b of every MFMA to chain b.  Where fewer than four chains have a product to form -- the fold of a wave's four
+// segments: two products, then one -- the NBI x NJ output tiles of a product are dealt over the nb = 2 or 4 blocks that would
+// otherwise multiply slots nobody reads: ceil(NBI NJ / nb) x NBI instructions per product instead of NBI NJ x NBI (D = 9: 40 and
+// 20 instead of 75).  An output tile is still NBI instructions in K order from a zero accumulator on the same operands; the blocks
+// of an instruction are independent, so every element has the bits mm_img gives it.
+struct SDTile {
+  int I, J;
+  bool on;  // false: the block idles in this task (it repeats tile (0, 0) and does not write it)
+};
+
+template <int D>
+constexpr int sd_split_tasks(int nb) {
+  return (SD<D>::NBI * SD<D>::NJ + nb - 1) / nb;
+}
+
+// The deal (block, task) -> (I, J).  A block stays on one column J where it can, so that its lanes read one column of right-operand
+// tiles: every column is cut into runs of `per` rows, one run per block, and the rows left over at the bottom of the columns are
+// pooled, column by column, on the blocks behind.  D = 9, nb = 4: columns 0, 1, 2 with rows 0 .. 3 on blocks 0, 1, 2 and row 4 of
+// the three columns on block 3; nb = 2: column 0 and rows 0 .. 2 of column 1 | rows 3, 4 of column 1 and column 2.
+// Banks of the A-fragment reads (ds_read_b64, 32-lane groups on 64 dword banks, see SD<D>::IMG): a lane reads row 4 I + rho of its
+// image, stride W doubles with W odd, and an image has at most 24 rows -- blocks that read ONE image (nb = 4) at different I touch
+// different rows and so different banks, at the same I they read the same address: no conflict for any deal.  Two pairs that read
+// two images 2 IMG = 24 (mod 32) doubles apart (nb = 2) meet in a bank only where their rows differ by 8, that is I by exactly 2:
+// a two-way conflict in some tasks (D = 9: three of eight), which no deal of 15 tiles over two blocks avoids in all tasks and
+// which costs one LDS cycle against the 16 of the instruction it feeds.
+template <int D>
+constexpr SDTile sd_split_deal(int nb, int blk, int task) {
+  constexpr int NBI = SD<D>::NBI, NJ = SD<D>::NJ;
+  const int per = sd_split_tasks<D>(nb);
+  const int full = NBI / per, rem = NBI % per;  // whole runs per column, rows left over per column
+  if (blk < NJ * full) return SDTile{(blk % full) * per + task, blk / full, true};
+  const int idx = (blk - NJ * full) * per + task;
+  if (rem == 0 || idx >= NJ * rem) return SDTile{0, 0, false};
+  return SDTile{full * per + idx % rem, idx / rem, true};
+}
+
+// every output tile exactly once
+template <int D>
+constexpr bool sd_split_deal_ok(int nb) {
+  constexpr int NBI = SD<D>::NBI, NJ = SD<D>::NJ;
+  int seen[NBI][NJ] = {};
+  for (int blk = 0; blk < nb; ++blk)
+    for (int t = 0; t < sd_split_tasks<D>(nb); ++t) {
+      const SDTile s = sd_split_deal<D>(nb, blk, t);
+      if (s.I < 0 || s.I >= NBI || s.J < 0 || s.J >= NJ) return false;
+      if (s.on) ++seen[s.I][s.J];
+    }
+  for (int I = 0; I < NBI; ++I)
+    for (int J = 0; J < NJ; ++J)
+      if (seen[I][J] != 1) return false;
+  return true;
+}
+#define C3P_SD_DEAL_OK(D) static_assert(sd_split_deal_ok<D>(2) && sd_split_deal_ok<D>(4), "split product: every output tile exactly once")
+C3P_SD_DEAL_OK(2); C3P_SD_DEAL_OK(3); C3P_SD_DEAL_OK(4); C3P_SD_DEAL_OK(5); C3P_SD_DEAL_OK(6); C3P_SD_DEAL_OK(7);
+C3P_SD_DEAL_OK(8); C3P_SD_DEAL_OK(9); C3P_SD_DEAL_OK(10); C3P_SD_DEAL_OK(11); C3P_SD_DEAL_OK(12);
+#undef C3P_SD_DEAL_OK
+static_assert(sd_split_deal<9>(4, 2, 3).I == 3 && sd_split_deal<9>(4, 2, 3).J == 2 && sd_split_deal<9>(4, 3, 1).I == 4 &&
+                  sd_split_deal<9>(4, 3, 1).J == 1 && !sd_split_deal<9>(4, 3, 3).on,
+              "D = 9 over four blocks: a column each on blocks 0 .. 2, the last row on block 3");
+
+// The lane's tile of task t (blk: the lane's block within its product, 0 .. NB - 1) as image offsets: A fragments start at
+// I 4 W, the tile itself (right operand, output) at I 4 W + J 4.
+template <int D, int NB>
+__device__ __forceinline__ void split_offsets(int blk, int (&aoff)[sd_split_tasks<D>(NB)], int (&coff)[sd_split_tasks<D>(NB)],
+                                              int (&joff)[sd_split_tasks<D>(NB)], bool (&on)[sd_split_tasks<D>(NB)]) {
+  using C = SD<D>;
+#pragma unroll
+  for (int t = 0; t < sd_split_tasks<D>(NB); ++t) {
+    int I = sd_split_deal<D>(NB, 0, t).I, J = sd_split_deal<D>(NB, 0, t).J;
+    bool o = sd_split_deal<D>(NB, 0, t).on;
+#pragma unroll
+    for (int q = 1; q < NB; ++q) {
+      I = blk == q ? sd_split_deal<D>(NB, q, t).I : I;
+      J = blk == q ? sd_split_deal<D>(NB, q, t).J : J;
+      o = blk == q ? sd_split_deal<D>(NB, q, t).on : o;
+    }
+    aoff[t] = I * 4 * C::W;
+    joff[t] = J * 4;
+    coff[t] = I * 4 * C::W + J * 4;
+    on[t] = o;
+  }
+}
+
+// C = A B with the output tiles dealt over NB blocks.  `a`: the left operand's image plus the lane's A-fragment offset (roff of
+// mm_img less the chain's image base); `bc`: the right operand's image plus the lane's D-layout offset r W + c.  The product is
+// written over the right operand's image, after all reads (two wave_syncs).  K is the outer loop, as in mm_img: the
+// instructions of a step are independent of one another and the A and B reads of step K + 1 are in flight under them.
+template <int D, int NB>
+__device__ __forceinline__ void mm_split(const double* a, double* bc, unsigned negmask, int blk) {
+  using C = SD<D>;
+  constexpr int NT = sd_split_tasks<D>(NB);
+  int aoff[NT], coff[NT], joff[NT];
+  bool on[NT];
+  split_offsets<D, NB>(blk, aoff, coff, joff, on);
+  double ra[2][NT], rb[2][NT], acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    ra[0][t] = flip_sign(lds_ld(a + aoff[t]), negmask);
+    rb[0][t] = lds_ld(bc + joff[t]);
+    acc[t] = 0.0;
+  }
+#pragma unroll
+  for (int K = 0; K < C::NBI; ++K) {
+    if (K + 1 < C::NBI) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        ra[(K + 1) & 1][t] = flip_sign(lds_ld(a + aoff[t] + (K + 1) * 2), negmask);
+        rb[(K + 1) & 1][t] = lds_ld(bc + (K + 1) * 4 * C::W + joff[t]);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = mfma4(ra[K & 1][t], rb[K & 1][t], acc[t]);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  wave_sync();
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    if (on[t]) bc[coff[t]] = acc[t];
+  wave_sync();
+}
+
 struct LanePos {
   int r, b, c;
   int idx16;  // position among the chain's 16 lanes
@@ -1865,19 +1987,42 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
       ti = c3p_phase_add(ti, __shfl_xor(ti, 4));
       ti = c3p_phase_add(ti, __shfl_xor(ti, 8));
       const int rrest = roff - lp.b * IMG;
-      const int roff1 = ((lp.b + 1) & 3) * IMG + rrest;  // A fragments of the NEXT chain's image
-      const int roff2 = ((lp.b + 2) & 3) * IMG + rrest;
       double V[NBI][NJ], Wt[NBI][NJ];
       // Wt (slot 0) = M3 M2 M1 M0 of the four slots' matrices; `in_image`: the chains' images hold M already
+      // Only two of the four slots have a first product to form and one the second.  The workgroup-per-sample instances of
+      // D = 5 .. 9 deal each product's output tiles over the blocks of the slots that have none (mm_split: D = 9, 40 + 20 matrix
+      // instructions instead of 75 + 75); every element has the bits of the other form, which the remaining instances keep, so the
+      // two modes stay bit for bit equal at equal segments.  Not dealt, by the resource figures (profiles/r10):
+      //  * up to D = 4 a product has one or two tiles -- a deal saves at most two instructions a product, less than the trip
+      //    through the image that returns the result to slot 0's registers;
+      //  * D = 10 .. 12 -- the deal's per-lane offsets cost these instances registers they do not have (VGPR spills 328 -> 597 at
+      //    D = 11, 565 -> 668 at D = 12 in this mode);
+      //  * the one-wave instances -- the last arriver inlines the fold a second time, and every one of D = 9 .. 12 took more
+      //    scratch with the deal (124 -> 136 B/lane at D = 9, 340 -> 428 at D = 12).
+      constexpr bool FOLD_SPLIT = MW && NBI * NJ > 2 && D <= 9;
       auto fold_slots = [&](const double (&M)[NBI][NJ], bool in_image) {
-#pragma unroll
-        for (int I = 0; I < NBI; ++I)
-#pragma unroll
-          for (int J = 0; J < NJ; ++J) V[I][J] = Wt[I][J] = 0.0;
         if (!in_image) write_image<D>(M, img, woff);
-        mm_img<D>(img, roff1, negmask, M, V);  // slots 0, 2: M_{b+1} M_b
-        write_image<D>(V, img, woff);
-        mm_img<D>(img, roff2, negmask, V, Wt);  // slot 0: (M3 M2)(M1 M0)
+        if constexpr (FOLD_SPLIT) {
+          const int wrest = woff - lp.b * IMG;
+          // block pairs {0, 1} and {2, 3}: M1 M0 over image 0, M3 M2 over image 2
+          mm_split<D, 2>(img + ((lp.b & 2) + 1) * IMG + rrest, img + (lp.b & 2) * IMG + wrest, negmask, lp.b & 1);
+          // all four blocks: (M3 M2)(M1 M0) over image 0, from which every slot takes it in register order
+          mm_split<D, 4>(img + 2 * IMG + rrest, img + wrest, negmask, lp.b);
+#pragma unroll
+          for (int I = 0; I < NBI; ++I)
+#pragma unroll
+            for (int J = 0; J < NJ; ++J) Wt[I][J] = img[wrest + I * 4 * W + J * 4];
+        } else {
+          const int roff1 = ((lp.b + 1) & 3) * IMG + rrest;  // A fragments of the NEXT chain's image
+          const int roff2 = ((lp.b + 2) & 3) * IMG + rrest;
+#pragma unroll
+          for (int I = 0; I < NBI; ++I)
+#pragma unroll
+            for (int J = 0; J < NJ; ++J) V[I][J] = Wt[I][J] = 0.0;
+          mm_img<D>(img, roff1, negmask, M, V);  // slots 0, 2: M_{b+1} M_b
+          write_image<D>(V, img, woff);
+          mm_img<D>(img, roff2, negmask, V, Wt);  // slot 0: (M3 M2)(M1 M0)
+        }
       };
       fold_slots(U, img_holds_U);
       SD_TICK(tka);
