@@ -511,8 +511,9 @@ __device__ __forceinline__ void rcomb(double (&out)[RD<D>::NB][RD<D>::NB], doubl
 //   general matrix (GMat, the chain state): core, column border cr (r form) / cc (c form), row border rc[J] = M[D-1][4J+c], s.
 // Border of a product: column = core x vector on the vector unit (one FMA per tile and lane + a quad reduction by DPP),
 // its c form by one lane swap; corner = dot product (quad reduction); the ROW border of a chain product is a vector-matrix
-// product whose sum runs over the r lanes (16 apart: no DPP reach) -- it stays on the matrix cores as ONE A tile per K-step
-// whose only row is the border (4 MFMAs instead of the 10 of the padded tiles).  Measured in isolation
+// product whose sum runs over the r lanes (16 apart: no DPP reach) -- it stayed on the matrix cores as ONE A tile per K-step
+// whose only row is the border (4 MFMAs instead of the 10 of the padded tiles).  (Since then every border sum is a reduction over r
+// by a matrix instruction against a tile of ones: mm_s8 and chain_step8 below.)  Measured in isolation
 // (tools/ubench_sym9.hip, profiles/r04/ubench_sym9.txt): a dependent symmetric product 284 ns against 315 ns per wave at two
 // waves per SIMD.
 // ---------------------------------------------------------------------------------------------
@@ -700,103 +701,124 @@ __device__ __forceinline__ void s8_comb(SMat<NC>& out, double c0, double c1, dou
 }
 
 
-// chain step in real blocks for the core + border form: (Ur + i Ui) <- (C - i S)(Ur + i Ui) with three real products
-// (T1 = C Ur, T2 = S Ui, T3 = (C - S)(Ur + Ui): Re = T1 + T2, Im = T3 - T1 + T2), C and S symmetric (complete operand form).
-// Round 6: no lane swaps and no DPP reductions.  The column border and the corner are reduced over r by a matrix instruction
-// against ones (see mm_s8; the partial products use the TRANSPOSED tile of the symmetric left operand and the r form `cr` of the
-// state's column border, so the c form `cc` is not carried any more); the row border comes out of its matrix instructions already
-// replicated over r, because the A tile holds the border row of the left operand in EVERY row instead of row 0 alone.
+// chain step in real blocks for the core + border form: (Ur + i Ui) <- (C - i S)(Ur + i Ui), C and S symmetric (left-operand form:
+// core tiles complete, vr, s).
+// Core (the NC x NC tiles, on the matrix cores): three real products, T1 = C Ur, T2 = S Ui, T3 = (C - S)(Ur + Ui), Re = T1 + T2,
+// Im = T3 - T1 + T2.  The rank-1 term of the border (column of the left operand times row of the state) is the initial value of the
+// three accumulators, in the same 3M form.
+// Border (row, column, corner): 3M saves a product on the matrix cores only -- on the vector unit add, mul and fma cost the same, so the
+// border uses the direct form Re = C Ur + S Ui, Im = C Ui - S Ur as fma chains.  No lane swaps, no DPP reductions: every border sum
+// has its sum index on r (for the symmetric left operand: its transposed tile, or its r-form border vr, which is also its border row)
+// and is reduced by ONE matrix instruction against a tile of ones, the k = D-1 term riding in as the accumulator:
+//   column, corner: A = partials, B = 1 -> D[i][j] = sum_r t(r, c = i), the r form replicated over c (cr, s; see mm_s8);
+//   row:            A = 1, B = partials -> D[i][j] = sum_r t(r, c = j), the c form replicated over r (rc).
+// Every right-hand side reads the old state; every vector operation that feeds a matrix instruction is issued before the first one
+// (a vector instruction that reads a matrix result waits ~45 cycles, the other way round costs two wait states).
 template <int NC>
 __device__ __forceinline__ void chain_step8(const SMat<NC>& Cc, const SMat<NC>& Sc, GMat<NC>& Ur, GMat<NC>& Ui, const LanePos& lp,
                                             int tail_lane, int row0_lane) {
   (void)lp, (void)tail_lane, (void)row0_lane;
-  SMat<NC> Dm;
-  GMat<NC> Us;
+  double Dm[NC][NC], Us[NC][NC], T1[NC][NC], T2[NC][NC], T3[NC][NC];
 #pragma unroll
-  for (int I = 0; I < NC; ++I) {
+  for (int I = 0; I < NC; ++I)
 #pragma unroll
     for (int J = 0; J < NC; ++J) {
-      Dm.m[I][J] = Cc.m[I][J] - Sc.m[I][J];
-      Us.m[I][J] = Ur.m[I][J] + Ui.m[I][J];
+      Dm[I][J] = Cc.m[I][J] - Sc.m[I][J];
+      Us[I][J] = Ur.m[I][J] + Ui.m[I][J];
     }
-    Dm.vr[I] = Cc.vr[I] - Sc.vr[I];
-    Us.cr[I] = Ur.cr[I] + Ui.cr[I];
-    Us.rc[I] = Ur.rc[I] + Ui.rc[I];
+  {
+    double dv[NC], us[NC];
+#pragma unroll
+    for (int I = 0; I < NC; ++I) {
+      dv[I] = Cc.vr[I] - Sc.vr[I];
+      us[I] = Ur.rc[I] + Ui.rc[I];
+    }
+#pragma unroll
+    for (int I = 0; I < NC; ++I)
+#pragma unroll
+      for (int J = 0; J < NC; ++J) {
+        T1[I][J] = Cc.vr[I] * Ur.rc[J];
+        T2[I][J] = Sc.vr[I] * Ui.rc[J];
+        T3[I][J] = dv[I] * us[J];
+      }
   }
-  Dm.s = Cc.s - Sc.s;
-  Us.s = Ur.s + Ui.s;
-  double T1[NC][NC], T2[NC][NC], T3[NC][NC], R1[NC], R2[NC], R3[NC];
+  // row border, lane (r, c): sum_K M[D-1][4K+r] U[4K+r][4J+c]; accumulator M[D-1][D-1] U[D-1][4J+c]
+  double tr[NC], ti[NC], ar[NC], ai[NC];
+#pragma unroll
+  for (int J = 0; J < NC; ++J) {
+    tr[J] = Cc.vr[0] * Ur.m[0][J];
+    ti[J] = Cc.vr[0] * Ui.m[0][J];
+#pragma unroll
+    for (int K = 1; K < NC; ++K) {
+      tr[J] = fma(Cc.vr[K], Ur.m[K][J], tr[J]);
+      ti[J] = fma(Cc.vr[K], Ui.m[K][J], ti[J]);
+    }
+#pragma unroll
+    for (int K = 0; K < NC; ++K) {
+      tr[J] = fma(Sc.vr[K], Ui.m[K][J], tr[J]);
+      ti[J] = fma(-Sc.vr[K], Ur.m[K][J], ti[J]);
+    }
+    ar[J] = fma(Sc.s, Ui.rc[J], Cc.s * Ur.rc[J]);
+    ai[J] = fma(-Sc.s, Ur.rc[J], Cc.s * Ui.rc[J]);
+  }
+  // column border, lane (r, c): sum_K M[4I+c][4K+r] U[4K+r][D-1]; accumulator M[4I+r][D-1] U[D-1][D-1]
+  // corner: sum_I M[D-1][4I+r] U[4I+r][D-1]; accumulator M[D-1][D-1] U[D-1][D-1]
+  double pr[NC], pi[NC], qr[NC], qi[NC];
+  double cr_ = Cc.vr[0] * Ur.cr[0], ci_ = Cc.vr[0] * Ui.cr[0];
 #pragma unroll
   for (int I = 0; I < NC; ++I) {
+    pr[I] = Cc.m[0][I] * Ur.cr[0];
+    pi[I] = Cc.m[0][I] * Ui.cr[0];
 #pragma unroll
-    for (int J = 0; J < NC; ++J) T1[I][J] = T2[I][J] = T3[I][J] = 0.0;
-    R1[I] = R2[I] = R3[I] = 0.0;
+    for (int K = 1; K < NC; ++K) {
+      pr[I] = fma(Cc.m[K][I], Ur.cr[K], pr[I]);
+      pi[I] = fma(Cc.m[K][I], Ui.cr[K], pi[I]);
+    }
+#pragma unroll
+    for (int K = 0; K < NC; ++K) {
+      pr[I] = fma(Sc.m[K][I], Ui.cr[K], pr[I]);
+      pi[I] = fma(-Sc.m[K][I], Ur.cr[K], pi[I]);
+    }
+    qr[I] = fma(Sc.vr[I], Ui.s, Cc.vr[I] * Ur.s);
+    qi[I] = fma(-Sc.vr[I], Ur.s, Cc.vr[I] * Ui.s);
+    if (I > 0) {
+      cr_ = fma(Cc.vr[I], Ur.cr[I], cr_);
+      ci_ = fma(Cc.vr[I], Ui.cr[I], ci_);
+    }
   }
 #pragma unroll
-  for (int K = 0; K < NC; ++K) {
+  for (int I = 0; I < NC; ++I) {
+    cr_ = fma(Sc.vr[I], Ui.cr[I], cr_);
+    ci_ = fma(-Sc.vr[I], Ur.cr[I], ci_);
+  }
+  const double er = fma(Sc.s, Ui.s, Cc.s * Ur.s), ei = fma(-Sc.s, Ur.s, Cc.s * Ui.s);
+  // the matrix instructions: core, then the border reductions straight into the state
+#pragma unroll
+  for (int K = 0; K < NC; ++K)
 #pragma unroll
     for (int I = 0; I < NC; ++I)
 #pragma unroll
       for (int J = 0; J < NC; ++J) {
         T1[I][J] = mfma4(Cc.m[K][I], Ur.m[K][J], T1[I][J]);
         T2[I][J] = mfma4(Sc.m[K][I], Ui.m[K][J], T2[I][J]);
-        T3[I][J] = mfma4(Dm.m[K][I], Us.m[K][J], T3[I][J]);
+        T3[I][J] = mfma4(Dm[K][I], Us[K][J], T3[I][J]);
       }
-    // row border: A tile = the border row of the left operand in every row (vr[K]: lane (r, c) holds M[4K+r][D-1] = M[D-1][4K+r])
-#pragma unroll
-    for (int J = 0; J < NC; ++J) {
-      R1[J] = mfma4(Cc.vr[K], Ur.m[K][J], R1[J]);
-      R2[J] = mfma4(Sc.vr[K], Ui.m[K][J], R2[J]);
-      R3[J] = mfma4(Dm.vr[K], Us.m[K][J], R3[J]);
-    }
-  }
-  // column border and corner: partial products with the sum index on r, the three products combined before the reduction
-  double pr[NC], pi[NC], cr_ = 0.0, ci_ = 0.0;
 #pragma unroll
   for (int I = 0; I < NC; ++I) {
-    double p1 = 0.0, p2 = 0.0, p3 = 0.0;
-#pragma unroll
-    for (int K = 0; K < NC; ++K) {
-      p1 = fma(Cc.m[K][I], Ur.cr[K], p1);
-      p2 = fma(Sc.m[K][I], Ui.cr[K], p2);
-      p3 = fma(Dm.m[K][I], Us.cr[K], p3);
-    }
-    pr[I] = p1 + p2;
-    pi[I] = (p3 - p1) + p2;
-    const double c1 = Cc.vr[I] * Ur.cr[I], c2 = Sc.vr[I] * Ui.cr[I], c3 = Dm.vr[I] * Us.cr[I];
-    cr_ += c1 + c2;
-    ci_ += (c3 - c1) + c2;
+    Ur.rc[I] = mfma4(1.0, tr[I], ar[I]);
+    Ui.rc[I] = mfma4(1.0, ti[I], ai[I]);
+    Ur.cr[I] = mfma4(pr[I], 1.0, qr[I]);
+    Ui.cr[I] = mfma4(pi[I], 1.0, qi[I]);
   }
-  const double e1 = Cc.s * Ur.s, e2 = Sc.s * Ui.s, e3 = Dm.s * Us.s;
-  const double sr = mfma4(cr_, 1.0, e1 + e2), si = mfma4(ci_, 1.0, (e3 - e1) + e2);
-  double colr[NC], coli[NC], rowr[NC], rowi[NC];
-#pragma unroll
-  for (int I = 0; I < NC; ++I) {
-    const double q1 = Cc.vr[I] * Ur.s, q2 = Sc.vr[I] * Ui.s, q3 = Dm.vr[I] * Us.s;
-    colr[I] = mfma4(pr[I], 1.0, q1 + q2);
-    coli[I] = mfma4(pi[I], 1.0, (q3 - q1) + q2);
-    // row border: the k = D-1 term on top of the matrix-core sums (every lane holds the row)
-    const double r1 = fma(Cc.s, Ur.rc[I], R1[I]), r2 = fma(Sc.s, Ui.rc[I], R2[I]), r3 = fma(Dm.s, Us.rc[I], R3[I]);
-    rowr[I] = r1 + r2;
-    rowi[I] = (r3 - r1) + r2;
-  }
+  Ur.s = mfma4(cr_, 1.0, er);
+  Ui.s = mfma4(ci_, 1.0, ei);
 #pragma unroll
   for (int I = 0; I < NC; ++I)
 #pragma unroll
     for (int J = 0; J < NC; ++J) {
-      const double t1 = fma(Cc.vr[I], Ur.rc[J], T1[I][J]), t2 = fma(Sc.vr[I], Ui.rc[J], T2[I][J]), t3 = fma(Dm.vr[I], Us.rc[J], T3[I][J]);
-      Ur.m[I][J] = t1 + t2;
-      Ui.m[I][J] = (t3 - t1) + t2;
+      Ur.m[I][J] = T1[I][J] + T2[I][J];
+      Ui.m[I][J] = (T3[I][J] - T1[I][J]) + T2[I][J];
     }
-#pragma unroll
-  for (int I = 0; I < NC; ++I) {
-    Ur.cr[I] = colr[I];
-    Ui.cr[I] = coli[I];
-    Ur.rc[I] = rowr[I];
-    Ui.rc[I] = rowi[I];
-  }
-  Ur.s = sr;
-  Ui.s = si;
 }
 
 // q = 4 plan: degree 4r, s squarings, from a bound on ||X||_1
