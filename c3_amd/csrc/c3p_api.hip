@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 #include <cstdio>
@@ -449,6 +450,28 @@ void fill_chain(Args& a, const PwcProblem& P, long S) {
   a.S = (int)S;
   a.Lmax = (int)((P.N + S - 1) / S);
 }
+// The same for supplied per-slice generators X_n = coef hs[b,n] (no tables, no signals, K = 0): the chain kernels and the general
+// sweep kernels of both families read them from fields of one name.  `meta`: the hmeta pre-pass (trace shift and norm per matrix).
+struct Supplied {
+  const cplx* hs;
+  long hs_bstride;
+  const double* meta;
+  double coef_r, coef_i;
+  int B, N, Dm;
+};
+template <class Args>
+void fill_supplied(Args& a, const Supplied& X, long S) {
+  a.hs = X.hs;
+  a.hs_bstride = X.hs_bstride;
+  a.meta = X.meta;
+  a.coef_r = X.coef_r;
+  a.coef_i = X.coef_i;
+  a.B = X.B;
+  a.N = X.N;
+  a.Dm = X.Dm;
+  a.S = (int)S;
+  a.Lmax = (int)((X.N + S - 1) / S);
+}
 
 // ordered combine of `count` matrices per sample (cur: [B,count,Dm,Dm]) into U_out on the supplied-matrix mode of a chain kernel
 // (launch: c3p_launch_smalld_chain at Dm <= 12, c3p_launch_midd_chain at 13 <= Dm <= 40)
@@ -769,17 +792,7 @@ int run_xg_midd(DeviceWs* w, const cplx* hs, long hs_bstride, double coef_r, dou
   if (ws_get(w, SL_TABLES, (size_t)B * N * 4 * sizeof(double), &mv)) return -1;
   LAUNCH_TRY(c3p_launch_hmeta(hs, hs_bstride, (long)B * N, N, D, coef_r, coef_i, (double*)mv, st));
   MidArgs a = {};
-  a.hs = hs;
-  a.hs_bstride = hs_bstride;
-  a.meta = (const double*)mv;
-  a.coef_r = coef_r;
-  a.coef_i = coef_i;
-  a.B = B;
-  a.K = 0;
-  a.N = N;
-  a.Dm = D;
-  a.S = (int)S;
-  a.Lmax = (int)((N + S - 1) / S);
+  fill_supplied(a, Supplied{hs, hs_bstride, (const double*)mv, coef_r, coef_i, B, N, D}, S);
   a.mode = C3P_MODE_EXPM;
   a.dUs_out = dUs_out;
   a.no_t18 = c3p_opt_on(C3P_OPT_no_t18) ? 1 : 0;
@@ -812,17 +825,7 @@ int run_xg_smalld(DeviceWs* w, const cplx* hs, long hs_bstride, double coef_r, d
   LAUNCH_TRY(c3p_launch_hmeta(hs, hs_bstride, (long)B * N, N, D, coef_r, coef_i, (double*)mv, st));
   SmallArgs a = {};
   a.no_t18n = opt_no_t18n();
-  a.hs = hs;
-  a.hs_bstride = hs_bstride;
-  a.meta = (const double*)mv;
-  a.coef_r = coef_r;
-  a.coef_i = coef_i;
-  a.B = B;
-  a.K = 0;
-  a.N = N;
-  a.Dm = D;
-  a.S = S;
-  a.Lmax = (N + S - 1) / S;
+  fill_supplied(a, Supplied{hs, hs_bstride, (const double*)mv, coef_r, coef_i, B, N, D}, S);
   a.mode = C3P_MODE_EXPM;
   a.dUs_out = dUs_out;
   const bool fuse = (S > 1) && (S % 4 == 0) && !c3p_opt_on(C3P_OPT_no_fuse);
@@ -932,6 +935,53 @@ int run_vjp_smalld(DeviceWs* w, GradArgs& G, hipStream_t st) {
   return 0;
 }
 
+// ---- the general-generator sweep: forward chain kernel (segment products + slice propagators), general scan of c3p_grad.hip
+// (prefix at the start, left adjoint at the end of every segment), backward sweep kernel.  What its four users share: ----
+// the store between the kernels, one block of Dm x Dm matrices: pre [B,S] | dUs [B,N] (with_dus: the forward chain of this call
+// writes the slice propagators here; a taped sweep reads them from the tape) | pstore [B,N]
+struct SweepStore {
+  cplx *pre, *dUs, *pstore;
+};
+int get_sweep_store(DeviceWs* w, Slot slot, int B, long S, int N, int Dm, bool with_dus, SweepStore* s) {
+  const size_t msz = (size_t)Dm * Dm;
+  void* v;
+  if (ws_get(w, slot, ((size_t)B * S + (with_dus ? 2 : 1) * (size_t)B * N) * msz * sizeof(cplx), &v)) return -1;
+  s->pre = (cplx*)v;
+  s->dUs = with_dus ? s->pre + (size_t)B * S * msz : nullptr;
+  s->pstore = s->pre + ((size_t)B * S + (with_dus ? (size_t)B * N : 0)) * msz;
+  return 0;
+}
+// the scan's record: segment products in, left adjoints (Mb) and prefixes (pre) out
+void fill_general_scan(GradArgs& G, int B, int K, int N, int Dm, long S, cplx* seg, cplx* Mb, cplx* pre, const cplx* Ubar,
+                       const double* fr_phase) {
+  G.Ubar = Ubar;
+  G.fr_phase = fr_phase;
+  G.B = B;
+  G.K = K;
+  G.N = N;
+  G.D = Dm;
+  G.ld = Dm | 1;
+  G.S = (int)S;
+  G.seg = seg;
+  G.Mb = Mb;
+  G.pre = pre;
+  G.general = 1;
+}
+int general_scan(int B, int K, int N, int Dm, long S, cplx* seg, cplx* Mb, cplx* pre, const cplx* Ubar, const double* fr_phase,
+                 hipStream_t st) {
+  GradArgs G = {};
+  fill_general_scan(G, B, K, N, Dm, S, seg, Mb, pre, Ubar, fr_phase);
+  LAUNCH_TRY(c3p_launch_grad_scan_general(G, false, st));
+  return 0;
+}
+// segments of the mid-D general sweep (one workgroup per CU: two to four rounds), before the LDS rule of the caller
+long midd_grad_segments(int B, int N, int Dm) {
+  long S = ((Dm <= 32 ? 1024 : 512) + B - 1) / B;
+  const long smax = N / 8 > 1 ? N / 8 : 1;
+  if (S > smax) S = smax;
+  return S < 1 ? 1 : S;
+}
+
 // Lindblad gradient on the small-D MFMA kernels (superoperators up to 12 x 12, D <= 3), general-generator form: slice
 // propagators + segment products from the forward chain kernel, the general scan of c3p_grad.hip (prefix at the start, left
 // adjoint at the end of every segment), then smalld_grad_general_kernel.  In two halves around a block of memory that holds
@@ -1021,34 +1071,19 @@ int lind_small_backward(DeviceWs* w, const LindSmallBufs& bf, const PwcProblem& 
   const int B = P.B, K = P.K, N = P.N, Dm = P.Dm;
   const int nsamp = P.nsamp();
   const size_t tdoubles = (size_t)nsamp * c3p_smalld_table_doubles(Dm, K);
-  const size_t msz = (size_t)Dm * Dm * sizeof(cplx);
-  void *mv, *bv;
-  if (ws_get(w, SL_SEG_B, (size_t)B * S * msz, &mv)) return -1;
-  if (ws_get(w, SL_SEG_A, ((size_t)B * S + (size_t)B * N) * msz, &bv)) return -1;  // (SL_OUT0 stages grad_signals, SL_OUT1 is the untaped block)
-  cplx* pre = (cplx*)bv;
-  cplx* pstore = pre + (size_t)B * S * Dm * Dm;
-  GradArgs G = {};
-  G.Ubar = Ubar;
-  G.fr_phase = P.fr_phase;
-  G.B = B;
-  G.K = K;
-  G.N = N;
-  G.D = Dm;
-  G.ld = Dm | 1;
-  G.S = S;
-  G.seg = bf.seg;
-  G.Mb = (cplx*)mv;
-  G.pre = pre;
-  G.general = 1;
-  LAUNCH_TRY(c3p_launch_grad_scan_general(G, false, st));
+  void* mv;
+  SweepStore ss;
+  if (ws_get(w, SL_SEG_B, (size_t)B * S * Dm * Dm * sizeof(cplx), &mv)) return -1;
+  if (get_sweep_store(w, SL_SEG_A, B, S, N, Dm, false, &ss)) return -1;  // (SL_OUT0 stages grad_signals, SL_OUT1 is the untaped block)
+  if (general_scan(B, K, N, Dm, S, bf.seg, (cplx*)mv, ss.pre, Ubar, P.fr_phase, st)) return -1;
   SmallGradArgs g = {};
   g.tables = bf.tabs;
   g.tables_h = bf.tabs + tdoubles;
   fill_chain(g, P, S);
-  g.Mb = G.Mb;
-  g.pre = pre;
+  g.Mb = (cplx*)mv;
+  g.pre = ss.pre;
   g.dUs = bf.dus;
-  g.pstore = pstore;
+  g.pstore = ss.pstore;
   g.grad = grad;
   LAUNCH_TRY(c3p_launch_smalld_grad_general(g, st));
   return 0;
@@ -1085,7 +1120,11 @@ bool lind_smallr_ok(bool hermitian, int D, int Dm, int K, int N, int S) {
   return hermitian && c3p_smallr_supported(D, Dm, K) && !c3p_opt_on(C3P_OPT_no_smallr) &&
          c3p_smallr_lds_bytes(Dm, K, (N + S - 1) / S) <= (size_t)60 * 1024 && c3p_smallr_grad_lds_bytes(Dm, K, (N + S - 1) / S) <= (size_t)60 * 1024;
 }
-// forward half; seg_complex (workspace, [B,S,Dm,Dm]) receives the segment products in the reference's vectorisation for U
+// forward half; seg_complex (workspace, [B,S,Dm,Dm]) receives the segment products in the reference's vectorisation for U.
+// Not one function with the Hermitian sub-branch of lind_small_forward, alike as they look: that one builds ONE real table set in
+// SL_TABLES (c3p_launch_smallr_prep, a workspace request) beside the two complex sets and stores complex matrices for the complex
+// sweep; this one builds the table PAIR in the tape (c3p_launch_smallr_prep_pair, no request) and stores real ones.  Merged, one
+// of the two would change its launch log or its workspace requests.
 int lind_smallr_forward(const LindSmallRBufs& bf, const PwcProblem& P, int S, cplx* seg_complex, hipStream_t st) {
   LAUNCH_TRY(c3p_launch_smallr_prep_pair(regd_prep_args(P), P.nsamp(), bf.tabs, bf.tabs_t, bf.flags, st));
   SmallRArgs ra = {};
@@ -1120,38 +1159,34 @@ int lind_smallr_backward(DeviceWs* w, const LindSmallRBufs& bf, const PwcProblem
   return 0;
 }
 
-// two qubits (16 x 16 superoperators), declared Hermitian: both halves on the real kernels; 1 = not applicable
-int run_vjp_lind_smallr16(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double* grad, hipStream_t st) {
-  const int B = P.B, K = P.K, N = P.N, D = P.D, Dm = P.Dm;
-  const int S = pick_segments_r(B, N, K, Dm, P.per_sample(), true);
-  if (S < 0 || !lind_smallr_ok(true, D, Dm, K, N, S)) return 1;
+// Both halves on the real kernels (declared Hermitian Hamiltonians) on S segments, around `block_bytes` of SL_OUT1: the block of
+// the real layout at 16 x 16, the larger block of the complex halves at D <= 3 (one request per shape, Hermitian or not).
+int run_vjp_lind_real(DeviceWs* w, const PwcProblem& P, int S, size_t block_bytes, const cplx* Ubar, double* grad, hipStream_t st) {
+  const int B = P.B, K = P.K, N = P.N, Dm = P.Dm;
   const int nsamp = P.nsamp();
-  const LindSmallSizes zr = lind_smallr_sizes(B, K, N, Dm, S, nsamp);
   void *blk, *sc;
-  if (ws_get(w, SL_OUT1, zr.total(), &blk)) return -1;
-  if (ws_get(w, SL_OUT2, (size_t)B * S * Dm * Dm * sizeof(cplx), &sc)) return -1;
-  const LindSmallRBufs rb = lind_smallr_carve(blk, zr, nsamp, Dm, K);
+  if (ws_get(w, SL_OUT1, block_bytes, &blk)) return -1;
+  if (ws_get(w, SL_OUT2, (size_t)B * S * Dm * Dm * sizeof(cplx), &sc)) return -1;  // (the complex segment products: not needed here)
+  const LindSmallRBufs rb = lind_smallr_carve(blk, lind_smallr_sizes(B, K, N, Dm, S, nsamp), nsamp, Dm, K);
   if (lind_smallr_forward(rb, P, S, (cplx*)sc, st)) return -1;
   return lind_smallr_backward(w, rb, P, S, Ubar, grad, st) ? -1 : 0;
+}
+// two qubits (16 x 16 superoperators), declared Hermitian; 1 = not applicable
+int run_vjp_lind_smallr16(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double* grad, hipStream_t st) {
+  const int S = pick_segments_r(P.B, P.N, P.K, P.Dm, P.per_sample(), true);
+  if (S < 0 || !lind_smallr_ok(true, P.D, P.Dm, P.K, P.N, S)) return 1;
+  return run_vjp_lind_real(w, P, S, lind_smallr_sizes(P.B, P.K, P.N, P.Dm, S, P.nsamp()).total(), Ubar, grad, st);
 }
 
 // Returns 1 when not applicable.
 int run_vjp_lind_smalld(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double* grad, bool hermitian, hipStream_t st) {
   const int B = P.B, K = P.K, N = P.N, D = P.D, Dm = P.Dm;
-  const int nsamp = P.nsamp();
   const int S = lind_small_segments(B, K, N, Dm, P.per_sample());
   if (S < 0) return 1;
-  const LindSmallSizes z = lind_small_sizes(B, K, N, Dm, S, nsamp);
+  const LindSmallSizes z = lind_small_sizes(B, K, N, Dm, S, P.nsamp());
+  if (lind_smallr_ok(hermitian, D, Dm, K, N, S)) return run_vjp_lind_real(w, P, S, z.total(), Ubar, grad, st);
   void* blk;
   if (ws_get(w, SL_OUT1, z.total(), &blk)) return -1;
-  if (lind_smallr_ok(hermitian, D, Dm, K, N, S)) {
-    const LindSmallSizes zr = lind_smallr_sizes(B, K, N, Dm, S, nsamp);
-    const LindSmallRBufs rb = lind_smallr_carve(blk, zr, nsamp, Dm, K);
-    void* sc;
-    if (ws_get(w, SL_OUT2, (size_t)B * S * Dm * Dm * sizeof(cplx), &sc)) return -1;  // (the complex segment products: not needed here)
-    if (lind_smallr_forward(rb, P, S, (cplx*)sc, st)) return -1;
-    return lind_smallr_backward(w, rb, P, S, Ubar, grad, st) ? -1 : 0;
-  }
   const LindSmallBufs bf = lind_small_carve(blk, z);
   if (lind_small_forward(w, bf, P, S, hermitian, st)) return -1;
   return lind_small_backward(w, bf, P, S, Ubar, grad, st) ? -1 : 0;
@@ -1209,10 +1244,7 @@ int run_vjp_lind_midd(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double
   int nig, nj, wd;
   if (!c3p_midd_geometry(Dm, &nig, &nj, &wd) || K > 16) return 1;
   if (!((nig == 2 && nj == 4) || (nig == 4 && nj == 7) || (nig == 5 && nj == 9))) return 1;
-  long S = ((Dm <= 32 ? 1024 : 512) + B - 1) / B;  // one workgroup per CU: two to four rounds
-  const long smax = N / 8 > 1 ? N / 8 : 1;
-  if (S > smax) S = smax;
-  if (S < 1) S = 1;
+  long S = midd_grad_segments(B, N, Dm);
   auto lds_need = [&](long s) { return c3p_midd_grad_image_bytes(Dm) + (size_t)K * ((N + s - 1) / s) * sizeof(double); };
   while (lds_need(S) > (size_t)150 * 1024 && S < N) ++S;
   if (lds_need(S) > (size_t)150 * 1024) return 1;
@@ -1228,45 +1260,30 @@ int run_vjp_lind_midd(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double
   p.tables = tabs + tdoubles;
   LAUNCH_TRY(c3p_launch_midd_prep(p, nsamp, st));
   const size_t msz = (size_t)Dm * Dm * sizeof(cplx);
-  void *sv, *mv, *bv;
+  void *sv, *mv;
+  SweepStore ss;
   if (ws_get(w, SL_SEG_A, (size_t)B * S * msz, &sv)) return -1;
   if (ws_get(w, SL_SEG_B, (size_t)B * S * msz, &mv)) return -1;
-  if (ws_get(w, SL_OUT1, ((size_t)B * S + 2 * (size_t)B * N) * msz, &bv)) return -1;  // (SL_OUT0 stages grad_signals)
-  cplx* pre = (cplx*)bv;
-  cplx* dUs = pre + (size_t)B * S * Dm * Dm;
-  cplx* pstore = dUs + (size_t)B * N * Dm * Dm;
+  if (get_sweep_store(w, SL_OUT1, B, S, N, Dm, true, &ss)) return -1;  // (SL_OUT0 stages grad_signals)
   MidArgs a = {};
   a.tables = tabs;
   fill_chain(a, P, S);
   a.mode = C3P_MODE_LINDBLAD;
   a.seg_out = (cplx*)sv;
-  a.dUs_out = dUs;
+  a.dUs_out = ss.dUs;
   a.no_t18 = c3p_opt_on(C3P_OPT_no_t18) ? 1 : 0;
   a.no_t18n = opt_no_t18n();
   a.no_real = 1;
   LAUNCH_TRY(c3p_launch_midd_chain(a, st));
-  GradArgs G = {};
-  G.Ubar = Ubar;
-  G.fr_phase = P.fr_phase;
-  G.B = B;
-  G.K = K;
-  G.N = N;
-  G.D = Dm;
-  G.ld = Dm | 1;
-  G.S = (int)S;
-  G.seg = (cplx*)sv;
-  G.Mb = (cplx*)mv;
-  G.pre = pre;
-  G.general = 1;
-  LAUNCH_TRY(c3p_launch_grad_scan_general(G, false, st));
+  if (general_scan(B, K, N, Dm, S, (cplx*)sv, (cplx*)mv, ss.pre, Ubar, P.fr_phase, st)) return -1;
   MidGradArgs g = {};
   g.tables = tabs;
   g.tables_h = tabs + tdoubles;
   fill_chain(g, P, S);
-  g.Mb = G.Mb;
-  g.pre = pre;
-  g.dUs = dUs;
-  g.pstore = pstore;
+  g.Mb = (cplx*)mv;
+  g.pre = ss.pre;
+  g.dUs = ss.dUs;
+  g.pstore = ss.pstore;
   g.grad = grad;
   LAUNCH_TRY(c3p_launch_midd_grad_general(g, st));
   return 0;
@@ -1276,121 +1293,53 @@ int run_vjp_lind_midd(DeviceWs* w, const PwcProblem& P, const cplx* Ubar, double
 // on-chip general-generator sweeps (D <= 40): hmeta pre-pass, forward chain kernel in its supplied-generator mode (segment
 // products + slice propagators), general scan, then the small-D / mid-D sweep kernel in its supplied-generator mode.
 // Nothing is assumed about the generators.  Returns 1 when not applicable.
-int run_vjp_xg_general(DeviceWs* w, const cplx* hs, long hs_bstride, double coef_r, double coef_i, int B, int N, int D,
-                       const double* fr_phase, const cplx* Ubar, cplx* zout, hipStream_t st) {
-  const bool small = D <= kSmallDLimit && c3p_smalld_supported(D);
-  int nig = 0, nj = 0, wd = 0;
-  if (!small && !c3p_midd_geometry(D, &nig, &nj, &wd)) return 1;
-  long S;
-  if (small) {
-    S = pick_segments(B, N, 0, D, false, 4096);
-    if (S < 0) return 1;
-  } else {
-    S = ((D <= 32 ? 1024 : 512) + B - 1) / B;
-    const long smax = N / 8 > 1 ? N / 8 : 1;
-    if (S > smax) S = smax;
-    if (S < 1) S = 1;
-    if (c3p_midd_grad_image_bytes(D) > (size_t)150 * 1024) return 1;
-  }
-  void *mv, *sv, *bv, *av;
+template <class Chain, class Grad>
+int xg_general_sweep(DeviceWs* w, hipError_t (*chain)(const Chain&, hipStream_t), hipError_t (*sweep)(const Grad&, hipStream_t), Chain a,
+                     Supplied X, long S, const double* fr_phase, const cplx* Ubar, cplx* zout, hipStream_t st) {
+  const int B = X.B, N = X.N, D = X.Dm;
+  void *mv, *sv, *av;
+  SweepStore ss;
   if (ws_get(w, SL_TABLES, (size_t)B * N * 4 * sizeof(double), &mv)) return -1;
   const size_t msz = (size_t)D * D * sizeof(cplx);
   if (ws_get(w, SL_SEG_A, (size_t)B * S * msz, &sv)) return -1;
   if (ws_get(w, SL_SEG_B, (size_t)B * S * msz, &av)) return -1;
-  if (ws_get(w, SL_OUT1, ((size_t)B * S + 2 * (size_t)B * N) * msz, &bv)) return -1;  // (SL_OUT0 stages gen_bar_out)
-  cplx* pre = (cplx*)bv;
-  cplx* dUs = pre + (size_t)B * S * D * D;
-  cplx* pstore = dUs + (size_t)B * N * D * D;
-  LAUNCH_TRY(c3p_launch_hmeta(hs, hs_bstride, (long)B * N, N, D, coef_r, coef_i, (double*)mv, st));
-  const int Lmax = (int)((N + S - 1) / S);
-  if (small) {
+  if (get_sweep_store(w, SL_OUT1, B, S, N, D, true, &ss)) return -1;  // (SL_OUT0 stages gen_bar_out)
+  LAUNCH_TRY(c3p_launch_hmeta(X.hs, X.hs_bstride, (long)B * N, N, D, X.coef_r, X.coef_i, (double*)mv, st));
+  X.meta = (const double*)mv;
+  fill_supplied(a, X, S);
+  a.mode = C3P_MODE_EXPM;
+  a.seg_out = (cplx*)sv;
+  a.dUs_out = ss.dUs;
+  LAUNCH_TRY(chain(a, st));
+  if (general_scan(B, 0, N, D, S, (cplx*)sv, (cplx*)av, ss.pre, Ubar, fr_phase, st)) return -1;
+  Grad g = {};
+  fill_supplied(g, X, S);
+  g.Mb = (cplx*)av;
+  g.pre = ss.pre;
+  g.dUs = ss.dUs;
+  g.pstore = ss.pstore;
+  g.zout = zout;
+  LAUNCH_TRY(sweep(g, st));
+  return 0;
+}
+int run_vjp_xg_general(DeviceWs* w, const cplx* hs, long hs_bstride, double coef_r, double coef_i, int B, int N, int D,
+                       const double* fr_phase, const cplx* Ubar, cplx* zout, hipStream_t st) {
+  const Supplied X = {hs, hs_bstride, nullptr, coef_r, coef_i, B, N, D};  // (meta: the sweep's hmeta pre-pass)
+  if (D <= kSmallDLimit && c3p_smalld_supported(D)) {
+    const int S = pick_segments(B, N, 0, D, false, 4096);
+    if (S < 0) return 1;
     SmallArgs a = {};
     a.no_t18n = opt_no_t18n();
-    a.hs = hs;
-    a.hs_bstride = hs_bstride;
-    a.meta = (const double*)mv;
-    a.coef_r = coef_r;
-    a.coef_i = coef_i;
-    a.B = B;
-    a.N = N;
-    a.Dm = D;
-    a.S = (int)S;
-    a.Lmax = Lmax;
-    a.mode = C3P_MODE_EXPM;
-    a.seg_out = (cplx*)sv;
-    a.dUs_out = dUs;
-    LAUNCH_TRY(c3p_launch_smalld_chain(a, st));
-  } else {
-    MidArgs a = {};
-    a.hs = hs;
-    a.hs_bstride = hs_bstride;
-    a.meta = (const double*)mv;
-    a.coef_r = coef_r;
-    a.coef_i = coef_i;
-    a.B = B;
-    a.N = N;
-    a.Dm = D;
-    a.S = (int)S;
-    a.Lmax = Lmax;
-    a.mode = C3P_MODE_EXPM;
-    a.seg_out = (cplx*)sv;
-    a.dUs_out = dUs;
-    a.no_t18 = c3p_opt_on(C3P_OPT_no_t18) ? 1 : 0;
-    a.no_t18n = opt_no_t18n();
-    a.no_real = 1;
-    LAUNCH_TRY(c3p_launch_midd_chain(a, st));
+    return xg_general_sweep(w, c3p_launch_smalld_chain, c3p_launch_smalld_grad_general, a, X, S, fr_phase, Ubar, zout, st);
   }
-  GradArgs G = {};
-  G.Ubar = Ubar;
-  G.fr_phase = fr_phase;
-  G.B = B;
-  G.N = N;
-  G.D = D;
-  G.ld = D | 1;
-  G.S = (int)S;
-  G.seg = (cplx*)sv;
-  G.Mb = (cplx*)av;
-  G.pre = pre;
-  G.general = 1;
-  LAUNCH_TRY(c3p_launch_grad_scan_general(G, false, st));
-  if (small) {
-    SmallGradArgs g = {};
-    g.Mb = G.Mb;
-    g.pre = pre;
-    g.dUs = dUs;
-    g.pstore = pstore;
-    g.zout = zout;
-    g.hs = hs;
-    g.hs_bstride = hs_bstride;
-    g.meta = (const double*)mv;
-    g.coef_r = coef_r;
-    g.coef_i = coef_i;
-    g.B = B;
-    g.N = N;
-    g.Dm = D;
-    g.S = (int)S;
-    g.Lmax = Lmax;
-    LAUNCH_TRY(c3p_launch_smalld_grad_general(g, st));
-  } else {
-    MidGradArgs g = {};
-    g.Mb = G.Mb;
-    g.pre = pre;
-    g.dUs = dUs;
-    g.pstore = pstore;
-    g.zout = zout;
-    g.hs = hs;
-    g.hs_bstride = hs_bstride;
-    g.meta = (const double*)mv;
-    g.coef_r = coef_r;
-    g.coef_i = coef_i;
-    g.B = B;
-    g.N = N;
-    g.Dm = D;
-    g.S = (int)S;
-    g.Lmax = Lmax;
-    LAUNCH_TRY(c3p_launch_midd_grad_general(g, st));
-  }
-  return 0;
+  int nig = 0, nj = 0, wd = 0;
+  if (!c3p_midd_geometry(D, &nig, &nj, &wd)) return 1;
+  if (c3p_midd_grad_image_bytes(D) > (size_t)150 * 1024) return 1;
+  MidArgs a = {};
+  a.no_t18 = c3p_opt_on(C3P_OPT_no_t18) ? 1 : 0;
+  a.no_t18n = opt_no_t18n();
+  a.no_real = 1;
+  return xg_general_sweep(w, c3p_launch_midd_chain, c3p_launch_midd_grad_general, a, X, midd_grad_segments(B, N, D), fr_phase, Ubar, zout, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -1830,6 +1779,131 @@ int build_clp(DeviceWs* w, const void* d_col, int C, int D, int B, int flags, co
   *clp = (const cplx*)v;
   *bs = (flags & C3P_COL_PER_SAMPLE) ? gsz : 0;
   return 0;
+}
+
+// One open-system gradient call (c3p_pwc_lindblad_vjp and the two model-cotangent entries) between its argument checks and its
+// result: the workspace lock, the staged operands, the dissipator, the problem record and, for the model entries, where the operator
+// cotangents go.  open() once, kernel families over the sample chunks, served(kernel) once.
+struct LindGradCall {
+  std::optional<WsLock> lk;
+  DeviceWs* w = nullptr;
+  hipStream_t st = nullptr;
+  Stage sg{nullptr, nullptr};
+  int flags = 0;
+  PwcProblem P = {};
+  const cplx* ubar = nullptr;  // [B,Dm,Dm]
+  double* grad = nullptr;      // [B,K,N]
+  LindModelOut mo = {};        // want_model only
+
+  // The checks every entry makes (`own`: the entry's extra ones, in their place), then lock, staging, dissipator and records.
+  // 0 = go on, 1 = nothing to do (B = 0), -1 = error.  grad_signals may be NULL for a model entry (the sweep then writes into SL_OUT0).
+  template <class Own>
+  int open(const char* entry, int bad_flags, bool want_model, Own&& own, const void* h0, int64_t h0_bstride, const void* hks,
+           int64_t hks_bstride, const double* signals, const void* col_ops, int C, double dt, int B, int K, int N, int D, int flags_,
+           const double* fr_phase, const void* U_bar, double* grad_signals, void* grad_h0, void* grad_hks, void* grad_col_ops, void* stream) {
+    if (B < 0 || K <= 0 || N <= 0 || D <= 0 || C <= 0) return fail("bad sizes B=%d K=%d N=%d D=%d C=%d", B, K, N, D, C);
+    if (flags_ & bad_flags) return fail("%s: unsupported flag", entry);
+    if (own()) return -1;
+    if (B == 0) return 1;
+    if (!h0 || !hks || !signals || !col_ops || !U_bar || (want_model ? !grad_h0 || !grad_hks || !grad_col_ops : !grad_signals))
+      return fail("NULL pointer argument");
+    if (h0_bstride < 0 || hks_bstride < 0) return fail("negative batch stride");
+    const size_t cs = sizeof(cplx);
+    const int Dm = D * D;
+    flags = flags_;
+    st = (hipStream_t)stream;
+    lk.emplace(st);
+    w = lk->w;
+    if (!w) return fail("no HIP device");
+    if (!lk->ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+    sg.w = w, sg.st = st;
+    const void *d_h0 = h0, *d_hks = hks, *d_sig = signals, *d_ph = fr_phase, *d_ub = U_bar, *d_col = col_ops;
+    void* d_grad = grad_signals;
+    cplx *g_h0 = (cplx*)grad_h0, *g_hks = (cplx*)grad_hks, *g_col = (cplx*)grad_col_ops;
+    if (flags & C3P_HOST_PTRS) {
+      if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)D * D) * cs, &d_h0)) return -1;
+      if (sg.in(hks, staged_elems(B, hks_bstride, (size_t)K * D * D) * cs, &d_hks)) return -1;
+      if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
+      if (sg.in(col_ops, col_elems(flags, B, C, D) * cs, &d_col)) return -1;
+      if (sg.in(U_bar, (size_t)B * Dm * Dm * cs, &d_ub)) return -1;
+      if (fr_phase && sg.in(fr_phase, (size_t)B * Dm * sizeof(double), &d_ph)) return -1;
+      if (sg.out(grad_signals, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;  // SL_OUT0 (SL_OUT1 is the sweep's store)
+      if (want_model) {  // the three operator cotangents are staged in one block of their own
+        void* blk;
+        const size_t n0 = (size_t)B * D * D, nk = (size_t)B * K * D * D, nc = (size_t)B * C * D * D;
+        if (ws_get(w, SL_LMODEL_OUT, (n0 + nk + nc) * cs, &blk)) return -1;
+        g_h0 = (cplx*)blk, g_hks = g_h0 + n0, g_col = g_hks + nk;
+        sg.backs.push_back({grad_h0, g_h0, n0 * cs});
+        sg.backs.push_back({grad_hks, g_hks, nk * cs});
+        sg.backs.push_back({grad_col_ops, g_col, nc * cs});
+      }
+    }
+    if (!d_grad) {  // grad_signals not wanted: the sweep still writes it
+      if (ws_get(w, SL_OUT0, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
+    }
+    const cplx* clp;
+    long clp_bs;
+    if (build_clp(w, d_col, C, D, B, flags, &clp, &clp_bs, st)) return -1;
+    P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, clp, clp_bs, dt, B, K, N, D, Dm, 1, (const double*)d_ph};
+    ubar = (const cplx*)d_ub;
+    grad = (double*)d_grad;
+    if (want_model) mo = {(const cplx*)d_col, col_bstride(flags, C, D), C, g_h0, g_hks, g_col};
+    return 0;
+  }
+  // the switches that take a call off the on-chip sweeps
+  bool on_chip() const { return !(flags & C3P_FORCE_GENERIC) && !c3p_opt_on(C3P_OPT_tiled_grad) && !c3p_opt_on(C3P_OPT_valu_grad); }
+  // One kernel family over the call, from the start of the timed span: run(chunk, U_bar, grad_signals, b0) on chunks of samples that
+  // keep `bytes_per_sample` of forward intermediates below the budget (grad_chunk_samples), until one does not return 0; what that
+  // one returned (1 = the family declined: go on to the next, -1 = error), else 0.
+  template <class Run>
+  int chunks(size_t bytes_per_sample, Run&& run) {
+    if (record_start(w, st)) return -1;
+    return in_chunks(P.B, grad_chunk_samples(w, bytes_per_sample),
+                     [&](long b0, int nb) { return run(P.chunk(b0, nb), ubar_at(P, ubar, b0), grad_at(P, grad, b0), b0); });
+  }
+  // the same, through to the result of the call where the family served it: 0 / -1, or 1 = declined
+  template <class Run>
+  int family(size_t bytes_per_sample, int kernel, Run&& run) {
+    const int rc = chunks(bytes_per_sample, run);
+    return rc == 0 ? served(kernel) : rc;
+  }
+  // a family served the call: the kernel it reports, the end of the timed span, the staged results back
+  int served(int kernel) {
+    g_last_kernel = kernel;
+    if (record_stop(w, st)) return -1;
+    if (flags & C3P_HOST_PTRS) return sg.finish();
+    return 0;
+  }
+};
+
+// The plan of a taped open-system evaluation for (B, K, N, D): kernel family, segment count, tape size.  Host arithmetic on the
+// option table as it is now; c3p_pwc_lindblad_tape_bytes reports it, both taped calls check the caller's tape against it.
+enum TapeFamily {
+  TAPE_NONE = 0,
+  TAPE_SMALL,   // D = 2, 3: the small-D kernels; real or complex layout by C3P_HERMITIAN_H (lind_smallr_ok), the complex size
+  TAPE_REAL16,  // D = 4: the real Hermitian-basis kernels only (the taped calls then need C3P_HERMITIAN_H)
+  TAPE_REGR     // D = 7, 8, 9: the Hermitian-basis kernels of c3p_regr.hip
+};
+struct LindTapePlan {
+  TapeFamily family;
+  int segments;
+  size_t bytes;
+};
+LindTapePlan lind_tape_plan(int B, int K, int N, int D) {
+  const LindTapePlan none = {TAPE_NONE, 0, 0};
+  if (B > 0 && K >= 1 && K <= 8 && N > 0 && D == 4) {
+    const int S = c3p_opt_on(C3P_OPT_no_smallr) ? -1 : pick_segments_r(B, N, K, 16, true, true);
+    return S > 0 ? LindTapePlan{TAPE_REAL16, S, lind_smallr_sizes(B, K, N, 16, S, B).total()} : none;
+  }
+  if (B > 0 && K >= 1 && K <= 8 && N > 0 && D >= 2 && D <= 3) {
+    // superoperators up to 9 x 9 on the small-D kernels: tables, segment products and the slice propagators (the generator is
+    // not anti-Hermitian: the backward sweep cannot recompute prefixes from the adjoint side); per-sample operators need S % 4 = 0
+    const int S = lind_small_segments(B, K, N, D * D, true);
+    return S > 0 ? LindTapePlan{TAPE_SMALL, S, lind_small_sizes(B, K, N, D * D, S, B).total()} : none;
+  }
+  if (B <= 0 || K < 1 || N <= 0 || D <= 0 || !c3p_regr_supported(D, D * D) || K > 16) return none;
+  const long S = lind_regr_segments(B, N);
+  return {TAPE_REGR, (int)S, lind_regr_sizes(B, K, N, D * D, S, B).total()};
 }
 
 int pwc_common(int lindblad, const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride,
@@ -2808,28 +2882,18 @@ static int run_vjp_lind_valu(DeviceWs* w, const PwcProblem& P, const cplx* ub, d
   A.hks = (const cplx*)tab + gsz;
   A.hks_bstride = A.h0_bstride;
   A.signals = P.signals;
-  A.fr_phase = P.fr_phase;
-  A.Ubar = ub;
   A.dt = P.dt;
-  A.B = nb;
-  A.K = K;
-  A.N = N;
-  A.D = Dm;
-  A.ld = Dm | 1;
   A.grad = grad;
-  A.general = 1;
   long S = 4096 / nb;
   if (S > N / 8) S = N / 8;
   if (S < 1) S = 1;
-  A.S = (int)S;
-  void* v;
-  if (ws_get(w, SL_SEG_A, (size_t)nb * A.S * gsz * cs, &v)) return -1;
-  A.seg = (cplx*)v;
-  if (ws_get(w, SL_SEG_B, (size_t)nb * A.S * gsz * cs, &v)) return -1;
-  A.Mb = (cplx*)v;
-  if (ws_get(w, SL_OUT1, ((size_t)nb * A.S + (size_t)nb * N) * gsz * cs, &v)) return -1;  // (SL_OUT0 stages grad_signals)
-  A.pre = (cplx*)v;
-  A.pstore = A.pre + (size_t)nb * A.S * gsz;
+  void *sv, *mv, *v;
+  SweepStore ss;
+  if (ws_get(w, SL_SEG_A, (size_t)nb * S * gsz * cs, &sv)) return -1;
+  if (ws_get(w, SL_SEG_B, (size_t)nb * S * gsz * cs, &mv)) return -1;
+  if (get_sweep_store(w, SL_OUT1, nb, S, N, Dm, false, &ss)) return -1;  // (SL_OUT0 stages grad_signals)
+  fill_general_scan(A, nb, K, N, Dm, S, (cplx*)sv, (cplx*)mv, ss.pre, ub, P.fr_phase);
+  A.pstore = ss.pstore;
   const bool global = c3p_grad_lds_bytes_general(Dm) > 150 * 1024;
   *global_out = global;
   if (global) {
@@ -2856,174 +2920,90 @@ static int run_vjp_lind_valu(DeviceWs* w, const PwcProblem& P, const cplx* ub, d
 int c3p_pwc_lindblad_vjp(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
                          const void* col_ops, int C, double dt, int B, int K, int N, int D, int flags, const double* fr_phase,
                          const void* U_bar, double* grad_signals, void* stream) {
-  if (B < 0 || K <= 0 || N <= 0 || D <= 0 || C <= 0) return fail("bad sizes B=%d K=%d N=%d D=%d C=%d", B, K, N, D, C);
-  if (flags & (C3P_PER_SLICE_H | C3P_ORDER_RIGHT)) return fail("c3p_pwc_lindblad_vjp: unsupported flag");
-  if (B == 0) return 0;
-  if (!h0 || !hks || !signals || !col_ops || !U_bar || !grad_signals) return fail("NULL pointer argument");
-  if (h0_bstride < 0 || hks_bstride < 0) return fail("negative batch stride");
-  const size_t cs = sizeof(cplx);
-  const int Dm = D * D;
-  hipStream_t st = (hipStream_t)stream;
-  WsLock lk(st);
-  DeviceWs* w = lk.w;
-  if (!w) return fail("no HIP device");
-  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-  Stage sg{w, st};
-  const void *d_h0 = h0, *d_hks = hks, *d_sig = signals, *d_ph = fr_phase, *d_ub = U_bar, *d_col = col_ops;
-  void* d_grad = grad_signals;
-  if (flags & C3P_HOST_PTRS) {
-    if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)D * D) * cs, &d_h0)) return -1;
-    if (sg.in(hks, staged_elems(B, hks_bstride, (size_t)K * D * D) * cs, &d_hks)) return -1;
-    if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
-    if (sg.in(col_ops, col_elems(flags, B, C, D) * cs, &d_col)) return -1;
-    if (sg.in(U_bar, (size_t)B * Dm * Dm * cs, &d_ub)) return -1;
-    if (fr_phase && sg.in(fr_phase, (size_t)B * Dm * sizeof(double), &d_ph)) return -1;
-    if (sg.out(grad_signals, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
-  }
-  const cplx* clp;
-  long clp_bs;
-  if (build_clp(w, d_col, C, D, B, flags, &clp, &clp_bs, st)) return -1;
-  const PwcProblem P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, clp, clp_bs, dt, B, K, N, D, Dm,
-                        1, (const double*)d_ph};
-  const cplx* p_ub = (const cplx*)d_ub;
-  double* p_grad = (double*)d_grad;
+  LindGradCall c;
+  const int rc0 = c.open("c3p_pwc_lindblad_vjp", C3P_PER_SLICE_H | C3P_ORDER_RIGHT, false, [] { return 0; }, h0, h0_bstride, hks, hks_bstride,
+                         signals, col_ops, C, dt, B, K, N, D, flags, fr_phase, U_bar, grad_signals, nullptr, nullptr, nullptr, stream);
+  if (rc0) return rc0 < 0 ? -1 : 0;
+  DeviceWs* w = c.w;
+  hipStream_t st = c.st;
+  const int Dm = c.P.Dm;
   // The general-generator sweeps keep the slice propagators and the prefix of every slice: 2 N D^4 complex per sample.  Large
   // batches are processed in chunks of samples that keep that below 24 GB (C3P_GRAD_CHUNK overrides the chunk size).
-  const size_t general_store = 2 * (size_t)N * Dm * Dm * cs;
-  // a family that served the call: the kernel it reports, the end of the timed span, the staged results back
-  auto served = [&](int kernel) -> int {
-    g_last_kernel = kernel;
-    if (record_stop(w, st)) return -1;
-    if (flags & C3P_HOST_PTRS) return sg.finish();
-    return 0;
-  };
-  if (Dm <= kSmallDLimit && c3p_smalld_supported(Dm) && K <= 8 && !(flags & C3P_FORCE_GENERIC) && !c3p_opt_on(C3P_OPT_tiled_grad) &&
-      !c3p_opt_on(C3P_OPT_valu_grad)) {
+  const size_t general_store = 2 * (size_t)N * Dm * Dm * sizeof(cplx);
+  const bool on_chip = c.on_chip();
+  if (Dm <= kSmallDLimit && c3p_smalld_supported(Dm) && K <= 8 && on_chip) {
     // superoperators up to 12 x 12 (D <= 3): the general-generator sweep on the small-D matrix-core kernels
-    if (record_start(w, st)) return -1;
-    const int rc = in_chunks(B, grad_chunk_samples(w, general_store), [&](long b0, int nb) {
-      return run_vjp_lind_smalld(w, P.chunk(b0, nb), ubar_at(P, p_ub, b0), grad_at(P, p_grad, b0), (flags & C3P_HERMITIAN_H) != 0, st);
+    const int rc = c.family(general_store, C3P_KERNEL_SMALLD, [&](const PwcProblem& Pc, const cplx* ub, double* g, long) {
+      return run_vjp_lind_smalld(w, Pc, ub, g, (flags & C3P_HERMITIAN_H) != 0, st);
     });
-    if (rc < 0) return -1;
-    if (rc == 0) return served(C3P_KERNEL_SMALLD);
+    if (rc != 1) return rc;
   }
-  if (D == 4 && (flags & C3P_HERMITIAN_H) && K <= 8 && !(flags & C3P_FORCE_GENERIC) && !c3p_opt_on(C3P_OPT_no_smallr) &&
-      !c3p_opt_on(C3P_OPT_tiled_grad) && !c3p_opt_on(C3P_OPT_valu_grad)) {
+  if (D == 4 && (flags & C3P_HERMITIAN_H) && K <= 8 && on_chip && !c3p_opt_on(C3P_OPT_no_smallr)) {
     // two qubits with declared Hermitian Hamiltonians: the real Hermitian-basis kernels of c3p_smallr.hip, both halves
-    if (record_start(w, st)) return -1;
-    const int rc = in_chunks(B, grad_chunk_samples(w, general_store), [&](long b0, int nb) {
-      return run_vjp_lind_smallr16(w, P.chunk(b0, nb), ubar_at(P, p_ub, b0), grad_at(P, p_grad, b0), st);
-    });
-    if (rc < 0) return -1;
-    if (rc == 0) return served(C3P_KERNEL_MFMA);
+    const int rc = c.family(general_store, C3P_KERNEL_MFMA,
+                            [&](const PwcProblem& Pc, const cplx* ub, double* g, long) { return run_vjp_lind_smallr16(w, Pc, ub, g, st); });
+    if (rc != 1) return rc;
   }
   // 49 x 49 .. 81 x 81 superoperators (D = 7, 8, 9; cfg4) and, zero padded in the 49 class, 36 x 36 (D = 6): on-chip backward sweep in
   // the Hermitian basis, real arithmetic; the transposed local prefix of every slice (N D^4 doubles per sample) is kept in HBM:
   // chunks of samples below the budget.  1 = a Hamiltonian is not Hermitian (the caller goes on to the complex sweeps).
   auto try_regr = [&]() -> int {
-    if (record_start(w, st)) return -1;
-    const int rc = in_chunks(B, grad_chunk_samples(w, (size_t)N * Dm * Dm * sizeof(double)), [&](long b0, int nb) {
-      const int rc = run_vjp_lind_regr(w, P.chunk(b0, nb), ubar_at(P, p_ub, b0), grad_at(P, p_grad, b0), st);
+    return c.family((size_t)N * Dm * Dm * sizeof(double), C3P_KERNEL_MFMA, [&](const PwcProblem& Pc, const cplx* ub, double* g, long b0) {
+      const int rc = run_vjp_lind_regr(w, Pc, ub, g, st);
       if (rc == 1 && b0 > 0) return fail("internal: the Hermitian-basis sweep declined a later chunk");
       return rc;
     });
-    if (rc != 0) return rc;
-    return served(C3P_KERNEL_MFMA);
   };
-  const bool regr_ok = lind_regr_grad_ok(D, Dm) && !(flags & C3P_FORCE_GENERIC) && !c3p_opt_on(C3P_OPT_tiled_grad) &&
-                       !c3p_opt_on(C3P_OPT_valu_grad) && !c3p_opt_on(C3P_OPT_no_hermitian_basis);
+  const bool regr_ok = lind_regr_grad_ok(D, Dm) && on_chip && !c3p_opt_on(C3P_OPT_no_hermitian_basis);
   if (regr_ok && D == 6) {
     const int rc = try_regr();
-    if (rc <= 0) return rc;
+    if (rc != 1) return rc;
   }
-  if (Dm >= 13 && Dm <= 36 && !(flags & C3P_FORCE_GENERIC) && !c3p_opt_on(C3P_OPT_tiled_grad) && !c3p_opt_on(C3P_OPT_valu_grad)) {
+  if (Dm >= 13 && Dm <= 36 && on_chip) {
     // 16 x 16 .. 36 x 36 superoperators (D = 4, 5, 6): the same sweep on the mid-D matrix-core kernels
-    if (record_start(w, st)) return -1;
-    const int rc = in_chunks(B, grad_chunk_samples(w, general_store), [&](long b0, int nb) {
-      return run_vjp_lind_midd(w, P.chunk(b0, nb), ubar_at(P, p_ub, b0), grad_at(P, p_grad, b0), st);
-    });
-    if (rc < 0) return -1;
-    if (rc == 0) return served(C3P_KERNEL_MFMA);
+    const int rc = c.family(general_store, C3P_KERNEL_MFMA,
+                            [&](const PwcProblem& Pc, const cplx* ub, double* g, long) { return run_vjp_lind_midd(w, Pc, ub, g, st); });
+    if (rc != 1) return rc;
   }
   if (Dm <= 36 && !c3p_opt_on(C3P_OPT_tiled_grad)) {
     // the same sweep in three VALU kernels on dense generator tables (c3p_grad.hip, general form): fallback and second opinion
     bool global = false;
-    if (record_start(w, st)) return -1;
-    const int rc = in_chunks(B, grad_chunk_samples(w, general_store), [&](long b0, int nb) {
-      return run_vjp_lind_valu(w, P.chunk(b0, nb), ubar_at(P, p_ub, b0), grad_at(P, p_grad, b0), nullptr, &global, st);
+    const int rc = c.chunks(general_store, [&](const PwcProblem& Pc, const cplx* ub, double* g, long) {
+      return run_vjp_lind_valu(w, Pc, ub, g, nullptr, &global, st);
     });
     if (rc != 0) return -1;
-    return served(global ? C3P_KERNEL_GENERIC_GLOBAL : C3P_KERNEL_GENERIC_LDS);
+    return c.served(global ? C3P_KERNEL_GENERIC_GLOBAL : C3P_KERNEL_GENERIC_LDS);
   }
   if (regr_ok && D != 6) {
     const int rc = try_regr();
-    if (rc <= 0) return rc;
+    if (rc != 1) return rc;
   }
   if (record_start(w, st)) return -1;
-  if (run_vjp_tiled(w, P, p_ub, p_grad, st)) return -1;
-  return served(C3P_KERNEL_MFMA);
+  if (run_vjp_tiled(w, c.P, c.ubar, c.grad, st)) return -1;
+  return c.served(C3P_KERNEL_MFMA);
 }
 
 int c3p_pwc_lindblad_model_vjp(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
                                const void* col_ops, int C, double dt, int B, int K, int N, int D, int flags, const double* fr_phase,
                                const void* U_bar, double* grad_signals, void* grad_h0, void* grad_hks, void* grad_col_ops, void* stream) {
-  if (B < 0 || K <= 0 || N <= 0 || D <= 0 || C <= 0) return fail("bad sizes B=%d K=%d N=%d D=%d C=%d", B, K, N, D, C);
-  if (flags & (C3P_PER_SLICE_H | C3P_ORDER_RIGHT)) return fail("c3p_pwc_lindblad_model_vjp: unsupported flag");
-  if (D > 6)
-    return fail("c3p_pwc_lindblad_model_vjp: D=%d, the model-operator cotangents of the Lindblad path are served for D <= 6 "
-                "(superoperators up to 36 x 36); c3p_pwc_lindblad_model_vjp_hb serves D = 7, 8, 9 for Hermitian Hamiltonians", D);
-  if (B == 0) return 0;
-  if (!h0 || !hks || !signals || !col_ops || !U_bar || !grad_h0 || !grad_hks || !grad_col_ops) return fail("NULL pointer argument");
-  if (h0_bstride < 0 || hks_bstride < 0) return fail("negative batch stride");
-  const size_t cs = sizeof(cplx);
-  const int Dm = D * D;
-  hipStream_t st = (hipStream_t)stream;
-  WsLock lk(st);
-  DeviceWs* w = lk.w;
-  if (!w) return fail("no HIP device");
-  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-  Stage sg{w, st};
-  const void *d_h0 = h0, *d_hks = hks, *d_sig = signals, *d_ph = fr_phase, *d_ub = U_bar, *d_col = col_ops;
-  void* d_grad = grad_signals;
-  cplx *g_h0 = (cplx*)grad_h0, *g_hks = (cplx*)grad_hks, *g_col = (cplx*)grad_col_ops;
-  if (flags & C3P_HOST_PTRS) {
-    if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)D * D) * cs, &d_h0)) return -1;
-    if (sg.in(hks, staged_elems(B, hks_bstride, (size_t)K * D * D) * cs, &d_hks)) return -1;
-    if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
-    if (sg.in(col_ops, col_elems(flags, B, C, D) * cs, &d_col)) return -1;
-    if (sg.in(U_bar, (size_t)B * Dm * Dm * cs, &d_ub)) return -1;
-    if (fr_phase && sg.in(fr_phase, (size_t)B * Dm * sizeof(double), &d_ph)) return -1;
-    if (sg.out(grad_signals, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;  // SL_OUT0 (SL_OUT1 is the sweep's store)
-    // the three operator cotangents are staged in one block of their own
-    void* blk;
-    const size_t n0 = (size_t)B * Dm, nk = (size_t)B * K * Dm, nc = (size_t)B * C * Dm;
-    if (ws_get(w, SL_LMODEL_OUT, (n0 + nk + nc) * cs, &blk)) return -1;
-    g_h0 = (cplx*)blk, g_hks = g_h0 + n0, g_col = g_hks + nk;
-    sg.backs.push_back({grad_h0, g_h0, n0 * cs});
-    sg.backs.push_back({grad_hks, g_hks, nk * cs});
-    sg.backs.push_back({grad_col_ops, g_col, nc * cs});
-  }
-  if (!d_grad) {  // grad_signals not wanted: the sweep still writes it
-    if (ws_get(w, SL_OUT0, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
-  }
-  const cplx* clp;
-  long clp_bs;
-  if (build_clp(w, d_col, C, D, B, flags, &clp, &clp_bs, st)) return -1;
-  const PwcProblem P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, clp, clp_bs, dt, B, K, N, D, Dm,
-                        1, (const double*)d_ph};
-  const LindModelOut mo = {(const cplx*)d_col, col_bstride(flags, C, D), C, g_h0, g_hks, g_col};
+  LindGradCall c;
+  auto own = [&]() -> int {
+    if (D > 6)
+      return fail("c3p_pwc_lindblad_model_vjp: D=%d, the model-operator cotangents of the Lindblad path are served for D <= 6 "
+                  "(superoperators up to 36 x 36); c3p_pwc_lindblad_model_vjp_hb serves D = 7, 8, 9 for Hermitian Hamiltonians", D);
+    return 0;
+  };
+  const int rc0 = c.open("c3p_pwc_lindblad_model_vjp", C3P_PER_SLICE_H | C3P_ORDER_RIGHT, true, own, h0, h0_bstride, hks, hks_bstride, signals,
+                         col_ops, C, dt, B, K, N, D, flags, fr_phase, U_bar, grad_signals, grad_h0, grad_hks, grad_col_ops, stream);
+  if (rc0) return rc0 < 0 ? -1 : 0;
   bool global = false;
-  if (record_start(w, st)) return -1;
   // chunks of samples as in c3p_pwc_lindblad_vjp: the sweep keeps 2 N D^4 complex per sample
-  const int rc = in_chunks(B, grad_chunk_samples(w, 2 * (size_t)N * Dm * Dm * cs), [&](long b0, int nb) {
-    const LindModelOut mc = mo.at(P, b0);
-    return run_vjp_lind_valu(w, P.chunk(b0, nb), ubar_at(P, (const cplx*)d_ub, b0), grad_at(P, (double*)d_grad, b0), &mc, &global, st);
+  const int rc = c.chunks(2 * (size_t)N * c.P.Dm * c.P.Dm * sizeof(cplx), [&](const PwcProblem& Pc, const cplx* ub, double* g, long b0) {
+    const LindModelOut mc = c.mo.at(c.P, b0);
+    return run_vjp_lind_valu(c.w, Pc, ub, g, &mc, &global, c.st);
   });
   if (rc != 0) return -1;
-  g_last_kernel = global ? C3P_KERNEL_GENERIC_GLOBAL : C3P_KERNEL_GENERIC_LDS;
-  if (record_stop(w, st)) return -1;
-  if (flags & C3P_HOST_PTRS) return sg.finish();
-  return 0;
+  return c.served(global ? C3P_KERNEL_GENERIC_GLOBAL : C3P_KERNEL_GENERIC_LDS);
 }
 
 // The model-operator cotangents at D = 7, 8, 9 (and D = 6 under regr_grad_d6) from the Hermitian-basis sweep: the sweep of
@@ -3032,92 +3012,37 @@ int c3p_pwc_lindblad_model_vjp_hb(const void* h0, int64_t h0_bstride, const void
                                   const void* col_ops, int C, double dt, int B, int K, int N, int D, int flags, const double* fr_phase,
                                   const void* U_bar, double* grad_signals, void* grad_h0, void* grad_hks, void* grad_col_ops,
                                   void* stream) {
-  if (B < 0 || K <= 0 || N <= 0 || D <= 0 || C <= 0) return fail("bad sizes B=%d K=%d N=%d D=%d C=%d", B, K, N, D, C);
-  if (flags & (C3P_PER_SLICE_H | C3P_ORDER_RIGHT | C3P_FORCE_GENERIC)) return fail("c3p_pwc_lindblad_model_vjp_hb: unsupported flag");
+  LindGradCall c;
   const int Dm = D * D;
-  if (!lind_regr_grad_ok(D, Dm))
-    return fail("c3p_pwc_lindblad_model_vjp_hb: D=%d, the Hermitian-basis sweep serves D = 7, 8, 9 (D = 6 under regr_grad_d6); "
-                "c3p_pwc_lindblad_model_vjp serves D <= 6", D);
-  if (K > 16) return fail("c3p_pwc_lindblad_model_vjp_hb: K=%d, the Hermitian-basis sweep serves 1 <= K <= 16", K);
-  if (B == 0) return 0;
-  if (!h0 || !hks || !signals || !col_ops || !U_bar || !grad_h0 || !grad_hks || !grad_col_ops) return fail("NULL pointer argument");
-  if (h0_bstride < 0 || hks_bstride < 0) return fail("negative batch stride");
-  const size_t cs = sizeof(cplx);
-  hipStream_t st = (hipStream_t)stream;
-  WsLock lk(st);
-  DeviceWs* w = lk.w;
-  if (!w) return fail("no HIP device");
-  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-  Stage sg{w, st};
-  const void *d_h0 = h0, *d_hks = hks, *d_sig = signals, *d_ph = fr_phase, *d_ub = U_bar, *d_col = col_ops;
-  void* d_grad = grad_signals;
-  cplx *g_h0 = (cplx*)grad_h0, *g_hks = (cplx*)grad_hks, *g_col = (cplx*)grad_col_ops;
-  if (flags & C3P_HOST_PTRS) {
-    if (sg.in(h0, staged_elems(B, h0_bstride, (size_t)D * D) * cs, &d_h0)) return -1;
-    if (sg.in(hks, staged_elems(B, hks_bstride, (size_t)K * D * D) * cs, &d_hks)) return -1;
-    if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
-    if (sg.in(col_ops, col_elems(flags, B, C, D) * cs, &d_col)) return -1;
-    if (sg.in(U_bar, (size_t)B * Dm * Dm * cs, &d_ub)) return -1;
-    if (fr_phase && sg.in(fr_phase, (size_t)B * Dm * sizeof(double), &d_ph)) return -1;
-    if (grad_signals && sg.out(grad_signals, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
-    // the three operator cotangents are staged in one block of their own
-    void* blk;
-    const size_t n0 = (size_t)B * D * D, nk = (size_t)B * K * D * D, nc = (size_t)B * C * D * D;
-    if (ws_get(w, SL_LMODEL_OUT, (n0 + nk + nc) * cs, &blk)) return -1;
-    g_h0 = (cplx*)blk, g_hks = g_h0 + n0, g_col = g_hks + nk;
-    sg.backs.push_back({grad_h0, g_h0, n0 * cs});
-    sg.backs.push_back({grad_hks, g_hks, nk * cs});
-    sg.backs.push_back({grad_col_ops, g_col, nc * cs});
-  }
-  if (!d_grad) {  // grad_signals not wanted: the sweep still writes it
-    if (ws_get(w, SL_OUT0, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
-  }
-  const cplx* clp;
-  long clp_bs;
-  if (build_clp(w, d_col, C, D, B, flags, &clp, &clp_bs, st)) return -1;
-  const PwcProblem P = {(const cplx*)d_h0, h0_bstride, (const cplx*)d_hks, hks_bstride, (const double*)d_sig, clp, clp_bs, dt, B, K, N, D, Dm,
-                        1, (const double*)d_ph};
-  const LindModelOut mo = {(const cplx*)d_col, col_bstride(flags, C, D), C, g_h0, g_hks, g_col};
-  if (record_start(w, st)) return -1;
+  auto own = [&]() -> int {
+    if (!lind_regr_grad_ok(D, Dm))
+      return fail("c3p_pwc_lindblad_model_vjp_hb: D=%d, the Hermitian-basis sweep serves D = 7, 8, 9 (D = 6 under regr_grad_d6); "
+                  "c3p_pwc_lindblad_model_vjp serves D <= 6", D);
+    if (K > 16) return fail("c3p_pwc_lindblad_model_vjp_hb: K=%d, the Hermitian-basis sweep serves 1 <= K <= 16", K);
+    return 0;
+  };
+  const int rc0 = c.open("c3p_pwc_lindblad_model_vjp_hb", C3P_PER_SLICE_H | C3P_ORDER_RIGHT | C3P_FORCE_GENERIC, true, own, h0, h0_bstride, hks,
+                         hks_bstride, signals, col_ops, C, dt, B, K, N, D, flags, fr_phase, U_bar, grad_signals, grad_h0, grad_hks, grad_col_ops, stream);
+  if (rc0) return rc0 < 0 ? -1 : 0;
   // chunks of samples as in c3p_pwc_lindblad_vjp: the transposed prefixes (N D^4 doubles per sample) and the sums of the generator
   // cotangents (S (1 + K) D^4 doubles per sample, S <= 32)
   const size_t per_sample = ((size_t)N + (size_t)32 * (1 + K)) * Dm * Dm * sizeof(double);
-  const int rc = in_chunks(B, grad_chunk_samples(w, per_sample), [&](long b0, int nb) {
-    const LindModelOut mc = mo.at(P, b0);
-    const int rc = run_vjp_lind_regr(w, P.chunk(b0, nb), ubar_at(P, (const cplx*)d_ub, b0), grad_at(P, (double*)d_grad, b0), st, &mc);
+  const int rc = c.chunks(per_sample, [&](const PwcProblem& Pc, const cplx* ub, double* g, long b0) {
+    const LindModelOut mc = c.mo.at(c.P, b0);
+    const int rc = run_vjp_lind_regr(c.w, Pc, ub, g, c.st, &mc);
     if (rc == 1)
       return fail("c3p_pwc_lindblad_model_vjp_hb: h0 / hks must be Hermitian (the generator is not real in the Hermitian basis)");
     return rc;
   });
   if (rc != 0) return -1;
-  g_last_kernel = C3P_KERNEL_MFMA;
-  if (record_stop(w, st)) return -1;
-  if (flags & C3P_HOST_PTRS) return sg.finish();
-  return 0;
+  return c.served(C3P_KERNEL_MFMA);
 }
 
 // ---- open-system evaluation from ONE forward pass: a caller-owned tape between c3p_pwc_lindblad_taped and its vjp ----
 size_t c3p_pwc_lindblad_tape_bytes(int B, int K, int N, int D, int* segments_out) {
-  if (B > 0 && K >= 1 && K <= 8 && N > 0 && D == 4) {
-    // two qubits: the real Hermitian-basis kernels only (the taped calls then need C3P_HERMITIAN_H)
-    const int S = c3p_opt_on(C3P_OPT_no_smallr) ? -1 : pick_segments_r(B, N, K, 16, true, true);
-    if (segments_out) *segments_out = S > 0 ? S : 0;
-    return S > 0 ? lind_smallr_sizes(B, K, N, 16, S, B).total() : 0;
-  }
-  if (B > 0 && K >= 1 && K <= 8 && N > 0 && D >= 2 && D <= 3) {
-    // superoperators up to 9 x 9 on the small-D kernels: tables, segment products and the slice propagators (the generator is
-    // not anti-Hermitian: the backward sweep cannot recompute prefixes from the adjoint side); per-sample operators need S % 4 = 0
-    const int S = lind_small_segments(B, K, N, D * D, true);
-    if (segments_out) *segments_out = S > 0 ? S : 0;
-    return S > 0 ? lind_small_sizes(B, K, N, D * D, S, B).total() : 0;
-  }
-  if (B <= 0 || K < 1 || N <= 0 || D <= 0 || !c3p_regr_supported(D, D * D) || K > 16) {
-    if (segments_out) *segments_out = 0;
-    return 0;
-  }
-  const long S = lind_regr_segments(B, N);
-  if (segments_out) *segments_out = (int)S;
-  return lind_regr_sizes(B, K, N, D * D, S, B).total();
+  const LindTapePlan plan = lind_tape_plan(B, K, N, D);
+  if (segments_out) *segments_out = plan.segments;
+  return plan.bytes;
 }
 
 int c3p_pwc_lindblad_taped(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals,
@@ -3132,29 +3057,32 @@ int c3p_pwc_lindblad_taped(const void* h0, int64_t h0_bstride, const void* hks, 
   if (!h0 || !hks || !signals || !col_ops || C <= 0 || !U_out || !tape) return fail("NULL pointer argument");
   if (h0_bstride < 0 || hks_bstride < 0) return fail("negative batch stride");
   if (segments < 1 || segments > N) return fail("bad segment count %d", segments);
-  PwcProblem P = {(const cplx*)h0, h0_bstride, (const cplx*)hks, hks_bstride, signals, nullptr, 0, dt, B, K, N, D, Dm, 1, fr_phase};  // (clp: below)
-  if (D <= 4) {
+  if (D > 4 && !c3p_regr_supported(D, Dm)) return fail("the taped Lindblad evaluation serves D = 2, 3, 4 (small-D tile kernels) and D = 7, 8, 9 (Hermitian-basis kernels), got D=%d", D);
+  // the segment count is the library's choice (c3p_pwc_lindblad_tape_bytes): the chain, scan and backward kernels are tuned and
+  // tested for that range only, and the tape layout follows from it
+  const LindTapePlan plan = lind_tape_plan(B, K, N, D);
+  if (plan.family == TAPE_NONE || plan.segments != segments)
+    return fail("taped Lindblad evaluation: shape not served or segment count %d != %d (c3p_pwc_lindblad_tape_bytes)", segments, plan.segments);
+  if (tape_bytes < plan.bytes) return fail("tape too small: %zu bytes, need %zu (c3p_pwc_lindblad_tape_bytes)", tape_bytes, plan.bytes);
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  DeviceWs* w = lk.w;
+  if (!w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  const size_t cs = sizeof(cplx);
+  void* clp;
+  if (ws_get(w, SL_CLP, (size_t)Dm * Dm * cs, &clp)) return -1;
+  LAUNCH_TRY(c3p_launch_clp((const cplx*)col_ops, C, D, 1, (cplx*)clp, st));
+  const PwcProblem P = {(const cplx*)h0, h0_bstride, (const cplx*)hks, hks_bstride, signals, (const cplx*)clp, 0, dt, B, K, N, D, Dm, 1, fr_phase};
+  if (plan.family != TAPE_REGR) {
     // small-D kernels: the forward half of run_vjp_lind_smalld writes into the tape, U = the ordered product of its segments
-    int seg_chk = 0;
-    const size_t need = c3p_pwc_lindblad_tape_bytes(B, K, N, D, &seg_chk);
-    if (need == 0 || seg_chk != segments) return fail("taped Lindblad evaluation: shape not served or segment count %d != %d (c3p_pwc_lindblad_tape_bytes)", segments, seg_chk);
-    if (tape_bytes < need) return fail("tape too small: %zu bytes, need %zu (c3p_pwc_lindblad_tape_bytes)", tape_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    WsLock lk(st);
-    DeviceWs* w = lk.w;
-    if (!w) return fail("no HIP device");
-    if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-    void* clp;
-    if (ws_get(w, SL_CLP, (size_t)Dm * Dm * sizeof(cplx), &clp)) return -1;
-    LAUNCH_TRY(c3p_launch_clp((const cplx*)col_ops, C, D, 1, (cplx*)clp, st));
-    P.clp = (const cplx*)clp;
     if (lind_smallr_ok((flags & C3P_HERMITIAN_H) != 0, D, Dm, K, N, segments)) {
       // declared Hermitian: the tape holds the REAL tables, segment products and slice propagators (c3p_pwc_lindblad_vjp_taped
       // must be given the same flag); U from the complex copies of the segment products
       const int nsamp = P.nsamp();
       const LindSmallRBufs rb = lind_smallr_carve(tape, lind_smallr_sizes(B, K, N, Dm, segments, nsamp), nsamp, Dm, K);
       void* sc;
-      if (ws_get(w, SL_OUT2, (size_t)B * segments * Dm * Dm * sizeof(cplx), &sc)) return -1;
+      if (ws_get(w, SL_OUT2, (size_t)B * segments * Dm * Dm * cs, &sc)) return -1;
       if (record_start(w, st)) return -1;
       if (lind_smallr_forward(rb, P, segments, (cplx*)sc, st)) return -1;
       if (record_stop(w, st)) return -1;
@@ -3170,33 +3098,13 @@ int c3p_pwc_lindblad_taped(const void* h0, int64_t h0_bstride, const void* hks, 
     if (record_stop(w, st)) return -1;
     g_last_kernel = C3P_KERNEL_SMALLD;
     if (segments == 1) {
-      HIP_TRY(hipMemcpyAsync(U_out, bf.seg, (size_t)B * Dm * Dm * sizeof(cplx), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(U_out, bf.seg, (size_t)B * Dm * Dm * cs, hipMemcpyDeviceToDevice, st));
       if (fr_phase) LAUNCH_TRY(c3p_launch_rowphase((cplx*)U_out, fr_phase, B, Dm, st));
       return 0;
     }
     return combine_chain(c3p_launch_smalld_chain, w, bf.seg, B, segments, Dm, 0, fr_phase, (cplx*)U_out, st) ? -1 : 0;
   }
-  if (!c3p_regr_supported(D, Dm)) return fail("the taped Lindblad evaluation serves D = 2, 3, 4 (small-D tile kernels) and D = 7, 8, 9 (Hermitian-basis kernels), got D=%d", D);
-  {
-    // the segment count is the library's choice (c3p_pwc_lindblad_tape_bytes), as at D <= 4: the chain, scan and backward kernels
-    // are tuned and tested for that range only, and the tape layout follows from it
-    int seg_chk = 0;
-    if (c3p_pwc_lindblad_tape_bytes(B, K, N, D, &seg_chk) == 0 || seg_chk != segments)
-      return fail("taped Lindblad evaluation: shape not served or segment count %d != %d (c3p_pwc_lindblad_tape_bytes)", segments, seg_chk);
-  }
-  const LindRegrSizes z = lind_regr_sizes(B, K, N, Dm, segments, B);
-  if (tape_bytes < z.total()) return fail("tape too small: %zu bytes, need %zu (c3p_pwc_lindblad_tape_bytes)", tape_bytes, z.total());
-  hipStream_t st = (hipStream_t)stream;
-  WsLock lk(st);
-  DeviceWs* w = lk.w;
-  if (!w) return fail("no HIP device");
-  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-  const size_t cs = sizeof(cplx);
-  void* clp;
-  if (ws_get(w, SL_CLP, (size_t)Dm * Dm * cs, &clp)) return -1;
-  LAUNCH_TRY(c3p_launch_clp((const cplx*)col_ops, C, D, 1, (cplx*)clp, st));
-  P.clp = (const cplx*)clp;
-  const LindRegrBufs bf = lind_regr_carve(tape, z);
+  const LindRegrBufs bf = lind_regr_carve(tape, lind_regr_sizes(B, K, N, Dm, segments, B));
   if (record_start(w, st)) return -1;
   const int rc = lind_regr_forward(w, bf, P, segments, st);
   if (rc < 0) return -1;
@@ -3241,55 +3149,41 @@ int c3p_pwc_lindblad_vjp_taped(const void* tape, size_t tape_bytes, int segments
   const int Dm = D * D;
   if (!tape || !signals || !U_bar || !grad_signals) return fail("NULL pointer argument");
   if (segments < 1 || segments > N) return fail("bad segment count %d", segments);
+  if (D > 4 && !c3p_regr_supported(D, Dm)) return fail("the taped Lindblad evaluation serves D = 2, 3, 4 and D = 7, 8, 9, got D=%d", D);
+  // the plan from the option table as it is NOW: an option that changes the segment count (or the kernel family) between the
+  // taped forward call and this one would reinterpret the tape -- refuse what can be detected
+  const LindTapePlan plan = lind_tape_plan(B, K, N, D);
+  if (plan.family == TAPE_NONE || plan.segments != segments)
+    return D <= 4 ? fail("taped Lindblad evaluation: shape not served or segment count %d != %d", segments, plan.segments)
+                  : fail("taped Lindblad vjp: segment count %d != %d (c3p_pwc_lindblad_tape_bytes; were library options changed since the forward call?)", segments, plan.segments);
+  if (tape_bytes < plan.bytes) return fail("tape too small: %zu bytes, need %zu", tape_bytes, plan.bytes);
   // the operators are in the tape: of them the backward halves read only whether the tables are per sample (a nonzero stride)
   const PwcProblem P = {nullptr, per_sample_operators ? 1 : 0, nullptr, 0, signals, nullptr, 0, 0.0, B, K, N, D, Dm, 1, fr_phase};
-  if (D <= 4) {
-    int seg_chk = 0;
-    const size_t need = c3p_pwc_lindblad_tape_bytes(B, K, N, D, &seg_chk);
-    if (need == 0 || seg_chk != segments) return fail("taped Lindblad evaluation: shape not served or segment count %d != %d", segments, seg_chk);
-    if (tape_bytes < need) return fail("tape too small: %zu bytes, need %zu", tape_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    WsLock lk(st);
-    DeviceWs* w = lk.w;
-    if (!w) return fail("no HIP device");
-    if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-    if (lind_smallr_ok((flags & C3P_HERMITIAN_H) != 0, D, Dm, K, N, segments)) {
-      const int nsamp = P.nsamp();
-      const LindSmallRBufs rb = lind_smallr_carve(const_cast<void*>(tape), lind_smallr_sizes(B, K, N, Dm, segments, nsamp), nsamp, Dm, K);
-      if (record_start(w, st)) return -1;
-      if (lind_smallr_backward(w, rb, P, segments, (const cplx*)U_bar, grad_signals, st)) return -1;
-      if (record_stop(w, st)) return -1;
-      g_last_kernel = Dm > 12 ? C3P_KERNEL_MFMA : C3P_KERNEL_SMALLD;
-      return 0;
-    }
-    if (D == 4) return fail("the taped Lindblad evaluation at D = 4 needs C3P_HERMITIAN_H, as given to c3p_pwc_lindblad_taped");
-    const LindSmallBufs bf = lind_small_carve(const_cast<void*>(tape), lind_small_sizes(B, K, N, Dm, segments, B));
-    if (record_start(w, st)) return -1;
-    if (lind_small_backward(w, bf, P, segments, (const cplx*)U_bar, grad_signals, st)) return -1;
-    if (record_stop(w, st)) return -1;
-    g_last_kernel = C3P_KERNEL_SMALLD;
-    return 0;
-  }
-  if (!c3p_regr_supported(D, Dm)) return fail("the taped Lindblad evaluation serves D = 2, 3, 4 and D = 7, 8, 9, got D=%d", D);
-  {
-    // recomputed from the option table as it is NOW: an option that changes the segment count (or the kernel family) between
-    // the taped forward call and this one would reinterpret the tape -- refuse what can be detected
-    int seg_chk = 0;
-    if (c3p_pwc_lindblad_tape_bytes(B, K, N, D, &seg_chk) == 0 || seg_chk != segments)
-      return fail("taped Lindblad vjp: segment count %d != %d (c3p_pwc_lindblad_tape_bytes; were library options changed since the forward call?)", segments, seg_chk);
-  }
-  const LindRegrSizes z = lind_regr_sizes(B, K, N, Dm, segments, B);
-  if (tape_bytes < z.total()) return fail("tape too small: %zu bytes, need %zu", tape_bytes, z.total());
+  void* tp = const_cast<void*>(tape);
   hipStream_t st = (hipStream_t)stream;
   WsLock lk(st);
   DeviceWs* w = lk.w;
   if (!w) return fail("no HIP device");
   if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-  const LindRegrBufs bf = lind_regr_carve(const_cast<void*>(tape), z);
-  if (record_start(w, st)) return -1;
-  if (lind_regr_backward(w, bf, P, segments, (const cplx*)U_bar, grad_signals, st)) return -1;
-  if (record_stop(w, st)) return -1;
-  g_last_kernel = C3P_KERNEL_MFMA;
+  int rc, kernel;
+  if (plan.family == TAPE_REGR) {
+    kernel = C3P_KERNEL_MFMA;
+    if (record_start(w, st)) return -1;
+    rc = lind_regr_backward(w, lind_regr_carve(tp, lind_regr_sizes(B, K, N, Dm, segments, B)), P, segments, (const cplx*)U_bar, grad_signals, st);
+  } else if (lind_smallr_ok((flags & C3P_HERMITIAN_H) != 0, D, Dm, K, N, segments)) {
+    const int nsamp = P.nsamp();
+    kernel = Dm > 12 ? C3P_KERNEL_MFMA : C3P_KERNEL_SMALLD;
+    if (record_start(w, st)) return -1;
+    rc = lind_smallr_backward(w, lind_smallr_carve(tp, lind_smallr_sizes(B, K, N, Dm, segments, nsamp), nsamp, Dm, K), P, segments, (const cplx*)U_bar,
+                              grad_signals, st);
+  } else {
+    if (D == 4) return fail("the taped Lindblad evaluation at D = 4 needs C3P_HERMITIAN_H, as given to c3p_pwc_lindblad_taped");
+    kernel = C3P_KERNEL_SMALLD;
+    if (record_start(w, st)) return -1;
+    rc = lind_small_backward(w, lind_small_carve(tp, lind_small_sizes(B, K, N, Dm, segments, B)), P, segments, (const cplx*)U_bar, grad_signals, st);
+  }
+  if (rc || record_stop(w, st)) return -1;
+  g_last_kernel = kernel;
   return 0;
 }
 
