@@ -1484,7 +1484,8 @@ int run_pwc_tiled(DeviceWs* w, const ChainArgs& a, bool per_slice, cplx* U_out, 
   const bool lindblad = a.mode == C3P_MODE_LINDBLAD;
   const bool per_sample = !per_slice && (a.h0_bstride != 0 || a.hks_bstride != 0 || a.clp_bstride != 0);
   const int K = per_slice ? 0 : a.K;
-  const int Bc = c3p_tiled_chunk(a.Dm, K, a.B, per_sample, (size_t)24 << 30);
+  int Bc = c3p_tiled_chunk(a.Dm, K, a.B, per_sample, (size_t)24 << 30);
+  if (c3p_opt(C3P_OPT_tiled_chunk) > 0 && c3p_opt(C3P_OPT_tiled_chunk) < Bc) Bc = (int)c3p_opt(C3P_OPT_tiled_chunk);  // (tests: a second chunk)
   void* v;
   if (ws_get(w, SL_SCRATCH, c3p_tiled_ws_bytes(a.Dm, K, Bc, per_sample), &v)) return -1;
   TiledArgs t = {};
@@ -1693,7 +1694,8 @@ int run_vjp_tiled(DeviceWs* w, const PwcProblem& P, const cplx* U_bar, double* g
                   cplx* zout = nullptr) {
   const int B = P.B, K = P.K, N = P.N, Dm = P.Dm;
   const bool per_sample = !per_slice && P.per_sample();
-  const int Bc = c3p_tiled_vjp_chunk(Dm, K, N, B, per_sample, grad_store_budget(w, SL_SCRATCH));
+  int Bc = c3p_tiled_vjp_chunk(Dm, K, N, B, per_sample, grad_store_budget(w, SL_SCRATCH));
+  if (c3p_opt(C3P_OPT_tiled_chunk) > 0 && c3p_opt(C3P_OPT_tiled_chunk) < Bc) Bc = (int)c3p_opt(C3P_OPT_tiled_chunk);  // (tests: a second chunk)
   void* v;
   if (ws_get(w, SL_SCRATCH, c3p_tiled_vjp_ws_bytes(Dm, K, N, Bc, per_sample), &v)) return -1;
   if (g_dry) return 0;

@@ -74,12 +74,14 @@ def col_bound(h0, hks, sig, dt, b, n0=0, n1=None):
 # inputs (all cached: one draw and one reference per case, shared by the GPU tests and the CPU checks)
 # ------------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def unitary_case(D, kind, target, per_sample=False, nb=B, n=N):
+def unitary_case(D, kind, target, per_sample=False, nb=B, n=N, K=None, phase=None):
     """operators (real symmetric or complex Hermitian), signals of magnitude 2.4 .. 4 and random sign, and dt such that
     the largest column-wise bound of a whole sample is `target`: every segment's bound lies in (0.6 target, target].
-    K = 3 for odd D, 1 for even D; frame phases in half the cases."""
-    rng = np.random.default_rng(5000 + 97 * D + int(10 * target) + (1 if kind == "real" else 0) + (500 if per_sample else 0) + n)
-    K = 3 if D % 2 else 1
+    K = 3 for odd D, 1 for even D; frame phases in half the cases.  (K, phase: set by tests/test_gpu_tiled_sweep.py, which
+    shares these operators; left at None they change nothing.)"""
+    rng = np.random.default_rng(5000 + 97 * D + int(10 * target) + (1 if kind == "real" else 0) + (500 if per_sample else 0) + n
+                                + (0 if K is None else 100000 * K + 1000 * nb))
+    K = (3 if D % 2 else 1) if K is None else K
     # A multi-level system in the lab frame: a drift that is mostly diagonal (centred at zero) and drives without a diagonal, every
     # table trace-free with a set 1-norm, plus a small multiple of the identity (the trace shift mu_k of its table).  Why the
     # structure: the oracle restates TensorFlow's expm, which takes the trace along and does not scale a matrix of 1-norm below
@@ -98,7 +100,7 @@ def unitary_case(D, kind, target, per_sample=False, nb=B, n=N):
     sig = 4.0 * rng.uniform(0.6, 1.0, size=(nb, K, n)) * rng.choice([-1.0, 1.0], size=(nb, K, n))
     dt = target / max(col_bound(h0, hks, sig, 1.0, b) for b in range(nb))
     Ubar = rng.normal(size=(nb, D, D)) + 1j * rng.normal(size=(nb, D, D))
-    ph = rng.uniform(0, 6, size=(nb, D)) if (D + int(10 * target) + int(per_sample)) % 2 else None
+    ph = rng.uniform(0, 6, size=(nb, D)) if ((D + int(10 * target) + int(per_sample)) % 2 if phase is None else phase) else None
     return tuple(_frozen(x) if isinstance(x, np.ndarray) else x for x in (h0, hks, sig, dt, Ubar, ph))
 
 
@@ -169,24 +171,25 @@ def handed_over(per_sample, S):
 
 
 @functools.lru_cache(maxsize=None)
-def lindblad_case(D, C, hermitian, n=N, col_scale=0.1, per_sample_col=False, K=None):
+def lindblad_case(D, C, hermitian, n=N, col_scale=0.1, per_sample_col=False, K=None, nb=B, phase=None):
     """the operators of test_lindblad_vjp_small_superoperators_general_sweep (dt = 0.3) with weaker collapse operators, so that 20
-    time units of dissipation leave the gradient well above roundoff; non-Hermitian: h0 + 0.1 x complex Gaussian"""
-    rng = np.random.default_rng(7100 + 100 * D + 10 * C + int(hermitian) + n + (3 if per_sample_col else 0))
+    time units of dissipation leave the gradient well above roundoff; non-Hermitian: h0 + 0.1 x complex Gaussian
+    (nb, phase: set by tests/test_gpu_tiled_sweep.py; at their defaults they change nothing)"""
+    rng = np.random.default_rng(7100 + 100 * D + 10 * C + int(hermitian) + n + (3 if per_sample_col else 0) + (0 if nb == B else 1000 * nb))
     herm = lambda s: s * _mat(rng, D, "complex")
     K = (3 if C == 1 else 1) if K is None else K
     h0 = herm(0.8)
     if not hermitian:
         h0 = h0 + 0.1 * (rng.normal(size=(D, D)) + 1j * rng.normal(size=(D, D)))
     hks = np.stack([herm(0.5) for _ in range(K)])
-    shape = (B, C, D, D) if per_sample_col else (C, D, D)
+    shape = (nb, C, D, D) if per_sample_col else (C, D, D)
     col = col_scale * (rng.normal(size=shape) + 1j * rng.normal(size=shape))
     if per_sample_col:
-        col = col * np.array([0.5, 1.0, 2.0])[:, None, None, None]  # a kernel that reads another sample's dissipator misses by O(1)
-    sig = rng.uniform(-1, 1, size=(B, K, n))
+        col = col * np.resize([0.5, 1.0, 2.0], nb)[:, None, None, None]  # a kernel that reads another sample's dissipator misses by O(1)
+    sig = rng.uniform(-1, 1, size=(nb, K, n))
     Dm = D * D
-    Ubar = rng.normal(size=(B, Dm, Dm)) + 1j * rng.normal(size=(B, Dm, Dm))
-    ph = rng.uniform(0, 2 * np.pi, size=(B, Dm)) if (D + C) % 2 else None
+    Ubar = rng.normal(size=(nb, Dm, Dm)) + 1j * rng.normal(size=(nb, Dm, Dm))
+    ph = rng.uniform(0, 2 * np.pi, size=(nb, Dm)) if ((D + C) % 2 if phase is None else phase) else None
     return tuple(_frozen(x) if isinstance(x, np.ndarray) else x for x in (h0, hks, sig, 0.3, col, Ubar, ph))
 
 
@@ -194,14 +197,15 @@ def lindblad_case(D, C, hermitian, n=N, col_scale=0.1, per_sample_col=False, K=N
 def lindblad_want(*key):
     h0, hks, sig, dt, col, Ubar, ph = lindblad_case(*key)
     return _frozen(np.stack([o.pwc_lindblad_signal_gradient(h0, hks, col[b] if col.ndim == 4 else col, sig[b], dt, Ubar[b], None if ph is None else ph[b])
-                             for b in range(B)]))
+                             for b in range(sig.shape[0])]))
 
 
 @functools.lru_cache(maxsize=None)
-def per_slice_case(D, hermitian):
+def per_slice_case(D, hermitian, nb=B, n=N, loss=0.05):
     """the slice Hamiltonians of test_per_slice_vjp_on_chip_sweeps: Hermitian, or lossy and non-normal (a sixth of the loss there: 67
-    slices of it leave the cotangents at a fifth of their size, not at 1e-4)"""
-    rng = np.random.default_rng(7300 + 10 * D + int(hermitian))
+    slices of it leave the cotangents at a fifth of their size, not at 1e-4; tests/test_gpu_tiled_sweep.py takes four slices at the
+    full loss, 0.3)"""
+    rng = np.random.default_rng(7300 + 10 * D + int(hermitian) + (0 if (nb, n) == (B, N) else 1000 * nb + n))
     s = 0.5 / np.sqrt(D)
 
     def mat():
@@ -210,11 +214,11 @@ def per_slice_case(D, hermitian):
             return h
         g = rng.normal(size=(D, D)) + 1j * rng.normal(size=(D, D))
         up = np.triu(rng.normal(size=(D, D)), 1) * (1.0 + np.arange(D)[:, None]) / D
-        return h - 1j * 0.05 * s * (g @ g.conj().T) / D + 0.5 * s * up
+        return h - 1j * loss * s * (g @ g.conj().T) / D + 0.5 * s * up
 
-    Hs = np.stack([np.stack([mat() for _ in range(N)]) for _ in range(B)])
-    Ubar = rng.normal(size=(B, D, D)) + 1j * rng.normal(size=(B, D, D))
-    ph = rng.uniform(0, 2 * np.pi, size=(B, D))
+    Hs = np.stack([np.stack([mat() for _ in range(n)]) for _ in range(nb)])
+    Ubar = rng.normal(size=(nb, D, D)) + 1j * rng.normal(size=(nb, D, D))
+    ph = rng.uniform(0, 2 * np.pi, size=(nb, D))
     return _frozen(Hs), 1.1, _frozen(Ubar), _frozen(ph)
 
 
