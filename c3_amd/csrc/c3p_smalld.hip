@@ -1358,101 +1358,135 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
           mus_i = c3p_phase_add(ph, (double)(valid ? len : 0) * c3p_phase_add(0.0, tab[MAT + 1]));
           wave_sync();
         }
-        auto split_loop = [&](auto deg6_tag, auto k_tag) {
+        // The slots t < tfast are real slices of all four chains of the wave (the chains of a wave differ by at most one slice, so
+        // at most the last slot is padding for some of them)
+        int tfast = valid ? len : 0;
+        tfast = min(tfast, __shfl_xor(tfast, 4));
+        tfast = min(tfast, __shfl_xor(tfast, 8));
+        tfast = min(__builtin_amdgcn_readfirstlane(tfast), tmax);
+        // One slice: E = cos Y - i sin Y as Cm = cos Y and acc = sin Y, both in left-operand form.
+        //   WEIGHTED: Y = a_0 T_0 + sum_k a_k T_k with the a_0 row (a padded slot gives Y = 0, E = I).  Otherwise the slot is a real
+        //     slice of a segment without squarings: rscale = 1, so a_0 T_0 = -T_0 exactly and the drift is the negated addend of the
+        //     first multiply-add -- no a_0, no multiplies.
+        //   SQ: the ps_r squarings follow.  vc: fetch the c-form borders of Cm and acc, which only the squarings and the first slice
+        //     of a segment read (a constant at every call but the run-time-K one).
+        auto slice_exp = [&](int t, auto deg6_tag, auto k_tag, auto weighted_tag, auto sq_tag, bool vc, SM& Cm, SM& acc) {
           constexpr bool DEG6 = decltype(deg6_tag)::value;  // true = the degree-6 pair, false = the degree-8 pair
           constexpr int KC = decltype(k_tag)::value;        // K at compile time (0 .. 2); -1 = the run-time loop over the tables
+          constexpr bool WEIGHTED = decltype(weighted_tag)::value, SQ = decltype(sq_tag)::value;
+          static_assert(WEIGHTED || (KC >= 0 && !SQ), "the unweighted drift is the form of compile-time K without squarings");
           const double* ap = sg + lp.b * SG;
-          for (int t = 0; t < tmax; ++t) {
-            SM Y;
-            {
-              // (K = 0 has no amplitude rows: the drift weight comes from the slot's mask)
-              const double a0 = KC == 0 ? ((valid && t < len) ? -rscale : 0.0) : ap[K * A.Lmax + t];
+          SM Y;
+          if constexpr (WEIGHTED) {
+            // (K = 0 has no amplitude rows: the drift weight comes from the slot's mask)
+            const double a0 = (KC == 0 || (KC < 0 && K == 0)) ? ((valid && t < len) ? -rscale : 0.0) : ap[K * A.Lmax + t];
 #pragma unroll
-              for (int I = 0; I < NC; ++I) {
+            for (int I = 0; I < NC; ++I) {
 #pragma unroll
-                for (int J = 0; J < NC; ++J) Y.m[I][J] = a0 * lds_ld(tab + so[I] + J * 4);
-                Y.vr[I] = a0 * lds_ld(tab + sro[I]);
-                Y.vc[I] = a0 * lds_ld(tab + sco[I]);
-              }
-              Y.s = a0 * lds_ld(tab + sso);
+              for (int J = 0; J < NC; ++J) Y.m[I][J] = a0 * lds_ld(tab + so[I] + J * 4);
+              Y.vr[I] = a0 * lds_ld(tab + sro[I]);
+              Y.vc[I] = a0 * lds_ld(tab + sco[I]);
             }
-            auto add_table = [&](int k) {
-              const double ak = ap[k * A.Lmax + t];
-              const double* tk = tab + (k + 1) * (MAT + 4);
+            Y.s = a0 * lds_ld(tab + sso);
+          } else if constexpr (KC == 0) {
 #pragma unroll
-              for (int I = 0; I < NC; ++I) {
+            for (int I = 0; I < NC; ++I) {
 #pragma unroll
-                for (int J = 0; J < NC; ++J) Y.m[I][J] = fma(ak, lds_ld(tk + so[I] + J * 4), Y.m[I][J]);
-                Y.vr[I] = fma(ak, lds_ld(tk + sro[I]), Y.vr[I]);
-                Y.vc[I] = fma(ak, lds_ld(tk + sco[I]), Y.vc[I]);
-              }
-              Y.s = fma(ak, lds_ld(tk + sso), Y.s);
-            };
-            if constexpr (KC >= 0) {
-#pragma unroll
-              for (int k = 0; k < KC; ++k) add_table(k);
-            } else {
-              for (int k = 0; k < K; ++k) add_table(k);
+              for (int J = 0; J < NC; ++J) Y.m[I][J] = -lds_ld(tab + so[I] + J * 4);
+              Y.vr[I] = -lds_ld(tab + sro[I]);
+              Y.vc[I] = -lds_ld(tab + sco[I]);
             }
-            SM W1, W2, W3, Cm, Sp, acc, acs;
-            s8_zero(W1), s8_zero(W2), s8_zero(W3);
-            mm_s8(Y, Y, W1);  // W = Y^2
-            s8_finish(W1, swap_lane, tail_lane);
-            mm_s8(W1, W1, W2);  // W^2
-            s8_finish(W2, swap_lane, tail_lane);
-            // The Horner factors are the LEFT operands of the paired product (everything commutes): they are combined on the 6
-            // registers a product accumulates into (upper core tiles, r-form border, corner) and completed by ONE lane swap each;
-            // the shared right operand (W^3 / W^4) is completed in full; a power that is never a product operand is not completed.
-            if constexpr (DEG6) {
-              // degree 6: cos = (c0 + c1 W + c2 W^2) + W^3 (c3 + c4 W + c5 W^2 + c6 W^3)
-              mm_s8(W1, W2, W3);
-              s8_finish(W3, swap_lane, tail_lane);
-              s8_comb<NC, true, true>(acc, c3p_mm6_cos[3], c3p_mm6_cos[4], c3p_mm6_cos[5], c3p_mm6_cos[6], W1, W2, W3, lp);
-              s8_comb<NC, true, true>(acs, c3p_mm6_sinc[3], c3p_mm6_sinc[4], c3p_mm6_sinc[5], c3p_mm6_sinc[6], W1, W2, W3, lp);
-              s8_finish_lower(acc, swap_lane);
-              s8_finish_lower(acs, swap_lane);
-              s8_comb<NC, false, true>(Cm, c3p_mm6_cos[0], c3p_mm6_cos[1], c3p_mm6_cos[2], 0.0, W1, W2, W3, lp);
-              s8_comb<NC, false, true>(Sp, c3p_mm6_sinc[0], c3p_mm6_sinc[1], c3p_mm6_sinc[2], 0.0, W1, W2, W3, lp);
-              mm_s8x2r(acc, acs, W3, Cm, Sp);  // Cm = cos Y, Sp = sin(Y) / Y
-            } else {
-              // degree 8: cos = (c0 + c1 W + c2 W^2 + c3 W^3) + W^4 (c4 + c5 W + c6 W^2 + c7 W^3 + c8 W^4); W^3 is not a product operand
-              SM W4;
-              s8_zero(W4);
-              mm_s8(W1, W2, W3);
-              mm_s8(W2, W2, W4);
-              s8_finish(W4, swap_lane, tail_lane);
-              s8_comb<NC, true, true>(acc, c3p_mm8_cos[4], c3p_mm8_cos[5], c3p_mm8_cos[6], c3p_mm8_cos[7], W1, W2, W3, lp);
-              s8_comb<NC, true, true>(acs, c3p_mm8_sinc[4], c3p_mm8_sinc[5], c3p_mm8_sinc[6], c3p_mm8_sinc[7], W1, W2, W3, lp);
+            Y.s = -lds_ld(tab + sso);
+          } else {
+            const double a1 = ap[t];
+            const double* t1 = tab + (MAT + 4);
 #pragma unroll
-              for (int I = 0; I < NC; ++I) {
+            for (int I = 0; I < NC; ++I) {
 #pragma unroll
-                for (int J = I; J < NC; ++J) {
-                  acc.m[I][J] = fma(c3p_mm8_cos[8], W4.m[I][J], acc.m[I][J]);
-                  acs.m[I][J] = fma(c3p_mm8_sinc[8], W4.m[I][J], acs.m[I][J]);
-                }
-                acc.vr[I] = fma(c3p_mm8_cos[8], W4.vr[I], acc.vr[I]);
-                acs.vr[I] = fma(c3p_mm8_sinc[8], W4.vr[I], acs.vr[I]);
-              }
-              acc.s = fma(c3p_mm8_cos[8], W4.s, acc.s);
-              acs.s = fma(c3p_mm8_sinc[8], W4.s, acs.s);
-              s8_finish_lower(acc, swap_lane);
-              s8_finish_lower(acs, swap_lane);
-              s8_comb<NC, true, true>(Cm, c3p_mm8_cos[0], c3p_mm8_cos[1], c3p_mm8_cos[2], c3p_mm8_cos[3], W1, W2, W3, lp);
-              s8_comb<NC, true, true>(Sp, c3p_mm8_sinc[0], c3p_mm8_sinc[1], c3p_mm8_sinc[2], c3p_mm8_sinc[3], W1, W2, W3, lp);
-              mm_s8x2r(acc, acs, W4, Cm, Sp);  // Cm = cos Y, Sp = sin(Y) / Y
+              for (int J = 0; J < NC; ++J) Y.m[I][J] = fma(a1, lds_ld(t1 + so[I] + J * 4), -lds_ld(tab + so[I] + J * 4));
+              Y.vr[I] = fma(a1, lds_ld(t1 + sro[I]), -lds_ld(tab + sro[I]));
+              Y.vc[I] = fma(a1, lds_ld(t1 + sco[I]), -lds_ld(tab + sco[I]));
             }
-            // cos Y, sin Y / Y and sin Y are LEFT operands from here on (sin Y = (sin Y / Y) Y, the chain step): lower tiles only;
-            // their c-form borders are only fetched for the squarings and the first slice of a segment
-            s8_finish_lower(Cm, swap_lane);
-            s8_finish_lower(Sp, swap_lane);
-            s8_zero(acc);
-            mm_s8(Sp, Y, acc);  // acc = sin Y
+            Y.s = fma(a1, lds_ld(t1 + sso), -lds_ld(tab + sso));
+          }
+          auto add_table = [&](int k) {
+            const double ak = ap[k * A.Lmax + t];
+            const double* tk = tab + (k + 1) * (MAT + 4);
+#pragma unroll
+            for (int I = 0; I < NC; ++I) {
+#pragma unroll
+              for (int J = 0; J < NC; ++J) Y.m[I][J] = fma(ak, lds_ld(tk + so[I] + J * 4), Y.m[I][J]);
+              Y.vr[I] = fma(ak, lds_ld(tk + sro[I]), Y.vr[I]);
+              Y.vc[I] = fma(ak, lds_ld(tk + sco[I]), Y.vc[I]);
+            }
+            Y.s = fma(ak, lds_ld(tk + sso), Y.s);
+          };
+          if constexpr (KC >= 0) {
+#pragma unroll
+            for (int k = WEIGHTED ? 0 : 1; k < KC; ++k) add_table(k);
+          } else {
+            for (int k = 0; k < K; ++k) add_table(k);
+          }
+          SM W1, W2, W3, Sp, acs;
+          s8_zero(W1), s8_zero(W2), s8_zero(W3);
+          mm_s8(Y, Y, W1);  // W = Y^2
+          s8_finish(W1, swap_lane, tail_lane);
+          mm_s8(W1, W1, W2);  // W^2
+          s8_finish(W2, swap_lane, tail_lane);
+          // The Horner factors are the LEFT operands of the paired product (everything commutes): they are combined on the 6
+          // registers a product accumulates into (upper core tiles, r-form border, corner) and completed by ONE lane swap each;
+          // the shared right operand (W^3 / W^4) is completed in full; a power that is never a product operand is not completed.
+          if constexpr (DEG6) {
+            // degree 6: cos = (c0 + c1 W + c2 W^2) + W^3 (c3 + c4 W + c5 W^2 + c6 W^3)
+            mm_s8(W1, W2, W3);
+            s8_finish(W3, swap_lane, tail_lane);
+            s8_comb<NC, true, true>(acc, c3p_mm6_cos[3], c3p_mm6_cos[4], c3p_mm6_cos[5], c3p_mm6_cos[6], W1, W2, W3, lp);
+            s8_comb<NC, true, true>(acs, c3p_mm6_sinc[3], c3p_mm6_sinc[4], c3p_mm6_sinc[5], c3p_mm6_sinc[6], W1, W2, W3, lp);
             s8_finish_lower(acc, swap_lane);
-            if (ps_r > 0 || t == 0) {
-              s8_finish_vc(Cm, tail_lane);
-              s8_finish_vc(acc, tail_lane);
+            s8_finish_lower(acs, swap_lane);
+            s8_comb<NC, false, true>(Cm, c3p_mm6_cos[0], c3p_mm6_cos[1], c3p_mm6_cos[2], 0.0, W1, W2, W3, lp);
+            s8_comb<NC, false, true>(Sp, c3p_mm6_sinc[0], c3p_mm6_sinc[1], c3p_mm6_sinc[2], 0.0, W1, W2, W3, lp);
+            mm_s8x2r(acc, acs, W3, Cm, Sp);  // Cm = cos Y, Sp = sin(Y) / Y
+          } else {
+            // degree 8: cos = (c0 + c1 W + c2 W^2 + c3 W^3) + W^4 (c4 + c5 W + c6 W^2 + c7 W^3 + c8 W^4); W^3 is not a product operand
+            SM W4;
+            s8_zero(W4);
+            mm_s8(W1, W2, W3);
+            mm_s8(W2, W2, W4);
+            s8_finish(W4, swap_lane, tail_lane);
+            s8_comb<NC, true, true>(acc, c3p_mm8_cos[4], c3p_mm8_cos[5], c3p_mm8_cos[6], c3p_mm8_cos[7], W1, W2, W3, lp);
+            s8_comb<NC, true, true>(acs, c3p_mm8_sinc[4], c3p_mm8_sinc[5], c3p_mm8_sinc[6], c3p_mm8_sinc[7], W1, W2, W3, lp);
+#pragma unroll
+            for (int I = 0; I < NC; ++I) {
+#pragma unroll
+              for (int J = I; J < NC; ++J) {
+                acc.m[I][J] = fma(c3p_mm8_cos[8], W4.m[I][J], acc.m[I][J]);
+                acs.m[I][J] = fma(c3p_mm8_sinc[8], W4.m[I][J], acs.m[I][J]);
+              }
+              acc.vr[I] = fma(c3p_mm8_cos[8], W4.vr[I], acc.vr[I]);
+              acs.vr[I] = fma(c3p_mm8_sinc[8], W4.vr[I], acs.vr[I]);
             }
-            // squarings: cos 2Y = (C - S)(C + S), sin 2Y = 2 S C
+            acc.s = fma(c3p_mm8_cos[8], W4.s, acc.s);
+            acs.s = fma(c3p_mm8_sinc[8], W4.s, acs.s);
+            s8_finish_lower(acc, swap_lane);
+            s8_finish_lower(acs, swap_lane);
+            s8_comb<NC, true, true>(Cm, c3p_mm8_cos[0], c3p_mm8_cos[1], c3p_mm8_cos[2], c3p_mm8_cos[3], W1, W2, W3, lp);
+            s8_comb<NC, true, true>(Sp, c3p_mm8_sinc[0], c3p_mm8_sinc[1], c3p_mm8_sinc[2], c3p_mm8_sinc[3], W1, W2, W3, lp);
+            mm_s8x2r(acc, acs, W4, Cm, Sp);  // Cm = cos Y, Sp = sin(Y) / Y
+          }
+          // cos Y, sin Y / Y and sin Y are LEFT operands from here on (sin Y = (sin Y / Y) Y, the chain step): lower tiles only;
+          // their c-form borders are only fetched for the squarings and the first slice of a segment
+          s8_finish_lower(Cm, swap_lane);
+          s8_finish_lower(Sp, swap_lane);
+          s8_zero(acc);
+          mm_s8(Sp, Y, acc);  // acc = sin Y
+          s8_finish_lower(acc, swap_lane);
+          if (vc) {
+            s8_finish_vc(Cm, tail_lane);
+            s8_finish_vc(acc, tail_lane);
+          }
+          // squarings: cos 2Y = (C - S)(C + S), sin 2Y = 2 S C
+          if constexpr (SQ) {
             for (int it = 0; it < ps_r; ++it) {
               SM Dm, Sm, C2, SC;
 #pragma unroll
@@ -1487,34 +1521,60 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
               s8_finish(Cm, swap_lane, tail_lane);
               s8_finish(acc, swap_lane, tail_lane);
             }
-            if (t == 0) {  // U <- E = C - i S
-#pragma unroll
-              for (int I = 0; I < NC; ++I) {
-#pragma unroll
-                for (int J = 0; J < NC; ++J) {
-                  Gr.m[I][J] = Cm.m[I][J];
-                  Gi.m[I][J] = -acc.m[I][J];
-                }
-                Gr.cr[I] = Cm.vr[I], Gr.cc[I] = Cm.vc[I], Gr.rc[I] = Cm.vc[I];
-                Gi.cr[I] = -acc.vr[I], Gi.cc[I] = -acc.vc[I], Gi.rc[I] = -acc.vc[I];
-              }
-              Gr.s = Cm.s;
-              Gi.s = -acc.s;
-            } else {
-              chain_step8(Cm, acc, Gr, Gi, lp, tail_lane, row0_lane);
-            }
           }
         };
-        // (both choices are made per segment OUTSIDE the slice loop; K > 2 keeps the run-time loop over the tables)
+        // The slices t0 .. t1 - 1 of a segment whose first slice is in the state: exponential + chain step, one basic block per slice
+        auto step_loop = [&](int t0, int t1, auto deg6_tag, auto k_tag, auto weighted_tag, auto sq_tag, bool vc) {
+          for (int t = t0; t < t1; ++t) {
+            SM Cm, acc;
+            slice_exp(t, deg6_tag, k_tag, weighted_tag, sq_tag, vc, Cm, acc);
+            chain_step8(Cm, acc, Gr, Gi, lp, tail_lane, row0_lane);
+          }
+        };
+        // All choices are made per segment OUTSIDE the slice loop.  The first slice is peeled: U <- E = C - i S, the one place a
+        // segment without squarings needs the c-form borders; it goes through the weighted run-time-K form (once per segment, and a
+        // single copy per degree).  Then, with compile-time K = 0 .. 2:
+        //   ps_r == 0: the slots that are real for the whole wave in the unweighted form without squarings; a padded last slot is
+        //              left to the weighted run-time-K loop (a_0 = 0 where the chain has ended);
+        //   ps_r > 0:  the weighted form with its squarings.
+        // K > 2 keeps the weighted run-time loop over the tables for either (one copy per degree, zero trips otherwise).
         auto split_loop_k = [&](auto deg6_tag) {
+          constexpr std::true_type yes{};
+          constexpr std::false_type no{};
+          constexpr std::integral_constant<int, -1> krt{};
+          {
+            SM Cm, acc;
+            slice_exp(0, deg6_tag, krt, yes, yes, true, Cm, acc);
+#pragma unroll
+            for (int I = 0; I < NC; ++I) {
+#pragma unroll
+              for (int J = 0; J < NC; ++J) {
+                Gr.m[I][J] = Cm.m[I][J];
+                Gi.m[I][J] = -acc.m[I][J];
+              }
+              Gr.cr[I] = Cm.vr[I], Gr.cc[I] = Cm.vc[I], Gr.rc[I] = Cm.vc[I];
+              Gi.cr[I] = -acc.vr[I], Gi.cc[I] = -acc.vc[I], Gi.rc[I] = -acc.vc[I];
+            }
+            Gr.s = Cm.s;
+            Gi.s = -acc.s;
+          }
+          int t0 = 1;  // first slot left to the run-time-K loop
+          auto split_loop = [&](auto k_tag) {
+            if (ps_r == 0) {
+              step_loop(1, tfast, deg6_tag, k_tag, no, no, false);
+              t0 = max(tfast, 1);
+            } else {
+              step_loop(1, tmax, deg6_tag, k_tag, yes, yes, true);
+              t0 = tmax;
+            }
+          };
           if (K == 2)
-            split_loop(deg6_tag, std::integral_constant<int, 2>{});
+            split_loop(std::integral_constant<int, 2>{});
           else if (K == 1)
-            split_loop(deg6_tag, std::integral_constant<int, 1>{});
+            split_loop(std::integral_constant<int, 1>{});
           else if (K == 0)
-            split_loop(deg6_tag, std::integral_constant<int, 0>{});
-          else
-            split_loop(deg6_tag, std::integral_constant<int, -1>{});
+            split_loop(std::integral_constant<int, 0>{});
+          step_loop(t0, tmax, deg6_tag, krt, yes, yes, ps_r > 0);
         };
         if (deg6)
           split_loop_k(std::true_type{});
