@@ -343,6 +343,16 @@ static inline bool tiled_unitary_grad(int D, int B) {
   return valu > tiled;
 }
 
+// Segments per sample of the VALU backward sweeps (c3p_grad.hip, unitary and general form): one workgroup per (sample, segment),
+// 4096 of them in flight, and at least eight slices per segment.  valu_grad_segments pins the count (tests), clamped to 1 .. N: an
+// empty segment would make grad_seg_kernel write out a buffer it never filled.
+static inline long valu_grad_segments(int B, int N) {
+  long S = 4096 / B;
+  if (S > N / 8) S = N / 8;
+  if (c3p_opt(C3P_OPT_valu_grad_segments) > 0) S = std::min<long>(c3p_opt(C3P_OPT_valu_grad_segments), N);
+  return S < 1 ? 1 : S;
+}
+
 // One piecewise-constant call after staging: device pointers and sizes.  A batch stride of 0 means one operator set shared
 // by all samples.  Every runner below takes this record; the sample chunks of the gradient entry points are cut here only.
 struct PwcProblem {
@@ -2886,9 +2896,7 @@ static int run_vjp_lind_valu(DeviceWs* w, const PwcProblem& P, const cplx* ub, d
   A.signals = P.signals;
   A.dt = P.dt;
   A.grad = grad;
-  long S = 4096 / nb;
-  if (S > N / 8) S = N / 8;
-  if (S < 1) S = 1;
+  const long S = valu_grad_segments(nb, N);
   void *sv, *mv, *v;
   SweepStore ss;
   if (ws_get(w, SL_SEG_A, (size_t)nb * S * gsz * cs, &sv)) return -1;
@@ -3609,10 +3617,7 @@ static int unitary_vjp_branch_a(const void* h0, int64_t h0_bstride, const void* 
   }
   if (!done && D > 64) return fail("the VALU gradient kernels support D <= 64, got %d", D);
   if (!done) {
-    long S = 4096 / B;
-    if (S > N / 8) S = N / 8;
-    if (S < 1) S = 1;
-    A.S = (int)S;
+    A.S = (int)valu_grad_segments(B, N);
     void* v;
     if (ws_get(w, SL_SEG_A, (size_t)B * A.S * D * D * cs, &v)) return -1;
     A.seg = (cplx*)v;

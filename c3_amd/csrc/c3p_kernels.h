@@ -44,7 +44,8 @@
   X(ode_no_seg)         /* ODE: no time segments for small final-state batches */                                     \
   X(ode_no_split)       /* ODE: rho-valued states with K > 4: lane-row kernel whatever the operators are (no device-side split) */ \
   X(ode_lind_wg)        /* ODE: Lindblad steps at 33 <= D <= 48 on the workgroup kernel of round 1 (A/B: not the matrix-core one) */ \
-  X(tiled_chunk)        /* tiled path: at most this many samples per chunk (forward and sweep) */
+  X(tiled_chunk)        /* tiled path: at most this many samples per chunk (forward and sweep) */                      \
+  X(valu_grad_segments) /* VALU backward sweeps (c3p_grad.hip): segments per sample, clamped to 1 .. N (tests) */
 
 enum C3pOption {
 #define C3P_OPT_ENUM(n) C3P_OPT_##n,

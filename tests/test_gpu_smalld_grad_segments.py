@@ -232,12 +232,14 @@ GOAL = {9: ([3, 3], [0, 1]), 3: ([3], [0])}  # D -> (dims, index)
 
 
 @functools.lru_cache(maxsize=None)
-def goal_case(D):
-    h0, hks, sig, dt, _, _ = unitary_case(D, "real", 1.5, False)
+def goal_case(D, key=None, goal=None):
+    """(key, goal: the unitary_case key and the (dims, index) of a dimension GOAL does not list, set by
+    tests/test_gpu_valu_grad_sweep.py; left at None they change nothing)"""
+    h0, hks, sig, dt, _, _ = unitary_case(*((D, "real", 1.5, False) if key is None else key))
     rng = np.random.default_rng(7500 + D)
-    L = 2 ** len(GOAL[D][1])
+    L = 2 ** len((GOAL[D] if goal is None else goal)[1])
     q, _ = np.linalg.qr(rng.normal(size=(L, L)) + 1j * rng.normal(size=(L, L)))
-    ph = rng.uniform(0, 6, size=(B, D))
+    ph = rng.uniform(0, 6, size=(sig.shape[0], D))
     return h0, hks, sig, dt, _frozen(q), _frozen(ph)
 
 
