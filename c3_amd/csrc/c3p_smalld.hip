@@ -508,7 +508,8 @@ __device__ __forceinline__ void rcomb(double (&out)[RD<D>::NB][RD<D>::NB], doubl
 // at all) and the last row / column / corner are carried separately, per chain, in the lanes of its MFMA block:
 //   symmetric matrix (SMat): core tiles (upper, lower mirrored for operands), the border column twice -- vr[I] = M[4I+r][D-1]
 //     (replicated over c) and vc[J] = M[4J+c][D-1] (replicated over r) --, the corner s (all 16 lanes);
-//   general matrix (GMat, the chain state): core, column border cr (r form) / cc (c form), row border rc[J] = M[D-1][4J+c], s.
+//   general matrix (GMat, the chain state): core and row border rc[J] = M[D-1][4J+c] of the real and of the imaginary part; the column
+//     border and the corner of the complex state as ONE packed register each (GBorder).
 // Border of a product: column = core x vector on the vector unit (one FMA per tile and lane + a quad reduction by DPP),
 // its c form by one lane swap; corner = dot product (quad reduction); the ROW border of a chain product is a vector-matrix
 // product whose sum runs over the r lanes (16 apart: no DPP reach) -- it stayed on the matrix cores as ONE A tile per K-step
@@ -526,9 +527,28 @@ struct SMat {
 template <int NC>
 struct GMat {
   double m[NC][NC];
-  double cr[NC], cc[NC], rc[NC];
-  double s;
+  double rc[NC];
 };
+// Column border and corner of the chain state U = Ur + i Ui, PACKED: Re and Im dealt over the quad index c of the lane, one register
+// holding {Re, Im, -Re, -Im} in the lanes c = 0 .. 3 (chain_step8 below)
+template <int NC>
+struct GBorder {
+  double Pc[NC];  // lane (r, c): {Ur, Ui, -Ur, -Ui}[4K+r][D-1] for c = 0 .. 3
+  double Ps;      // lane (r, c): {Ur, Ui, -Ur, -Ui}[D-1][D-1], replicated over r
+};
+// the packed value of a lane from the real and imaginary parts it holds
+__device__ __forceinline__ double border_pack(double re, double im, int c) {
+  const double v = (c & 1) ? im : re;
+  return (c & 2) ? -v : v;
+}
+// quad rotation, lane c reads lane (c + 1) mod 4 of its quad: {Re, Im, -Re, -Im} -> {Im, -Re, -Im, Re}, -i times the packed vector.
+// DPP quad_perm [1,2,3,0], no sign flips and no LDS
+__device__ __forceinline__ double quad_rot1(double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_mov_dpp(lo, 0x39, 0xf, 0xf, true);
+  hi = __builtin_amdgcn_mov_dpp(hi, 0x39, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
 
 template <int NC>
 __device__ __forceinline__ void s8_zero(SMat<NC>& a) {
@@ -706,18 +726,24 @@ __device__ __forceinline__ void s8_comb(SMat<NC>& out, double c0, double c1, dou
 // Core (the NC x NC tiles, on the matrix cores): three real products, T1 = C Ur, T2 = S Ui, T3 = (C - S)(Ur + Ui), Re = T1 + T2,
 // Im = T3 - T1 + T2.  The rank-1 term of the border (column of the left operand times row of the state) is the initial value of the
 // three accumulators, in the same 3M form.
-// Border (row, column, corner): 3M saves a product on the matrix cores only -- on the vector unit add, mul and fma cost the same, so the
-// border uses the direct form Re = C Ur + S Ui, Im = C Ui - S Ur as fma chains.  No lane swaps, no DPP reductions: every border sum
-// has its sum index on r (for the symmetric left operand: its transposed tile, or its r-form border vr, which is also its border row)
-// and is reduced by ONE matrix instruction against a tile of ones, the k = D-1 term riding in as the accumulator:
-//   column, corner: A = partials, B = 1 -> D[i][j] = sum_r t(r, c = i), the r form replicated over c (cr, s; see mm_s8);
-//   row:            A = 1, B = partials -> D[i][j] = sum_r t(r, c = j), the c form replicated over r (rc).
+// Row border: 3M saves a product on the matrix cores only -- on the vector unit add, mul and fma cost the same, so the row border uses
+// the direct form Re = C Ur + S Ui, Im = C Ui - S Ur as fma chains.  No lane swaps, no DPP reductions: the sum index is on r (the r-form
+// border vr of the symmetric left operand is also its border row) and ONE matrix instruction against a tile of ones reduces it, the
+// k = D-1 term riding in as the accumulator: A = 1, B = partials -> D[i][j] = sum_r t(r, c = j), the c form replicated over r (rc).
+// Column border and corner: the packed registers of GBorder ARE a right-operand tile whose four columns are {u, -i u, -u, i u} read as
+// real pairs, and the quad rotation Q of a packed register P is -i P.  So column c of C P + S Q is {C ur + S ui, C ui - S ur, -, -} =
+// {Re', Im', -Re', -Im'}, the packed form again:
+//   Pc'[I] = sum_K mfma(C.m[K][I], Pc[K]) + mfma(S.m[K][I], Qc[K])    accumulator C.vr[I] Ps + S.vr[I] Qs (the k = D-1 term)
+//   Ps'    = mfma(1, sum_K C.vr[K] Pc[K] + S.vr[K] Qc[K], C.s Ps + S.s Qs)   (ones as A: column sums, replicated over r)
+// The state stays packed from slice to slice; only the rotations are formed per step, at the head of the step.
 // Every right-hand side reads the old state; every vector operation that feeds a matrix instruction is issued before the first one
 // (a vector instruction that reads a matrix result waits ~45 cycles, the other way round costs two wait states).
 template <int NC>
-__device__ __forceinline__ void chain_step8(const SMat<NC>& Cc, const SMat<NC>& Sc, GMat<NC>& Ur, GMat<NC>& Ui, const LanePos& lp,
-                                            int tail_lane, int row0_lane) {
-  (void)lp, (void)tail_lane, (void)row0_lane;
+__device__ __forceinline__ void chain_step8(const SMat<NC>& Cc, const SMat<NC>& Sc, GMat<NC>& Ur, GMat<NC>& Ui, GBorder<NC>& Ub) {
+  double Qc[NC];
+#pragma unroll
+  for (int K = 0; K < NC; ++K) Qc[K] = quad_rot1(Ub.Pc[K]);
+  const double Qs = quad_rot1(Ub.Ps);
   double Dm[NC][NC], Us[NC][NC], T1[NC][NC], T2[NC][NC], T3[NC][NC];
 #pragma unroll
   for (int I = 0; I < NC; ++I)
@@ -761,57 +787,39 @@ __device__ __forceinline__ void chain_step8(const SMat<NC>& Cc, const SMat<NC>& 
     ar[J] = fma(Sc.s, Ui.rc[J], Cc.s * Ur.rc[J]);
     ai[J] = fma(-Sc.s, Ur.rc[J], Cc.s * Ui.rc[J]);
   }
-  // column border, lane (r, c): sum_K M[4I+c][4K+r] U[4K+r][D-1]; accumulator M[4I+r][D-1] U[D-1][D-1]
-  // corner: sum_I M[D-1][4I+r] U[4I+r][D-1]; accumulator M[D-1][D-1] U[D-1][D-1]
-  double pr[NC], pi[NC], qr[NC], qi[NC];
-  double cr_ = Cc.vr[0] * Ur.cr[0], ci_ = Cc.vr[0] * Ui.cr[0];
+  // column border, packed: the k = D-1 term M[4I+r][D-1] U[D-1][D-1] as the accumulator of the tile products below
+  // corner, lane (r, c): sum_K M[D-1][4K+r] U[4K+r][D-1] of column c; accumulator M[D-1][D-1] U[D-1][D-1]
+  double Pn[NC];
 #pragma unroll
-  for (int I = 0; I < NC; ++I) {
-    pr[I] = Cc.m[0][I] * Ur.cr[0];
-    pi[I] = Cc.m[0][I] * Ui.cr[0];
+  for (int I = 0; I < NC; ++I) Pn[I] = fma(Sc.vr[I], Qs, Cc.vr[I] * Ub.Ps);
+  double ts = Cc.vr[0] * Ub.Pc[0];
 #pragma unroll
-    for (int K = 1; K < NC; ++K) {
-      pr[I] = fma(Cc.m[K][I], Ur.cr[K], pr[I]);
-      pi[I] = fma(Cc.m[K][I], Ui.cr[K], pi[I]);
-    }
+  for (int K = 1; K < NC; ++K) ts = fma(Cc.vr[K], Ub.Pc[K], ts);
 #pragma unroll
-    for (int K = 0; K < NC; ++K) {
-      pr[I] = fma(Sc.m[K][I], Ui.cr[K], pr[I]);
-      pi[I] = fma(-Sc.m[K][I], Ur.cr[K], pi[I]);
-    }
-    qr[I] = fma(Sc.vr[I], Ui.s, Cc.vr[I] * Ur.s);
-    qi[I] = fma(-Sc.vr[I], Ur.s, Cc.vr[I] * Ui.s);
-    if (I > 0) {
-      cr_ = fma(Cc.vr[I], Ur.cr[I], cr_);
-      ci_ = fma(Cc.vr[I], Ui.cr[I], ci_);
-    }
-  }
-#pragma unroll
-  for (int I = 0; I < NC; ++I) {
-    cr_ = fma(Sc.vr[I], Ui.cr[I], cr_);
-    ci_ = fma(-Sc.vr[I], Ur.cr[I], ci_);
-  }
-  const double er = fma(Sc.s, Ui.s, Cc.s * Ur.s), ei = fma(-Sc.s, Ur.s, Cc.s * Ui.s);
-  // the matrix instructions: core, then the border reductions straight into the state
+  for (int K = 0; K < NC; ++K) ts = fma(Sc.vr[K], Qc[K], ts);
+  const double es = fma(Sc.s, Qs, Cc.s * Ub.Ps);
+  // the matrix instructions: core and column border, then the border reductions straight into the state
 #pragma unroll
   for (int K = 0; K < NC; ++K)
 #pragma unroll
-    for (int I = 0; I < NC; ++I)
+    for (int I = 0; I < NC; ++I) {
+      Pn[I] = mfma4(Cc.m[K][I], Ub.Pc[K], Pn[I]);
 #pragma unroll
       for (int J = 0; J < NC; ++J) {
         T1[I][J] = mfma4(Cc.m[K][I], Ur.m[K][J], T1[I][J]);
         T2[I][J] = mfma4(Sc.m[K][I], Ui.m[K][J], T2[I][J]);
         T3[I][J] = mfma4(Dm[K][I], Us[K][J], T3[I][J]);
       }
+      Pn[I] = mfma4(Sc.m[K][I], Qc[K], Pn[I]);
+    }
 #pragma unroll
   for (int I = 0; I < NC; ++I) {
     Ur.rc[I] = mfma4(1.0, tr[I], ar[I]);
     Ui.rc[I] = mfma4(1.0, ti[I], ai[I]);
-    Ur.cr[I] = mfma4(pr[I], 1.0, qr[I]);
-    Ui.cr[I] = mfma4(pi[I], 1.0, qi[I]);
   }
-  Ur.s = mfma4(cr_, 1.0, er);
-  Ui.s = mfma4(ci_, 1.0, ei);
+  Ub.Ps = mfma4(1.0, ts, es);
+#pragma unroll
+  for (int I = 0; I < NC; ++I) Ub.Pc[I] = Pn[I];
 #pragma unroll
   for (int I = 0; I < NC; ++I)
 #pragma unroll
@@ -1320,7 +1328,8 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
         static_assert(!SPLIT || (D % 4 == 1 && D > 4 && !DUS), "core + border form: D = 5, 9 without slice output");
         constexpr int NC = (D - 1) / 4;
         typedef SMat<NC> SM;
-        GMat<NC> Gr, Gi;  // the chain state
+        GMat<NC> Gr, Gi;  // the chain state: core and row border in real blocks,
+        GBorder<NC> Gb;   // column border and corner packed
         int so[NC], sro[NC], sco[NC];
 #pragma unroll
         for (int I = 0; I < NC; ++I) {
@@ -1528,7 +1537,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
           for (int t = t0; t < t1; ++t) {
             SM Cm, acc;
             slice_exp(t, deg6_tag, k_tag, weighted_tag, sq_tag, vc, Cm, acc);
-            chain_step8(Cm, acc, Gr, Gi, lp, tail_lane, row0_lane);
+            chain_step8(Cm, acc, Gr, Gi, Gb);
           }
         };
         // All choices are made per segment OUTSIDE the slice loop.  The first slice is peeled: U <- E = C - i S, the one place a
@@ -1552,11 +1561,11 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
                 Gr.m[I][J] = Cm.m[I][J];
                 Gi.m[I][J] = -acc.m[I][J];
               }
-              Gr.cr[I] = Cm.vr[I], Gr.cc[I] = Cm.vc[I], Gr.rc[I] = Cm.vc[I];
-              Gi.cr[I] = -acc.vr[I], Gi.cc[I] = -acc.vc[I], Gi.rc[I] = -acc.vc[I];
+              Gr.rc[I] = Cm.vc[I];
+              Gi.rc[I] = -acc.vc[I];
+              Gb.Pc[I] = border_pack(Cm.vr[I], -acc.vr[I], lp.c);
             }
-            Gr.s = Cm.s;
-            Gi.s = -acc.s;
+            Gb.Ps = border_pack(Cm.s, -acc.s, lp.c);
           }
           int t0 = 1;  // first slot left to the run-time-K loop
           auto split_loop = [&](auto k_tag) {
@@ -1594,19 +1603,14 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
             img[lp.b * IMG + (2 * i) * W + 4 * J + lp.c] = Gr.m[I][J];
             img[lp.b * IMG + (2 * i + 1) * W + 4 * J + lp.c] = Gi.m[I][J];
           }
-          if (lp.c == 0) {
-            img[lp.b * IMG + (2 * i) * W + D - 1] = Gr.cr[I];
-            img[lp.b * IMG + (2 * i + 1) * W + D - 1] = Gi.cr[I];
-          }
+          // (packed column border: the lanes c = 0 and c = 1 hold Re and Im)
+          if (lp.c < 2) img[lp.b * IMG + (2 * i + lp.c) * W + D - 1] = Gb.Pc[I];
           if (lp.r == 0) {
             img[lp.b * IMG + (2 * (D - 1)) * W + 4 * I + lp.c] = Gr.rc[I];
             img[lp.b * IMG + (2 * (D - 1) + 1) * W + 4 * I + lp.c] = Gi.rc[I];
           }
         }
-        if (lp.idx16 == 0) {
-          img[lp.b * IMG + (2 * (D - 1)) * W + D - 1] = Gr.s;
-          img[lp.b * IMG + (2 * (D - 1) + 1) * W + D - 1] = Gi.s;
-        }
+        if (lp.r == 0 && lp.c < 2) img[lp.b * IMG + (2 * (D - 1) + lp.c) * W + D - 1] = Gb.Ps;
         wave_sync();
 #pragma unroll
         for (int I = 0; I < NBI; ++I)
@@ -2396,7 +2400,9 @@ hipError_t launch_chain_t(const SmallArgs& A, hipStream_t st) {
         // (the complex loop of the same kernel keeps 640: profiles/r06/sweep_skew_complex.txt -- its samples re-split on the device)
         // (D = 9 with the column-wise norm bound -- no workgroup of cfg2 on the seven-product loop any more: 704, long segments of
         // 44 slices instead of 43, 0.6 us faster than 700 in every run of profiles/r09/sweep_skew.json; D = 5 was not re-swept)
-        int skew = ((D == 9 || D == 5) && !c3p_opt_on(C3P_OPT_no_split81)) ? (D == 9 ? 704 : 700) : 640, skew_c = 640;
+        // (re-swept on the loop with the no-squaring body and the packed column border: D = 9 736, long segments of 46 slices, the
+        // fastest of 688 .. 736 in every round; D = 5 716, the fastest of 684 .. 716 -- profiles/r14/sweep_skew.json)
+        int skew = ((D == 9 || D == 5) && !c3p_opt_on(C3P_OPT_no_split81)) ? (D == 9 ? 736 : 716) : 640, skew_c = 640;
         if (c3p_opt(C3P_OPT_mw_skew) >= 0) skew = skew_c = (int)c3p_opt(C3P_OPT_mw_skew);
         if (skew > 500 && skew < 900) {
           const int h = A.S / 2;
