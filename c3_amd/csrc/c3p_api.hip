@@ -31,6 +31,7 @@
 #include "c3p_seq.h"
 #include "c3p_seq_vjp.h"
 #include "c3p_ode_vjp.h"
+#include "c3p_dress.h"
 
 namespace {
 
@@ -98,7 +99,7 @@ int fail(const char* fmt, ...) {
   } while (0)
 
 // Per-device workspace slots, grown lazily, freed by c3p_shutdown().
-enum Slot { SL_SEG_A = 0, SL_SEG_B, SL_SCRATCH, SL_CLP, SL_TABLES, SL_COUNTERS, SL_COUNTERS2, SL_IN0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_SEG_F, SL_SEQ_FLAG, SL_SEQ_VJP_WS, SL_SEQ_VJP_SLAB, SL_ODE_VJP_WS, SL_LMODEL_PART, SL_LMODEL_OUT, SL_COUNT };
+enum Slot { SL_SEG_A = 0, SL_SEG_B, SL_SCRATCH, SL_CLP, SL_TABLES, SL_COUNTERS, SL_COUNTERS2, SL_IN0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_IN6, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_OUT4, SL_SEG_F, SL_SEQ_FLAG, SL_SEQ_VJP_WS, SL_SEQ_VJP_SLAB, SL_ODE_VJP_WS, SL_LMODEL_PART, SL_LMODEL_OUT, SL_COUNT };
 
 struct DeviceWs {
   std::mutex mu;  // one lock per device: calls on different GPUs of one process do not serialise
@@ -1755,7 +1756,7 @@ struct Stage {
       return 0;
     }
     void* d;
-    if (in_slot > SL_IN5) return fail("internal: out of input staging slots");
+    if (in_slot > SL_IN6) return fail("internal: out of input staging slots");
     if (ws_get(w, (Slot)in_slot++, bytes, &d)) return -1;
     HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, st));
     *dev = d;
@@ -1767,7 +1768,7 @@ struct Stage {
       return 0;
     }
     void* d;
-    if (out_slot > SL_OUT3) return fail("internal: out of output staging slots");
+    if (out_slot > SL_OUT4) return fail("internal: out of output staging slots");
     if (ws_get(w, (Slot)out_slot++, bytes, &d)) return -1;
     backs.push_back({host, d, bytes});
     *dev = d;
@@ -3908,6 +3909,103 @@ int c3p_synth_chain_vjp(const double* env_params, const int32_t* env_shapes, con
   double* gcs = gcar_part + awg;
   double* part = gcs + gcs_elems;
   LAUNCH_TRY(c3p_launch_chain_vjp(C, (const double*)d_gs, gcs, part, giq, gcar_part, (double*)d_ge, (double*)d_gc, (double*)d_gl, st));
+  if (flags & C3P_HOST_PTRS) return sg.finish();
+  return 0;
+}
+
+int c3p_dress(const void* H, const void* ops, int64_t ops_bstride, int P, int M, int D, int flags, double* eig_out, void* T_out,
+              void* h0_out, void* ops_out, int32_t* status_out, void* stream) {
+  if (P < 0 || M < 0 || ops_bstride < 0) return fail("bad sizes P=%d M=%d ops_bstride=%lld", P, M, (long long)ops_bstride);
+  if (D < 2 || D > C3P_DRESS_MAX_D) return fail("c3p_dress serves 2 <= D <= %d, got D=%d", C3P_DRESS_MAX_D, D);
+  if (P == 0) return 0;
+  if (!H) return fail("NULL drift Hamiltonian");
+  if (M > 0 && ops_out && !ops) return fail("ops is NULL but M=%d", M);
+  const size_t cs = sizeof(cplx), dd = (size_t)D * D;
+  if (ops_bstride != 0 && (size_t)ops_bstride < (size_t)M * dd) return fail("ops_bstride=%lld is smaller than one operator list (%zu)", (long long)ops_bstride, M * dd);
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  DeviceWs* w = lk.w;
+  if (!w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  Stage sg{w, st};
+  const void *d_H = H, *d_ops = ops;
+  void *d_eig = eig_out, *d_T = T_out, *d_h0 = h0_out, *d_oo = ops_out, *d_st = status_out;
+  if (flags & C3P_HOST_PTRS) {
+    if (sg.in(H, (size_t)P * dd * cs, &d_H)) return -1;
+    if (sg.in(M > 0 ? ops : nullptr, ((size_t)(P - 1) * ops_bstride + (size_t)M * dd) * cs, &d_ops)) return -1;
+    if (sg.out(eig_out, (size_t)P * D * sizeof(double), &d_eig)) return -1;
+    if (sg.out(T_out, (size_t)P * dd * cs, &d_T)) return -1;
+    if (sg.out(h0_out, (size_t)P * dd * cs, &d_h0)) return -1;
+    if (sg.out(ops_out, (size_t)P * M * dd * cs, &d_oo)) return -1;
+    if (sg.out(status_out, (size_t)P * sizeof(int32_t), &d_st)) return -1;
+  }
+  DressArgs a = {};
+  a.H = (const cplx*)d_H;
+  a.ops = (const cplx*)d_ops;
+  a.ops_bstride = (long)ops_bstride;
+  a.P = P;
+  a.M = M;
+  a.D = D;
+  a.eig = (double*)d_eig;
+  a.T = (cplx*)d_T;
+  a.h0 = (cplx*)d_h0;
+  a.ops_out = M > 0 ? (cplx*)d_oo : nullptr;
+  a.status = (int*)d_st;
+  g_last_kernel = C3P_KERNEL_DRESS;
+  HIP_TRY(c3p_launch_dress(a, st));
+  if (flags & C3P_HOST_PTRS) return sg.finish();
+  return 0;
+}
+
+int c3p_dress_vjp(const void* T, const double* eig, const void* ops, int64_t ops_bstride, int P, int M, int D, int flags,
+                  const double* eig_bar, const void* h0_bar, const void* ops_bar, const void* T_bar, void* H_bar_out,
+                  void* ops_bare_bar_out, int32_t* status_out, void* stream) {
+  if (P < 0 || M < 0 || ops_bstride < 0) return fail("bad sizes P=%d M=%d ops_bstride=%lld", P, M, (long long)ops_bstride);
+  if (D < 2 || D > C3P_DRESS_MAX_D) return fail("c3p_dress_vjp serves 2 <= D <= %d, got D=%d", C3P_DRESS_MAX_D, D);
+  if (P == 0) return 0;
+  if (!T || !eig) return fail("NULL transform / eigenvalues (the results of c3p_dress)");
+  if (M > 0 && ops_bar && !ops) return fail("ops is NULL but M=%d cotangents are given", M);
+  const size_t cs = sizeof(cplx), dd = (size_t)D * D;
+  if (ops_bstride != 0 && (size_t)ops_bstride < (size_t)M * dd) return fail("ops_bstride=%lld is smaller than one operator list (%zu)", (long long)ops_bstride, M * dd);
+  const bool have_ops = M > 0 && ops_bar;
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  DeviceWs* w = lk.w;
+  if (!w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  Stage sg{w, st};
+  const void *d_T = T, *d_eig = eig, *d_ops = ops, *d_eb = eig_bar, *d_hb = h0_bar, *d_ob = ops_bar, *d_tb = T_bar;
+  void *d_H = H_bar_out, *d_ab = ops_bare_bar_out, *d_st = status_out;
+  const size_t abar_bytes = have_ops ? (ops_bstride ? (size_t)P : 1) * M * dd * cs : 0;
+  if (flags & C3P_HOST_PTRS) {
+    if (sg.in(T, (size_t)P * dd * cs, &d_T)) return -1;
+    if (sg.in(eig, (size_t)P * D * sizeof(double), &d_eig)) return -1;
+    if (sg.in(have_ops ? ops : nullptr, ((size_t)(P - 1) * ops_bstride + (size_t)M * dd) * cs, &d_ops)) return -1;
+    if (sg.in(eig_bar, (size_t)P * D * sizeof(double), &d_eb)) return -1;
+    if (sg.in(h0_bar, (size_t)P * dd * cs, &d_hb)) return -1;
+    if (sg.in(have_ops ? ops_bar : nullptr, (size_t)P * M * dd * cs, &d_ob)) return -1;
+    if (sg.in(T_bar, (size_t)P * dd * cs, &d_tb)) return -1;
+    if (sg.out(H_bar_out, (size_t)P * dd * cs, &d_H)) return -1;
+    if (sg.out(ops_bare_bar_out, abar_bytes, &d_ab)) return -1;
+    if (sg.out(status_out, (size_t)P * sizeof(int32_t), &d_st)) return -1;
+  }
+  DressVjpArgs a = {};
+  a.T = (const cplx*)d_T;
+  a.eig = (const double*)d_eig;
+  a.ops = (const cplx*)d_ops;
+  a.ops_bstride = (long)ops_bstride;
+  a.P = P;
+  a.M = have_ops ? M : 0;
+  a.D = D;
+  a.eig_bar = (const double*)d_eb;
+  a.h0_bar = (const cplx*)d_hb;
+  a.ops_bar = have_ops ? (const cplx*)d_ob : nullptr;
+  a.T_bar = (const cplx*)d_tb;
+  a.H_bar = (cplx*)d_H;
+  a.ops_bare_bar = have_ops ? (cplx*)d_ab : nullptr;
+  a.status = (int*)d_st;
+  g_last_kernel = C3P_KERNEL_DRESS_VJP;
+  HIP_TRY(c3p_launch_dress_vjp(a, st));
   if (flags & C3P_HOST_PTRS) return sg.finish();
   return 0;
 }

@@ -485,3 +485,115 @@ def sensitivity_sweep(h0_of, hks_of, sweep_values: Sequence[float], gate_signals
             psi_init = psi_init[0]
     r = goal_run_batched(h0, hks, sig, dt, [data_set] * P, psi_init, label_indices, device=device, col_ops=col)
     return {"values": np.asarray(vals), "goals": r["goals"], "sim_vals": r["sim_vals"]}
+
+
+def _bare_operator_list(hks_bare, col_ops_bare, P: int, device):
+    """Control Hamiltonians [K,D,D] / [P,K,D,D] and collapse operators (None, [C,D,D] or [P,C,D,D]) as the one list `dress_batch`
+    takes: (ops, K, hks_shared, col_shared); ops is [K+C,D,D] when both are shared, else [P,K+C,D,D]."""
+    if device is not None:
+        import torch
+
+        conv = lambda v: v.to(device=device, dtype=torch.complex128) if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.complex128), device=device)
+        cat, expand = torch.cat, (lambda v: v[None].expand((P,) + tuple(v.shape)))
+    else:
+        conv = lambda v: np.asarray(v.detach().cpu().numpy() if propagation._is_torch(v) else v, dtype=np.complex128)
+        cat, expand = np.concatenate, (lambda v: np.broadcast_to(v[None], (P,) + tuple(v.shape)))
+    hk = conv(hks_bare)
+    if hk.ndim not in (3, 4):
+        raise C3PropError(f"C3:Error: hks_bare has shape {tuple(hk.shape)}; expected [K,D,D] or [P,K,D,D]")
+    K = int(hk.shape[-3])
+    if col_ops_bare is None:
+        return hk, K, hk.ndim == 3, True
+    col = conv(col_ops_bare)
+    if col.ndim not in (3, 4):
+        raise C3PropError(f"C3:Error: col_ops_bare has shape {tuple(col.shape)}; expected [C,D,D] or [P,C,D,D]")
+    hk_shared, col_shared = hk.ndim == 3, col.ndim == 3
+    if hk_shared != col_shared:  # one list per set as soon as either differs between the sets
+        hk = expand(hk) if hk_shared else hk
+        col = expand(col) if col_shared else col
+    return cat([hk, col], -3), K, hk_shared, col_shared
+
+
+def goal_run_dressed_with_grad(H_bare, hks_bare, gate_signals: Dict, dt: float, data_sets: Sequence[Dict], psi_init, label_indices, *, col_ops_bare=None,
+                               fr_phase: Optional[Dict] = None, device=None) -> Dict:
+    """`goal_run_batched_with_grad` from the BARE model: the P drift Hamiltonians `H_bare` [P,D,D] (or one, [D,D]) are dressed on the
+    device (`dressing.dress_batch`: Model.update_dressed for every set in one launch), with them the control Hamiltonians `hks_bare`
+    [K,D,D] / [P,K,D,D] and, for an open system, the collapse operators `col_ops_bare` [C,D,D] / [P,C,D,D]; the goal and its
+    gradient are those of `goal_run_batched_with_grad` on the dressed operators, and its cotangents grad_h0, grad_hks and grad_col_ops
+    are pushed back through `dressing.dress_batch_vjp`.  With `device` nothing leaves the GPU in between.  2 <= D <= 40; `psi_init`,
+    `fr_phase` and the labels refer to the dressed frame, as in `goal_run_batched_with_grad`.
+
+    Returns that function's dict plus
+      "grad_H_bare" [P,D,D]   d goal / d H_bare[p] (Hermitian; a model shared by the sets: sum over p, or `model_param_grads`);
+      "grad_hks_bare", "grad_col_ops_bare"   cotangents of the bare operators: per set for per-set operators, summed over the sets
+                              for shared ones ("grad_col_ops_bare" None for a closed system);
+      "eigenframe" [P,D], "status" int32 [P] (dressing.RECOVERED / DEGENERATE bits of the two dressing calls).
+
+    The bare Hamiltonian of the chip models is linear in the parameters, H = sum_t theta_t G_t with constant matrices G [T,D,D]
+    (`workloads.bare_drift`), so the exact parameter gradient needs no derivative of the eigendecomposition:
+
+        r = goal_run_dressed_with_grad(H_bare, hks_bare, signals, dt, data_sets, psi0, labels)
+        grad_theta = model_param_grads(r["grad_H_bare"], r["grad_hks_bare"], dh0=G)
+    """
+    from . import dressing
+
+    P = len(data_sets)
+    if device is not None:
+        import torch
+
+        H = H_bare.to(device=device, dtype=torch.complex128) if torch.is_tensor(H_bare) else torch.as_tensor(np.asarray(H_bare, dtype=np.complex128), device=device)
+        H = H[None].expand(P, -1, -1).contiguous() if H.ndim == 2 else H
+    else:
+        H = np.asarray(H_bare.detach().cpu().numpy() if propagation._is_torch(H_bare) else H_bare, dtype=np.complex128)
+        H = np.broadcast_to(H[None], (P,) + H.shape).copy() if H.ndim == 2 else H
+    if H.ndim != 3 or int(H.shape[0]) != P:
+        raise C3PropError(f"C3:Error: H_bare has shape {tuple(H.shape)}, but there are {P} data sets")
+    ops, K, hk_shared, col_shared = _bare_operator_list(hks_bare, col_ops_bare, P, device)
+    d = dressing.dress_batch(H, ops)
+    hks = d["ops"][:, :K]
+    col = None if col_ops_bare is None else d["ops"][:, K:]
+    r = goal_run_batched_with_grad(d["h0"], hks, gate_signals, dt, data_sets, psi_init, label_indices, fr_phase=fr_phase, device=device, col_ops=col)
+    g_ops = r["grad_hks"]
+    if col is not None:
+        g_ops = (torch.cat if device is not None else np.concatenate)([g_ops, r["grad_col_ops"]], 1)
+    v = dressing.dress_batch_vjp(d["transform"], d["eigenframe"], ops, grad_h0=r["grad_h0"], grad_ops=g_ops)
+    gb = v["grad_ops"]
+    per_set = gb.ndim == 4
+    g_hk = gb[..., :K, :, :]
+    g_col = None if col is None else gb[..., K:, :, :]
+    if per_set and hk_shared:
+        g_hk = g_hk.sum(0)
+    if per_set and col is not None and col_shared:
+        g_col = g_col.sum(0)
+    out = dict(r)
+    st = np.asarray(dressing._host(d["status"])) | np.asarray(dressing._host(v["status"]))
+    out.update({"grad_H_bare": v["grad_H"], "grad_hks_bare": g_hk, "grad_col_ops_bare": g_col, "eigenframe": d["eigenframe"], "status": st})
+    return out
+
+
+def sensitivity_sweep_dressed(H_bare_of, hks_bare, sweep_values: Sequence[float], gate_signals_one: Dict, dt: float, data_set: Dict, psi_init, label_indices, *,
+                              device=None, col_ops_bare_of=None, psi_init_of=None) -> Dict:
+    """`sensitivity_sweep` from the bare model: `H_bare_of(v)` builds the bare drift Hamiltonian at sweep value v, and ONE batched
+    `dressing.dress_batch` call dresses every point (with the control Hamiltonians `hks_bare` [K,D,D] and, for an open system, the
+    bare collapse operators `col_ops_bare_of(v)` [C,D,D]) instead of one host eigendecomposition per point.  `psi_init_of` as in
+    `sensitivity_sweep`.  Also returns the "eigenframe" [P,D] of the points."""
+    from . import dressing
+
+    vals = list(sweep_values)
+    P = len(vals)
+    H = np.stack([np.asarray(H_bare_of(v), dtype=np.complex128) for v in vals])
+    col_bare = None if col_ops_bare_of is None else np.stack([np.asarray(col_ops_bare_of(v), dtype=np.complex128) for v in vals])
+    ops, K, _, _ = _bare_operator_list(hks_bare, col_bare, P, device)
+    if device is not None:
+        import torch
+
+        H = torch.as_tensor(H, device=device)
+    d = dressing.dress_batch(H, ops)
+    sig = {g: np.broadcast_to(np.asarray(s, dtype=np.float64)[None], (P,) + tuple(np.shape(s))).copy() for g, s in gate_signals_one.items()}
+    if psi_init_of is not None:
+        psi_init = np.stack([np.asarray(psi_init_of(v), dtype=np.complex128).reshape(-1) for v in vals])  # [P,D] or [P,D^2]
+        if P == 1:
+            psi_init = psi_init[0]
+    col = None if col_bare is None else d["ops"][:, K:]
+    r = goal_run_batched(d["h0"], d["ops"][:, :K], sig, dt, [data_set] * P, psi_init, label_indices, device=device, col_ops=col)
+    return {"values": np.asarray(vals), "goals": r["goals"], "sim_vals": r["sim_vals"], "eigenframe": dressing._host(d["eigenframe"])}

@@ -83,6 +83,8 @@ extern "C" {
 #define C3P_KERNEL_SEQ 9 /* indexed gate-sequence chains (c3p_seq.hip)                          */
 #define C3P_KERNEL_SEQ_VJP 10 /* reverse sweep of the indexed gate-sequence chains (c3p_seq_vjp.hip)  */
 #define C3P_KERNEL_ODE_VJP 11 /* discrete adjoint of the ODE state solvers (c3p_ode_vjp.hip)           */
+#define C3P_KERNEL_DRESS 12 /* batched dressing: Jacobi eigensolver, frame rule, T^+ A T (c3p_dress.hip) */
+#define C3P_KERNEL_DRESS_VJP 13 /* vector-Jacobian product of the dressing step (c3p_dress.hip)         */
 
 /* ODE solver / step ids (propagation.py:27-32 solver_slicing; :886-904 steps) */
 #define C3P_SOLVER_RK4 0
@@ -528,6 +530,40 @@ int c3p_seq_chain_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int 
 int c3p_seq_state_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int P, const int32_t* seqs, int S, int Lmax,
                       const int32_t* lengths, const void* psi0, int64_t psi0_bstride, const void* out_bar, int flags, void* G_bar,
                       void* psi0_bar, void* out, void* stream);
+
+/* Dressing of P models in one launch: Model.update_dressed (c3/model.py:453-534) -- the eigendecomposition of the drift
+ * Hamiltonian, the reorder rule of reorder_frame (ordered=True) and T^+ A T for every control and collapse operator.
+ *   H        c128 [P,D,D] bare drift Hamiltonians, Hermitian (the lower triangle is read, as eigh does); 2 <= D <= 40
+ *   ops      c128 [M,D,D] (ops_bstride 0: one list for every set) or [P,M,D,D] (ops_bstride = elements between two lists);
+ *            control Hamiltonians and collapse operators in one list, not necessarily Hermitian; M = 0: none
+ *   eig_out  f64  [P,D]   the eigenvalues in the reordered frame (the reference's `eigenframe`)
+ *   T_out    c128 [P,D,D] the transform: column i is the eigenvector that overlaps bare state i most (every column's largest
+ *            |v|^2 above 0.5), else the reference's greedy assignment (status bit 1); its phase makes T[i,i] real and positive --
+ *            for a real symmetric H this is the reference's sign(Re v) rule, for a complex one it defines what the reference
+ *            leaves to LAPACK's phase convention
+ *   h0_out   c128 [P,D,D] diag(eig_out) exactly (the reference's T^+ H T differs from it by rounding noise eps ||H||)
+ *   ops_out  c128 [P,M,D,D] T_p^+ A_m T_p
+ *   status_out int32 [P]: bit 1 = reordered by the greedy branch, 4 = the solver did not converge in 30 sweeps (e.g. NaN input;
+ *            the outputs of that set are not valid)
+ * Any output may be NULL.  Cyclic Jacobi, converged at off(A) <= D 2^-52 ||A||_F: every threshold is relative, results are
+ * bitwise reproducible.  One launch, no workspace. */
+int c3p_dress(const void* H, const void* ops, int64_t ops_bstride, int P, int M, int D, int flags, double* eig_out, void* T_out,
+              void* h0_out, void* ops_out, int32_t* status_out, void* stream);
+
+/* Vector-Jacobian product of c3p_dress (d loss = Re sum conj(Xbar) dX): from T and eig AS RETURNED by it (nothing is solved
+ * again) and the cotangents
+ *   eig_bar  f64  [P,D] or NULL;   h0_bar c128 [P,D,D] or NULL (h0 = diag(eig): Re diag(h0_bar) adds to eig_bar)
+ *   ops_bar  c128 [P,M,D,D] or NULL: cotangents of the dressed operators;   T_bar c128 [P,D,D] or NULL
+ * returns
+ *   H_bar_out         c128 [P,D,D]: the gradient on the Hermitian H (a Hermitian matrix)
+ *   ops_bare_bar_out  c128 [P,M,D,D] = T Gbar_m T^+ for per-set operators; [M,D,D], summed over the sets in a fixed order, for
+ *                     shared ones (ops_bstride 0)
+ *   status_out        int32 [P]: bit 2 = a pair of eigenvalues closer than 2^-40 max|e| was met; it contributes zero (the
+ *                     reference's gradient is infinite there)
+ * Outputs may be NULL.  The permutation and the greedy branch are locally constant and contribute nothing. */
+int c3p_dress_vjp(const void* T, const double* eig, const void* ops, int64_t ops_bstride, int P, int M, int D, int flags,
+                  const double* eig_bar, const void* h0_bar, const void* ops_bar, const void* T_bar, void* H_bar_out,
+                  void* ops_bare_bar_out, int32_t* status_out, void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
