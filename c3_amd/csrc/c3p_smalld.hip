@@ -925,15 +925,77 @@ __device__ __forceinline__ void store_plain(const double (&zh)[SD<D>::NBI][SD<D>
   }
 }
 
+// Cross-lane steps of the prologue's reductions on the register path (no LDS round trip, ~50 cycles each on a cold CU):
+// DPP inside a row of 16 lanes, v_permlane16_swap / v_permlane32_swap across rows.  All 64 lanes are active at every call.
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
+  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_XOR3 = 0x1B;                // quad_perm [1,0,3,2], [2,3,0,1], [3,2,1,0]
+constexpr int DPP_HALF_MIRROR = 0x141;                                          // row_half_mirror: lane i of eight reads 7 - i
+constexpr int DPP_ROR1 = 0x121, DPP_ROR2 = 0x122, DPP_ROR4 = 0x124, DPP_ROR8 = 0x128;  // row_ror (row_ror:8 is lane ^ 8)
+// (a, b) = (v of the lane with bit 4 clear, v of the lane with bit 4 set) of the pair {lane, lane ^ 16}, in both lanes
+__device__ __forceinline__ void pair_xor16(double v, double& a, double& b) {
+  const unsigned lo = __double2loint(v), hi = __double2hiint(v);
+  const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+  const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  a = __hiloint2double(rh[0], rl[0]);
+  b = __hiloint2double(rh[1], rl[1]);
+}
+// the same for the pair {lane, lane ^ 32}
+__device__ __forceinline__ void pair_xor32(double v, double& a, double& b) {
+  const unsigned lo = __double2loint(v), hi = __double2hiint(v);
+  const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+  const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  a = __hiloint2double(rh[0], rl[0]);
+  b = __hiloint2double(rh[1], rl[1]);
+}
+// max over {lane, lane ^ 16, lane ^ 32, lane ^ 48}
+__device__ __forceinline__ double rows_max(double v) {
+  double a, b;
+  pair_xor16(v, a, b);
+  v = fmax(a, b);
+  pair_xor32(v, a, b);
+  return fmax(a, b);
+}
+// v_lane + v_{lane ^ o} for o = 32, 16, 8, 4, 2, 1 in this order: the association of the former __shfl_xor loop (an addition
+// commutes, so both lanes of a pair hold the same bits after every step -- which is what lets row_ror:4 stand for lane ^ 4:
+// behind the step o = 8 the lanes i ^ 4 and i ^ 12, one of which it reads, are equal)
 __device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  double a, b;
+  pair_xor32(v, a, b);
+  v = a + b;
+  pair_xor16(v, a, b);
+  v = a + b;
+  v += dpp_f64<DPP_ROR8>(v);
+  v += dpp_f64<DPP_ROR4>(v);
+  v += dpp_f64<DPP_XOR2>(v);
+  v += dpp_f64<DPP_XOR1>(v);
   return v;
 }
-__device__ __forceinline__ double wave_max64(double v) {
+// the maxima of N values over the wave as ONE latency chain: the steps of the N reductions side by side (a maximum is exact
+// and free of order)
+template <int N>
+__device__ __forceinline__ void wave_max64(double (&v)[N]) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
+  for (int n = 0; n < N; ++n) v[n] = fmax(v[n], dpp_f64<DPP_ROR1>(v[n]));
+#pragma unroll
+  for (int n = 0; n < N; ++n) v[n] = fmax(v[n], dpp_f64<DPP_ROR2>(v[n]));
+#pragma unroll
+  for (int n = 0; n < N; ++n) v[n] = fmax(v[n], dpp_f64<DPP_ROR4>(v[n]));
+#pragma unroll
+  for (int n = 0; n < N; ++n) v[n] = fmax(v[n], dpp_f64<DPP_ROR8>(v[n]));
+#pragma unroll
+  for (int n = 0; n < N; ++n) v[n] = rows_max(v[n]);
+}
+// max over the 16 lanes of a chain (lane bits 0, 1, 4, 5)
+__device__ __forceinline__ double chain_max16(double v) {
+  v = fmax(v, dpp_f64<DPP_XOR1>(v));
+  v = fmax(v, dpp_f64<DPP_XOR2>(v));
+  return rows_max(v);
 }
 
 // Column sums of |G|, the block the segment's norm bound is formed from (c3p_sd_segment_norm below): SD_CSW doubles per table,
@@ -974,10 +1036,16 @@ __device__ __forceinline__ void sd_colsums(const double* tab, int K, double* csb
 // every table's widest column meet in one column it does not have.  One fma chain per column in the order of the tables, then
 // the maximum over the chain's lanes: every kernel that decides on this bound gets the same bits.  `maxk(k)` is the chain's
 // max_t |c_k(t)| on the segment, uniform over the chain's lanes.
+// the lane's column of the bound; the chain kernel takes the maximum over its lanes on the register path
 template <class F>
-__device__ __forceinline__ double c3p_sd_segment_norm(const double* csb, int K, int idx16, F&& maxk) {
+__device__ __forceinline__ double c3p_sd_segment_col(const double* csb, int K, int idx16, F&& maxk) {
   double v = csb[idx16];
   for (int k = 0; k < K; ++k) v = fma(maxk(k), csb[(k + 1) * SD_CSW + idx16], v);
+  return v;
+}
+template <class F>
+__device__ __forceinline__ double c3p_sd_segment_norm(const double* csb, int K, int idx16, F&& maxk) {
+  double v = c3p_sd_segment_col(csb, K, idx16, maxk);
   v = fmax(v, __shfl_xor(v, 1));
   v = fmax(v, __shfl_xor(v, 2));
   v = fmax(v, __shfl_xor(v, 16));
@@ -988,28 +1056,37 @@ __device__ __forceinline__ double c3p_sd_segment_norm(const double* csb, int K, 
 // The wave builds its own tables in LDS (unitary mode): G = -i dt (h - tr h / D) as half images plus
 // {Re mu, Im mu, ||G||_1, max |Re G|} -- what smalld_prep_kernel writes, without a dependent launch in
 // front of the chain kernel (~12 us of a 250 us batch).
-template <int D>
-__device__ __forceinline__ void build_tables(const SmallArgs& A, int sample, double* tab, double* csb, int lane, int first = 0, int step = 1) {
+// `under_loads()` is work of the caller that needs no table: it runs once, behind the issue of the first table's loads (the
+// kernel's cold global accesses) or, in a wave that builds no table, at once.
+template <int D, class F>
+__device__ __forceinline__ void build_tables(const SmallArgs& A, int sample, double* tab, double* csb, int lane, int first, int step,
+                                             F&& under_loads) {
+  // the elements are rounded as products first, the diagonal's shift is a second rounding: a fused -x dt - mu gives other tables
+#pragma clang fp contract(off)
   using C = SD<D>;
   constexpr int MAT = C::MAT, W = C::W;
   constexpr int NE = (D * D + 63) / 64;
+  if (first > A.K) under_loads();
   for (int ti = first; ti <= A.K; ti += step) {  // (a workgroup of several waves deals the tables to its waves)
     double* out = tab + ti * (MAT + 4);
     const cplx* h = (ti == 0) ? A.h0 + (long)sample * A.h0_bstride
                               : A.hks + (long)sample * A.hks_bstride + (long)(ti - 1) * D * D;
+    // every load of the table is in flight before the first is waited for: the address is clamped and the value selected
+    // behind the load (a load under `e < D * D` put a branch and a wait between the two of D = 9, both cold misses)
+    cplx x[NE];
+#pragma unroll
+    for (int q = 0; q < NE; ++q) x[q] = h[min(lane + 64 * q, D * D - 1)];
+    if (ti == first) under_loads();
     for (int e = lane; e < MAT; e += 64) out[e] = 0.0;
     double gr[NE], gi[NE];
     double tim = 0.0;
 #pragma unroll
     for (int q = 0; q < NE; ++q) {
       const int e = lane + 64 * q;
-      gr[q] = gi[q] = 0.0;
-      if (e < D * D) {
-        const cplx x = h[e];
-        gr[q] = x.y * A.dt;  // -i dt h
-        gi[q] = -x.x * A.dt;
-        if (e / D == e % D) tim += gi[q];
-      }
+      const bool in = e < D * D;
+      gr[q] = in ? x[q].y * A.dt : 0.0;  // -i dt h
+      gi[q] = in ? -x[q].x * A.dt : 0.0;
+      if (in && e / D == e % D) tim += gi[q];
     }
     // (round 6) the shift is IMAGINARY only: a real shift (lossy Hamiltonians) makes the shifted chain product grow like
     // e^{|Re mu| n} while e^{sum mu} underflows -- inf * 0 over a long segment (tools/fuzz_r06.py found it on the Lindblad tables)
@@ -1034,7 +1111,6 @@ __device__ __forceinline__ void build_tables(const SmallArgs& A, int sample, dou
     wave_sync();
     const double cs = sd_colsum<D>(out, lane);
     if (lane < SD_CSW) csb[ti * SD_CSW + lane] = cs;
-    const double nrm = wave_max64(cs);
     // the real fast path also needs Y = -Im G symmetric (Hermitian input).  Dressed operators V^T H V are
     // symmetric only to rounding (measured 5e-16 relative), so asymmetry below 1e-14 ||G|| counts as none;
     // anything larger is folded into the flag and sends the sample to the complex path.
@@ -1048,10 +1124,13 @@ __device__ __forceinline__ void build_tables(const SmallArgs& A, int sample, dou
         rsk = fmax(rsk, fabs(gr[q] + out[(2 * j) * W + i]));  // G + G^H = 0 <=> Hermitian Hamiltonian (diagonal: 2 Re G_ii)
       }
     }
-    asym = wave_max64(asym);
-    rsk = wave_max64(rsk);
+    // the four maxima come down together.  The asymmetry joins the maximum of |Re G| behind the reduction: it is uniform, and
+    // max_lanes fmax(x_lane, a) = fmax(max_lanes x_lane, a)
+    double red[4] = {cs, asym, rsk, remax};
+    wave_max64(red);
+    const double nrm = red[0];
+    asym = red[1], rsk = red[2], remax = red[3];
     if (asym > 1e-14 * nrm) remax = fmax(remax, asym);
-    remax = wave_max64(remax);
     // (round 6) NEGATIVE: complex but skew-Hermitian to rounding -- a normal generator: T18 with the economised parameters
     if (remax > 0.0 && fmax(asym, rsk) <= 1e-14 * nrm) remax = -remax;
     if (lane == 0) {
@@ -1103,19 +1182,32 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
   // XCD-aware block order: workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  Logical block
   // (bid % 8) * (nb / 8) + bid / 8 keeps consecutive logical blocks -- the waves of one sample, which exchange their
   // segment partials in the fused combine -- on ONE XCD.
-  long lblock = blockIdx.x;
-  if constexpr (MW)
-    lblock = (long)blockIdx.x * nwv + wv;  // workgroup = sample, wave = four consecutive segments
-  else if ((gridDim.x & 7) == 0)
-    lblock = (long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  const long chain = lblock * 4 + lp.b;
-  const long nchains = (long)A.B * A.S;
-  const bool valid = chain < nchains;
-  const long cc = valid ? chain : nchains - 1;
-  const int sample = (int)(cc / A.S);
-  const int seg = (int)(cc - (long)sample * A.S);
-  int n0 = (int)(((long)seg * A.N) / A.S);
-  int n1 = (int)(((long)(seg + 1) * A.N) / A.S);
+  // Workgroup per sample: the workgroup IS the sample (the launch has B workgroups of S / 4 waves, so every chain is valid) and
+  // the wave holds four consecutive segments -- no division stands in front of the kernel's first, cold loads.  S is 8, 16 or
+  // 32 there (launch_chain_t), so the quotients by S and by S / 2 below are shifts of the same 64-bit products.
+  long cc;
+  int sample, seg, n0, n1;
+  bool valid;
+  const int sshift = 31 - __clz(A.S);  // (MW) S = 1 << sshift
+  if constexpr (MW) {
+    valid = true;
+    sample = blockIdx.x;
+    seg = 4 * wv + lp.b;
+    cc = (long)sample * A.S + seg;
+    n0 = (int)(((long)seg * A.N) >> sshift);
+    n1 = (int)(((long)(seg + 1) * A.N) >> sshift);
+  } else {
+    long lblock = blockIdx.x;
+    if ((gridDim.x & 7) == 0) lblock = (long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const long chain = lblock * 4 + lp.b;
+    const long nchains = (long)A.B * A.S;
+    valid = chain < nchains;
+    cc = valid ? chain : nchains - 1;
+    sample = (int)(cc / A.S);
+    seg = (int)(cc - (long)sample * A.S);
+    n0 = (int)(((long)seg * A.N) / A.S);
+    n1 = (int)(((long)(seg + 1) * A.N) / A.S);
+  }
   int len, tmax;
   // uneven segments (MW): the first S / 2 chains (waves 0 .. 3, the older wave of each SIMD) take `seg_long` slices each, the
   // others share the rest; the wave iterates over the longest of its four chains
@@ -1123,15 +1215,16 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
     if (MW && seg_long > 0) {
       const int h = A.S >> 1;
       const long rest = (long)A.N - (long)h * seg_long;
-      n0 = seg < h ? seg * seg_long : h * seg_long + (int)(((long)(seg - h) * rest) / h);
-      n1 = seg + 1 <= h ? (seg + 1) * seg_long : h * seg_long + (int)(((long)(seg + 1 - h) * rest) / h);
+      n0 = seg < h ? seg * seg_long : h * seg_long + (int)(((long)(seg - h) * rest) >> (sshift - 1));
+      n1 = seg + 1 <= h ? (seg + 1) * seg_long : h * seg_long + (int)(((long)(seg + 1 - h) * rest) >> (sshift - 1));
     }
     len = n1 - n0;
     tmax = A.Lmax;
     if (MW && seg_long > 0) {
+      // (the four chains of a wave are the lanes i, i + 4, i + 8, i + 12 of a row)
       int m = len;
-      m = max(m, __shfl_xor(m, 4));
-      m = max(m, __shfl_xor(m, 8));
+      m = max(m, __builtin_amdgcn_mov_dpp(m, DPP_ROR4, 0xf, 0xf, true));
+      m = max(m, __builtin_amdgcn_mov_dpp(m, DPP_ROR8, 0xf, 0xf, true));
       tmax = __builtin_amdgcn_readfirstlane(m);
     }
   };
@@ -1191,6 +1284,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
     // ---- prologue: tables and this segment's control amplitudes into LDS ----
     // all four chains of a wave share the sample when tables are per sample (S % 4 == 0)
     double nrm = 0.0;
+    bool realH = false, normalG = false;  // (supplied generators: neither)
     if constexpr (XG) {
       const double* mt = A.meta + ((long)sample * A.N + n0) * 4;
       for (int t = lp.idx16; t < A.Lmax; t += 16)
@@ -1199,6 +1293,8 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
       nrm = fmax(nrm, __shfl_xor(nrm, 2));
       nrm = fmax(nrm, __shfl_xor(nrm, 16));
       nrm = fmax(nrm, __shfl_xor(nrm, 32));
+      nrm = fmax(nrm, __shfl_xor(nrm, 4));
+      nrm = fmax(nrm, __shfl_xor(nrm, 8));
     } else {
     // (MW: table k is built by wave k mod nwv; the barrier comes after the waves have fetched their control amplitudes)
     // The waves that build a table issue the loads of their control amplitudes FIRST (K <= 2, segments up to 48 slices: six
@@ -1216,19 +1312,13 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
           pre[k][i] = (k < K && valid && t < len) ? sk[t] : 0.0;
         }
     }
-    if (A.inline_tables) {
-      build_tables<D>(A, __builtin_amdgcn_readfirstlane(sample), tab, csb, lane, wv, nwv);
-    } else {
-      const double* gt0 = A.tables + (long)(A.tab_per_sample ? sample : 0) * (1 + K) * (MAT + 4);
-      for (int e = (MW ? (int)threadIdx.x : lane); e < (1 + K) * (MAT + 4); e += 64 * nwv) tab[e] = gt0[e];
-      // tables of the prep kernel: their column sums are formed here, from the copy in LDS and dealt to the waves as a table
-      // build is (the barriers below publish the block)
-      __syncthreads();
-      sd_colsums<D>(tab, K, csb, lane, wv, nwv);
-    }
-    if constexpr (!MW) __syncthreads();
-    // segment-wide bound on ||X||_1, column by column (c3p_sd_segment_norm)  -> one plan per segment
-    // (MW: the amplitudes are fetched while wave 0 builds the tables, their maxima taken from LDS after the barrier)
+    // segment-wide bound on ||X||_1, column by column (c3p_sd_segment_col)  -> one plan per segment
+    // (MW: the amplitudes are fetched, and the chains' max_t |c_k(t)| taken, while the tables are on their way: they need no
+    // table.  The maxima of up to PF_K control lines wait in registers; beyond that they are read back from LDS)
+    double cm[PF_K];
+#pragma unroll
+    for (int k = 0; k < PF_K; ++k) cm[k] = 0.0;
+    const bool cm_regs = MW && K <= PF_K;
     auto seg_max = [&](int k, bool from_lds) {
       const double* s = A.signals + ((long)sample * K + k) * A.N + n0;
       double cmax = 0.0;
@@ -1242,58 +1332,90 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
         }
         cmax = fmax(cmax, fabs(v));
       }
-      cmax = fmax(cmax, __shfl_xor(cmax, 1));
-      cmax = fmax(cmax, __shfl_xor(cmax, 2));
-      cmax = fmax(cmax, __shfl_xor(cmax, 16));
-      cmax = fmax(cmax, __shfl_xor(cmax, 32));
-      return cmax;
+      return chain_max16(cmax);
     };
-    SD_TICK(tk8);
-    if constexpr (MW) {
+    auto keep_max = [&](int k, double m) {
+#pragma unroll
+      for (int q = 0; q < PF_K; ++q)
+        if (k == q) cm[q] = m;
+    };
+    // (MW) the segment's amplitudes into the wave's LDS rows, their maxima into cm
+    auto fetch_amplitudes = [&]() {
       if (prefetch) {
 #pragma unroll
-        for (int k = 0; k < PF_K; ++k)
+        for (int k = 0; k < PF_K; ++k) {
+          double m = 0.0;
 #pragma unroll
           for (int i = 0; i < PF_T; ++i) {
             const int t = lp.idx16 + 16 * i;
             if (k < K && t < A.Lmax) sg[lp.b * SG + k * A.Lmax + t] = pre[k][i];
+            m = fmax(m, fabs(pre[k][i]));  // (zero past the segment's end)
           }
+          cm[k] = chain_max16(m);
+        }
       } else {
-        for (int k = 0; k < K; ++k) (void)seg_max(k, false);
+        for (int k = 0; k < K; ++k) keep_max(k, seg_max(k, false));
       }
-      SD_TICK(tk9);
-      __syncthreads();  // the tables of wave 0 are in place
+    };
+    if (A.inline_tables) {
+      build_tables<D>(A, __builtin_amdgcn_readfirstlane(sample), tab, csb, lane, wv, nwv, [&]() {
+        if constexpr (MW) fetch_amplitudes();
+      });
+    } else {
+      const double* gt0 = A.tables + (long)(A.tab_per_sample ? sample : 0) * (1 + K) * (MAT + 4);
+      for (int e = (MW ? (int)threadIdx.x : lane); e < (1 + K) * (MAT + 4); e += 64 * nwv) tab[e] = gt0[e];
+      if constexpr (MW) fetch_amplitudes();
+      // tables of the prep kernel: their column sums are formed here, from the copy in LDS and dealt to the waves as a table
+      // build is (the barriers below publish the block)
+      __syncthreads();
+      sd_colsums<D>(tab, K, csb, lane, wv, nwv);
+    }
+    SD_TICK(tk8);
+    SD_TICK(tk9);
+    __syncthreads();  // the tables and their column sums are in place
+    // The flags of the K + 1 tables, read ONCE and without an early exit (the reads of the first PF_K + 1 are independent):
+    // every table purely imaginary (flag 0: real Hamiltonians) -> real fast path; every table skew-Hermitian to rounding (flag
+    // <= 0; negative: complex skew-Hermitian) -> the schemes for normal generators
+    bool all_real = true, all_normal = true;
+    {
+      double f[PF_K + 1];
+#pragma unroll
+      for (int q = 0; q <= PF_K; ++q) f[q] = tab[min(q, K) * (MAT + 4) + MAT + 3];
+#pragma unroll
+      for (int q = 0; q <= PF_K; ++q) all_real = all_real & (f[q] == 0.0), all_normal = all_normal & (f[q] <= 0.0);
+      for (int k = PF_K + 1; k <= K; ++k) {
+        const double fk = tab[k * (MAT + 4) + MAT + 3];
+        all_real = all_real & (fk == 0.0), all_normal = all_normal & (fk <= 0.0);
+      }
+    }
+    realH = __builtin_amdgcn_readfirstlane((int)((A.mode == C3P_MODE_UNITARY) && all_real)) != 0;
+    normalG = (A.mode == C3P_MODE_UNITARY) && !(A.no_t18n & 1) && all_normal;
+    if constexpr (MW) {
       // a sample on the COMPLEX loop has its own split (the two waves of a SIMD finish together at a different ratio there): the
       // table flags are known only now, so its waves fetch their amplitudes a second time (~1 us of a 285 us kernel)
-      if (A.seg_long_c > 0 && A.seg_long_c != A.seg_long) {
-        bool re = (A.mode == C3P_MODE_UNITARY);
-        for (int k = 0; k <= K; ++k) re = re && (tab[k * (MAT + 4) + MAT + 3] == 0.0);
-        if (__builtin_amdgcn_readfirstlane((int)re) == 0) {
-          wave_sync();
-          split_segments(A.seg_long_c);
-          for (int k = 0; k < K; ++k) (void)seg_max(k, false);
-          wave_sync();
-        }
+      if (A.seg_long_c > 0 && A.seg_long_c != A.seg_long && !realH) {
+        wave_sync();
+        split_segments(A.seg_long_c);
+        for (int k = 0; k < K; ++k) keep_max(k, seg_max(k, false));
+        wave_sync();
       }
     }
-    nrm = c3p_sd_segment_norm(csb, K, lp.idx16, [&](int k) { return seg_max(k, MW); });
+    {
+      double col[1] = {c3p_sd_segment_col(csb, K, lp.idx16, [&](int k) {
+        static_assert(PF_K == 2, "the select below reads cm[0] and cm[1]");
+        if (cm_regs) return k == 0 ? cm[0] : cm[1];
+        return seg_max(k, MW);
+      })};
+      wave_max64(col);  // over the columns of a chain and over the wave's four chains
+      nrm = col[0];
     }
-    nrm = fmax(nrm, __shfl_xor(nrm, 4));
-    nrm = fmax(nrm, __shfl_xor(nrm, 8));
+    }
     nrm = readfirstlane_f64(nrm);
-    // every table of this sample purely imaginary (real Hamiltonians) -> real fast path
-    bool realH = !XG && (A.mode == C3P_MODE_UNITARY);
-    if constexpr (!XG)
-      for (int k = 0; k <= K; ++k) realH = realH && (tab[k * (MAT + 4) + MAT + 3] == 0.0);
-    realH = __builtin_amdgcn_readfirstlane((int)realH) != 0;
     // plan of the complex loop (not evaluated on the real path: its threshold loops cost ~0.5 us of a workgroup's prologue).
     // (round 6) Hermitian Hamiltonians -- every table flagged skew-Hermitian -- take the schemes for normal generators
     MfmaPlan plan = {0, 0, 0};
     int t18n = 0;
     if (!realH) {
-      bool normalG = !XG && (A.mode == C3P_MODE_UNITARY) && !(A.no_t18n & 1);
-      if constexpr (!XG)
-        for (int k = 0; k <= K; ++k) normalG = normalG && (tab[k * (MAT + 4) + MAT + 3] <= 0.0);  // negative: complex skew-Hermitian; zero: real symmetric Hamiltonian
       t18n = __builtin_amdgcn_readfirstlane((int)normalG);
       plan = c3p_pick_plan_mfma(nrm, t18n ? C3P_T18N_THETA : C3P_T18_THETA, t18n != 0 && !(A.no_t18n & 2));
     }
@@ -1301,7 +1423,10 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
     const int ps = __builtin_amdgcn_readfirstlane(plan.s);
     const int t18 = __builtin_amdgcn_readfirstlane(plan.t18);
     const double scale = ldexp(1.0, -ps);
-    __syncthreads();
+    // Behind the barrier above a wave reads the tables and the column sums, which nothing writes again, and reads and writes its
+    // own images and amplitude rows.  Workgroup per sample: no second barrier (the next is the one in front of the final fold).
+    // One wave: the column sums stand in the wave's images, and this one keeps the loop's image writes behind their reads.
+    if constexpr (!MW) __syncthreads();
     SD_TICK(tk1);
 
     if (realH) {
@@ -1360,18 +1485,23 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
           }
           if (K > 0)
             for (int t = lp.idx16; t < A.Lmax; t += 16) sg[lp.b * SG + K * A.Lmax + t] = (valid && t < len) ? -rscale : 0.0;
-          ph = c3p_phase_add(ph, __shfl_xor(ph, 1));
-          ph = c3p_phase_add(ph, __shfl_xor(ph, 2));
-          ph = c3p_phase_add(ph, __shfl_xor(ph, 16));
-          ph = c3p_phase_add(ph, __shfl_xor(ph, 32));
+          // (lane ^ 1, 2, 16, 32 in this order on the register path: c3p_phase_add depends on acc + inc alone, so it commutes and
+          // both lanes of a pair form the same bits)
+          double pa, pb;
+          ph = c3p_phase_add(ph, dpp_f64<DPP_XOR1>(ph));
+          ph = c3p_phase_add(ph, dpp_f64<DPP_XOR2>(ph));
+          pair_xor16(ph, pa, pb);
+          ph = c3p_phase_add(pa, pb);
+          pair_xor32(ph, pa, pb);
+          ph = c3p_phase_add(pa, pb);
           mus_i = c3p_phase_add(ph, (double)(valid ? len : 0) * c3p_phase_add(0.0, tab[MAT + 1]));
           wave_sync();
         }
         // The slots t < tfast are real slices of all four chains of the wave (the chains of a wave differ by at most one slice, so
         // at most the last slot is padding for some of them)
         int tfast = valid ? len : 0;
-        tfast = min(tfast, __shfl_xor(tfast, 4));
-        tfast = min(tfast, __shfl_xor(tfast, 8));
+        tfast = min(tfast, __builtin_amdgcn_mov_dpp(tfast, DPP_ROR4, 0xf, 0xf, true));
+        tfast = min(tfast, __builtin_amdgcn_mov_dpp(tfast, DPP_ROR8, 0xf, 0xf, true));
         tfast = min(__builtin_amdgcn_readfirstlane(tfast), tmax);
         // One slice: E = cos Y - i sin Y as Cm = cos Y and acc = sin Y, both in left-operand form.
         //   WEIGHTED: Y = a_0 T_0 + sum_k a_k T_k with the a_0 row (a padded slot gives Y = 0, E = I).  Otherwise the slot is a real
@@ -2067,11 +2197,13 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
   if constexpr (!GIVEN) {
     if (A.fuse) {
       // (1) fold the wave's four consecutive segments: W = U3 U2 U1 U0 (later segment on the left)
+      // (lane ^ 4 is row_half_mirror of quad_perm [3,2,1,0] -- 7 - (i ^ 3) = i ^ 4 inside eight lanes --, lane ^ 8 is row_ror:8: the
+      // association of the sums is the one of the shuffles they replace)
       double tr = mus_r, ti = mus_i;
-      tr += __shfl_xor(tr, 4);
-      tr += __shfl_xor(tr, 8);
-      ti = c3p_phase_add(ti, __shfl_xor(ti, 4));
-      ti = c3p_phase_add(ti, __shfl_xor(ti, 8));
+      tr += dpp_f64<DPP_HALF_MIRROR>(dpp_f64<DPP_XOR3>(tr));
+      tr += dpp_f64<DPP_ROR8>(tr);
+      ti = c3p_phase_add(ti, dpp_f64<DPP_HALF_MIRROR>(dpp_f64<DPP_XOR3>(ti)));
+      ti = c3p_phase_add(ti, dpp_f64<DPP_ROR8>(ti));
       const int rrest = roff - lp.b * IMG;
       double V[NBI][NJ], Wt[NBI][NJ];
       // Wt (slot 0) = M3 M2 M1 M0 of the four slots' matrices; `in_image`: the chains' images hold M already
@@ -2119,6 +2251,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
       const int lo = (lp.b * nW) >> 2, hi = ((lp.b + 1) * nW) >> 2;
       const int cnt = hi - lo;
       const int cmax = (nW + 3) >> 2;
+      // (the phase factors stay behind the fold: in front of it they shorten nothing that can be measured, profiles/r16)
       double sn, cs;
       sincos(ti, &sn, &cs);
       // (Hermitian Hamiltonians: the trace shifts are imaginary, tr = 0 exactly -- skip the double-precision exp of the fold)
