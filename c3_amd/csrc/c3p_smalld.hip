@@ -2259,7 +2259,8 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
       if (__ballot(tr != 0.0) != 0) er = exp(tr);
       SD_TICK(tkb);
       if constexpr (MW) {
-        // (2) the waves of the sample are the waves of this workgroup and wave 0 folds their partials behind a barrier.  A partial
+        // (2) the waves of the sample are the waves of this workgroup and their partials are folded behind a barrier (by wave 0; by
+        // the tree of (3) where the fold is dealt).  A partial
         // is handed over in the layout its consumer reads: scaled by the wave's e^{tr + i ti} in registers (scale_rows, the
         // arithmetic of store_plain: with equal segments this mode is bit for bit the one-wave mode, tests/test_gpu_round2.py) and
         // written as the image of the wave's chain 0 (the wave's other three images take the unused slots of Wt), from which wave 0
@@ -2282,10 +2283,45 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
           printf("sd wave %d: slices %d, prologue to the table barrier %lld, behind it %lld, loop ends at %lld (100 MHz ticks after the wave's start); "
                  "layout %lld products %lld phase %lld partial store %lld\n", wv, tmax, tk9 - tk0, tk1 - tk9, tkl - tk0, tk2 - tkl, tka - tk2, tkb - tka, tk3 - tkb);
 #endif
+        const int pstride = 4 * IMG + 4 * SG;  // partial p is image 0 of wave p
+        if constexpr (FOLD_SPLIT) {
+          // (3) the tree ((P7 P6)(P5 P4))((P3 P2)(P1 P0)) over the waves, a workgroup barrier between its levels: at stride st = 1,
+          // 2, 4 wave q < nW / (2 st) forms P_{(2q+1) st} P_{2q st} over the right operand's image, all four blocks of the wave on
+          // the one product (mm_split<D, 4>: one product per SIMD at the first level, where wave 0 alone formed the four of them
+          // block by block, and the pair products of the second on two waves).  An output tile is the NBI instructions in K order
+          // from a zero accumulator on the same operands that the other form gives it (nW = 2: its products with the identity
+          // slots return their operand).  A stage's images are written by one wave each and read by no other wave of the stage;
+          // the barrier orders them before the next stage's reads.  Every wave passes every barrier and returns behind the last.
+          const int wrest = woff - lp.b * IMG;
+          double* const p0 = img - wv * pstride;
+          SD_TICK(tk5);
+          for (int st = 1; st < nW; st <<= 1) {
+            if (st > 1) {
+              __syncthreads();
+#ifdef C3P_SD_TIMING
+              if (st == 2) tk6 = wall_clock64();
+#endif
+            }
+            if (2 * st * wv < nW) mm_split<D, 4>(p0 + (2 * wv + 1) * st * pstride + rrest, p0 + 2 * wv * st * pstride + wrest, negmask, lp.b);
+          }
+          if (wv != 0) return;
+#pragma unroll
+          for (int I = 0; I < NBI; ++I)
+#pragma unroll
+            for (int J = 0; J < NJ; ++J) Wt[I][J] = p0[wrest + I * 4 * W + J * 4];
+          SD_TICK(tk7);
+          store_plain<D>(Wt, dst, 1.0, 0.0, ph, lp, lp.b == 0, phc, phs);
+#ifdef C3P_SD_TIMING
+          SD_TICK(tk4);
+          if (tk6 == 0) tk6 = tk7;
+          if (blockIdx.x == 0 && threadIdx.x == 0)
+            printf("sd timing (100 MHz ticks): tables %lld signals %lld prologue %lld loop %lld fold4+store %lld barrier %lld level1 %lld fold2 %lld store %lld total %lld\n", tk8 - tk0, tk9 - tk8, tk1 - tk0, tk2 - tk1, tk3 - tk2, tk5 - tk3, tk6 - tk5, tk7 - tk6, tk4 - tk7, tk4 - tk0);
+#endif
+          return;
+        }
         if (wv != 0) return;
         SD_TICK(tk5);
-        // slot b takes a contiguous quarter of the nW partials (none: the identity); partial p is image 0 of wave p
-        const int pstride = 4 * IMG + 4 * SG;
+        // slot b takes a contiguous quarter of the nW partials (none: the identity)
         const int woff0 = woff - lp.b * IMG;
 #pragma unroll
         for (int I = 0; I < NBI; ++I)

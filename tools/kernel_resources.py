@@ -5,7 +5,7 @@ import re, subprocess, sys
 pat = sys.argv[1] if len(sys.argv) > 1 else ""
 rows, cur = [], None
 for line in sys.stdin:
-    m = re.search(r"remark:\s+(.*?): (\S+) \[-Rpass", line)
+    m = re.search(r"remark:\s+(?:\S+:\d+:\d+:\s+)?(.*?): (\S+) \[-Rpass", line)  # (with or without a file:line:col: prefix)
     if not m:
         continue
     k, v = m.group(1).strip(), m.group(2)
