@@ -184,12 +184,10 @@ static_assert(sd_split_deal<9>(4, 2, 3).I == 3 && sd_split_deal<9>(4, 2, 3).J ==
                   sd_split_deal<9>(4, 3, 1).J == 1 && !sd_split_deal<9>(4, 3, 3).on,
               "D = 9 over four blocks: a column each on blocks 0 .. 2, the last row on block 3");
 
-// The lane's tile of task t (blk: the lane's block within its product, 0 .. NB - 1) as image offsets: A fragments start at
-// I 4 W, the tile itself (right operand, output) at I 4 W + J 4.
+// The lane's tile (I, J) of task t (blk: the lane's block within its product, 0 .. NB - 1)
 template <int D, int NB>
-__device__ __forceinline__ void split_offsets(int blk, int (&aoff)[sd_split_tasks<D>(NB)], int (&coff)[sd_split_tasks<D>(NB)],
-                                              int (&joff)[sd_split_tasks<D>(NB)], bool (&on)[sd_split_tasks<D>(NB)]) {
-  using C = SD<D>;
+__device__ __forceinline__ void split_tiles(int blk, int (&tI)[sd_split_tasks<D>(NB)], int (&tJ)[sd_split_tasks<D>(NB)],
+                                            bool (&on)[sd_split_tasks<D>(NB)]) {
 #pragma unroll
   for (int t = 0; t < sd_split_tasks<D>(NB); ++t) {
     int I = sd_split_deal<D>(NB, 0, t).I, J = sd_split_deal<D>(NB, 0, t).J;
@@ -200,24 +198,39 @@ __device__ __forceinline__ void split_offsets(int blk, int (&aoff)[sd_split_task
       J = blk == q ? sd_split_deal<D>(NB, q, t).J : J;
       o = blk == q ? sd_split_deal<D>(NB, q, t).on : o;
     }
-    aoff[t] = I * 4 * C::W;
-    joff[t] = J * 4;
-    coff[t] = I * 4 * C::W + J * 4;
+    tI[t] = I;
+    tJ[t] = J;
     on[t] = o;
   }
 }
 
+// Epilogue of mm_split: called once with the block's finished tiles acc[t] = tile (tI[t], tJ[t]) of the product, in D-layout (the
+// Re / Im partner of an element is lane ^ 16 of the same register), between the K loop and the write-back.  WRITE: the tiles go to
+// the image afterwards (false: the epilogue has taken them where they belong and the image keeps the right operand).
+struct SplitPlain {
+  static constexpr bool WRITE = true;
+  template <int NT>
+  __device__ __forceinline__ void operator()(double (&)[NT], const int (&)[NT], const int (&)[NT], const bool (&)[NT]) const {}
+};
+
 // C = A B with the output tiles dealt over NB blocks.  `a`: the left operand's image plus the lane's A-fragment offset (roff of
 // mm_img less the chain's image base); `bc`: the right operand's image plus the lane's D-layout offset r W + c.  The product is
-// written over the right operand's image, after all reads (two wave_syncs).  K is the outer loop, as in mm_img: the
-// instructions of a step are independent of one another and the A and B reads of step K + 1 are in flight under them.
-template <int D, int NB>
-__device__ __forceinline__ void mm_split(const double* a, double* bc, unsigned negmask, int blk) {
+// written over the right operand's image, after all reads (two wave_syncs), unless the epilogue takes it elsewhere.  K is the
+// outer loop, as in mm_img: the instructions of a step are independent of one another and the A and B reads of step K + 1 are
+// in flight under them.
+template <int D, int NB, class Epi = SplitPlain>
+__device__ __forceinline__ void mm_split(const double* a, double* bc, unsigned negmask, int blk, const Epi& epi = Epi{}) {
   using C = SD<D>;
   constexpr int NT = sd_split_tasks<D>(NB);
-  int aoff[NT], coff[NT], joff[NT];
+  int tI[NT], tJ[NT], aoff[NT], coff[NT], joff[NT];  // A fragments start at I 4 W, the tile itself (right operand, output) at I 4 W + J 4
   bool on[NT];
-  split_offsets<D, NB>(blk, aoff, coff, joff, on);
+  split_tiles<D, NB>(blk, tI, tJ, on);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    aoff[t] = tI[t] * 4 * C::W;
+    joff[t] = tJ[t] * 4;
+    coff[t] = aoff[t] + joff[t];
+  }
   double ra[2][NT], rb[2][NT], acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -238,11 +251,14 @@ __device__ __forceinline__ void mm_split(const double* a, double* bc, unsigned n
     for (int t = 0; t < NT; ++t) acc[t] = mfma4(ra[K & 1][t], rb[K & 1][t], acc[t]);
     __builtin_amdgcn_sched_barrier(0);
   }
-  wave_sync();
+  epi(acc, tI, tJ, on);
+  if constexpr (Epi::WRITE) {
+    wave_sync();
 #pragma unroll
-  for (int t = 0; t < NT; ++t)
-    if (on[t]) bc[coff[t]] = acc[t];
-  wave_sync();
+    for (int t = 0; t < NT; ++t)
+      if (on[t]) bc[coff[t]] = acc[t];
+    wave_sync();
+  }
 }
 
 struct LanePos {
@@ -882,6 +898,91 @@ __device__ __forceinline__ void scale_rows(const double (&zh)[SD<D>::NBI][SD<D>:
       out[I][J] = (lp.r & 1) ? fma(pr[I], zh[I][J], pi[I] * oth[I][J]) : fma(pr[I], zh[I][J], -pi[I] * oth[I][J]);
 }
 
+// ---- scale_rows and store_plain on the tiles of a dealt product (epilogues of mm_split<D, 4>) ----
+// The block that formed a tile holds it whole: every element gets the exchange and the fma that scale_rows gives it, on the same
+// operands, without the trip through the image that hands the product to one block in register order.
+__device__ __forceinline__ double scale_elem(double mine, double oth, double pr, double pi, int r) {
+  return (r & 1) ? fma(pr, mine, pi * oth) : fma(pr, mine, -pi * oth);
+}
+
+// the product times one complex factor pr + i pi, written to the image (scale_rows with the same factor in every row)
+struct SplitScale {
+  static constexpr bool WRITE = true;
+  double pr, pi;
+  int r;
+  template <int NT>
+  __device__ __forceinline__ void operator()(double (&acc)[NT], const int (&)[NT], const int (&)[NT], const bool (&)[NT]) const {
+    double oth[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) oth[t] = __shfl_xor(acc[t], 16);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = scale_elem(acc[t], oth[t], pr, pi, r);
+  }
+};
+
+// cos / sin of the row phases of the rows of the lane's dealt tiles (row_phase_factors for SplitStore)
+template <int D>
+__device__ __forceinline__ void dealt_row_phase_factors(const double* row_phase, const LanePos& lp, double (&pc)[sd_split_tasks<D>(4)],
+                                                        double (&ps)[sd_split_tasks<D>(4)]) {
+  constexpr int NT = sd_split_tasks<D>(4);
+  int tI[NT], tJ[NT];
+  bool on[NT];
+  split_tiles<D, 4>(lp.b, tI, tJ, on);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int row = 2 * tI[t] + (lp.r >> 1);
+    pc[t] = 1.0, ps[t] = 0.0;
+    if (row_phase != nullptr && on[t] && row < D) sincos(row_phase[row], &ps[t], &pc[t]);
+  }
+}
+
+// the product with its rows times their phases, stored as a plain complex [D][D] array and not written to the image
+// (store_plain with sr = 1, si = 0 and the factors of dealt_row_phase_factors)
+template <int D>
+struct SplitStore {
+  static constexpr bool WRITE = false;
+  double* dst;
+  const double (&pc)[sd_split_tasks<D>(4)];
+  const double (&ps)[sd_split_tasks<D>(4)];
+  int r, c;
+  template <int NT>
+  __device__ __forceinline__ void operator()(double (&acc)[NT], const int (&tI)[NT], const int (&tJ)[NT], const bool (&on)[NT]) const {
+    constexpr double sr = 1.0, si = 0.0;
+    double oth[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) oth[t] = __shfl_xor(acc[t], 16);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int row = 2 * tI[t] + (r >> 1), col = 4 * tJ[t] + c;
+      const double pr = sr * pc[t] - si * ps[t], pi = sr * ps[t] + si * pc[t];
+      if (on[t] && row < D && col < D) dst[(row * D + col) * 2 + (r & 1)] = scale_elem(acc[t], oth[t], pr, pi, r);
+    }
+  }
+};
+
+// SplitStore over the deal of four blocks: every double of the [D][D] complex result is stored by exactly one (block, task, lane)
+// and the index of every store lies inside the result
+template <int D>
+constexpr bool sd_split_store_ok() {
+  int seen[D * D * 2] = {};
+  for (int blk = 0; blk < 4; ++blk)
+    for (int t = 0; t < sd_split_tasks<D>(4); ++t)
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+          const SDTile s = sd_split_deal<D>(4, blk, t);
+          const int row = 2 * s.I + (r >> 1), col = 4 * s.J + c;
+          if (!(s.on && row < D && col < D)) continue;
+          const int idx = (row * D + col) * 2 + (r & 1);
+          if (idx < 0 || idx >= D * D * 2) return false;
+          ++seen[idx];
+        }
+  for (int i = 0; i < D * D * 2; ++i)
+    if (seen[i] != 1) return false;
+  return true;
+}
+static_assert(sd_split_store_ok<5>() && sd_split_store_ok<6>() && sd_split_store_ok<7>() && sd_split_store_ok<8>() && sd_split_store_ok<9>(),
+              "dealt store: every element of the result exactly once, nothing outside it");
+
 template <int D, bool WRITE_THROUGH = false>
 __device__ __forceinline__ void store_plain(const double (&zh)[SD<D>::NBI][SD<D>::NJ], double* dst,
                                             double sr, double si, const double* row_phase,
@@ -1157,7 +1258,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
   const int wv = MW ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
   const int nwv = MW ? (int)(blockDim.x >> 6) : 1;
 #ifdef C3P_SD_TIMING
-  long long tk0 = wall_clock64(), tk1 = 0, tk2 = 0, tk3 = 0, tk4 = 0, tk5 = 0, tk6 = 0, tk7 = 0, tk8 = 0, tk9 = 0, tkl = 0, tka = 0, tkb = 0;
+  long long tk0 = wall_clock64(), tk1 = 0, tk2 = 0, tk3 = 0, tk4 = 0, tk5 = 0, tk6 = 0, tk7 = 0, tk8 = 0, tk9 = 0, tkl = 0, tka = 0, tkb = 0, tkc = 0;
 #define SD_TICK(v) v = wall_clock64()
 #else
 #define SD_TICK(v)
@@ -2207,6 +2308,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
       const int rrest = roff - lp.b * IMG;
       double V[NBI][NJ], Wt[NBI][NJ];
       // Wt (slot 0) = M3 M2 M1 M0 of the four slots' matrices; `in_image`: the chains' images hold M already
+      // (where the fold is dealt the product does not come back to registers: it goes to image 0 times the wave's factor, see below)
       // Only two of the four slots have a first product to form and one the second.  The workgroup-per-sample instances of
       // D = 5 .. 9 deal each product's output tiles over the blocks of the slots that have none (mm_split: D = 9, 40 + 20 matrix
       // instructions instead of 75 + 75); every element has the bits of the other form, which the remaining instances keep, so the
@@ -2218,18 +2320,26 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
       //  * the one-wave instances -- the last arriver inlines the fold a second time, and every one of D = 9 .. 12 took more
       //    scratch with the deal (124 -> 136 B/lane at D = 9, 340 -> 428 at D = 12).
       constexpr bool FOLD_SPLIT = MW && NBI * NJ > 2 && D <= 9;
+      // the wave's factor e^{tr + i ti} = er (cs + i sn)
+      double sn, cs, er = 1.0;
+      auto wave_factor = [&]() {
+        sincos(ti, &sn, &cs);
+        // (Hermitian Hamiltonians: the trace shifts are imaginary, tr = 0 exactly -- skip the double-precision exp of the fold)
+        if (__ballot(tr != 0.0) != 0) er = exp(tr);
+      };
       auto fold_slots = [&](const double (&M)[NBI][NJ], bool in_image) {
         if (!in_image) write_image<D>(M, img, woff);
         if constexpr (FOLD_SPLIT) {
           const int wrest = woff - lp.b * IMG;
           // block pairs {0, 1} and {2, 3}: M1 M0 over image 0, M3 M2 over image 2
           mm_split<D, 2>(img + ((lp.b & 2) + 1) * IMG + rrest, img + (lp.b & 2) * IMG + wrest, negmask, lp.b & 1);
-          // all four blocks: (M3 M2)(M1 M0) over image 0, from which every slot takes it in register order
-          mm_split<D, 4>(img + 2 * IMG + rrest, img + wrest, negmask, lp.b);
-#pragma unroll
-          for (int I = 0; I < NBI; ++I)
-#pragma unroll
-            for (int J = 0; J < NJ; ++J) Wt[I][J] = img[wrest + I * 4 * W + J * 4];
+          SD_TICK(tkc);
+          // (here the factor is what the second product's epilogue needs, and its latency lies under the LDS traffic of the products)
+          wave_factor();
+          SD_TICK(tkb);
+          // all four blocks: (M3 M2)(M1 M0) over image 0, every tile scaled by the wave's factor where it was formed: image 0 is the
+          // wave's partial as the tree of (3) reads it, written once (tr and ti are the same in every lane of the wave)
+          mm_split<D, 4>(img + 2 * IMG + rrest, img + wrest, negmask, lp.b, SplitScale{er * cs, er * sn, lp.r});
         } else {
           const int roff1 = ((lp.b + 1) & 3) * IMG + rrest;  // A fragments of the NEXT chain's image
           const int roff2 = ((lp.b + 2) & 3) * IMG + rrest;
@@ -2251,37 +2361,48 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
       const int lo = (lp.b * nW) >> 2, hi = ((lp.b + 1) * nW) >> 2;
       const int cnt = hi - lo;
       const int cmax = (nW + 3) >> 2;
-      // (the phase factors stay behind the fold: in front of it they shorten nothing that can be measured, profiles/r16)
-      double sn, cs;
-      sincos(ti, &sn, &cs);
-      // (Hermitian Hamiltonians: the trace shifts are imaginary, tr = 0 exactly -- skip the double-precision exp of the fold)
-      double er = 1.0;
-      if (__ballot(tr != 0.0) != 0) er = exp(tr);
-      SD_TICK(tkb);
+      // (where the fold is not dealt the phase factors stay behind it: in front of it they shorten nothing that can be measured,
+      // profiles/r16)
+      if constexpr (!FOLD_SPLIT) {
+        wave_factor();
+        SD_TICK(tkb);
+      }
       if constexpr (MW) {
         // (2) the waves of the sample are the waves of this workgroup and their partials are folded behind a barrier (by wave 0; by
         // the tree of (3) where the fold is dealt).  A partial
         // is handed over in the layout its consumer reads: scaled by the wave's e^{tr + i ti} in registers (scale_rows, the
         // arithmetic of store_plain: with equal segments this mode is bit for bit the one-wave mode, tests/test_gpu_round2.py) and
         // written as the image of the wave's chain 0 (the wave's other three images take the unused slots of Wt), from which wave 0
-        // reads right operands in register order and streams left operands as they are.
-        {
+        // reads right operands in register order and streams left operands as they are.  Where the fold is dealt, the second product
+        // of fold_slots has done both in its epilogue.
+        if constexpr (!FOLD_SPLIT) {
           double pr[NBI], pi[NBI];
 #pragma unroll
           for (int I = 0; I < NBI; ++I) pr[I] = er * cs, pi[I] = er * sn;
           scale_rows<D>(Wt, pr, pi, lp, V);
+          write_image<D>(V, img, woff);
         }
-        write_image<D>(V, img, woff);
         SD_TICK(tk3);
         // (wave 0 -- the older wave of its SIMD, through its loop first -- evaluates the row phases of the final store
-        // while it waits for the others: five double-precision sincos, 1.5 us otherwise spent after the barrier)
-        double phc[NBI], phs[NBI];
-        if (wv == 0) row_phase_factors<D>(ph, lp, phc, phs);
+        // while it waits for the others: five double-precision sincos, 1.5 us otherwise spent after the barrier; where the fold is
+        // dealt, those of the rows of the lane's tiles of the last product, one per task)
+        double phc[NBI], phs[NBI], dphc[sd_split_tasks<D>(4)], dphs[sd_split_tasks<D>(4)];
+        if (wv == 0) {
+          if constexpr (FOLD_SPLIT)
+            dealt_row_phase_factors<D>(ph, lp, dphc, dphs);
+          else
+            row_phase_factors<D>(ph, lp, phc, phs);
+        }
         __syncthreads();
 #ifdef C3P_SD_TIMING
-        if (blockIdx.x == 7 && lane == 0)
-          printf("sd wave %d: slices %d, prologue to the table barrier %lld, behind it %lld, loop ends at %lld (100 MHz ticks after the wave's start); "
-                 "layout %lld products %lld phase %lld partial store %lld\n", wv, tmax, tk9 - tk0, tk1 - tk9, tkl - tk0, tk2 - tkl, tka - tk2, tkb - tka, tk3 - tkb);
+        if (blockIdx.x == 7 && lane == 0) {
+          if constexpr (FOLD_SPLIT)
+            printf("sd wave %d: slices %d, prologue to the table barrier %lld, behind it %lld, loop ends at %lld (100 MHz ticks after the wave's start); "
+                   "layout %lld product 1 %lld phase %lld product 2 with scale and store %lld\n", wv, tmax, tk9 - tk0, tk1 - tk9, tkl - tk0, tk2 - tkl, tkc - tk2, tkb - tkc, tk3 - tkb);
+          else
+            printf("sd wave %d: slices %d, prologue to the table barrier %lld, behind it %lld, loop ends at %lld (100 MHz ticks after the wave's start); "
+                   "layout %lld products %lld phase %lld partial store %lld\n", wv, tmax, tk9 - tk0, tk1 - tk9, tkl - tk0, tk2 - tkl, tka - tk2, tkb - tka, tk3 - tkb);
+        }
 #endif
         const int pstride = 4 * IMG + 4 * SG;  // partial p is image 0 of wave p
         if constexpr (FOLD_SPLIT) {
@@ -2294,28 +2415,31 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
           // the barrier orders them before the next stage's reads.  Every wave passes every barrier and returns behind the last.
           const int wrest = woff - lp.b * IMG;
           double* const p0 = img - wv * pstride;
+          // The last level (st = nW / 2, wave 0 alone) has no consumer in LDS: every block scales the tiles it formed by their rows'
+          // frame phases and stores them to the result (SplitStore: the arithmetic of store_plain), and the image is not written.
           SD_TICK(tk5);
-          for (int st = 1; st < nW; st <<= 1) {
+          auto level_barrier = [&](int st) {
             if (st > 1) {
               __syncthreads();
 #ifdef C3P_SD_TIMING
               if (st == 2) tk6 = wall_clock64();
 #endif
             }
+          };
+          int st = 1;
+          for (; 2 * st < nW; st <<= 1) {
+            level_barrier(st);
             if (2 * st * wv < nW) mm_split<D, 4>(p0 + (2 * wv + 1) * st * pstride + rrest, p0 + 2 * wv * st * pstride + wrest, negmask, lp.b);
           }
+          level_barrier(st);
           if (wv != 0) return;
-#pragma unroll
-          for (int I = 0; I < NBI; ++I)
-#pragma unroll
-            for (int J = 0; J < NJ; ++J) Wt[I][J] = p0[wrest + I * 4 * W + J * 4];
           SD_TICK(tk7);
-          store_plain<D>(Wt, dst, 1.0, 0.0, ph, lp, lp.b == 0, phc, phs);
+          mm_split<D, 4>(p0 + st * pstride + rrest, p0 + wrest, negmask, lp.b, SplitStore<D>{dst, dphc, dphs, lp.r, lp.c});
 #ifdef C3P_SD_TIMING
           SD_TICK(tk4);
           if (tk6 == 0) tk6 = tk7;
           if (blockIdx.x == 0 && threadIdx.x == 0)
-            printf("sd timing (100 MHz ticks): tables %lld signals %lld prologue %lld loop %lld fold4+store %lld barrier %lld level1 %lld fold2 %lld store %lld total %lld\n", tk8 - tk0, tk9 - tk8, tk1 - tk0, tk2 - tk1, tk3 - tk2, tk5 - tk3, tk6 - tk5, tk7 - tk6, tk4 - tk7, tk4 - tk0);
+            printf("sd timing (100 MHz ticks): tables %lld signals %lld prologue %lld loop %lld fold4+store %lld barrier %lld level1 %lld level2 %lld last product with store %lld total %lld\n", tk8 - tk0, tk9 - tk8, tk1 - tk0, tk2 - tk1, tk3 - tk2, tk5 - tk3, tk6 - tk5, tk7 - tk6, tk4 - tk7, tk4 - tk0);
 #endif
           return;
         }
