@@ -3,7 +3,8 @@
 Everything here is computed in x87 long double (64-bit mantissa, eps = 1.08e-19): 2^11 finer than the double
 precision of the kernels under test, so an error of a few units of 2^-53 is measured, not guessed.  The module holds
 
-* the references: `expm_ld`, `chain_ld`, `kron_ld`, `overlap_ld`, `infid_ld`;
+* the references: `expm_ld`, `chain_ld`, `kron_ld`, `overlap_ld`, `infid_ld`, and `pwc_ld` (the assembled piecewise-constant
+  propagators of `propagate_batch`, unitary and Lindblad; cases in tests/pwc_cases.py, GPU tests in tests/test_gpu_pwc_extended.py);
 * the checkers shared by the CPU tests (tests/test_extended_ref.py) and the GPU tests
   (tests/test_gpu_matrix_routines.py, tests/test_gpu_fidelity_epilogue.py): each asserts its bar and RETURNS the
   ratio it asserted on, so it can be printed and recorded;
@@ -95,6 +96,58 @@ def chain_ld(M, right: bool = False):
     return acc
 
 
+def lindblad_generator_ld(H, col_ops):
+    """L(H) = -i (H (x) 1 - 1 (x) H^T) + sum_c [ C (x) conj(C) - (C^+C (x) 1 + 1 (x) (C^+C)^T) / 2 ] of H[..., D, D] in complex
+    long double: the row-major vectorisation of `oracle.lindblad_generator` / `lindblad_dissipator` (rho_ij at row i D + j)."""
+    H, col = to_ld(H), to_ld(col_ops)
+    D = H.shape[-1]
+    one = np.eye(D, dtype=CLD)
+    clp = np.zeros((D * D, D * D), dtype=CLD)
+    for C in col:
+        CC = np.conj(C.T) @ C
+        clp = clp + kron_ld(C, np.conj(C)) - (kron_ld(CC, one) + kron_ld(one, CC.T)) / LD(2)
+    return CLD(-1j) * (kron_ld(H, one) - kron_ld(one, np.swapaxes(H, -1, -2))) + clp
+
+
+def pwc_generators_ld(h0, hks, signals, dt, *, col_ops=None):
+    """X[B, N, Dm, Dm] of the piecewise-constant problem in complex long double: X_n = -i dt H_n, or dt L(H_n) with collapse
+    operators; H_n = h0 + sum_k c_k(n) hk, or (hks = signals = None: branch B) the per-slice Hamiltonians h0[N, D, D] /
+    [B, N, D, D] themselves.  Operators shared ([D,D], [K,D,D], [C,D,D]) or per sample ([B,..]).  The inputs are doubles:
+    their conversion is exact, every operation after it rounds at eps_ld."""
+    h0 = to_ld(h0)
+    if hks is None or signals is None:
+        H = h0 if h0.ndim == 4 else h0[None]
+    else:
+        sig = np.asarray(signals, dtype=np.float64).astype(LD)
+        B, K, N = sig.shape
+        hks = to_ld(hks)
+        H = np.empty((B, N) + h0.shape[-2:], dtype=CLD)
+        for b in range(B):
+            hb = h0[b] if h0.ndim == 3 else h0
+            kb = hks[b] if hks.ndim == 4 else hks
+            H[b] = hb[None]
+            for k in range(K):
+                H[b] = H[b] + sig[b, k][:, None, None] * kb[k][None]
+    if col_ops is None:
+        return CLD(-1j) * LD(dt) * H
+    col = np.asarray(col_ops)
+    return np.stack([LD(dt) * lindblad_generator_ld(H[b], col[b] if col.ndim == 4 else col) for b in range(H.shape[0])])
+
+
+def pwc_ld(h0, hks, signals, dt, *, col_ops=None, fr_phase=None, want_dUs=False):
+    """U[B, Dm, Dm] of `propagate_batch` in complex long double: `expm_ld` of every slice generator (`pwc_generators_ld`),
+    `chain_ld` (later slice on the left), then the row phases diag(exp(i fr_phase[b])), fr_phase [B, Dm].  With `want_dUs`
+    returns (U, dUs[B, N, Dm, Dm])."""
+    X = pwc_generators_ld(h0, hks, signals, dt, col_ops=col_ops)
+    dUs = expm_ld(X)
+    U = np.stack([chain_ld(dUs[b]) for b in range(X.shape[0])])
+    if fr_phase is not None:
+        ph = np.asarray(fr_phase, dtype=np.float64).astype(LD)
+        assert ph.shape == U.shape[:2], (ph.shape, U.shape)
+        U = (np.cos(ph) + CLD(1j) * np.sin(ph))[:, :, None] * U
+    return (U, dUs) if want_dUs else U
+
+
 def kron_ld(A, B):
     """Batched Kronecker product out[.., i Db + p, j Db + q] = A[.., i, j] B[.., p, q] in complex long double."""
     A, B = to_ld(A), to_ld(B)
@@ -169,6 +222,7 @@ def chain_err(P, ref) -> float:
 
 
 CHAIN_FACTOR = 8.0
+EXPM_SLICE_FACTOR = 8.0  # (= EXPM_FACTOR: the 8 R_CPU of the expm bars, per slice)
 
 
 def check_chain(P, ref, e_cpu: float, factor: float = CHAIN_FACTOR) -> float:
@@ -182,6 +236,37 @@ def check_chain(P, ref, e_cpu: float, factor: float = CHAIN_FACTOR) -> float:
     e = max(chain_err(P[b], ref[b]) for b in range(P.shape[0]))
     ratio = 0.0 if e == 0.0 else (np.inf if e_cpu == 0.0 else e / e_cpu)
     assert ratio <= factor, f"chain error {e:.3g} is {ratio:.3g} x the double-precision fold's {e_cpu:.3g} (bar {factor:g})"
+    return ratio
+
+
+def pwc_err(U, ref) -> float:
+    """Worst ||U_b - ref_b||_F over the samples of one propagator stack, in long double."""
+    U = np.asarray(U)
+    assert U.shape == ref.shape, (U.shape, ref.shape)
+    return max(chain_err(U[b], ref[b]) for b in range(U.shape[0]))
+
+
+def check_pwc(U, ref, e_cpu: float, factor: float = CHAIN_FACTOR) -> float:
+    """Every sample of the assembled propagators U[B, Dm, Dm] must stay within factor x e_cpu of `pwc_ld`'s, e_cpu the worst
+    error over the samples of the double-precision CPU routes.  Returns worst error / e_cpu."""
+    U = np.asarray(U)
+    assert U.ndim == 3 and U.dtype == np.complex128, (U.shape, U.dtype)
+    return check_chain(U, ref, e_cpu, factor)
+
+
+def slices_ratio(dUs, X, dUs_ref) -> float:
+    """Worst `expm_ratio` over the slice propagators dUs[B, N, Dm, Dm] of generators X (long double) against `expm_ld`'s."""
+    dUs = np.asarray(dUs)
+    assert dUs.shape == X.shape == dUs_ref.shape, (dUs.shape, X.shape, dUs_ref.shape)
+    return max(expm_ratio(dUs[b, n], X[b, n], dUs_ref[b, n]) for b in range(X.shape[0]) for n in range(X.shape[1]))
+
+
+def check_pwc_slices(dUs, X, dUs_ref, r_cpu: float, factor: float = EXPM_SLICE_FACTOR) -> float:
+    """The `dUs` route: every slice's `expm_ratio` within factor x r_cpu, r_cpu the worst ratio of scipy and the oracle over
+    the same slices.  Returns worst ratio / r_cpu."""
+    r = slices_ratio(dUs, X, dUs_ref)
+    ratio = 0.0 if r == 0.0 else (np.inf if r_cpu == 0.0 else r / r_cpu)
+    assert ratio <= factor, f"slice error ratio {r:.3g} is {ratio:.3g} x the CPU routes' {r_cpu:.3g} (bar {factor:g})"
     return ratio
 
 
