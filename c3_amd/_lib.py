@@ -23,7 +23,7 @@ COL_PER_SAMPLE = 0x40  # Lindblad PWC entries: col_ops is [B,C,D,D], one set of 
 SEQ_PSI0_PER_SAMPLE = 0x80  # c3p_seq_chain / c3p_seq_chain_vjp, state mode: psi0 is [P,M]
 HERMITIAN_H = 0x10  # c3p_pwc_lindblad: the caller declares h0 / hks Hermitian (D = 2, 3: real arithmetic in the Hermitian basis)
 
-KERNEL_NAMES = {0: "none", 1: "generic_lds", 2: "generic_global", 3: "smalld", 4: "mfma", 5: "ode_wg", 6: "ode_row", 7: "ode_mfma", 8: "ode_row_or_wg", 9: "seq", 10: "seq_vjp", 11: "ode_vjp", 12: "dress", 13: "dress_vjp"}
+KERNEL_NAMES = {0: "none", 1: "generic_lds", 2: "generic_global", 3: "smalld", 4: "mfma", 5: "ode_wg", 6: "ode_row", 7: "ode_mfma", 8: "ode_row_or_wg", 9: "seq", 10: "seq_vjp", 11: "ode_vjp", 12: "dress", 13: "dress_vjp", 14: "readout", 15: "readout_vjp"}
 
 SOLVERS = {"rk4": 0, "rk38": 1, "rk5": 2, "tsit5": 3}
 STEPS = {"schrodinger": 0, "von_neumann": 1, "lindblad": 2}
@@ -75,6 +75,8 @@ SIGNATURES = {
     "c3p_ode_solve_vjp": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     "c3p_dress": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c3p_dress_vjp": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c3p_readout_goal": (_i, [_vp, _i, _i, _i, _i, _vp, _i64, _i, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "c3p_readout_goal_vjp": (_i, [_vp, _i, _i, _i, _i, _vp, _i64, _i, _vp, _vp, _i64, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -32,6 +32,7 @@
 #include "c3p_seq_vjp.h"
 #include "c3p_ode_vjp.h"
 #include "c3p_dress.h"
+#include "c3p_readout.h"
 
 namespace {
 
@@ -99,7 +100,7 @@ int fail(const char* fmt, ...) {
   } while (0)
 
 // Per-device workspace slots, grown lazily, freed by c3p_shutdown().
-enum Slot { SL_SEG_A = 0, SL_SEG_B, SL_SCRATCH, SL_CLP, SL_TABLES, SL_COUNTERS, SL_COUNTERS2, SL_IN0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_IN6, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_OUT4, SL_SEG_F, SL_SEQ_FLAG, SL_SEQ_VJP_WS, SL_SEQ_VJP_SLAB, SL_ODE_VJP_WS, SL_LMODEL_PART, SL_LMODEL_OUT, SL_COUNT };
+enum Slot { SL_SEG_A = 0, SL_SEG_B, SL_SCRATCH, SL_CLP, SL_TABLES, SL_COUNTERS, SL_COUNTERS2, SL_IN0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_IN6, SL_IN7, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_OUT4, SL_OUT5, SL_OUT6, SL_SEG_F, SL_SEQ_FLAG, SL_SEQ_VJP_WS, SL_SEQ_VJP_SLAB, SL_ODE_VJP_WS, SL_LMODEL_PART, SL_LMODEL_OUT, SL_COUNT };
 
 struct DeviceWs {
   std::mutex mu;  // one lock per device: calls on different GPUs of one process do not serialise
@@ -1756,7 +1757,7 @@ struct Stage {
       return 0;
     }
     void* d;
-    if (in_slot > SL_IN6) return fail("internal: out of input staging slots");
+    if (in_slot > SL_IN7) return fail("internal: out of input staging slots");
     if (ws_get(w, (Slot)in_slot++, bytes, &d)) return -1;
     HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, st));
     *dev = d;
@@ -1768,7 +1769,7 @@ struct Stage {
       return 0;
     }
     void* d;
-    if (out_slot > SL_OUT4) return fail("internal: out of output staging slots");
+    if (out_slot > SL_OUT6) return fail("internal: out of output staging slots");
     if (ws_get(w, (Slot)out_slot++, bytes, &d)) return -1;
     backs.push_back({host, d, bytes});
     *dev = d;
@@ -4008,6 +4009,119 @@ int c3p_dress_vjp(const void* T, const double* eig, const void* ops, int64_t ops
   HIP_TRY(c3p_launch_dress_vjp(a, st));
   if (flags & C3P_HOST_PTRS) return sg.finish();
   return 0;
+}
+
+// c3p_readout_goal (goal_weights, x_bar_out, ... null, vjp false) and c3p_readout_goal_vjp: checks, staging, workspace, launches.
+static int readout_common(bool vjp, const void* x, int P, int S, int M, int D, const double* conf, int64_t conf_bstride, int R,
+                          const double* label_w, const double* rescale, int64_t rescale_bstride, const double* meas,
+                          const double* stds, const double* shots, int estimator, const double* goal_weights, int flags,
+                          double* sim_out, double* sim_raw_out, double* goals_out, void* x_bar_out, double* conf_bar_out,
+                          double* rescale_bar_out, double* pop_bar_out, void* stream) {
+  const char* entry = vjp ? "c3p_readout_goal_vjp" : "c3p_readout_goal";
+  if (P < 0 || S < 0 || conf_bstride < 0) return fail("%s: bad sizes P=%d S=%d conf_bstride=%lld", entry, P, S, (long long)conf_bstride);
+  if (D < 2 || D > C3P_READOUT_MAX_D) return fail("%s serves 2 <= D <= %d, got D=%d", entry, C3P_READOUT_MAX_D, D);
+  if (M != D && M != D * D) return fail("%s: M=%d is neither D=%d (kets) nor D^2=%d (density vectors)", entry, M, D, D * D);
+  if (R < 1) return fail("%s: R=%d, the read-out needs at least one row", entry, R);
+  if (R > C3P_READOUT_MAX_D) return fail("%s serves R <= %d, got R=%d", entry, C3P_READOUT_MAX_D, R);
+  if (!conf && R != D) return fail("%s: without a confusion matrix R must be D=%d, got R=%d", entry, D, R);
+  if (estimator < C3P_EST_G_LL_PRIME || estimator > C3P_EST_RMS_SIM_STDS_DIST) return fail("%s: unknown estimator id %d", entry, estimator);
+  if (!sim_out || !goals_out) return fail("%s: NULL sim_out / goals_out", entry);
+  if (vjp && !x_bar_out) return fail("%s: NULL x_bar_out", entry);
+  const size_t rd = (size_t)R * D;
+  if (conf && conf_bstride != 0 && (size_t)conf_bstride < rd) return fail("%s: conf_bstride=%lld is smaller than one confusion matrix (%zu)", entry, (long long)conf_bstride, rd);
+  if (rescale && rescale_bstride != 0 && rescale_bstride != 2) return fail("%s: rescale_bstride=%lld, expected 0 (shared) or 2", entry, (long long)rescale_bstride);
+  if (P == 0 || S == 0) return 0;
+  if (!x || !meas || !shots) return fail("%s: NULL x / meas / shots", entry);
+  if (estimator == C3P_EST_RMS_EXP_STDS_DIST && !stds) return fail("%s: rms_exp_stds_dist reads stds, which is NULL", entry);
+  if (vjp && !goal_weights) return fail("%s: NULL goal_weights", entry);
+  const int V = label_w ? 1 : R;
+  const size_t ds = sizeof(double), cs = sizeof(cplx);
+  const size_t nx = (size_t)P * S * M, nv = (size_t)P * S * V, npop = (size_t)P * S * D;
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  DeviceWs* w = lk.w;
+  if (!w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  Stage sg{w, st};
+  const void *d_x = x, *d_conf = conf, *d_lw = label_w, *d_rs = rescale, *d_meas = meas, *d_stds = stds, *d_shots = shots, *d_gw = goal_weights;
+  void *d_sim = sim_out, *d_raw = sim_raw_out, *d_goals = goals_out, *d_xb = x_bar_out, *d_cb = conf_bar_out, *d_rb = rescale_bar_out, *d_pb = pop_bar_out;
+  if (flags & C3P_HOST_PTRS) {
+    if (sg.in(x, nx * cs, &d_x)) return -1;
+    if (sg.in(conf, ((size_t)(P - 1) * conf_bstride + rd) * ds, &d_conf)) return -1;
+    if (sg.in(label_w, (size_t)R * ds, &d_lw)) return -1;
+    if (sg.in(rescale, ((size_t)(P - 1) * rescale_bstride + 2) * ds, &d_rs)) return -1;
+    if (sg.in(meas, nv * ds, &d_meas)) return -1;
+    if (sg.in(stds, nv * ds, &d_stds)) return -1;
+    if (sg.in(shots, nv * ds, &d_shots)) return -1;
+    if (sg.in(goal_weights, (size_t)P * ds, &d_gw)) return -1;
+    if (sg.out(sim_out, nv * ds, &d_sim)) return -1;
+    if (sg.out(sim_raw_out, nv * ds, &d_raw)) return -1;
+    if (sg.out(goals_out, (size_t)P * ds, &d_goals)) return -1;
+    if (sg.out(x_bar_out, nx * cs, &d_xb)) return -1;
+    if (sg.out(conf_bar_out, (size_t)P * rd * ds, &d_cb)) return -1;
+    if (sg.out(rescale_bar_out, (size_t)P * 2 * ds, &d_rb)) return -1;
+    if (sg.out(pop_bar_out, npop * ds, &d_pb)) return -1;
+  }
+  // workspace: the summands; for the reverse pass also sim_bar, v_bar, the populations and (not given by the caller) sim_raw
+  const bool own_raw = vjp && !d_raw;
+  const size_t wsd = nv + (vjp ? 2 * nv + npop + (own_raw ? nv : 0) : 0);
+  void* v;
+  if (ws_get(w, SL_SCRATCH, wsd * ds, &v)) return -1;
+  double* ws = (double*)v;
+  ReadoutArgs a = {};
+  a.x = (const cplx*)d_x;
+  a.P = P;
+  a.S = S;
+  a.M = M;
+  a.D = D;
+  a.R = R;
+  a.V = V;
+  a.density = M != D;
+  a.conf = (const double*)d_conf;
+  a.conf_bstride = (long)conf_bstride;
+  a.label_w = (const double*)d_lw;
+  a.rescale = (const double*)d_rs;
+  a.rescale_bstride = (long)rescale_bstride;
+  a.meas = (const double*)d_meas;
+  a.stds = (const double*)d_stds;
+  a.shots = (const double*)d_shots;
+  a.estimator = estimator;
+  a.sim = (double*)d_sim;
+  a.sim_raw = (double*)d_raw;
+  a.goals = (double*)d_goals;
+  a.terms = ws;
+  if (vjp) {
+    a.sim_bar = ws + nv;
+    a.v_bar = ws + 2 * nv;
+    a.pop = ws + 3 * nv;
+    if (own_raw) a.sim_raw = ws + 3 * nv + npop;
+    a.goal_weights = (const double*)d_gw;
+    a.x_bar = (cplx*)d_xb;
+    a.conf_bar = (double*)d_cb;
+    a.rescale_bar = (double*)d_rb;
+    a.pop_bar = (double*)d_pb;
+  }
+  g_last_kernel = vjp ? C3P_KERNEL_READOUT_VJP : C3P_KERNEL_READOUT;
+  HIP_TRY(vjp ? c3p_launch_readout_vjp(a, st) : c3p_launch_readout(a, st));
+  if (flags & C3P_HOST_PTRS) return sg.finish();
+  return 0;
+}
+
+int c3p_readout_goal(const void* x, int P, int S, int M, int D, const double* conf, int64_t conf_bstride, int R,
+                     const double* label_w, const double* rescale, int64_t rescale_bstride, const double* meas,
+                     const double* stds, const double* shots, int estimator, int flags, double* sim_out, double* sim_raw_out,
+                     double* goals_out, void* stream) {
+  return readout_common(false, x, P, S, M, D, conf, conf_bstride, R, label_w, rescale, rescale_bstride, meas, stds, shots, estimator,
+                        nullptr, flags, sim_out, sim_raw_out, goals_out, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+int c3p_readout_goal_vjp(const void* x, int P, int S, int M, int D, const double* conf, int64_t conf_bstride, int R,
+                         const double* label_w, const double* rescale, int64_t rescale_bstride, const double* meas,
+                         const double* stds, const double* shots, int estimator, const double* goal_weights, int flags,
+                         double* sim_out, double* sim_raw_out, double* goals_out, void* x_bar_out, double* conf_bar_out,
+                         double* rescale_bar_out, double* pop_bar_out, void* stream) {
+  return readout_common(true, x, P, S, M, D, conf, conf_bstride, R, label_w, rescale, rescale_bstride, meas, stds, shots, estimator,
+                        goal_weights, flags, sim_out, sim_raw_out, goals_out, x_bar_out, conf_bar_out, rescale_bar_out, pop_bar_out, stream);
 }
 
 }  // extern "C"

@@ -10,7 +10,10 @@ simulated populations against the measured ones with `g_LL_prime` (libraries/est
   signals[gate] [P,K,N] (+ per-set model operators)  --propagate_batch-->  U[gate] [P,D,D]
   sequences  --c3p_matmul_chain over P x sequences-->  U_seq [P,S,D,D]  -->  |U_seq psi0|^2  -->  sim_vals [P,S]
 
-Everything up to the populations stays in HBM.  The likelihood is a few flops per value and stays on the host.
+Everything up to the populations stays in HBM.  By default the likelihood (`g_LL_prime`, a perfect read-out) is evaluated on the host;
+with `readout=` (a `readout.Readout`: confusion rows, meas_scale, meas_offset -- an empty one too) or another `estimator=` the read-out
+model, the estimator and their reverse mode run on the device (c3p_readout_goal, c3p_readout_goal_vjp) and the result
+also holds "sim_vals_no_rescale" and, with the gradient, "grad_conf_rows", "grad_meas_scale", "grad_meas_offset".
 
 Open systems (`col_ops` given): the propagators are Lindblad superoperators [P,D^2,D^2], the sequence states density vectors
 and the populations their diagonal; `thermal_initial_state` mirrors InitialiseGround (libraries/tasks.py:46-88).
@@ -266,7 +269,51 @@ def process_batch(pops, label_indices: Optional[Sequence[int]] = None):
     return pops[..., idx].sum(-1)
 
 
-def goal_run_batched(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence[Dict], psi_init, label_indices, *, fr_phase: Optional[Dict] = None, device=None, col_ops=None) -> Dict:
+def _legacy_epilogue(readout, estimator) -> bool:
+    """True for the host epilogue (perfect read-out, g_LL_prime in numpy); a `Readout` -- an empty one too -- or another estimator
+    takes the device epilogue of `readout.readout_goal` / `readout_goal_vjp`."""
+    return readout is None and estimator == "g_LL_prime"
+
+
+def _host_or_none(a):
+    if a is None:
+        return None
+    return a.cpu().numpy() if propagation._is_torch(a) else np.asarray(a)
+
+
+def _readout_forward(x, D: int, data, readout, estimator, label_indices, P: int, n_seqs: int) -> Dict:
+    """Goals of the device epilogue from the sequence states x [P,S,M]; only the results leave the device."""
+    from . import readout as ro
+
+    r = ro.readout_goal(x, readout, data, label_indices, estimator, dim=D)
+    goals = _host_or_none(r["goals"])
+    return {"goal": g_LL_prime_combined(goals, [n_seqs] * P), "goals": goals, "sim_vals": _host_or_none(r["sim"]),
+            "sim_vals_no_rescale": _host_or_none(r["sim_raw"])}
+
+
+def _readout_backward(x, D: int, data, readout, estimator, label_indices, P: int, n_seqs: int):
+    """(result entries, x_bar) of the device epilogue: c3p_readout_goal_vjp with the weights w_p / sum w of `dv_g_LL_prime`.
+    The goals and simulated values stay where x is; `_readout_results` copies them out once the reverse sweep is enqueued."""
+    from . import readout as ro
+
+    weights = np.full(P, float(n_seqs)) / (float(n_seqs) * P)
+    if propagation._is_torch(x):
+        import torch
+
+        weights = torch.as_tensor(weights, device=x.device)
+    r = ro.readout_goal_vjp(x, readout, data, label_indices, estimator, weights, dim=D)
+    return r, r["x_bar"]
+
+
+def _readout_results(r, P: int, n_seqs: int) -> Dict:
+    goals = _host_or_none(r["goals"])
+    return {"goal": g_LL_prime_combined(goals, [n_seqs] * P), "goals": goals, "sim_vals": _host_or_none(r["sim"]),
+            "sim_vals_no_rescale": _host_or_none(r["sim_raw"]), "grad_conf_rows": r["grad_conf_rows"], "grad_meas_scale": r["grad_meas_scale"],
+            "grad_meas_offset": r["grad_meas_offset"]}
+
+
+def goal_run_batched(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence[Dict], psi_init, label_indices, *, fr_phase: Optional[Dict] = None, device=None, col_ops=None,
+                     readout=None, estimator: str = "g_LL_prime") -> Dict:
     """`ModelLearning.goal_run` (modellearning.py:285-360) with the `ipar` loop as one batch.
 
     `data_sets[p]` = {"seqs": [...], "results": [...], "results_std": [...], "shots": [...]} for parameter set
@@ -280,8 +327,15 @@ def goal_run_batched(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence
     Per parameter set: `col_ops` [P,C,D,D] gives set p its own collapse operators (T1, T2*, bath temperature differ between the
     sets), `psi_init` [P,D] or [P,D^2] (closed systems: [P,D]) its own initial state.  One state is recognised by its size, so P kets
     with P == D are read as one density vector: pass [P,D^2] there.
+
+    `readout` (a `readout.Readout`): the confusion matrix and the rescale of `Experiment.process` between the populations and the
+    estimator, shared or per set; `label_indices` then index the rows of the confusion matrix (`comp_state_labels`) when it has one.
+    `estimator`: a name of `readout.ESTIMATORS`.  With either, the sequence states go through c3p_readout_goal on the device and the
+    result also holds "sim_vals_no_rescale" (None without a rescale); with both at their defaults nothing changes.
     """
     P = len(data_sets)
+    if not _legacy_epilogue(readout, estimator):
+        return _goal_run_readout(h0, hks, gate_signals, dt, data_sets, psi_init, label_indices, fr_phase, device, col_ops, readout, estimator)
     if col_ops is not None:
         seqs = _check_data_sets(data_sets)
         sim = process_batch(_open_system_states(h0, hks, gate_signals, dt, col_ops, P, seqs, psi_init, fr_phase, device)[-1], label_indices)
@@ -302,7 +356,43 @@ def goal_run_batched(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence
     return {"goal": g_LL_prime_combined(goals, weights), "goals": goals, "sim_vals": sim}
 
 
-def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence[Dict], psi_init, label_indices, *, fr_phase: Optional[Dict] = None, device=None, col_ops=None) -> Dict:
+def _closed_system_states(h0, hks, gate_signals, dt, P: int, seqs, psi_init, fr_phase, device):
+    """(U[gate], psi0, x [P,S,D]): the sequence states of a closed system on the indexed path."""
+    from . import sequences as sq
+
+    Us = propagate_parameter_sets(h0, hks, gate_signals, dt, fr_phase=fr_phase, device=device)
+    first = next(iter(Us.values()))
+    if int(first.shape[0]) != P:
+        raise C3PropError("C3:Error: number of data sets and parameter sets differ")
+    D = int(first.shape[-1])
+    sets = _per_set_states(psi_init, D, P, (D,))
+    psi = np.asarray(psi_init, dtype=np.complex128).reshape(-1) if sets is None else sets
+    if device is not None:
+        import torch
+
+        psi = torch.as_tensor(psi, device=device)
+    return Us, psi, sq.evaluate_sequences_indexed(Us, seqs, "state", psi)
+
+
+def _goal_run_readout(h0, hks, gate_signals, dt, data_sets, psi_init, label_indices, fr_phase, device, col_ops, readout, estimator) -> Dict:
+    """`goal_run_batched` with the read-out model: sequence states on the indexed path, then c3p_readout_goal.  `label_indices`
+    index the rows of the confusion matrix (`comp_state_labels`) when `readout.conf_rows` is given, the states otherwise."""
+    from . import readout as ro
+
+    P = len(data_sets)
+    seqs = _check_data_sets(data_sets)
+    data = ro.stack_data(data_sets, device)  # (on its way before the first launch)
+    if col_ops is not None:
+        x = _open_system_states(h0, hks, gate_signals, dt, col_ops, P, seqs, psi_init, fr_phase, device)[4]
+        D = int(np.shape(h0)[-1])
+    else:
+        x = _closed_system_states(h0, hks, gate_signals, dt, P, seqs, psi_init, fr_phase, device)[2]
+        D = int(x.shape[-1])
+    return _readout_forward(x, D, data, readout, estimator, label_indices, P, len(seqs))
+
+
+def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets: Sequence[Dict], psi_init, label_indices, *, fr_phase: Optional[Dict] = None, device=None, col_ops=None,
+                               readout=None, estimator: str = "g_LL_prime") -> Dict:
     """`goal_run_batched` and the gradient of its combined goal -- what `ModelLearning.goal_run_with_grad` tapes
     (modellearning.py:362-440): model operators -> propagators -> sequence states -> label populations -> g_LL_prime,
     the per-set gradients combined by `dv_g_LL_prime`.
@@ -331,47 +421,52 @@ def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets
     D = 7, 8, 9 (two coupled qutrits) take the Hermitian-basis sweep (`hermitian_basis=True`): h0 / hks must be Hermitian, and
     "grad_h0" / "grad_hks" are then Hermitian matrices, the Hermitian part of the general cotangent -- exact in
     `model_param_grads` for every Hermitian dh0 / dhks, which is what a model parameter moves.
+
+    `readout` / `estimator` as in `goal_run_batched`: the epilogue is then ONE c3p_readout_goal_vjp call between the two sequence
+    calls, nothing touches the host in between, and the result also holds "grad_conf_rows" (a list of [P,d_q]), "grad_meas_scale" and
+    "grad_meas_offset" ([P]; None where the read-out has no such parameter; a shared read-out: sum over p) and "sim_vals_no_rescale".
     """
     P = len(data_sets)
     if col_ops is not None:
-        return _goal_run_open_with_grad(h0, hks, gate_signals, dt, data_sets, psi_init, label_indices, fr_phase, device, col_ops)
+        return _goal_run_open_with_grad(h0, hks, gate_signals, dt, data_sets, psi_init, label_indices, fr_phase, device, col_ops, readout, estimator)
     seqs = data_sets[0]["seqs"]
     for d in data_sets:
         if d["seqs"] != seqs:
             raise C3PropError("C3:Error: batched model learning needs the same sequences for every parameter set")
     from . import sequences as sq
 
-    Us = propagate_parameter_sets(h0, hks, gate_signals, dt, fr_phase=fr_phase, device=device)
-    first = next(iter(Us.values()))
-    if int(first.shape[0]) != P:
-        raise C3PropError("C3:Error: number of data sets and parameter sets differ")
-    D = int(first.shape[-1])
-    sets = _per_set_states(psi_init, D, P, (D,))
-    psi = np.asarray(psi_init, dtype=np.complex128).reshape(-1) if sets is None else sets
+    legacy = _legacy_epilogue(readout, estimator)
+    if not legacy:
+        from . import readout as ro
+
+        ro_data = ro.stack_data(data_sets, device)  # (on its way before the first launch)
     if device is not None:
         import torch
-
-        psi = torch.as_tensor(psi, device=device)
-    x = sq.evaluate_sequences_indexed(Us, seqs, "state", psi)  # [P,S,D]
-    pops = x.real**2 + x.imag**2
-    sim = process_batch(pops, label_indices)
-    sim_h = sim.cpu().numpy() if propagation._is_torch(sim) else np.asarray(sim)
-    goals = np.array([g_LL_prime(d["results"], sim_h[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)])
-    weights = [len(seqs)] * P
-    dgs = [g_LL_prime_grad(d["results"], sim_h[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)]
-    if any(np.shape(g) != sim_h.shape[1:] for g in dgs):
-        raise C3PropError(f"C3:Error: the results of a data set do not have the shape of its simulated values {sim_h.shape[1:]}")
-    # combined goal: d goal / d sim[p] = w_p / sum w * d g_p / d sim[p]
-    sim_bar = np.stack([w / np.sum(weights) * g for w, g in zip(weights, dgs)])
-    # sim = sum over the label rows of |x|^2 ([P,S]), or every population |x|^2 itself ([P,S,D], no labels):
-    # x_bar = 2 sim_bar x on the rows that enter
-    if label_indices is None:
-        pop_bar = sim_bar
-    else:
-        rows = np.zeros(D)
-        np.add.at(rows, list(label_indices), 1.0)  # a label listed twice counts twice, as in process_batch
-        pop_bar = sim_bar[..., None] * rows
-    x_bar = 2.0 * (torch.as_tensor(pop_bar, device=device) if device is not None else pop_bar) * x
+    Us, psi, x = _closed_system_states(h0, hks, gate_signals, dt, P, seqs, psi_init, fr_phase, device)  # x [P,S,D]
+    D = int(x.shape[-1])
+    ro_res = None
+    if legacy:
+        pops = x.real**2 + x.imag**2
+        sim = process_batch(pops, label_indices)
+        sim_h = sim.cpu().numpy() if propagation._is_torch(sim) else np.asarray(sim)
+        goals = np.array([g_LL_prime(d["results"], sim_h[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)])
+        weights = [len(seqs)] * P
+        dgs = [g_LL_prime_grad(d["results"], sim_h[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)]
+        if any(np.shape(g) != sim_h.shape[1:] for g in dgs):
+            raise C3PropError(f"C3:Error: the results of a data set do not have the shape of its simulated values {sim_h.shape[1:]}")
+        # combined goal: d goal / d sim[p] = w_p / sum w * d g_p / d sim[p]
+        sim_bar = np.stack([w / np.sum(weights) * g for w, g in zip(weights, dgs)])
+        # sim = sum over the label rows of |x|^2 ([P,S]), or every population |x|^2 itself ([P,S,D], no labels):
+        # x_bar = 2 sim_bar x on the rows that enter
+        if label_indices is None:
+            pop_bar = sim_bar
+        else:
+            rows = np.zeros(D)
+            np.add.at(rows, list(label_indices), 1.0)  # a label listed twice counts twice, as in process_batch
+            pop_bar = sim_bar[..., None] * rows
+        x_bar = 2.0 * (torch.as_tensor(pop_bar, device=device) if device is not None else pop_bar) * x
+    else:  # confusion, selection, rescale, estimator and their reverse mode in one call on the device
+        ro_res, x_bar = _readout_backward(x, D, ro_data, readout, estimator, label_indices, P, len(seqs))
     U_bar, psi_bar = sq.evaluate_sequences_indexed_vjp(Us, seqs, "state", x_bar, psi, want_psi0_bar=True)
     grad_h0 = grad_hks = None
     grad_signals, grad_ph = {}, ({} if fr_phase is not None else None)
@@ -391,39 +486,49 @@ def goal_run_batched_with_grad(h0, hks, gate_signals: Dict, dt: float, data_sets
             Ug, Ub = Us[gate], U_bar[gate]
             # U = diag(e^{i phi}) P  =>  d loss / d phi_i = -Im sum_j conj(Ubar_ij) U_ij (optimal_control.goal_run_with_grad)
             grad_ph[gate] = None if ph is None else (-(Ub.conj() * Ug).sum(-1).imag)
-    return {"goal": g_LL_prime_combined(goals, weights), "goals": goals, "sim_vals": sim_h, "grad_h0": grad_h0, "grad_hks": grad_hks,
-            "grad_signals": grad_signals, "grad_fr_phase": grad_ph, "grad_psi_init": psi_bar}
+    head = {"goal": g_LL_prime_combined(goals, weights), "goals": goals, "sim_vals": sim_h} if legacy else _readout_results(ro_res, P, len(seqs))
+    return {**head, "grad_h0": grad_h0, "grad_hks": grad_hks, "grad_signals": grad_signals, "grad_fr_phase": grad_ph, "grad_psi_init": psi_bar}
 
 
-def _goal_run_open_with_grad(h0, hks, gate_signals, dt, data_sets, psi_init, label_indices, fr_phase, device, col_ops) -> Dict:
+def _goal_run_open_with_grad(h0, hks, gate_signals, dt, data_sets, psi_init, label_indices, fr_phase, device, col_ops, readout=None,
+                             estimator: str = "g_LL_prime") -> Dict:
     """The open-system branch of `goal_run_batched_with_grad`."""
     from . import sequences as sq
 
     P = len(data_sets)
     seqs = _check_data_sets(data_sets)
+    legacy = _legacy_epilogue(readout, estimator)
+    if not legacy:
+        from . import readout as ro
+
+        ro_data = ro.stack_data(data_sets, device)  # (on its way before the first launch)
     args, col, Us, rho0, x, pops = _open_system_states(h0, hks, gate_signals, dt, col_ops, P, seqs, psi_init, fr_phase, device)
     D = int(pops.shape[-1])
-    sim = process_batch(pops, label_indices)
-    sim_h = sim.cpu().numpy() if propagation._is_torch(sim) else np.asarray(sim)
-    goals = np.array([g_LL_prime(d["results"], sim_h[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)])
-    weights = [len(seqs)] * P
-    dgs = [g_LL_prime_grad(d["results"], sim_h[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)]
-    if any(np.shape(g) != sim_h.shape[1:] for g in dgs):
-        raise C3PropError(f"C3:Error: the results of a data set do not have the shape of its simulated values {sim_h.shape[1:]}")
-    sim_bar = np.stack([w / np.sum(weights) * g for w, g in zip(weights, dgs)])
-    if label_indices is None:
-        pop_bar = sim_bar
-    else:
-        rows = np.zeros(D)
-        np.add.at(rows, list(label_indices), 1.0)  # a label listed twice counts twice, as in process_batch
-        pop_bar = sim_bar[..., None] * rows
-    # pops = Re x[n D + n]: x_bar is pop_bar on those entries (d loss = Re sum conj(x_bar) dx), zero elsewhere
-    x_bar = np.zeros(pop_bar.shape[:-1] + (D * D,), dtype=np.complex128)
-    x_bar[..., :: D + 1] = pop_bar
-    if device is not None:
-        import torch
+    ro_res = None
+    if legacy:
+        sim = process_batch(pops, label_indices)
+        sim_h = sim.cpu().numpy() if propagation._is_torch(sim) else np.asarray(sim)
+        goals = np.array([g_LL_prime(d["results"], sim_h[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)])
+        weights = [len(seqs)] * P
+        dgs = [g_LL_prime_grad(d["results"], sim_h[p], d["results_std"], d["shots"]) for p, d in enumerate(data_sets)]
+        if any(np.shape(g) != sim_h.shape[1:] for g in dgs):
+            raise C3PropError(f"C3:Error: the results of a data set do not have the shape of its simulated values {sim_h.shape[1:]}")
+        sim_bar = np.stack([w / np.sum(weights) * g for w, g in zip(weights, dgs)])
+        if label_indices is None:
+            pop_bar = sim_bar
+        else:
+            rows = np.zeros(D)
+            np.add.at(rows, list(label_indices), 1.0)  # a label listed twice counts twice, as in process_batch
+            pop_bar = sim_bar[..., None] * rows
+        # pops = Re x[n D + n]: x_bar is pop_bar on those entries (d loss = Re sum conj(x_bar) dx), zero elsewhere
+        x_bar = np.zeros(pop_bar.shape[:-1] + (D * D,), dtype=np.complex128)
+        x_bar[..., :: D + 1] = pop_bar
+        if device is not None:
+            import torch
 
-        x_bar = torch.as_tensor(x_bar, device=device)
+            x_bar = torch.as_tensor(x_bar, device=device)
+    else:
+        ro_res, x_bar = _readout_backward(x, D, ro_data, readout, estimator, label_indices, P, len(seqs))
     U_bar, rho0_bar = sq.evaluate_sequences_indexed_vjp(Us, seqs, "state", x_bar, rho0, superop=True, want_psi0_bar=True)
     grad_h0 = grad_hks = grad_col = None
     grad_signals, grad_ph = {}, ({} if fr_phase is not None else None)
@@ -437,8 +542,9 @@ def _goal_run_open_with_grad(h0, hks, gate_signals, dt, data_sets, psi_init, lab
         grad_col = gc if grad_col is None else grad_col + gc
         if grad_ph is not None:
             grad_ph[gate] = None if a[3] is None else (-(U_bar[gate].conj() * Us[gate]).sum(-1).imag)
-    return {"goal": g_LL_prime_combined(goals, weights), "goals": goals, "sim_vals": sim_h, "grad_h0": grad_h0, "grad_hks": grad_hks,
-            "grad_col_ops": grad_col, "grad_signals": grad_signals, "grad_fr_phase": grad_ph, "grad_psi_init": rho0_bar}
+    head = {"goal": g_LL_prime_combined(goals, weights), "goals": goals, "sim_vals": sim_h} if legacy else _readout_results(ro_res, P, len(seqs))
+    return {**head, "grad_h0": grad_h0, "grad_hks": grad_hks, "grad_col_ops": grad_col, "grad_signals": grad_signals, "grad_fr_phase": grad_ph,
+            "grad_psi_init": rho0_bar}
 
 
 def model_param_grads(grad_h0, grad_hks, dh0, dhks=None, grad_col_ops=None, dcol_ops=None):
@@ -465,7 +571,7 @@ def model_param_grads(grad_h0, grad_hks, dh0, dhks=None, grad_col_ops=None, dcol
 
 
 def sensitivity_sweep(h0_of, hks_of, sweep_values: Sequence[float], gate_signals_one: Dict, dt: float, data_set: Dict, psi_init, label_indices, *, device=None, col_ops_of=None,
-                      psi_init_of=None) -> Dict:
+                      psi_init_of=None, readout=None, estimator: str = "g_LL_prime") -> Dict:
     """`Sensitivity.sensitivity` for one swept model parameter (sensitivity.py:100-124): the goal at every sweep
     point, all points in one batch.  `h0_of(v)` / `hks_of(v)` build the (dressed) operators at value v -- the
     model update the reference performs per point (modellearning.py:227-232); the pulses are shared.
@@ -483,7 +589,7 @@ def sensitivity_sweep(h0_of, hks_of, sweep_values: Sequence[float], gate_signals
         psi_init = np.stack([np.asarray(psi_init_of(v), dtype=np.complex128).reshape(-1) for v in vals])  # [P,D] or [P,D^2]
         if P == 1:  # (one point: a single state, which is what a size of D or D^2 is read as)
             psi_init = psi_init[0]
-    r = goal_run_batched(h0, hks, sig, dt, [data_set] * P, psi_init, label_indices, device=device, col_ops=col)
+    r = goal_run_batched(h0, hks, sig, dt, [data_set] * P, psi_init, label_indices, device=device, col_ops=col, readout=readout, estimator=estimator)
     return {"values": np.asarray(vals), "goals": r["goals"], "sim_vals": r["sim_vals"]}
 
 
@@ -515,7 +621,7 @@ def _bare_operator_list(hks_bare, col_ops_bare, P: int, device):
 
 
 def goal_run_dressed_with_grad(H_bare, hks_bare, gate_signals: Dict, dt: float, data_sets: Sequence[Dict], psi_init, label_indices, *, col_ops_bare=None,
-                               fr_phase: Optional[Dict] = None, device=None) -> Dict:
+                               fr_phase: Optional[Dict] = None, device=None, readout=None, estimator: str = "g_LL_prime") -> Dict:
     """`goal_run_batched_with_grad` from the BARE model: the P drift Hamiltonians `H_bare` [P,D,D] (or one, [D,D]) are dressed on the
     device (`dressing.dress_batch`: Model.update_dressed for every set in one launch), with them the control Hamiltonians `hks_bare`
     [K,D,D] / [P,K,D,D] and, for an open system, the collapse operators `col_ops_bare` [C,D,D] / [P,C,D,D]; the goal and its
@@ -552,7 +658,8 @@ def goal_run_dressed_with_grad(H_bare, hks_bare, gate_signals: Dict, dt: float, 
     d = dressing.dress_batch(H, ops)
     hks = d["ops"][:, :K]
     col = None if col_ops_bare is None else d["ops"][:, K:]
-    r = goal_run_batched_with_grad(d["h0"], hks, gate_signals, dt, data_sets, psi_init, label_indices, fr_phase=fr_phase, device=device, col_ops=col)
+    r = goal_run_batched_with_grad(d["h0"], hks, gate_signals, dt, data_sets, psi_init, label_indices, fr_phase=fr_phase, device=device, col_ops=col, readout=readout,
+                                   estimator=estimator)
     g_ops = r["grad_hks"]
     if col is not None:
         g_ops = (torch.cat if device is not None else np.concatenate)([g_ops, r["grad_col_ops"]], 1)
@@ -572,7 +679,7 @@ def goal_run_dressed_with_grad(H_bare, hks_bare, gate_signals: Dict, dt: float, 
 
 
 def sensitivity_sweep_dressed(H_bare_of, hks_bare, sweep_values: Sequence[float], gate_signals_one: Dict, dt: float, data_set: Dict, psi_init, label_indices, *,
-                              device=None, col_ops_bare_of=None, psi_init_of=None) -> Dict:
+                              device=None, col_ops_bare_of=None, psi_init_of=None, readout=None, estimator: str = "g_LL_prime") -> Dict:
     """`sensitivity_sweep` from the bare model: `H_bare_of(v)` builds the bare drift Hamiltonian at sweep value v, and ONE batched
     `dressing.dress_batch` call dresses every point (with the control Hamiltonians `hks_bare` [K,D,D] and, for an open system, the
     bare collapse operators `col_ops_bare_of(v)` [C,D,D]) instead of one host eigendecomposition per point.  `psi_init_of` as in
@@ -595,5 +702,6 @@ def sensitivity_sweep_dressed(H_bare_of, hks_bare, sweep_values: Sequence[float]
         if P == 1:
             psi_init = psi_init[0]
     col = None if col_bare is None else d["ops"][:, K:]
-    r = goal_run_batched(d["h0"], d["ops"][:, :K], sig, dt, [data_set] * P, psi_init, label_indices, device=device, col_ops=col)
+    r = goal_run_batched(d["h0"], d["ops"][:, :K], sig, dt, [data_set] * P, psi_init, label_indices, device=device, col_ops=col, readout=readout,
+                         estimator=estimator)
     return {"values": np.asarray(vals), "goals": r["goals"], "sim_vals": r["sim_vals"], "eigenframe": dressing._host(d["eigenframe"])}

@@ -85,6 +85,8 @@ extern "C" {
 #define C3P_KERNEL_ODE_VJP 11 /* discrete adjoint of the ODE state solvers (c3p_ode_vjp.hip)           */
 #define C3P_KERNEL_DRESS 12 /* batched dressing: Jacobi eigensolver, frame rule, T^+ A T (c3p_dress.hip) */
 #define C3P_KERNEL_DRESS_VJP 13 /* vector-Jacobian product of the dressing step (c3p_dress.hip)         */
+#define C3P_KERNEL_READOUT 14 /* read-out epilogue: populations, confusion, rescale, estimator (c3p_readout.hip) */
+#define C3P_KERNEL_READOUT_VJP 15 /* its vector-Jacobian product (c3p_readout.hip)                              */
 
 /* ODE solver / step ids (propagation.py:27-32 solver_slicing; :886-904 steps) */
 #define C3P_SOLVER_RK4 0
@@ -564,6 +566,50 @@ int c3p_dress(const void* H, const void* ops, int64_t ops_bstride, int P, int M,
 int c3p_dress_vjp(const void* T, const double* eig, const void* ops, int64_t ops_bstride, int P, int M, int D, int flags,
                   const double* eig_bar, const void* h0_bar, const void* ops_bar, const void* T_bar, void* H_bar_out,
                   void* ops_bare_bar_out, int32_t* status_out, void* stream);
+
+/* Read-out epilogue of model learning: from the sequence states to the goals of P parameter sets in one call --
+ * Experiment.process (c3/experiment.py:355-407) with ConfusionMatrix.confuse and MeasurementRescale.rescale
+ * (c3/libraries/tasks.py:107-129,161-178), then an estimator of c3/libraries/estimators.py over the values of every set.
+ *   x        c128 [P,S,M] sequence states, as c3p_seq_chain returns them in state mode; M == D: kets, populations |x_n|^2;
+ *            M == D^2: density vectors, populations Re x[n (D + 1)].  2 <= D <= 81.
+ *   conf     f64  [R,D] (conf_bstride 0: one confusion matrix for every set) or [P,R,D] (conf_bstride = elements between
+ *            two of them); NULL: identity, R must be D.  c = conf pop.
+ *   label_w  f64  [R] or NULL: with it ONE value per sequence, v = sum_r label_w[r] c_r (V = 1; label_w[r] is how often label r
+ *            was listed); without it every c_r is a value (V = R).
+ *   rescale  f64  (scale, offset): [2] (rescale_bstride 0) or [P,2] (rescale_bstride 2); NULL: none.  sim = scale v + offset.
+ *   meas, stds, shots   f64 [P,S,V]: measured values, their standard deviations, shot counts (stds may be NULL unless the
+ *            estimator reads it: C3P_EST_RMS_EXP_STDS)
+ *   estimator  one of C3P_EST_*
+ *   sim_out     f64 [P,S,V];  sim_raw_out f64 [P,S,V] or NULL: v before the rescale (populations_no_rescale)
+ *   goals_out   f64 [P]
+ * sim outside (0,1) gives the inf / nan of the reference's arithmetic.  The sum over the S V values of a set runs in a fixed
+ * order that depends on S and V alone: the same call returns the same bits, and set p gives the same bits alone as inside a
+ * batch.  Two launches; the estimator's summands go through the workspace. */
+#define C3P_EST_G_LL_PRIME 0           /* mean(((m - s)^2 / (s (1 - s) / shots) - 1) / 2)                     */
+#define C3P_EST_NEG_LOGLKH_GAUSS 1     /* -mean(log N(m; s, sqrt(s (1 - s) / shots)))                          */
+#define C3P_EST_NEG_LOGLKH_GAUSS_NORM 2 /* -mean(log N(m; ..) - log N(s; ..)) = mean((m - s)^2 / (2 var))      */
+#define C3P_EST_NEG_LOGLKH_GAUSS_NORM_SUM 3 /* the same, summed                                               */
+#define C3P_EST_RMS_DIST 4             /* sqrt(mean((m - s)^2))                                                */
+#define C3P_EST_RMS_EXP_STDS_DIST 5    /* sqrt(mean(((m - s) / stds)^2))                                       */
+#define C3P_EST_RMS_SIM_STDS_DIST 6    /* sqrt(mean((m - s)^2 / (s (1 - s) / shots)))                          */
+int c3p_readout_goal(const void* x, int P, int S, int M, int D, const double* conf, int64_t conf_bstride, int R,
+                     const double* label_w, const double* rescale, int64_t rescale_bstride, const double* meas,
+                     const double* stds, const double* shots, int estimator, int flags, double* sim_out, double* sim_raw_out,
+                     double* goals_out, void* stream);
+
+/* c3p_readout_goal and the vector-Jacobian product of  sum_p goal_weights[p] goals[p]  (goal_weights f64 [P]: the w_p / sum w
+ * of dv_g_LL_prime).  Inputs as c3p_readout_goal; sim_out, sim_raw_out and goals_out are written with the same bits, and
+ *   x_bar_out        c128 [P,S,M], every entry written: the cotangent c3p_seq_chain_vjp reads (d loss = Re sum conj(x_bar) dx),
+ *                    2 pop_bar x for kets, pop_bar on the entries n (D + 1) and zero elsewhere for density vectors
+ *   conf_bar_out     f64 [P,R,D] or NULL;  rescale_bar_out f64 [P,2] (scale, offset) or NULL: always per set, also for a
+ *                    shared read-out (the caller sums over p, as with grad_h0)
+ *   pop_bar_out      f64 [P,S,D] or NULL
+ * The sums over the sequences run in a fixed order without atomics.  Four or five launches. */
+int c3p_readout_goal_vjp(const void* x, int P, int S, int M, int D, const double* conf, int64_t conf_bstride, int R,
+                         const double* label_w, const double* rescale, int64_t rescale_bstride, const double* meas,
+                         const double* stds, const double* shots, int estimator, const double* goal_weights, int flags,
+                         double* sim_out, double* sim_raw_out, double* goals_out, void* x_bar_out, double* conf_bar_out,
+                         double* rescale_bar_out, double* pop_bar_out, void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
