@@ -3914,6 +3914,183 @@ int c3p_synth_chain_vjp(const double* env_params, const int32_t* env_shapes, con
   return 0;
 }
 
+// ---- c3p_synth_tab / c3p_synth_tab_vjp: the chain entries with a coefficient table (C3P_ENVT_* shapes) ----------------------
+static int tab_block_len_host(int shape, int M) {
+  switch (shape) {
+    case C3P_ENVT_PWC:
+    case C3P_ENVT_FOURIER_COS:
+      return 2 * M;
+    case C3P_ENVT_PWC_SHAPE:
+    case C3P_ENVT_PWC_SYMMETRIC:
+      return M + 2;
+    default:
+      return 3 * M;  // C3P_ENVT_FOURIER_SIN
+  }
+}
+
+// host-pointer checks shared by c3p_synth_tab and its vjp: shape ids, blocks inside the row and apart from each other, the
+// per-shape sizes, the flags a table shape does not take
+static int tab_check_host(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
+                          int B, int K, int E, int Na) {
+  std::vector<std::pair<long, long>> blocks;  // [begin, end)
+  for (int a = 0; a < K * E; ++a) {
+    const int sh = env_shapes[a];
+    if (sh >= C3P_ENV_NSHAPES && (sh < C3P_ENVT_FIRST || sh >= C3P_ENVT_END))
+      return fail("env_shapes[%d]=%d is neither a C3P_ENV_* nor a C3P_ENVT_* id", a, sh);
+    if (sh < C3P_ENVT_FIRST) continue;
+    const long off = tab_index[2 * a], M = tab_index[2 * a + 1];
+    if (off < 0 || M < 1) return fail("tab_index[%d,%d]={%ld,%ld}: a table shape needs an offset >= 0 and M >= 1", a / E, a % E, off, M);
+    if (M > T || off + tab_block_len_host(sh, (int)M) > (long)T)
+      return fail("tab_index[%d,%d]={%ld,%ld}: the block of %d doubles leaves the row (T=%d)", a / E, a % E, off, M,
+                  M > T ? 0 : tab_block_len_host(sh, (int)M), T);
+    if (sh == C3P_ENVT_PWC && M != Na) return fail("component [%d,%d]: pwc holds one pair per AWG sample, M=%ld but Na=%d", a / E, a % E, M, Na);
+    if ((sh == C3P_ENVT_PWC_SHAPE || sh == C3P_ENVT_PWC_SYMMETRIC) && M < 2)
+      return fail("component [%d,%d]: an interpolated shape needs M >= 2 knots, got %ld", a / E, a % E, M);
+    blocks.push_back({off, off + tab_block_len_host(sh, (int)M)});
+  }
+  std::sort(blocks.begin(), blocks.end());
+  for (size_t i = 1; i < blocks.size(); ++i)
+    if (blocks[i].first < blocks[i - 1].second)
+      return fail("tab_index: the blocks [%ld,%ld) and [%ld,%ld) overlap (grad_tab would be ambiguous)", blocks[i - 1].first,
+                  blocks[i - 1].second, blocks[i].first, blocks[i].second);
+  // the layout stands: what the rows and the table hold
+  for (int a = 0; a < K * E; ++a) {
+    const int sh = env_shapes[a];
+    if (sh < C3P_ENVT_FIRST) continue;
+    const long off = tab_index[2 * a];
+    for (int b = 0; b < B; ++b) {
+      const int fl = (int)env_params[((size_t)b * K * E + a) * C3P_ENV_NPAR + C3P_ENV_FLAGS];
+      if (fl & C3P_ENVF_DRAG) return fail("env_params[%d,%d,%d]: C3P_ENVF_DRAG on a table shape is not served", b, a / E, a % E);
+      if (sh == C3P_ENVT_PWC && (fl & C3P_ENVF_T_BEFORE))
+        return fail("env_params[%d,%d,%d]: C3P_ENVF_T_BEFORE on pwc (the offset would be the array itself)", b, a / E, a % E);
+      if (sh == C3P_ENVT_PWC_SHAPE || sh == C3P_ENVT_PWC_SYMMETRIC) {
+        const double* blk = env_tab + (size_t)b * T + off;
+        if (!(blk[1] > blk[0])) return fail("env_tab[%d]: component [%d,%d] needs t_bin_end > t_bin_start, got %g and %g", b, a / E, a % E, blk[1], blk[0]);
+      }
+    }
+  }
+  return 0;
+}
+
+// One call of either entry; grad_signals == NULL: the forward call.
+static int synth_tab_common(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
+                            const double* carrier, const int32_t* line_kind, const double* line_params, double t_start, double t_end,
+                            double awg_res, double sim_res, int B, int K, int E, int flags, double* awg_iq_out, double* signals_out,
+                            const double* grad_signals, double* grad_env, double* grad_carrier, double* grad_line, double* grad_tab,
+                            void* stream) {
+  const bool vjp = grad_signals != nullptr, chain = line_kind != nullptr;
+  if (B < 0 || K <= 0 || E <= 0 || T < 0) return fail("bad sizes B=%d K=%d E=%d T=%d", B, K, E, T);
+  if (!(awg_res > 0.0) || !(sim_res > 0.0)) return fail("resolutions must be positive");
+  const double span = t_end > t_start ? t_end - t_start : t_start - t_end;
+  const int N = (int)(span * sim_res), Na = (int)(span * awg_res);  // devices.py:72-84
+  if (N <= 0 || Na <= 1) return fail("empty time grid: N=%d Na=%d", N, Na);
+  if (B == 0) return 0;
+  if (!env_params || !env_shapes || !carrier || !tab_index || (T > 0 && !env_tab)) return fail("NULL pointer argument");
+  if ((line_kind == nullptr) != (line_params == nullptr)) return fail("line_kind and line_params go together (both NULL: the standard drive line)");
+  if (!vjp && !signals_out) return fail("NULL pointer argument");
+  if (vjp && (!grad_env || !grad_carrier || (chain && !grad_line) || (T > 0 && !grad_tab))) return fail("NULL pointer argument");
+  if (flags & C3P_HOST_PTRS) {  // before any device work
+    if (chain && chain_check_host(line_kind, line_params, B, K, sim_res)) return -1;
+    if (tab_check_host(env_params, env_shapes, env_tab, tab_index, T, B, K, E, Na)) return -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  DeviceWs* w = lk.w;
+  if (!w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  Stage sg{w, st};
+  const void *d_env = env_params, *d_shape = env_shapes, *d_tab = env_tab, *d_tidx = tab_index, *d_car = carrier, *d_kind = line_kind,
+             *d_line = line_params, *d_gs = grad_signals;
+  void *d_iq = awg_iq_out, *d_sig = signals_out, *d_ge = grad_env, *d_gc = grad_carrier, *d_gl = grad_line, *d_gt = grad_tab;
+  const size_t lines = (size_t)B * K, awg = lines * 2 * Na;
+  if (flags & C3P_HOST_PTRS) {
+    if (sg.in(env_params, lines * E * C3P_ENV_NPAR * sizeof(double), &d_env)) return -1;
+    if (sg.in(env_shapes, (size_t)K * E * sizeof(int32_t), &d_shape)) return -1;
+    if (sg.in(env_tab, (size_t)B * T * sizeof(double), &d_tab)) return -1;
+    if (sg.in(tab_index, (size_t)K * E * 2 * sizeof(int32_t), &d_tidx)) return -1;
+    if (sg.in(carrier, lines * 2 * sizeof(double), &d_car)) return -1;
+    if (chain && sg.in(line_kind, (size_t)K * sizeof(int32_t), &d_kind)) return -1;
+    if (chain && sg.in(line_params, lines * C3P_LINE_NPAR * sizeof(double), &d_line)) return -1;
+    if (vjp) {
+      if (sg.in(grad_signals, lines * N * sizeof(double), &d_gs)) return -1;
+      if (sg.out(grad_env, lines * E * C3P_ENV_NPAR * sizeof(double), &d_ge)) return -1;
+      if (sg.out(grad_carrier, lines * 2 * sizeof(double), &d_gc)) return -1;
+      if (chain && sg.out(grad_line, lines * C3P_LINE_NPAR * sizeof(double), &d_gl)) return -1;
+      if (sg.out(grad_tab, (size_t)B * T * sizeof(double), &d_gt)) return -1;
+    } else {
+      if (sg.out(signals_out, lines * N * sizeof(double), &d_sig)) return -1;
+      if (awg_iq_out && sg.out(awg_iq_out, awg * sizeof(double), &d_iq)) return -1;
+    }
+  }
+  // scratch: [taps] | iq (unless the caller takes it) | vjp: giq | gcar_part (B*K*2*Na each) | [gcs [B,K,2,N] | part]
+  const size_t tap_stride = N > 1 ? (size_t)N - 1 : 1, tap_elems = chain ? lines * tap_stride : 0;
+  const size_t gcs_elems = chain && vjp ? lines * 2 * N : 0;
+  const size_t part_elems = chain && vjp ? lines * c3p_chain_tiles(N) * c3p_chain_part_stride() : 0;
+  const size_t iq_elems = (!vjp && d_iq) ? 0 : awg;
+  void* v;
+  if (ws_get(w, SL_SCRATCH, (tap_elems + iq_elems + (vjp ? 2 * awg : 0) + gcs_elems + part_elems) * sizeof(double), &v)) return -1;
+  double* p = (double*)v;
+  SynthChainArgs C;
+  SynthArgs& A = C.S;
+  A.env = (const double*)d_env;
+  A.shape = (const int*)d_shape;
+  A.carrier = (const double*)d_car;
+  A.t_start = t_start;
+  A.t_end = t_end;
+  A.awg_res = awg_res;
+  A.sim_res = sim_res;
+  A.B = B;
+  A.K = K;
+  A.E = E;
+  A.Na = Na;
+  A.N = N;
+  A.iq = iq_elems ? p + tap_elems : (double*)d_iq;
+  A.signals = (double*)d_sig;
+  C.kind = (const int*)d_kind;
+  C.line = (const double*)d_line;
+  C.taps = p;
+  C.tap_stride = (long)tap_stride;
+  SynthTabArgs X;
+  X.tab = (const double*)d_tab;
+  X.tidx = (const int*)d_tidx;
+  X.T = T;
+  if (!vjp) {
+    if (chain)
+      LAUNCH_TRY(c3p_launch_chain_tab(C, X, st));
+    else
+      LAUNCH_TRY(c3p_launch_synth_tab(A, X, st));
+  } else {
+    double* giq = A.iq + awg;
+    double* gcar_part = giq + awg;
+    double* gcs = gcar_part + awg;
+    double* part = gcs + gcs_elems;
+    if (chain)
+      LAUNCH_TRY(c3p_launch_chain_tab_vjp(C, X, (const double*)d_gs, gcs, part, giq, gcar_part, (double*)d_ge, (double*)d_gc, (double*)d_gl,
+                                          (double*)d_gt, st));
+    else
+      LAUNCH_TRY(c3p_launch_synth_tab_vjp(A, X, (const double*)d_gs, giq, gcar_part, (double*)d_ge, (double*)d_gc, (double*)d_gt, st));
+  }
+  if (flags & C3P_HOST_PTRS) return sg.finish();
+  return 0;
+}
+
+int c3p_synth_tab(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
+                  const double* carrier, const int32_t* line_kind, const double* line_params, double t_start, double t_end,
+                  double awg_res, double sim_res, int B, int K, int E, int flags, double* awg_iq_out, double* signals_out,
+                  void* stream) {
+  return synth_tab_common(env_params, env_shapes, env_tab, tab_index, T, carrier, line_kind, line_params, t_start, t_end, awg_res, sim_res,
+                          B, K, E, flags, awg_iq_out, signals_out, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+int c3p_synth_tab_vjp(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
+                      const double* carrier, const int32_t* line_kind, const double* line_params, double t_start, double t_end,
+                      double awg_res, double sim_res, int B, int K, int E, int flags, const double* grad_signals,
+                      double* grad_env, double* grad_carrier, double* grad_line, double* grad_tab, void* stream) {
+  if (!grad_signals) return fail("NULL pointer argument");
+  return synth_tab_common(env_params, env_shapes, env_tab, tab_index, T, carrier, line_kind, line_params, t_start, t_end, awg_res, sim_res,
+                          B, K, E, flags, nullptr, nullptr, grad_signals, grad_env, grad_carrier, grad_line, grad_tab, stream);
+}
+
 int c3p_dress(const void* H, const void* ops, int64_t ops_bstride, int P, int M, int D, int flags, double* eig_out, void* T_out,
               void* h0_out, void* ops_out, int32_t* status_out, void* stream) {
   if (P < 0 || M < 0 || ops_bstride < 0) return fail("bad sizes P=%d M=%d ops_bstride=%lld", P, M, (long long)ops_bstride);

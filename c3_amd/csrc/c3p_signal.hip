@@ -6,6 +6,8 @@
 // are produced in HBM where the propagator kernels read them.  Two launches: the AWG-resolution I/Q
 // (a few hundred samples per line), then upsampling + mixing, one thread per output sample (HBM-bound,
 // 8 B written per sample, nothing re-read from HBM: the I/Q rows stay in L2).
+// Envelope shapes whose parameters are an array of coefficients (c3/libraries/envelopes.py:31-68,104-125,142-191: pwc, pwc_shape,
+// pwc_symmetric, fourier_sin, fourier_cos) read a coefficient table beside the rows: the <true> instantiations of awg_iq_kernel and awg_bwd_kernel, and tab_bwd_kernel.
 #include <hip/hip_runtime.h>
 
 #include "c3p_common.h"
@@ -46,6 +48,9 @@ __device__ __forceinline__ EnvP load_env(const double* p) {
   return e;
 }
 
+// (TAB on the closed-form helpers only keeps the two kernel families apart: the instantiation the existing entries launch is
+// compiled as it was before the table shapes came)
+template <bool TAB>
 __device__ double shape_val(int shape, double t, const EnvP& p) {
   switch (shape) {
     case C3P_ENV_RECT:
@@ -84,10 +89,11 @@ __device__ double shape_val(int shape, double t, const EnvP& p) {
   }
 }
 
+template <bool TAB>
 __device__ double shape_der(int shape, double t, const EnvP& p) {
   switch (shape) {
     case C3P_ENV_GAUSSIAN_NONORM:
-      return -(t - p.t_final / 2) / (p.sigma * p.sigma) * shape_val(shape, t, p);
+      return -(t - p.t_final / 2) / (p.sigma * p.sigma) * shape_val<TAB>(shape, t, p);
     case C3P_ENV_FLATTOP:
     case C3P_ENV_FLATTOP_RISEFALL: {
       const double rf = p.risefall;
@@ -133,6 +139,7 @@ struct EnvEval {
 };
 
 // envelope of component `p` at AWG sample j (pulse.py:88-180)
+template <bool TAB>
 __device__ EnvEval env_eval(const SynthArgs& A, int shape, const EnvP& p, int j, double a0, double a1) {
   const double t = linspace_at(a0, a1, A.Na, j);
   const double t_first = linspace_at(a0, a1, A.Na, 0), t_second = linspace_at(a0, a1, A.Na, A.Na > 1 ? 1 : 0);
@@ -142,17 +149,17 @@ __device__ EnvEval env_eval(const SynthArgs& A, int shape, const EnvP& p, int j,
   const double tf_ = p.t_final;  // window = t_final of the component (gates.py:293-297)
   const double m = mask_val(ts_off, dt, tf_);
   const double t_before = 2 * off0 - off1;
-  const double offset = p.use_t_before ? shape_val(shape, t_before, p) : 0.0;
+  const double offset = p.use_t_before ? shape_val<TAB>(shape, t_before, p) : 0.0;
   EnvEval r;
   r.ts_off = ts_off;
-  r.er = m * (shape_val(shape, ts_off, p) - offset);
+  r.er = m * (shape_val<TAB>(shape, ts_off, p) - offset);
   r.ei_unit = 0.0;
   if (p.drag) {
-    double denv = m * shape_der(shape, ts_off, p);
+    double denv = m * shape_der<TAB>(shape, ts_off, p);
     if (p.use_t_before && j < 2) {
       double msum = 0.0;
       for (int i = 0; i < A.Na; ++i) msum += mask_val(linspace_at(a0, a1, A.Na, i) - t0, dt, tf_);
-      const double doff = shape_der(shape, t_before, p) * msum;
+      const double doff = shape_der<TAB>(shape, t_before, p) * msum;
       denv += (j == 0) ? -2 * doff : doff;
     }
     r.ei_unit = -denv * dt;
@@ -160,8 +167,115 @@ __device__ EnvEval env_eval(const SynthArgs& A, int shape, const EnvP& p, int j,
   return r;
 }
 
-// one thread per AWG sample (b, k, j)
-__global__ void awg_iq_kernel(SynthArgs A) {
+// ---- envelopes whose parameters are an array of coefficients (C3P_ENVT_*; envelopes.py:31-68,104-125,142-191) ----------------
+// A component's block lies at tab_index[k,e] = {offset, M} in its sample's row of env_tab.  Device-pointer calls cannot look at
+// the index table, so a block that does not lie inside the row contributes nothing (and receives no cotangent).
+__device__ __forceinline__ int tab_block_len(int shape, int M) {
+  switch (shape) {
+    case C3P_ENVT_PWC:
+    case C3P_ENVT_FOURIER_COS:
+      return 2 * M;
+    case C3P_ENVT_PWC_SHAPE:
+    case C3P_ENVT_PWC_SYMMETRIC:
+      return M + 2;
+    case C3P_ENVT_FOURIER_SIN:
+      return 3 * M;
+    default:
+      return 0;
+  }
+}
+__device__ __forceinline__ bool tab_block(const SynthTabArgs& X, int ke, int shape, int* off, int* M) {
+  const int o = X.tidx[2 * ke], m = X.tidx[2 * ke + 1];
+  *off = o;
+  *M = m;
+  if (o < 0 || m < 1 || m > X.T) return false;
+  return (long)o + tab_block_len(shape, m) <= (long)X.T;
+}
+
+// tfp.math.interp_regular_1d_grid(t, x0, x1, y[0..M-1], fill_value_below=0, fill_value_above=0) as the pair of knots and the
+// weight of the upper one: value = (1 - w) y[lo] + w y[lo + 1]; false outside [x0, x1]
+__device__ __forceinline__ bool interp_cell(double t, double x0, double x1, int M, int* lo, double* w) {
+  if (!(t >= x0 && t <= x1) || M < 2) return false;
+  double xi = (t - x0) / (x1 - x0) * (double)(M - 1);
+  xi = xi < 0.0 ? 0.0 : (xi > (double)(M - 1) ? (double)(M - 1) : xi);
+  int l = (int)floor(xi);
+  l = l > M - 2 ? M - 2 : l;
+  *lo = l;
+  *w = xi - (double)l;
+  return true;
+}
+__device__ __forceinline__ double mirror_time(int shape, double t, double t_final) {
+  return (shape == C3P_ENVT_PWC_SYMMETRIC && t > t_final / 2) ? t_final - t : t;
+}
+// weight of knot m in the interpolated shapes' value at time t
+__device__ __forceinline__ double hat_weight(int shape, double t, double t_final, double x0, double x1, int M, int m) {
+  int lo;
+  double w;
+  if (!interp_cell(mirror_time(shape, t, t_final), x0, x1, M, &lo, &w)) return 0.0;
+  return (lo == m ? 1.0 - w : 0.0) + (lo + 1 == m ? w : 0.0);
+}
+
+// real shape value of the four real table shapes at time t (blk = the component's block, M its length)
+__device__ double tab_shape_val(int shape, double t, double t_final, const double* blk, int M) {
+  switch (shape) {
+    case C3P_ENVT_PWC_SHAPE:
+    case C3P_ENVT_PWC_SYMMETRIC: {
+      int lo;
+      double w;
+      if (!interp_cell(mirror_time(shape, t, t_final), blk[0], blk[1], M, &lo, &w)) return 0.0;
+      return (1.0 - w) * blk[2 + lo] + w * blk[2 + lo + 1];
+    }
+    case C3P_ENVT_FOURIER_SIN: {
+      double s = 0.0;
+      for (int m = 0; m < M; ++m) s += blk[m] * sin(blk[M + m] * t + blk[2 * M + m]);
+      return s;
+    }
+    case C3P_ENVT_FOURIER_COS: {
+      double s = 0.0;
+      for (int m = 0; m < M; ++m) s += blk[m] * cos(blk[M + m] * t);
+      return s;
+    }
+    default:
+      return 0.0;
+  }
+}
+
+struct TabTimes {
+  double ts_off, dt, t_before, mask;
+};
+__device__ __forceinline__ TabTimes tab_times(const SynthArgs& A, const EnvP& p, int j, double a0, double a1) {
+  const double t0 = A.t_start + p.delay;
+  const double off0 = linspace_at(a0, a1, A.Na, 0) - t0, off1 = linspace_at(a0, a1, A.Na, A.Na > 1 ? 1 : 0) - t0;
+  TabTimes r;
+  r.ts_off = linspace_at(a0, a1, A.Na, j) - t0;
+  r.dt = off1 - off0;
+  r.t_before = 2 * off0 - off1;
+  r.mask = mask_val(r.ts_off, r.dt, p.t_final);
+  return r;
+}
+
+// complex envelope mask * (s(t) - [T_BEFORE] s(t_before)) of a table component at AWG sample j; pwc takes no offset, no table
+// shape a DRAG term
+__device__ void tab_env_eval(const SynthArgs& A, int shape, const EnvP& p, const double* blk, int M, int j, double a0, double a1,
+                             double* er, double* ei, double* ts_off) {
+  const TabTimes tt = tab_times(A, p, j, a0, a1);
+  *ts_off = tt.ts_off;
+  if (shape == C3P_ENVT_PWC) {
+    const bool in = j < M;
+    *er = in ? tt.mask * blk[j] : 0.0;
+    *ei = in ? tt.mask * blk[M + j] : 0.0;
+    return;
+  }
+  const double offset = p.use_t_before ? tab_shape_val(shape, tt.t_before, p.t_final, blk, M) : 0.0;
+  *er = tt.mask * (tab_shape_val(shape, tt.ts_off, p.t_final, blk, M) - offset);
+  *ei = 0.0;
+}
+
+// one thread per AWG sample (b, k, j); TAB: components with a C3P_ENVT_* id read their block of the coefficient table
+// (X is not read without TAB; the body stands in the kernel itself: handed on through an inlined helper, the argument record
+// costs the closed-form instantiation registers)
+template <bool TAB>
+__global__ void __launch_bounds__(TAB ? 128 : 1024) awg_iq_kernel(SynthArgs A, SynthTabArgs X) {
   const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long total = (long)A.B * A.K * A.Na;
   if (gid >= total) return;
@@ -175,7 +289,20 @@ __global__ void awg_iq_kernel(SynthArgs A) {
     const int shape = A.shape[k * A.E + e];
     if (shape < 0) continue;
     const EnvP p = load_env(A.env + (bk * A.E + e) * C3P_ENV_NPAR);
-    const EnvEval v = env_eval(A, shape, p, j, a0, a1);
+    if constexpr (TAB) {
+      if (shape >= C3P_ENVT_FIRST) {
+        int off, M;
+        if (!tab_block(X, k * A.E + e, shape, &off, &M)) continue;
+        double er, ei, ts_off;
+        tab_env_eval(A, shape, p, X.tab + (bk / A.K) * (long)X.T + off, M, j, a0, a1, &er, &ei, &ts_off);
+        double sn, cs;
+        sincos(p.xy - p.fo * ts_off, &sn, &cs);
+        re += p.amp * (er * cs - ei * sn);
+        im += p.amp * (er * sn + ei * cs);
+        continue;
+      }
+    }
+    const EnvEval v = env_eval<TAB>(A, shape, p, j, a0, a1);
     const double er = v.er, ei = v.ei_unit * p.delta;
     double sn, cs;
     sincos(p.xy - p.fo * v.ts_off, &sn, &cs);
@@ -247,8 +374,10 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-// step 2, one wavefront per drive line (b, k): reduce over the AWG samples
-__global__ void __launch_bounds__(64) awg_bwd_kernel(SynthArgs A, const double* giq, const double* gcar_part, double* genv,
+// step 2, one wavefront per drive line (b, k): reduce over the AWG samples.  The sums hold for a complex envelope er + i ei
+// (the DRAG term, or a pwc table component's quadrature row).
+template <bool TAB>
+__global__ void __launch_bounds__(64) awg_bwd_kernel(SynthArgs A, SynthTabArgs X, const double* giq, const double* gcar_part, double* genv,
                                                      double* gcar) {
   const long bk = blockIdx.x;
   const int k = (int)(bk % A.K);
@@ -274,20 +403,40 @@ __global__ void __launch_bounds__(64) awg_bwd_kernel(SynthArgs A, const double* 
     const int shape = A.shape[k * A.E + e];
     if (shape < 0) continue;
     const EnvP p = load_env(A.env + (bk * A.E + e) * C3P_ENV_NPAR);
+    bool tab = false;
+    const double* blk = nullptr;
+    int M = 0;
+    if constexpr (TAB) {
+      if (shape >= C3P_ENVT_FIRST) {
+        int off;
+        if (!tab_block(X, k * A.E + e, shape, &off, &M)) continue;
+        blk = X.tab + (bk / A.K) * (long)X.T + off;
+        tab = true;
+      }
+    }
     double g_amp = 0.0, g_xy = 0.0, g_fo = 0.0, g_delta = 0.0;
     for (int j = lane; j < A.Na; j += 64) {
-      const EnvEval v = env_eval(A, shape, p, j, a0, a1);
+      double er, ei, ei_unit, ts_off;
+      if (TAB && tab) {
+        tab_env_eval(A, shape, p, blk, M, j, a0, a1, &er, &ei, &ts_off);
+        ei_unit = 0.0;
+      } else {
+        const EnvEval v = env_eval<TAB>(A, shape, p, j, a0, a1);
+        er = v.er;
+        ei_unit = v.ei_unit;
+        ei = v.ei_unit * p.delta;
+        ts_off = v.ts_off;
+      }
       double sn, cs;
-      sincos(p.xy - p.fo * v.ts_off, &sn, &cs);
-      const double er = v.er, ei = v.ei_unit * p.delta;
+      sincos(p.xy - p.fo * ts_off, &sn, &cs);
       const double ur = er * cs - ei * sn, ui = er * sn + ei * cs;  // env e^{i phase}
       const double zr = p.amp * ur, zi = p.amp * ui;
       const double a = gI[j], b = gQ[j];
       g_amp += a * ur + b * ui;
       g_xy += -a * zi + b * zr;
-      g_fo += v.ts_off * (a * zi - b * zr);
+      g_fo += ts_off * (a * zi - b * zr);
       // d z / d delta = amp * i ei_unit e^{i phase}
-      g_delta += p.amp * v.ei_unit * (-a * sn + b * cs);
+      g_delta += p.amp * ei_unit * (-a * sn + b * cs);
     }
     g_amp = wave_sum(g_amp);
     g_xy = wave_sum(g_xy);
@@ -300,6 +449,154 @@ __global__ void __launch_bounds__(64) awg_bwd_kernel(SynthArgs A, const double* 
       out[C3P_ENV_DELTA] = g_delta;
     }
   }
+}
+// ---- cotangents of the coefficient table, gathered from giq: grad_tab [B,T] ---------------------------------------------------
+// With g_j = gI_j + i gQ_j and c_j = amp g_j exp(-i phase_j):  d L / d theta = sum_j mask_j (Re c_j Re d(s_j - s_before)/d theta +
+// Im c_j Im d(...)/d theta).  Every double of the row is written by exactly one lane: one finds the block its double lies in
+// (none: 0; the two t_bin slots: 0, they are not differentiated).  pwc is element-wise; a knot of the interpolated shapes sums
+// the AWG samples in the support of its hat, j ascending (two stretches for pwc_symmetric, and all samples for the at most two
+// knots that weigh t_before); a Fourier coefficient (b, k, e, m) takes a wavefront of its own, lanes over j, then the butterfly.
+// No atomics: repeated calls return the same bits.
+__device__ __forceinline__ void tab_cj(const SynthArgs& A, const EnvP& p, const double* gI, int j, double a0, double a1, TabTimes* tt,
+                                       double* cr, double* ci) {
+  *tt = tab_times(A, p, j, a0, a1);
+  double sn, cs;
+  sincos(p.xy - p.fo * tt->ts_off, &sn, &cs);
+  const double a = gI[j], b = gI[A.Na + j];
+  *cr = tt->mask * p.amp * (a * cs + b * sn);
+  *ci = tt->mask * p.amp * (b * cs - a * sn);
+}
+
+// AWG samples whose time lies in [lo, hi] (a sample of margin on both sides; the weight decides), inside [0, Na - 1]
+__device__ __forceinline__ void sample_range(double lo, double hi, double off0, double dt, int Na, int* ja, int* jb) {
+  double a = floor((lo - off0) / dt) - 1.0, b = ceil((hi - off0) / dt) + 1.0;
+  a = a > 0.0 ? a : 0.0;  // (a NaN bound leaves the whole range)
+  b = b < (double)(Na - 1) ? b : (double)(Na - 1);
+  *ja = a <= (double)(Na - 1) ? (int)a : Na;
+  *jb = b >= 0.0 ? (int)b : -1;
+}
+
+// the table component whose block holds double t of a row: false if none does
+__device__ __forceinline__ bool tab_find(const SynthArgs& A, const SynthTabArgs& X, int t, int* ke, int* shape, int* off, int* M) {
+  for (int q = 0; q < A.K * A.E; ++q) {
+    const int sh = A.shape[q];
+    if (sh < C3P_ENVT_FIRST || !tab_block(X, q, sh, off, M)) continue;
+    if (t >= *off && t < *off + tab_block_len(sh, *M)) {
+      *ke = q;
+      *shape = sh;
+      return true;
+    }
+  }
+  return false;
+}
+
+// blocks [0, tiles) of a sample: 64 consecutive doubles of its row, one per lane (the Fourier blocks are left to the blocks
+// below); blocks [tiles, tiles + T): one wavefront per double t, at work where t is amps[m] of a Fourier component
+__global__ void __launch_bounds__(64) tab_bwd_kernel(SynthArgs A, SynthTabArgs X, const double* giq, double* gtab, int tiles) {
+  const int lane = threadIdx.x;
+  const int per_b = tiles + X.T;
+  const long b = blockIdx.x / per_b;
+  const int part = (int)(blockIdx.x % per_b);
+  const double dta = 1.0 / A.awg_res;
+  const double a0 = A.t_start + dta / 2, a1 = A.t_end - dta / 2;
+  double* grow = gtab + b * (long)X.T;
+  int ke = -1, shape = -1, off = 0, M = 0;
+  if (part >= tiles) {
+    // Fourier coefficient m (wave-uniform): amps[m], freqs[m] and phases[m] from one pass, lanes over j, then the butterfly
+    const int t = part - tiles;
+    if (!tab_find(A, X, t, &ke, &shape, &off, &M)) return;
+    const bool fsin = shape == C3P_ENVT_FOURIER_SIN;
+    const int m = t - off;
+    if ((!fsin && shape != C3P_ENVT_FOURIER_COS) || m >= M) return;
+    const long bk = b * A.K + ke / A.E;
+    const EnvP p = load_env(A.env + (b * A.K * A.E + ke) * C3P_ENV_NPAR);
+    const double* gI = giq + bk * 2 * A.Na;
+    const double* blk = X.tab + b * (long)X.T + off;
+    const double am = blk[m], fr = blk[M + m], ph = fsin ? blk[2 * M + m] : 0.0;
+    double g_a = 0.0, g_f = 0.0, g_p = 0.0;
+    for (int j = lane; j < A.Na; j += 64) {
+      TabTimes tt;
+      double cr, ci, sn, cs, sb = 0.0, cb = 0.0;
+      tab_cj(A, p, gI, j, a0, a1, &tt, &cr, &ci);
+      const double tb = p.use_t_before ? tt.t_before : 0.0;
+      sincos(fr * tt.ts_off + ph, &sn, &cs);
+      if (p.use_t_before) sincos(fr * tb + ph, &sb, &cb);
+      if (fsin) {  // d/d amps = sin, d/d freqs = amps t cos, d/d phases = amps cos, each minus its value at t_before
+        g_a += cr * (sn - sb);
+        g_f += cr * (am * tt.ts_off * cs - am * tb * cb);
+        g_p += cr * (am * cs - am * cb);
+      } else {  // d/d amps = cos, d/d freqs = -amps t sin
+        g_a += cr * (cs - cb);
+        g_f += cr * (am * tb * sb - am * tt.ts_off * sn);
+      }
+    }
+    g_a = wave_sum(g_a);
+    g_f = wave_sum(g_f);
+    g_p = wave_sum(g_p);
+    if (lane == 0) {
+      grow[off + m] = g_a;
+      grow[off + M + m] = g_f;
+      if (fsin) grow[off + 2 * M + m] = g_p;
+    }
+    return;
+  }
+  const int t = part * 64 + lane;
+  if (t >= X.T) return;
+  const bool found = tab_find(A, X, t, &ke, &shape, &off, &M);
+  if (found && (shape == C3P_ENVT_FOURIER_SIN || shape == C3P_ENVT_FOURIER_COS)) return;
+  double out = 0.0;
+  if (found) {
+    const long bk = b * A.K + ke / A.E;
+    const EnvP p = load_env(A.env + (b * A.K * A.E + ke) * C3P_ENV_NPAR);
+    const double* gI = giq + bk * 2 * A.Na;
+    const int rel = t - off;
+    TabTimes tt;
+    double cr, ci;
+    if (shape == C3P_ENVT_PWC) {
+      const int j = rel < M ? rel : rel - M;
+      if (j < A.Na) {
+        tab_cj(A, p, gI, j, a0, a1, &tt, &cr, &ci);
+        out = rel < M ? cr : ci;
+      }
+    } else if (rel >= 2) {
+      const int m = rel - 2;
+      const double* blk = X.tab + b * (long)X.T + off;
+      const double x0 = blk[0], x1 = blk[1], tf_ = p.t_final;
+      tt = tab_times(A, p, 0, a0, a1);
+      const double off0 = tt.ts_off, dt = tt.dt;
+      const double wb = p.use_t_before ? hat_weight(shape, tt.t_before, tf_, x0, x1, M, m) : 0.0;
+      if (wb != 0.0) {
+        // this knot weighs the offset every sample carries
+        for (int j = 0; j < A.Na; ++j) {
+          tab_cj(A, p, gI, j, a0, a1, &tt, &cr, &ci);
+          out += cr * (hat_weight(shape, tt.ts_off, tf_, x0, x1, M, m) - wb);
+        }
+      } else {
+        const double h = (x1 - x0) / (double)(M - 1);
+        const double lo = x0 + (double)(m - 1) * h, hi = x0 + (double)(m + 1) * h;
+        int ja, jb, jc = A.Na, jd = -1;
+        sample_range(lo, hi, off0, dt, A.Na, &ja, &jb);
+        if (shape == C3P_ENVT_PWC_SYMMETRIC) sample_range(tf_ - hi, tf_ - lo, off0, dt, A.Na, &jc, &jd);
+        if (jc < ja) {  // the earlier stretch first
+          int s = ja;
+          ja = jc;
+          jc = s;
+          s = jb;
+          jb = jd;
+          jd = s;
+        }
+        for (int j = ja; j <= jb; ++j) {
+          tab_cj(A, p, gI, j, a0, a1, &tt, &cr, &ci);
+          out += cr * hat_weight(shape, tt.ts_off, tf_, x0, x1, M, m);
+        }
+        for (int j = jc > jb ? jc : jb + 1; j <= jd; ++j) {
+          tab_cj(A, p, gI, j, a0, a1, &tt, &cr, &ci);
+          out += cr * hat_weight(shape, tt.ts_off, tf_, x0, x1, M, m);
+        }
+      }
+    }
+  }
+  grow[t] = out;
 }
 
 // one thread per simulation sample (b, k, n): nearest-neighbour upsampling, IQ mixing, V -> Hz
@@ -321,25 +618,57 @@ __global__ void mix_kernel(SynthArgs A) {
 
 }  // namespace
 
-hipError_t c3p_launch_synth_vjp(const SynthArgs& A, const double* gsig, double* giq, double* gcar_part, double* genv,
-                                double* gcar, hipStream_t st) {
+namespace {
+// the AWG-resolution I/Q: the table-aware instantiation only where a coefficient table travels with the rows
+void launch_awg_iq(const SynthArgs& A, const SynthTabArgs* X, long ta, hipStream_t st) {
+  if (X)
+    C3P_LAUNCH(awg_iq_kernel<true>, dim3((unsigned)((ta + 127) / 128)), dim3(128), 0, st, A, *X);
+  else
+    C3P_LAUNCH(awg_iq_kernel<false>, dim3((unsigned)((ta + 127) / 128)), dim3(128), 0, st, A, SynthTabArgs{});
+}
+// giq -> genv, gcar (and, with a table, gtab)
+void launch_awg_bwd(const SynthArgs& A, const SynthTabArgs* X, const double* giq, const double* gcar_part, double* genv, double* gcar,
+                    double* gtab, hipStream_t st) {
+  const unsigned lines = (unsigned)(A.B * A.K);
+  if (!X) {
+    C3P_LAUNCH(awg_bwd_kernel<false>, dim3(lines), dim3(64), 0, st, A, SynthTabArgs{}, giq, gcar_part, genv, gcar);
+    return;
+  }
+  C3P_LAUNCH(awg_bwd_kernel<true>, dim3(lines), dim3(64), 0, st, A, *X, giq, gcar_part, genv, gcar);
+  const int tiles = (X->T + 63) / 64;
+  if (tiles > 0) C3P_LAUNCH(tab_bwd_kernel, dim3((unsigned)((long)A.B * (tiles + X->T))), dim3(64), 0, st, A, *X, giq, gtab, tiles);
+}
+
+hipError_t synth_vjp_impl(const SynthArgs& A, const SynthTabArgs* X, const double* gsig, double* giq, double* gcar_part, double* genv,
+                          double* gcar, double* gtab, hipStream_t st) {
   const long ta = (long)A.B * A.K * A.Na;
   if (ta == 0) return hipSuccess;
-  C3P_LAUNCH(awg_iq_kernel, dim3((unsigned)((ta + 127) / 128)), dim3(128), 0, st, A);
+  launch_awg_iq(A, X, ta, st);
   C3P_LAUNCH(mix_bwd_kernel, dim3((unsigned)ta), dim3(64), 0, st, A, gsig, giq, gcar_part);
-  C3P_LAUNCH(awg_bwd_kernel, dim3((unsigned)(A.B * A.K)), dim3(64), 0, st, A, (const double*)giq,
-                     (const double*)gcar_part, genv, gcar);
+  launch_awg_bwd(A, X, (const double*)giq, (const double*)gcar_part, genv, gcar, gtab, st);
   return hipGetLastError();
 }
 
-hipError_t c3p_launch_synth(const SynthArgs& A, hipStream_t st) {
+hipError_t synth_impl(const SynthArgs& A, const SynthTabArgs* X, hipStream_t st) {
   const long ta = (long)A.B * A.K * A.Na, ts = (long)A.B * A.K * A.N;
   if (ta == 0 || ts == 0) return hipSuccess;
-  C3P_LAUNCH(awg_iq_kernel, dim3((unsigned)((ta + 127) / 128)), dim3(128), 0, st, A);
+  launch_awg_iq(A, X, ta, st);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   C3P_LAUNCH(mix_kernel, dim3((unsigned)((ts + 255) / 256)), dim3(256), 0, st, A);
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t c3p_launch_synth_vjp(const SynthArgs& A, const double* gsig, double* giq, double* gcar_part, double* genv,
+                                double* gcar, hipStream_t st) {
+  return synth_vjp_impl(A, nullptr, gsig, giq, gcar_part, genv, gcar, nullptr, st);
+}
+hipError_t c3p_launch_synth(const SynthArgs& A, hipStream_t st) { return synth_impl(A, nullptr, st); }
+hipError_t c3p_launch_synth_tab(const SynthArgs& A, const SynthTabArgs& X, hipStream_t st) { return synth_impl(A, &X, st); }
+hipError_t c3p_launch_synth_tab_vjp(const SynthArgs& A, const SynthTabArgs& X, const double* gsig, double* giq, double* gcar_part,
+                                    double* genv, double* gcar, double* gtab, hipStream_t st) {
+  return synth_vjp_impl(A, &X, gsig, giq, gcar_part, genv, gcar, gtab, st);
 }
 
 // ---- the device chain of a flux line: AWG -> DAC -> Response -> Mixer -> VoltsToHertz | FluxTuning --------------------------
@@ -609,12 +938,13 @@ __global__ void __launch_bounds__(64) chain_bwd_awg_kernel(SynthChainArgs C, int
 
 }  // namespace
 
-hipError_t c3p_launch_chain(const SynthChainArgs& C, hipStream_t st) {
+namespace {
+hipError_t chain_impl(const SynthChainArgs& C, const SynthTabArgs* X, hipStream_t st) {
   const SynthArgs& A = C.S;
   const long lines = (long)A.B * A.K, ta = lines * A.Na;
   const int nt = (A.N + CH_TN - 1) / CH_TN;
   if (ta == 0 || A.N == 0) return hipSuccess;
-  C3P_LAUNCH(awg_iq_kernel, dim3((unsigned)((ta + 127) / 128)), dim3(128), 0, st, A);
+  launch_awg_iq(A, X, ta, st);
   C3P_LAUNCH(chain_taps_kernel, dim3((unsigned)lines), dim3(64), 0, st, C);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
@@ -622,16 +952,13 @@ hipError_t c3p_launch_chain(const SynthChainArgs& C, hipStream_t st) {
   return hipGetLastError();
 }
 
-int c3p_chain_tiles(int N) { return (N + CH_TN - 1) / CH_TN; }
-int c3p_chain_part_stride() { return CH_PS; }
-
-hipError_t c3p_launch_chain_vjp(const SynthChainArgs& C, const double* gsig, double* gcs, double* part, double* giq, double* gcar_part,
-                                double* genv, double* gcar, double* gline, hipStream_t st) {
+hipError_t chain_vjp_impl(const SynthChainArgs& C, const SynthTabArgs* X, const double* gsig, double* gcs, double* part, double* giq,
+                          double* gcar_part, double* genv, double* gcar, double* gline, double* gtab, hipStream_t st) {
   const SynthArgs& A = C.S;
   const long lines = (long)A.B * A.K, ta = lines * A.Na;
   const int nt = c3p_chain_tiles(A.N);
   if (ta == 0 || A.N == 0) return hipSuccess;
-  C3P_LAUNCH(awg_iq_kernel, dim3((unsigned)((ta + 127) / 128)), dim3(128), 0, st, A);
+  launch_awg_iq(A, X, ta, st);
   C3P_LAUNCH(chain_taps_kernel, dim3((unsigned)lines), dim3(64), 0, st, C);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
@@ -640,6 +967,22 @@ hipError_t c3p_launch_chain_vjp(const SynthChainArgs& C, const double* gsig, dou
              gcar_part, gline);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  C3P_LAUNCH(awg_bwd_kernel, dim3((unsigned)lines), dim3(64), 0, st, A, (const double*)giq, (const double*)gcar_part, genv, gcar);
+  launch_awg_bwd(A, X, (const double*)giq, (const double*)gcar_part, genv, gcar, gtab, st);
   return hipGetLastError();
+}
+}  // namespace
+
+int c3p_chain_tiles(int N) { return (N + CH_TN - 1) / CH_TN; }
+int c3p_chain_part_stride() { return CH_PS; }
+
+hipError_t c3p_launch_chain(const SynthChainArgs& C, hipStream_t st) { return chain_impl(C, nullptr, st); }
+hipError_t c3p_launch_chain_tab(const SynthChainArgs& C, const SynthTabArgs& X, hipStream_t st) { return chain_impl(C, &X, st); }
+hipError_t c3p_launch_chain_vjp(const SynthChainArgs& C, const double* gsig, double* gcs, double* part, double* giq, double* gcar_part,
+                                double* genv, double* gcar, double* gline, hipStream_t st) {
+  return chain_vjp_impl(C, nullptr, gsig, gcs, part, giq, gcar_part, genv, gcar, gline, nullptr, st);
+}
+hipError_t c3p_launch_chain_tab_vjp(const SynthChainArgs& C, const SynthTabArgs& X, const double* gsig, double* gcs, double* part,
+                                    double* giq, double* gcar_part, double* genv, double* gcar, double* gline, double* gtab,
+                                    hipStream_t st) {
+  return chain_vjp_impl(C, &X, gsig, gcs, part, giq, gcar_part, genv, gcar, gline, gtab, st);
 }

@@ -45,6 +45,8 @@ def goal_run_with_grad(
     fused: Optional[bool] = None,
     line_kinds=None,
     line_params=None,
+    env_tables=None,
+    table_index=None,
 ) -> Dict:
     """goals [B] and their gradients w.r.t. every envelope row, carrier pair and frame-rotation phase.
 
@@ -58,6 +60,10 @@ def goal_run_with_grad(
     `line_kinds` [K] / `line_params` [B,K,LINE_NPAR] (signals.pack_lines) send every line through the chain AWG -> DAC ->
     Response -> Mixer -> VoltsToHertz | FluxTuning instead of the standard drive line; the result then also holds
     "grad_line" [B,K,LINE_NPAR] (phi_0, phi, omega_0, anhar, d; rise_time is not differentiated), on every route below.
+
+    `env_tables` [B,T] / `table_index` [K,E,2] (signals.pack_table_components) bring the coefficients of sampled and Fourier
+    envelopes (pwc, pwc_shape, pwc_symmetric, fourier_sin, fourier_cos): the result then holds "grad_tables" [B,T], the
+    gradient w.r.t. every coefficient in the layout of env_tables -- what a GRAPE-style optimiser of the AWG samples steps along.
 
     `fused` (closed systems; default: wherever the library serves the shape) takes goal and gradient from ONE pass over the
     chains (`propagation.propagate_batch_goal_vjp`); False runs forward pass, cotangent and vector-Jacobian product as three
@@ -81,12 +87,18 @@ def goal_run_with_grad(
         if line_kinds is None or line_params is None:
             raise C3PropError("C3:Error: line_kinds and line_params go together")
         chain = {"line_kinds": line_kinds, "line_params": as_dev(line_params, np.float64)}
+    names = ("grad_env", "grad_carrier") + (("grad_line",) if chain else ())
+    if env_tables is not None or table_index is not None:
+        if env_tables is None or table_index is None:
+            raise C3PropError("C3:Error: env_tables and table_index go together")
+        chain = dict(chain, env_tables=as_dev(env_tables, np.float64), table_index=table_index)
+        names += ("grad_tables",)
     sig = signals.synthesize_signals(env, env_shapes, car, t_start, t_end, awg_res, sim_res, **chain)
 
     def synth_vjp(g_sig):
-        """{"grad_env", "grad_carrier"[, "grad_line"]} from d goal / d signals"""
+        """{"grad_env", "grad_carrier"[, "grad_line"][, "grad_tables"]} from d goal / d signals"""
         g = signals.synthesize_signals_vjp(env, env_shapes, car, t_start, t_end, awg_res, sim_res, g_sig, **chain)
-        return dict(zip(("grad_env", "grad_carrier", "grad_line"), g))
+        return dict(zip(names, g))
 
     if col_ops is not None:
         if not fid_func.startswith("lindbladian"):
@@ -147,6 +159,8 @@ def goal_run_ode_with_grad(
     step_function: str = "schrodinger",
     col_ops=None,
     device="cuda:0",
+    env_tables=None,
+    table_index=None,
 ) -> Dict:
     """State-transfer goals [B] and their gradients through the ODE state solvers -- the body of `goal_run_ode_only_final`
     (optimalcontrol.py:262-292: compute_final_state with an RK solver, then state_transfer_from_states, fidelities.py:793-816)
@@ -157,7 +171,7 @@ def goal_run_ode_with_grad(
     `init_state` [D,M] or [B,D,M] (M = 1: state vector; M = D: density matrix, steps "von_neumann" / "lindblad"), `target` a
     ket [D,1] or [B,D,1].  Returns {"goal": [B], "grad_env": [B,K,E,NPAR], "grad_carrier": [B,K,2], "init_bar": [B,D,M] (the
     cotangent of the initial state: a preceding gate's sweep starts from it), "states": [B,D,M] (the final states)} as
-    torch CUDA tensors."""
+    torch CUDA tensors; with `env_tables` / `table_index` (as in `goal_run_with_grad`) also "grad_tables" [B,T]."""
     import torch
 
     ts = signals.create_ts(t_start, t_end, sim_res)
@@ -169,11 +183,19 @@ def goal_run_ode_with_grad(
     car = as_dev(carrier, np.float64)
     h0d, hkd = as_dev(h0, np.complex128), as_dev(hks, np.complex128)
     cold = None if col_ops is None else as_dev(col_ops, np.complex128)
-    sig = signals.synthesize_signals(env, env_shapes, car, t_start, t_end, awg_res, sim_res)
+    tab = {}
+    if env_tables is not None or table_index is not None:
+        if env_tables is None or table_index is None:
+            raise C3PropError("C3:Error: env_tables and table_index go together")
+        tab = {"env_tables": as_dev(env_tables, np.float64), "table_index": table_index}
+    sig = signals.synthesize_signals(env, env_shapes, car, t_start, t_end, awg_res, sim_res, **tab)
     r = propagation.ode_goal_vjp(h0d, hkd, sig, dt, as_dev(init_state, np.complex128), as_dev(target, np.complex128),
                                  solver=solver, step_function=step_function, col_ops=cold)
-    g_env, g_car = signals.synthesize_signals_vjp(env, env_shapes, car, t_start, t_end, awg_res, sim_res, r["grad_signals"])
-    return {"goal": r["goal"], "grad_env": g_env, "grad_carrier": g_car, "init_bar": r["init_bar"], "states": r["states"]}
+    g = signals.synthesize_signals_vjp(env, env_shapes, car, t_start, t_end, awg_res, sim_res, r["grad_signals"], **tab)
+    out = {"goal": r["goal"], "grad_env": g[0], "grad_carrier": g[1], "init_bar": r["init_bar"], "states": r["states"]}
+    if tab:
+        out["grad_tables"] = g[2]
+    return out
 
 
 def robust_goal_run_with_grad(*args, **kwargs) -> Dict:
@@ -187,4 +209,6 @@ def robust_goal_run_with_grad(*args, **kwargs) -> Dict:
         out["grad_fr_phase"] = r["grad_fr_phase"].mean(dim=0)
     if "grad_line" in r:
         out["grad_line"] = r["grad_line"].mean(dim=0)
+    if "grad_tables" in r:
+        out["grad_tables"] = r["grad_tables"].mean(dim=0)
     return out

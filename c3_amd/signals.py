@@ -44,6 +44,19 @@ ENV_SLOTS = {
     "flags": 10,
 }
 ENV_NPAR = 12
+# shapes whose parameters are an array of coefficients: they read a block of the coefficient table that travels with the
+# rows (C3P_ENVT_* of include/c3prop.h; `pack_table_components`, `synthesize_signals(env_tables=, table_index=)`)
+TAB_SHAPES = {"pwc": 16, "pwc_shape": 17, "pwc_symmetric": 18, "fourier_sin": 19, "fourier_cos": 20}
+# the block of each: scalars first, then arrays of M doubles each, in this order
+TAB_LAYOUT = {
+    "pwc": ((), ("inphase", "quadrature")),
+    "pwc_shape": (("t_bin_start", "t_bin_end"), ("inphase",)),
+    "pwc_symmetric": (("t_bin_start", "t_bin_end"), ("inphase",)),
+    "fourier_sin": ((), ("amps", "freqs", "phases")),
+    "fourier_cos": ((), ("amps", "freqs")),
+}
+_TAB_NAMES = {v: k for k, v in TAB_SHAPES.items()}
+_TAB_KEYS = frozenset(k for sc, ar in TAB_LAYOUT.values() for k in sc + ar)
 ENVF_T_BEFORE = 1
 ENVF_DRAG = 2
 # what follows the mixer on a line, and the per-line parameter row of `c3p_synth_chain` (C3P_LINE_* of include/c3prop.h)
@@ -86,6 +99,85 @@ def pack_components(channels: Sequence[Sequence[Dict]], B: int = 1):
             if name != "no_drive" and "t_final" not in comp:
                 raise C3PropError("C3:Error: envelope component needs t_final")
     return env, shapes
+
+
+def table_block_len(shape: str, M: int) -> int:
+    """Doubles in the block of a table component with M coefficients per array."""
+    scalars, arrays = TAB_LAYOUT[shape]
+    return len(scalars) + len(arrays) * M
+
+
+def pack_table_components(channels: Sequence[Sequence[Dict]], B: int = 1, awg_samples: Optional[int] = None):
+    """`pack_components` for lines that also carry sampled or Fourier envelopes ->
+    (env_params [B,K,E,NPAR], env_shapes [K,E], env_tables [B,T], table_index [K,E,2]).
+
+    A component whose `shape` is one of TAB_SHAPES carries the reference's array parameters (envelopes.py:31-68,104-125,
+    142-191): `inphase` / `quadrature` (pwc: one pair per AWG sample), `t_bin_start`, `t_bin_end`, `inphase` (pwc_shape,
+    pwc_symmetric: M >= 2 knots), `amps`, `freqs`, `phases` (fourier_sin), `amps`, `freqs` (fourier_cos).  An array is [M]
+    (shared by the batch) or [B,M]; the scalars are shared or [B].  Its block lies at `table_index[k,e] = (offset, M)` in every
+    sample's row of `env_tables`, laid out as TAB_LAYOUT says; components without a table have (-1, 0).  The blocks follow
+    each other in the order of the components.  `awg_samples` (Na) lets the pwc length be checked here.
+    """
+    K = len(channels)
+    E = max(1, max(len(c) for c in channels))
+    for comps in channels:
+        for comp in comps:
+            stray = sorted(set(comp) & _TAB_KEYS) if comp["shape"] in ENV_SHAPES else []
+            if stray:
+                raise C3PropError(f"C3:Error: envelope shape {comp['shape']!r} takes no array parameter {stray[0]!r}")
+    plain = [[{k: v for k, v in comp.items() if k not in _TAB_KEYS} if comp["shape"] in TAB_SHAPES else comp for comp in comps] for comps in channels]
+    for comps in plain:
+        for comp in comps:
+            if comp["shape"] in TAB_SHAPES:
+                comp["shape"] = "rect"  # placeholder: the row's slots are packed as for any shape, the id is set below
+    env, shapes = pack_components(plain, B=B)
+    index = np.zeros((K, E, 2), dtype=np.int32)
+    index[..., 0] = -1
+    blocks, T = [], 0
+    for k, comps in enumerate(channels):
+        for e, comp in enumerate(comps):
+            name = comp["shape"]
+            if name not in TAB_SHAPES:
+                continue
+            if comp.get("drag", False):
+                raise C3PropError(f"C3:Error: DRAG on the table shape {name!r} is not available on the device")
+            if name == "pwc" and comp.get("use_t_before", False):
+                raise C3PropError("C3:Error: use_t_before on 'pwc' is refused (the reference's offset would be the array itself)")
+            scalars, arrays = TAB_LAYOUT[name]
+            for key in scalars + arrays:
+                if key not in comp:
+                    raise C3PropError(f"C3:Error: envelope shape {name!r} needs '{key}'")
+            cols = []
+            for key in scalars:
+                v = np.asarray(comp[key], dtype=np.float64)
+                if v.shape not in ((), (B,)):
+                    raise C3PropError(f"C3:Error: '{key}' must be a scalar or [{B}], got {v.shape}")
+                cols.append(np.broadcast_to(v.reshape(-1, 1), (B, 1)))
+            M = None
+            for key in arrays:
+                v = np.asarray(comp[key], dtype=np.float64)
+                if v.ndim not in (1, 2) or (v.ndim == 2 and v.shape[0] != B):
+                    raise C3PropError(f"C3:Error: '{key}' must be [M] or [{B},M], got {v.shape}")
+                if M is None:
+                    M = int(v.shape[-1])
+                    if M < 1:
+                        raise C3PropError(f"C3:Error: '{key}' of {name!r} is empty")
+                elif v.shape[-1] != M:
+                    raise C3PropError(f"C3:Error: '{key}' of {name!r} holds {v.shape[-1]} values, '{arrays[0]}' holds {M}")
+                cols.append(np.broadcast_to(v.reshape(-1, M), (B, M)))
+            if name in ("pwc_shape", "pwc_symmetric"):
+                if M < 2:
+                    raise C3PropError(f"C3:Error: {name!r} needs at least two knots, got {M}")
+                if not np.all(cols[1] > cols[0]):
+                    raise C3PropError(f"C3:Error: {name!r} needs t_bin_end > t_bin_start")
+            if name == "pwc" and awg_samples is not None and M != awg_samples:
+                raise C3PropError(f"C3:Error: 'pwc' holds one pair per AWG sample: {M} values for {awg_samples} samples")
+            shapes[k, e] = TAB_SHAPES[name]
+            index[k, e] = (T, M)
+            blocks += cols
+            T += table_block_len(name, M)
+    tables = np.ascontiguousarray(np.concatenate(blocks, axis=1)) if blocks else np.zeros((B, 0), dtype=np.float64)
+    return env, shapes, tables, index
 
 
 def response_tap_count(rise_time: float, sim_res: float) -> int:
@@ -138,13 +230,13 @@ _shapes_memo = TensorMemo()  # device shape tables: per tensor object (weak refe
 _shapes_upload: Dict[tuple, object] = {}  # content-keyed uploads of host tables
 
 
-def _shapes(call, env_shapes, K: int, E: int):
+def _shapes(call, env_shapes, K: int, E: int, tables: bool = False):
     """(host int32 [K,E], the array the library call takes): validated once per distinct table; on the device path the upload
     is cached -- an optimiser calls the synthesis and its vjp every iteration with the same shapes, and a pageable
     host-to-device copy per call is a synchronisation (and illegal inside a stream capture).  A device table is remembered
     per tensor OBJECT; the [K,E] check against the parameter rows runs on every call, hit or not."""
     on_dev = _is_torch(env_shapes) and env_shapes.is_cuda
-    mkey = (str(env_shapes.dtype), str(call.dev)) if on_dev else None  # the upload lives on call.dev (ADVICE r5)
+    mkey = (str(env_shapes.dtype), str(call.dev), tables) if on_dev else None  # the upload lives on call.dev (ADVICE r5)
     hit = _shapes_memo.get(env_shapes, mkey) if on_dev else None
     if hit is not None:
         if hit[0].shape != (K, E):
@@ -153,8 +245,11 @@ def _shapes(call, env_shapes, K: int, E: int):
     shapes_np = np.ascontiguousarray(np.asarray(env_shapes.cpu() if _is_torch(env_shapes) else env_shapes, dtype=np.int32))
     if shapes_np.shape != (K, E):
         raise C3PropError(f"C3:Error: env_shapes must be [{K},{E}], got {shapes_np.shape}")
-    if shapes_np.max(initial=-1) >= len(ENV_SHAPES):
-        raise C3PropError("C3:Error: env_shapes holds an unknown shape id")
+    unknown = shapes_np >= len(ENV_SHAPES)
+    if tables:  # only a call that brings a coefficient table takes the TAB_SHAPES ids
+        unknown &= ~np.isin(shapes_np, list(TAB_SHAPES.values()))
+    if unknown.any():
+        raise C3PropError("C3:Error: env_shapes holds an unknown shape id" + ("" if tables else " (the TAB_SHAPES need env_tables and table_index)"))
     if not call.device:
         return shapes_np, shapes_np
     key2 = (shapes_np.tobytes(), shapes_np.shape, str(call.dev))
@@ -166,6 +261,57 @@ def _shapes(call, env_shapes, K: int, E: int):
     if on_dev:
         _shapes_memo.put(env_shapes, mkey, (shapes_np, shp))
     return shapes_np, shp
+
+
+def _table_index(call, table_index, shapes_np: np.ndarray, T: int, Na: int):
+    """The index table as the library call takes it, treated as `_shapes` treats the shape table: checked on the host once per
+    distinct (index, shapes, T, Na) -- blocks inside the row and apart from each other, M = Na for pwc, M >= 2 for the
+    interpolated shapes -- and, on the device route, uploaded once."""
+    K, E = shapes_np.shape
+    on_dev = _is_torch(table_index) and table_index.is_cuda
+    mkey = ("tidx", str(call.dev), shapes_np.tobytes(), T, Na) if on_dev else None
+    hit = _shapes_memo.get(table_index, mkey) if on_dev else None
+    if hit is not None:
+        return hit
+    idx = np.ascontiguousarray(np.asarray(table_index.cpu() if _is_torch(table_index) else table_index, dtype=np.int32))
+    if idx.shape != (K, E, 2):
+        raise C3PropError(f"C3:Error: table_index must be [{K},{E},2], got {idx.shape}")
+    key = ("tidx", idx.tobytes(), shapes_np.tobytes(), T, Na, str(call.dev) if call.device else None)
+    up = _shapes_upload.get(key)
+    if up is None:
+        spans = []
+        for k in range(K):
+            for e in range(E):
+                name = _TAB_NAMES.get(int(shapes_np[k, e]))
+                if name is None:
+                    continue
+                off, M = (int(x) for x in idx[k, e])
+                if off < 0 or M < 1 or off + table_block_len(name, M) > T:
+                    raise C3PropError(f"C3:Error: table_index[{k},{e}]=({off},{M}): the block of {name!r} does not lie inside the row (T={T})")
+                if name == "pwc" and M != Na:
+                    raise C3PropError(f"C3:Error: component [{k},{e}]: 'pwc' holds one pair per AWG sample, M={M} but Na={Na}")
+                if name in ("pwc_shape", "pwc_symmetric") and M < 2:
+                    raise C3PropError(f"C3:Error: component [{k},{e}]: {name!r} needs at least two knots, got {M}")
+                spans.append((off, off + table_block_len(name, M)))
+        spans.sort()
+        for (a0, a1), (b0, b1) in zip(spans, spans[1:]):
+            if b0 < a1:
+                raise C3PropError(f"C3:Error: table_index: the blocks [{a0},{a1}) and [{b0},{b1}) overlap")
+        if len(_shapes_upload) > 64:
+            _shapes_upload.clear()
+        up = _shapes_upload[key] = call.torch.as_tensor(idx, device=call.dev) if call.device else idx
+    if on_dev:
+        _shapes_memo.put(table_index, mkey, up)
+    return up
+
+
+def _tables(call, env_tables, table_index, shapes_np, B: int, Na: int):
+    """(env_tab, tab_index, T) of a call with a coefficient table"""
+    tab = call.f64(env_tables)
+    if tab.ndim != 2 or int(tab.shape[0]) != B:
+        raise C3PropError(f"C3:Error: env_tables must be [{B},T], got {tuple(tab.shape)}")
+    T = int(tab.shape[1])
+    return tab, _table_index(call, table_index, shapes_np, T, Na), T
 
 
 def _lines(call, line_kinds, line_params, B: int, K: int, sim_res: float):
@@ -192,11 +338,15 @@ def _lines(call, line_kinds, line_params, B: int, K: int, sim_res: float):
     return knd, par
 
 
-def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, *, want_iq: bool = False, device=None, line_kinds=None, line_params=None):
+def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, *, want_iq: bool = False, device=None, line_kinds=None, line_params=None, env_tables=None, table_index=None):
     """signals [B,K,N] (and optionally the AWG-resolution I/Q [B,K,2,Na]) from parameter rows.
 
     With `line_kinds` [K] int32 and `line_params` [B,K,LINE_NPAR] (see `pack_lines`) every line runs the chain
     AWG -> DAC -> Response -> Mixer -> VoltsToHertz | FluxTuning (`c3p_synth_chain`); without them the standard drive line.
+
+    With `env_tables` [B,T] f64 and `table_index` [K,E,2] int32 (see `pack_table_components`) `env_shapes` may hold TAB_SHAPES
+    ids: sampled (pwc, pwc_shape, pwc_symmetric) and Fourier envelopes that read their coefficients from the table
+    (`c3p_synth_tab`, on either kind of line).  Without the two keywords every call goes where it went before them.
 
     env_params [B,K,E,NPAR] f64, env_shapes [K,E] int32, carrier [B,K,2] f64 = (LO angular
     frequency, V_to_Hz).  numpy in -> numpy out (staged by the library); with `device` (or any torch
@@ -208,12 +358,16 @@ def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: f
         env_params = torch.as_tensor(np.asarray(env_params, dtype=np.float64) if not _is_torch(env_params) else env_params, device=device)
     if (line_kinds is None) != (line_params is None):
         raise C3PropError("C3:Error: line_kinds and line_params go together")
-    call = _Call(env_params, carrier, line_params)
+    if (env_tables is None) != (table_index is None):
+        raise C3PropError("C3:Error: env_tables and table_index go together")
+    if device is not None and env_tables is not None and not _is_torch(env_tables):
+        env_tables = torch.as_tensor(np.asarray(env_tables, dtype=np.float64), device=device)
+    call = _Call(env_params, carrier, line_params, env_tables)
     env = call.f64(env_params)
     if env.ndim != 4 or env.shape[-1] != ENV_NPAR:
         raise C3PropError(f"C3:Error: env_params must be [B,K,E,{ENV_NPAR}], got {tuple(env.shape)}")
     B, K, E = (int(x) for x in env.shape[:3])
-    shapes_np, shp = _shapes(call, env_shapes, K, E)
+    shapes_np, shp = _shapes(call, env_shapes, K, E, tables=env_tables is not None)
     car = call.f64(carrier)
     if tuple(car.shape) != (B, K, 2):
         raise C3PropError(f"C3:Error: carrier must be [{B},{K},2], got {tuple(car.shape)}")
@@ -226,6 +380,15 @@ def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: f
     else:
         sig = np.empty((B, K, N), dtype=np.float64)
         iq = np.empty((B, K, 2, Na), dtype=np.float64) if want_iq else None
+    if env_tables is not None:
+        tab, tidx, T = _tables(call, env_tables, table_index, shapes_np, B, Na)
+        knd, par = _lines(call, line_kinds, line_params, B, K, sim_res) if line_kinds is not None else (None, None)
+        _lib.check(
+            _lib.load().c3p_synth_tab(
+                _ptr(env), _ptr(shp), _ptr(tab), _ptr(tidx), T, _ptr(car), _ptr(knd), _ptr(par), float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags, _ptr(iq), _ptr(sig), call.stream
+            )
+        )
+        return (sig, iq) if want_iq else sig
     if line_kinds is not None:
         knd, par = _lines(call, line_kinds, line_params, B, K, sim_res)
         _lib.check(
@@ -242,10 +405,13 @@ def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: f
     return (sig, iq) if want_iq else sig
 
 
-def synthesize_signals_vjp(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, grad_signals, *, line_kinds=None, line_params=None):
+def synthesize_signals_vjp(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, grad_signals, *, line_kinds=None, line_params=None, env_tables=None, table_index=None):
     """(grad_env [B,K,E,NPAR], grad_carrier [B,K,2]) from d loss / d signals [B,K,N]; with `line_kinds` / `line_params`
     (the chain of `synthesize_signals`) also grad_line [B,K,LINE_NPAR]: phi_0, phi, omega_0, anhar, d in their LINE_SLOTS,
-    0 for rise_time (the tap count is a floor) and, in grad_carrier, for V_to_Hz on a flux line.
+    0 for rise_time (the tap count is a floor) and, in grad_carrier, for V_to_Hz on a flux line.  With `env_tables` /
+    `table_index` (the coefficient table of `synthesize_signals`) grad_tables [B,T] is an additional last value: the
+    cotangent of every coefficient in the layout of env_tables, exactly 0 in the t_bin_start / t_bin_end slots (they are
+    not differentiated) and outside the blocks.
 
     Differentiates amp, xy_angle, freq_offset, delta (their ENV_SLOTS) and the carrier pair; the
     reference gets the same numbers from the tape that also covers the propagation
@@ -253,12 +419,14 @@ def synthesize_signals_vjp(env_params, env_shapes, carrier, t_start: float, t_en
     """
     if (line_kinds is None) != (line_params is None):
         raise C3PropError("C3:Error: line_kinds and line_params go together")
-    call = _Call(env_params, carrier, grad_signals, line_params)
+    if (env_tables is None) != (table_index is None):
+        raise C3PropError("C3:Error: env_tables and table_index go together")
+    call = _Call(env_params, carrier, grad_signals, line_params, env_tables)
     env = call.f64(env_params)
     if env.ndim != 4 or env.shape[-1] != ENV_NPAR:
         raise C3PropError(f"C3:Error: env_params must be [B,K,E,{ENV_NPAR}], got {tuple(env.shape)}")
     B, K, E = (int(x) for x in env.shape[:3])
-    shapes_np, shp = _shapes(call, env_shapes, K, E)
+    shapes_np, shp = _shapes(call, env_shapes, K, E, tables=env_tables is not None)
     car = call.f64(carrier)
     if tuple(car.shape) != (B, K, 2):
         raise C3PropError(f"C3:Error: carrier must be [{B},{K},2], got {tuple(car.shape)}")
@@ -275,6 +443,19 @@ def synthesize_signals_vjp(env_params, env_shapes, carrier, t_start: float, t_en
     else:
         genv = np.empty((B, K, E, ENV_NPAR), dtype=np.float64)
         gcar = np.empty((B, K, 2), dtype=np.float64)
+    if env_tables is not None:
+        tab, tidx, T = _tables(call, env_tables, table_index, shapes_np, B, Na)
+        knd = par = gline = None
+        if line_kinds is not None:
+            knd, par = _lines(call, line_kinds, line_params, B, K, sim_res)
+            gline = call.torch.empty((B, K, LINE_NPAR), dtype=call.torch.float64, device=call.dev) if call.device else np.empty((B, K, LINE_NPAR), dtype=np.float64)
+        gtab = call.torch.empty((B, T), dtype=call.torch.float64, device=call.dev) if call.device else np.empty((B, T), dtype=np.float64)
+        _lib.check(
+            _lib.load().c3p_synth_tab_vjp(
+                _ptr(env), _ptr(shp), _ptr(tab), _ptr(tidx), T, _ptr(car), _ptr(knd), _ptr(par), float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags, _ptr(gs), _ptr(genv), _ptr(gcar), _ptr(gline), _ptr(gtab), call.stream
+            )
+        )
+        return (genv, gcar, gline, gtab) if line_kinds is not None else (genv, gcar, gtab)
     if line_kinds is not None:
         knd, par = _lines(call, line_kinds, line_params, B, K, sim_res)
         gline = call.torch.empty((B, K, LINE_NPAR), dtype=call.torch.float64, device=call.dev) if call.device else np.empty((B, K, LINE_NPAR), dtype=np.float64)

@@ -457,6 +457,56 @@ int c3p_synth_chain_vjp(const double* env_params, const int32_t* env_shapes, con
                         int K, int E, int flags, const double* grad_signals, double* grad_env, double* grad_carrier,
                         double* grad_line, void* stream);
 
+/* Sampled and Fourier pulse envelopes: the parametrisations whose parameters are an array of coefficients
+ * (c3/libraries/envelopes.py:31-34 pwc, :37-68 pwc_shape, :104-125 pwc_symmetric, :142-168 fourier_sin, :171-191 fourier_cos).
+ * c3p_synth_tab takes the arguments of c3p_synth_chain plus a coefficient table that travels with the envelope rows:
+ *   env_shapes int32 [K,E]      C3P_ENV_* ids as before, or a C3P_ENVT_* id below for a component that reads the table
+ *   env_tab    f64 [B,T]        one flat row of T doubles per sample, holding every table component's block
+ *   tab_index  int32 [K,E,2]    {offset of the block in the row, M} per component, {-1, 0} for a component without a table
+ *   line_kind, line_params      may both be NULL: the standard drive line, exactly as c3p_synth_signals
+ * A component contributes amp * env * exp(i (xy_angle - freq_offset tau)) to the AWG-resolution I + iQ (gates.py:341-370),
+ * tau = t_awg - (t_start + delay), env = mask * (s(tau) - [C3P_ENVF_T_BEFORE] s(tau_before)) (pulse.py:98-141), with s per shape
+ * from the component's block:
+ *   C3P_ENVT_PWC            inphase[M], quadrature[M]          s_j = inphase[j] + i quadrature[j], one pair per AWG sample: M = Na
+ *   C3P_ENVT_PWC_SHAPE      t_bin_start, t_bin_end, inphase[M]  linear interpolation of inphase on the regular grid of M >= 2 knots
+ *                                                              from t_bin_start to t_bin_end (both included), 0 outside
+ *                                                              (tfp.math.interp_regular_1d_grid, fill values 0)
+ *   C3P_ENVT_PWC_SYMMETRIC  as C3P_ENVT_PWC_SHAPE              evaluated at tau > t_final / 2 ? t_final - tau : tau (the row's
+ *                                                              C3P_ENV_T_FINAL slot)
+ *   C3P_ENVT_FOURIER_SIN    amps[M], freqs[M], phases[M]       s = sum_m amps[m] sin(freqs[m] tau + phases[m])
+ *   C3P_ENVT_FOURIER_COS    amps[M], freqs[M]                  s = sum_m amps[m] cos(freqs[m] tau)
+ * The other slots of such a component's parameter row (amp, xy_angle, freq_offset, t_final, delay, flags) mean what they
+ * mean for the closed-form shapes.  Refused on host-pointer calls: a block that leaves the row, blocks that overlap, M != Na
+ * for pwc, M < 2 or t_bin_end <= t_bin_start for the interpolated shapes, C3P_ENVF_DRAG on a table shape, C3P_ENVF_T_BEFORE
+ * on pwc (the reference's offset would be the array itself).  Device-pointer calls do not synchronise and cannot look: a block
+ * that leaves the row contributes nothing, and those two flags are ignored where they are refused.  c3p_synth_signals and
+ * c3p_synth_chain keep refusing C3P_ENVT_* ids.
+ */
+#define C3P_ENVT_PWC 16
+#define C3P_ENVT_PWC_SHAPE 17
+#define C3P_ENVT_PWC_SYMMETRIC 18
+#define C3P_ENVT_FOURIER_SIN 19
+#define C3P_ENVT_FOURIER_COS 20
+#define C3P_ENVT_FIRST 16 /* table shape ids are C3P_ENVT_FIRST .. C3P_ENVT_END - 1 */
+#define C3P_ENVT_END 21
+
+int c3p_synth_tab(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
+                  const double* carrier, const int32_t* line_kind, const double* line_params, double t_start, double t_end,
+                  double awg_res, double sim_res, int B, int K, int E, int flags, double* awg_iq_out, double* signals_out,
+                  void* stream);
+
+/* Vector-Jacobian product of c3p_synth_tab: grad_env, grad_carrier and grad_line (NULL with line_kind NULL) as
+ * c3p_synth_chain_vjp -- the amp, xy_angle and freq_offset slots hold for the table shapes too -- and
+ *   grad_tab f64 [B,T]   d loss / d env_tab in the layout of env_tab: every coefficient (inphase, quadrature, amps, freqs,
+ *                        phases).  t_bin_start and t_bin_end are not differentiated: their slots, and every double that
+ *                        belongs to no block, are written as 0.
+ * Every sum runs in a fixed order without atomics: repeated calls return the same bits.
+ */
+int c3p_synth_tab_vjp(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
+                      const double* carrier, const int32_t* line_kind, const double* line_params, double t_start, double t_end,
+                      double awg_res, double sim_res, int B, int K, int E, int flags, const double* grad_signals,
+                      double* grad_env, double* grad_carrier, double* grad_line, double* grad_tab, void* stream);
+
 /* Fidelity epilogue: overlap[b] = tr(P^T U[b] P G^+), the number behind
  * unitary_infid = 1 - |overlap/L|^2 (c3/libraries/fidelities.py:154-184, tf_unitary_overlap
  * c3/utils/tf_utils.py:330-366) and average_infid = 1 - (|overlap|^2/L + 1)/(L + 1)
