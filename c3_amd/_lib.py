@@ -48,6 +48,9 @@ SIGNATURES = {
     "c3p_last_kernel_ms": (_d, []),
     "c3p_shutdown": (None, []),
     "c3p_pwc_unitary": (_i, [_vp, _i64, _vp, _i64, _vp, _d, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "c3p_pwc_record_bytes": (C.c_size_t, [_i, _i]),
+    "c3p_pwc_record_build": (_i, [_vp, _vp, _d, _i, _i, _i, _vp, _vp]),
+    "c3p_pwc_unitary_rec": (_i, [_vp, _i64, _vp, _i64, _vp, _d, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "c3p_pwc_lindblad": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _d, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "c3p_expm": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "c3p_matmul_chain": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

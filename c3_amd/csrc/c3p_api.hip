@@ -368,6 +368,8 @@ struct PwcProblem {
   double dt;
   int B, K, N, D, Dm, lindblad;
   const double* fr_phase;  // [B,Dm] or null
+  // model record of the small-D unitary tables (c3p_pwc_record_build) or null; only ever set for shared operators, so a chunk keeps it
+  const double* record;
   bool per_sample() const { return h0_bs != 0 || hk_bs != 0 || clp_bs != 0; }
   int nsamp() const { return per_sample() ? B : 1; }  // operator sets (tables) of the call
   // the problem of samples [b0, b0 + nb)
@@ -635,6 +637,7 @@ int run_pwc_smalld(DeviceWs* w, const PwcProblem& P, cplx* U_out, cplx* dUs_out,
   if (inline_tables) {
     // unitary mode: the chain kernel builds its tables itself (no dependent launch in front of it)
     a.inline_tables = 1;
+    if (!dUs_out) a.record = P.record;  // (the kernels that keep the slice propagators build inline)
     a.h0 = P.h0;
     a.h0_bstride = P.h0_bs;
     a.hks = P.hks;
@@ -1922,7 +1925,7 @@ LindTapePlan lind_tape_plan(int B, int K, int N, int D) {
 
 int pwc_common(int lindblad, const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride,
                const double* signals, const void* col_ops, int C, double dt, int B, int K, int N, int D,
-               int flags, const double* fr_phase, void* U_out, void* dUs_out, void* stream) {
+               int flags, const double* fr_phase, void* U_out, void* dUs_out, void* stream, const void* record = nullptr) {
   if (B < 0 || N < 0 || D <= 0 || K < 0) return fail("bad sizes B=%d K=%d N=%d D=%d", B, K, N, D);
   if (!U_out) return fail("U_out is NULL");
   if (B == 0) return 0;
@@ -1968,7 +1971,11 @@ int pwc_common(int lindblad, const void* h0, int64_t h0_bstride, const void* hks
   a.mode = lindblad ? C3P_MODE_LINDBLAD : C3P_MODE_UNITARY;
   a.dUs_out = (cplx*)d_dUs;
   if (lindblad && build_clp(w, d_col, C, D, B, flags, &a.clp, &a.clp_bstride, st)) return -1;
-  const PwcProblem P = {a.h0, a.h0_bstride, a.hks, a.hks_bstride, a.signals, a.clp, a.clp_bstride, dt, B, K, N, D, Dm, lindblad, a.fr_phase};
+  // a model record serves the unitary small-D table route with operators shared by the batch; every other call ignores it
+  const bool use_record = record && !lindblad && !per_slice && !(flags & (C3P_FORCE_GENERIC | C3P_HOST_PTRS)) && h0_bstride == 0 &&
+                          hks_bstride == 0 && c3p_pwc_record_bytes(D, K) != 0;
+  const PwcProblem P = {a.h0, a.h0_bstride, a.hks, a.hks_bstride, a.signals, a.clp, a.clp_bstride, dt, B, K, N, D, Dm, lindblad, a.fr_phase,
+                        use_record ? (const double*)record : nullptr};
   bool done = false;
   if (!(flags & C3P_FORCE_GENERIC) && per_slice && !lindblad && K == 0 && D <= kSmallDLimit && c3p_smalld_supported(D)) {
     // branch B (propagation.py:295-308): X_n = -i dt H_n
@@ -2213,6 +2220,38 @@ int c3p_pwc_unitary(const void* h0, int64_t h0_bstride, const void* hks, int64_t
                     const double* fr_phase, void* U_out, void* dUs_out, void* stream) {
   return pwc_common(0, h0, h0_bstride, hks, hks_bstride, signals, nullptr, 0, dt, B, K, N, D, flags,
                     fr_phase, U_out, dUs_out, stream);
+}
+
+size_t c3p_pwc_record_bytes(int D, int K) {
+  if (D < 2 || D > kSmallDLimit || !c3p_smalld_supported(D) || K < 0 || K > 8) return 0;  // the shapes run_pwc_smalld takes
+  return c3p_smalld_record_doubles(D, K) * sizeof(double);
+}
+
+int c3p_pwc_record_build(const void* h0, const void* hks, double dt, int K, int D, int flags, void* record, void* stream) {
+  if (c3p_pwc_record_bytes(D, K) == 0) return fail("c3p_pwc_record_build: no record is served for D=%d K=%d", D, K);
+  if (flags & C3P_HOST_PTRS) return fail("c3p_pwc_record_build: device pointers only");
+  if (!h0 || !record) return fail("c3p_pwc_record_build: h0 or record is NULL");
+  if (K > 0 && !hks) return fail("K > 0 but hks missing");
+  hipStream_t st = (hipStream_t)stream;
+  WsLock lk(st);
+  if (!lk.w) return fail("no HIP device");
+  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+  SmallArgs a = {};
+  a.h0 = (const cplx*)h0;
+  a.hks = (const cplx*)hks;
+  a.dt = dt;
+  a.K = K;
+  a.Dm = D;
+  g_last_kernel = C3P_KERNEL_SMALLD;
+  LAUNCH_TRY(c3p_launch_smalld_record(a, (double*)record, st));
+  return 0;
+}
+
+int c3p_pwc_unitary_rec(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride, const double* signals, double dt, int B,
+                        int K, int N, int D, int flags, const double* fr_phase, void* U_out, void* dUs_out, const void* record,
+                        void* stream) {
+  return pwc_common(0, h0, h0_bstride, hks, hks_bstride, signals, nullptr, 0, dt, B, K, N, D, flags, fr_phase, U_out, dUs_out, stream,
+                    record);
 }
 
 int c3p_pwc_lindblad(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride,

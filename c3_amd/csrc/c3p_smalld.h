@@ -40,6 +40,9 @@ struct SmallArgs {
   int seg_long_c;  // the same for samples that take the COMPLEX loop (its optimum differs: 640 against 700 per mille at D = 9); 0 = seg_long
   int* counters;   // [B], zeroed by the prep kernel of the same call
   cplx* final_out;  // [B,Dm,Dm]
+  // inline_tables with a prebuilt model record (c3p_launch_smalld_record; shared operators only): the workgroup copies the block
+  // build_tables would leave in LDS instead of forming it.  Null = build inline.
+  const double* record;  // [c3p_smalld_record_doubles(Dm, K)]
 };
 
 // Backward sweep of the control gradient (c3p_grad.hip for the method)
@@ -84,6 +87,10 @@ int c3p_smalld_mat_doubles(int Dm);
 int c3p_smalld_img_doubles(int Dm);  // per-chain LDS image buffer of the forward kernel
 size_t c3p_smalld_table_doubles(int Dm, int K);
 bool c3p_smalld_supported(int Dm);
+// the model record of the unitary table mode: the tables (c3p_smalld_table_doubles) and their column sums, as the chain kernel's
+// inline build leaves them in LDS.  The launch reads h0, hks (shared operators: the strides are not used), dt, K and Dm of `A`.
+size_t c3p_smalld_record_doubles(int Dm, int K);
+hipError_t c3p_launch_smalld_record(const SmallArgs& A, double* record, hipStream_t st);
 hipError_t c3p_launch_smalld_chain(const SmallArgs& A, hipStream_t st);
 hipError_t c3p_launch_smalld_grad(const SmallGradArgs& A, hipStream_t st);
 hipError_t c3p_launch_smalld_grad_general(const SmallGradArgs& A, hipStream_t st);  // general generators (Lindblad)

@@ -1458,7 +1458,33 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
         for (int k = 0; k < K; ++k) keep_max(k, seg_max(k, false));
       }
     };
-    if (A.inline_tables) {
+    if (A.record != nullptr) {
+      // The model record (smalld_record_kernel): the block build_tables leaves in LDS, formed once per model -- the tables with
+      // their four trailing words, then the column sums.  Every thread of the workgroup takes its share.  The first RU loads of a
+      // thread are issued together and stand directly behind the amplitude prefetch (all of them cold): nothing is waited for in
+      // between, and the amplitudes, issued first, are stored while the record is still on its way.
+      constexpr int RU = MW ? 2 : 8;
+      const int T = (1 + K) * (MAT + 4), R = T + (1 + K) * SD_CSW;
+      const int tid = MW ? (int)threadIdx.x : lane, rstep = 64 * nwv;
+      auto put = [&](int e, double v) {
+        if (e < T)
+          tab[e] = v;
+        else if (e < R)
+          csb[e - T] = v;
+      };
+      double rv[RU];
+#pragma unroll
+      for (int q = 0; q < RU; ++q) rv[q] = A.record[min(tid + q * rstep, R - 1)];
+      if constexpr (MW) fetch_amplitudes();
+#pragma unroll
+      for (int q = 0; q < RU; ++q) put(tid + q * rstep, rv[q]);
+      for (int e0 = tid + RU * rstep; e0 < R; e0 += RU * rstep) {  // (more than RU x the workgroup's threads: K > 2 or one wave)
+#pragma unroll
+        for (int q = 0; q < RU; ++q) rv[q] = A.record[min(e0 + q * rstep, R - 1)];
+#pragma unroll
+        for (int q = 0; q < RU; ++q) put(e0 + q * rstep, rv[q]);
+      }
+    } else if (A.inline_tables) {
       build_tables<D>(A, __builtin_amdgcn_readfirstlane(sample), tab, csb, lane, wv, nwv, [&]() {
         if constexpr (MW) fetch_amplitudes();
       });
@@ -1471,7 +1497,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
       __syncthreads();
       sd_colsums<D>(tab, K, csb, lane, wv, nwv);
     }
-    SD_TICK(tk8);
+    SD_TICK(tk8);  // `tables`: this wave's share of the tables and column sums is in LDS -- built here, or copied from the model record
     SD_TICK(tk9);
     __syncthreads();  // the tables and their column sums are in place
     // The flags of the K + 1 tables, read ONCE and without an early exit (the reads of the first PF_K + 1 are independent):
@@ -2439,7 +2465,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
           SD_TICK(tk4);
           if (tk6 == 0) tk6 = tk7;
           if (blockIdx.x == 0 && threadIdx.x == 0)
-            printf("sd timing (100 MHz ticks): tables %lld signals %lld prologue %lld loop %lld fold4+store %lld barrier %lld level1 %lld level2 %lld last product with store %lld total %lld\n", tk8 - tk0, tk9 - tk8, tk1 - tk0, tk2 - tk1, tk3 - tk2, tk5 - tk3, tk6 - tk5, tk7 - tk6, tk4 - tk7, tk4 - tk0);
+            printf("sd timing (100 MHz ticks): tables (%s) %lld signals %lld prologue %lld loop %lld fold4+store %lld barrier %lld level1 %lld level2 %lld last product with store %lld total %lld\n", A.record ? "record in LDS" : "built in LDS", tk8 - tk0, tk9 - tk8, tk1 - tk0, tk2 - tk1, tk3 - tk2, tk5 - tk3, tk6 - tk5, tk7 - tk6, tk4 - tk7, tk4 - tk0);
 #endif
           return;
         }
@@ -2475,7 +2501,7 @@ __global__ void __launch_bounds__((MW ? 512 : 64), 2) smalld_chain_kernel(SmallA
 #ifdef C3P_SD_TIMING
         SD_TICK(tk4);
         if (blockIdx.x == 0 && threadIdx.x == 0)
-          printf("sd timing (100 MHz ticks): tables %lld signals %lld prologue %lld loop %lld fold4+store %lld barrier %lld level1 %lld fold2 %lld store %lld total %lld\n", tk8 - tk0, tk9 - tk8, tk1 - tk0, tk2 - tk1, tk3 - tk2, tk5 - tk3, tk6 - tk5, tk7 - tk6, tk4 - tk7, tk4 - tk0);
+          printf("sd timing (100 MHz ticks): tables (%s) %lld signals %lld prologue %lld loop %lld fold4+store %lld barrier %lld level1 %lld fold2 %lld store %lld total %lld\n", A.record ? "record in LDS" : "built in LDS", tk8 - tk0, tk9 - tk8, tk1 - tk0, tk2 - tk1, tk3 - tk2, tk5 - tk3, tk6 - tk5, tk7 - tk6, tk4 - tk7, tk4 - tk0);
 #endif
         return;
       }
@@ -3800,6 +3826,31 @@ hipError_t launch_prep_t(const PrepArgs& P, int nsamp, hipStream_t st) {
   return hipGetLastError();
 }
 
+// The model record: one workgroup forms the block that the chain kernel's inline build leaves behind its table barrier -- the same
+// build_tables, table k by wave k mod 8, in this translation unit -- and copies it out of LDS as it stands: (1 + K) tables of
+// MAT + 4 doubles, then (1 + K) x SD_CSW column sums.  A chain launch that is handed the record copies it back (A.record).
+template <int D>
+__global__ void __launch_bounds__(512) smalld_record_kernel(SmallArgs A, double* record) {
+  constexpr int MAT = SD<D>::MAT;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nwv = (int)(blockDim.x >> 6);
+  const int T = (1 + A.K) * (MAT + 4), R = T + (1 + A.K) * SD_CSW;
+  double* tab = c3p_sd_lds;
+  double* csb = tab + T;
+  build_tables<D>(A, 0, tab, csb, lane, wv, nwv, []() {});
+  __syncthreads();
+  for (int e = threadIdx.x; e < R; e += blockDim.x) record[e] = tab[e];
+}
+
+template <int D>
+hipError_t launch_record_t(const SmallArgs& A, double* record, hipStream_t st) {
+  const size_t lds = (size_t)(1 + A.K) * (SD<D>::MAT + 4 + SD_CSW) * sizeof(double);
+  if (lds > 60 * 1024) return hipErrorInvalidValue;
+  C3P_LAUNCH(smalld_record_kernel<D>, dim3(1), dim3(512), lds, st, A, record);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 #define SD_DISPATCH(FN, ...)                                   \
@@ -3840,6 +3891,13 @@ int c3p_smalld_img_doubles(int Dm) {
 size_t c3p_smalld_table_doubles(int Dm, int K) { return (size_t)(1 + K) * (c3p_smalld_mat_doubles(Dm) + 4); }
 
 bool c3p_smalld_supported(int Dm) { return Dm >= 2 && Dm <= C3P_SMALLD_MAX; }
+
+size_t c3p_smalld_record_doubles(int Dm, int K) { return c3p_smalld_table_doubles(Dm, K) + (size_t)(1 + K) * SD_CSW; }
+
+hipError_t c3p_launch_smalld_record(const SmallArgs& A, double* record, hipStream_t st) {
+  const int Dm = A.Dm;
+  SD_DISPATCH(launch_record_t, A, record, st)
+}
 
 hipError_t c3p_launch_smalld_chain(const SmallArgs& A, hipStream_t st) {
   const int Dm = A.Dm;

@@ -1053,6 +1053,11 @@ class BatchPropagator:
     All tensors are torch CUDA tensors (complex128 / float64, contiguous).  `run()` issues
     exactly one C-ABI call on torch's current stream and returns the output tensor `U`
     (valid once that stream is synchronised).
+
+    Closed systems at 2 <= D <= 12 with operators shared by the batch: the generator tables of the model (h0, hks, dt) are
+    built once, here, into a model record the object owns (c3p_pwc_record_build), and `run()` hands it to the chain kernel
+    (c3p_pwc_unitary_rec), whose workgroups then copy the tables instead of rebuilding them in every launch -- same kernel,
+    same bits.  `run()` TRUSTS the record: after overwriting `self.h0` or `self.hks` in place call `rebuild_record()`.
     """
 
     def __init__(self, h0, hks, signals, dt, *, col_ops=None, fr_phase=None, want_dUs=False, force_generic=False, hermitian=None):
@@ -1088,6 +1093,23 @@ class BatchPropagator:
                 hermitian = herm(self.h0) and (self.K == 0 or herm(self.hks))
             if hermitian:
                 self.flags |= _lib.HERMITIAN_H
+        # the model record (None where the library serves none for this call: open systems, per-sample operators, want_dUs,
+        # force_generic, D outside 2 .. 12)
+        self.record = None
+        if not self.lind and self.h0_bs == 0 and self.hk_bs == 0 and not want_dUs and not force_generic:
+            nbytes = int(self.lib.c3p_pwc_record_bytes(self.D, self.K))
+            if nbytes:
+                self.record = torch.empty(nbytes // 8, dtype=f64, device=dev)
+                self.rebuild_record()
+
+    def rebuild_record(self):
+        """Build the model record again from `self.h0`, `self.hks` and `self.dt` as they are now: one small launch on torch's
+        current stream.  For callers that overwrite the operators in place; a no-op where no record is held."""
+        if self.record is None:
+            return
+        st = self.torch.cuda.current_stream(self.dev).cuda_stream
+        _lib.check(self.lib.c3p_pwc_record_build(self.h0.data_ptr(), self.hks.data_ptr() if self.K else None, self.dt, self.K, self.D, 0,
+                                                 self.record.data_ptr(), st))
 
     def run(self, out=None):
         """One C-ABI call on torch's current stream; `out` overrides the result tensor
@@ -1102,10 +1124,11 @@ class BatchPropagator:
                 None if self.dUs is None else self.dUs.data_ptr(), st,
             )
         else:
-            rc = self.lib.c3p_pwc_unitary(
+            rc = self.lib.c3p_pwc_unitary_rec(
                 self.h0.data_ptr(), self.h0_bs, self.hks.data_ptr(), self.hk_bs, self.signals.data_ptr(), self.dt,
                 self.B, self.K, self.N, self.D, self.flags, None if self.fr is None else self.fr.data_ptr(),
-                U.data_ptr(), None if self.dUs is None else self.dUs.data_ptr(), st,
+                U.data_ptr(), None if self.dUs is None else self.dUs.data_ptr(),
+                None if self.record is None else self.record.data_ptr(), st,
             )
         _lib.check(rc)
         return U

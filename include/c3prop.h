@@ -154,6 +154,24 @@ int c3p_pwc_unitary(const void* h0, int64_t h0_bstride, const void* hks, int64_t
                     const double* signals, double dt, int B, int K, int N, int D, int flags,
                     const double* fr_phase, void* U_out, void* dUs_out, void* stream);
 
+/* The same call with a prebuilt model record.  An optimiser or model-learning loop calls the propagator thousands of times with
+ * one model (h0, hks, dt) and new control amplitudes; at 2 <= D <= 12 every workgroup of the chain kernel otherwise rebuilds the
+ * generator tables of that model in each launch.  A record is that block, built once, bit for bit what the kernel builds:
+ *   c3p_pwc_record_bytes  size of the record for (D, K), or 0 where no record is served (D outside 2 .. 12, K > 8)
+ *   c3p_pwc_record_build  one launch on `stream` into `record` (device memory of the caller, c3p_pwc_record_bytes(D, K) bytes);
+ *                         h0 c128 [D,D], hks c128 [K,D,D], device pointers, operators shared by the batch
+ *   c3p_pwc_unitary_rec   c3p_pwc_unitary with `record`.  The record is used by the unitary table route with shared operators
+ *                         (both batch strides 0, no C3P_PER_SLICE_H, no C3P_FORCE_GENERIC, no C3P_HOST_PTRS, dUs_out NULL,
+ *                         prep_kernel option off); a NULL record or any other call takes the route of c3p_pwc_unitary exactly.
+ * The call trusts the record: it must have been built from the h0, hks, dt and K it is passed with (rebuild it after changing
+ * them in place).  The library keeps no table of records and keys nothing by device address; the run allocates nothing and
+ * launches nothing but what c3p_pwc_unitary launches.  Reference analogue: none. */
+size_t c3p_pwc_record_bytes(int D, int K);
+int c3p_pwc_record_build(const void* h0, const void* hks, double dt, int K, int D, int flags, void* record, void* stream);
+int c3p_pwc_unitary_rec(const void* h0, int64_t h0_bstride, const void* hks, int64_t hks_bstride,
+                        const double* signals, double dt, int B, int K, int N, int D, int flags,
+                        const double* fr_phase, void* U_out, void* dUs_out, const void* record, void* stream);
+
 /* Lindblad superoperator propagator (propagation.py:551-585):
  *   L[n] = -i (H[n] (x) I - I (x) H[n]^T) + sum_c [ (C(x)I)(I(x)C^T)^+ - 1/2 (C(x)I)^+(C(x)I) - 1/2 (I(x)C^T)(I(x)C^T)^+ ]
  *   U[b] = diag(exp(i fr_phase[b])) * prod_n exp(L[n] dt),   matrices are [D*D, D*D]
