@@ -3482,57 +3482,6 @@ int c3p_seq_state_vjp(const void* G, int64_t G_bstride, int n_gates, int M, int 
                         psi0_bar, out, stream);
 }
 
-int c3p_synth_signals(const double* env_params, const int32_t* env_shapes, const double* carrier,
-                      double t_start, double t_end, double awg_res, double sim_res, int B, int K,
-                      int E, int flags, double* awg_iq_out, double* signals_out, void* stream) {
-  if (B < 0 || K <= 0 || E <= 0) return fail("bad sizes B=%d K=%d E=%d", B, K, E);
-  if (!(awg_res > 0.0) || !(sim_res > 0.0)) return fail("resolutions must be positive");
-  const double span = t_end > t_start ? t_end - t_start : t_start - t_end;
-  const int N = (int)(span * sim_res), Na = (int)(span * awg_res);  // devices.py:72-84
-  if (N <= 0 || Na <= 1) return fail("empty time grid: N=%d Na=%d", N, Na);
-  if (B == 0) return 0;
-  if (!env_params || !env_shapes || !carrier || !signals_out) return fail("NULL pointer argument");
-  hipStream_t st = (hipStream_t)stream;
-  WsLock lk(st);
-  DeviceWs* w = lk.w;
-  if (!w) return fail("no HIP device");
-  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-  Stage sg{w, st};
-  const void *d_env = env_params, *d_shape = env_shapes, *d_car = carrier;
-  void *d_iq = awg_iq_out, *d_sig = signals_out;
-  const size_t iq_bytes = (size_t)B * K * 2 * Na * sizeof(double);
-  if (flags & C3P_HOST_PTRS) {
-    for (int a = 0; a < K * E; ++a)
-      if (env_shapes[a] >= C3P_ENV_NSHAPES) return fail("env_shapes[%d]=%d is not a C3P_ENV_* id", a, env_shapes[a]);
-    if (sg.in(env_params, (size_t)B * K * E * C3P_ENV_NPAR * sizeof(double), &d_env)) return -1;
-    if (sg.in(env_shapes, (size_t)K * E * sizeof(int32_t), &d_shape)) return -1;
-    if (sg.in(carrier, (size_t)B * K * 2 * sizeof(double), &d_car)) return -1;
-    if (sg.out(signals_out, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
-    if (awg_iq_out && sg.out(awg_iq_out, iq_bytes, &d_iq)) return -1;
-  }
-  if (!d_iq) {
-    if (ws_get(w, SL_SCRATCH, iq_bytes, &d_iq)) return -1;
-  }
-  SynthArgs A;
-  A.env = (const double*)d_env;
-  A.shape = (const int*)d_shape;
-  A.carrier = (const double*)d_car;
-  A.t_start = t_start;
-  A.t_end = t_end;
-  A.awg_res = awg_res;
-  A.sim_res = sim_res;
-  A.B = B;
-  A.K = K;
-  A.E = E;
-  A.Na = Na;
-  A.N = N;
-  A.iq = (double*)d_iq;
-  A.signals = (double*)d_sig;
-  LAUNCH_TRY(c3p_launch_synth(A, st));
-  if (flags & C3P_HOST_PTRS) return sg.finish();
-  return 0;
-}
-
 // fused goal of c3p_pwc_unitary_goal_vjp (device pointers after staging)
 struct GoalSpec {
   const int32_t* rows;
@@ -3752,62 +3701,8 @@ int c3p_pwc_unitary_goal_vjp(const void* h0, int64_t h0_bstride, const void* hks
                               nullptr, stream, &g);
 }
 
-int c3p_synth_signals_vjp(const double* env_params, const int32_t* env_shapes, const double* carrier,
-                          double t_start, double t_end, double awg_res, double sim_res, int B, int K,
-                          int E, int flags, const double* grad_signals, double* grad_env, double* grad_carrier,
-                          void* stream) {
-  if (B < 0 || K <= 0 || E <= 0) return fail("bad sizes B=%d K=%d E=%d", B, K, E);
-  if (!(awg_res > 0.0) || !(sim_res > 0.0)) return fail("resolutions must be positive");
-  const double span = t_end > t_start ? t_end - t_start : t_start - t_end;
-  const int N = (int)(span * sim_res), Na = (int)(span * awg_res);
-  if (N <= 0 || Na <= 1) return fail("empty time grid: N=%d Na=%d", N, Na);
-  if (B == 0) return 0;
-  if (!env_params || !env_shapes || !carrier || !grad_signals || !grad_env || !grad_carrier)
-    return fail("NULL pointer argument");
-  hipStream_t st = (hipStream_t)stream;
-  WsLock lk(st);
-  DeviceWs* w = lk.w;
-  if (!w) return fail("no HIP device");
-  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-  Stage sg{w, st};
-  const void *d_env = env_params, *d_shape = env_shapes, *d_car = carrier, *d_gs = grad_signals;
-  void *d_ge = grad_env, *d_gc = grad_carrier;
-  if (flags & C3P_HOST_PTRS) {
-    for (int a = 0; a < K * E; ++a)
-      if (env_shapes[a] >= C3P_ENV_NSHAPES) return fail("env_shapes[%d]=%d is not a C3P_ENV_* id", a, env_shapes[a]);
-    if (sg.in(env_params, (size_t)B * K * E * C3P_ENV_NPAR * sizeof(double), &d_env)) return -1;
-    if (sg.in(env_shapes, (size_t)K * E * sizeof(int32_t), &d_shape)) return -1;
-    if (sg.in(carrier, (size_t)B * K * 2 * sizeof(double), &d_car)) return -1;
-    if (sg.in(grad_signals, (size_t)B * K * N * sizeof(double), &d_gs)) return -1;
-    if (sg.out(grad_env, (size_t)B * K * E * C3P_ENV_NPAR * sizeof(double), &d_ge)) return -1;
-    if (sg.out(grad_carrier, (size_t)B * K * 2 * sizeof(double), &d_gc)) return -1;
-  }
-  // scratch: iq | giq | gcar_part, each B*K*2*Na doubles
-  const size_t part = (size_t)B * K * 2 * Na;
-  void* v;
-  if (ws_get(w, SL_SCRATCH, 3 * part * sizeof(double), &v)) return -1;
-  SynthArgs A;
-  A.env = (const double*)d_env;
-  A.shape = (const int*)d_shape;
-  A.carrier = (const double*)d_car;
-  A.t_start = t_start;
-  A.t_end = t_end;
-  A.awg_res = awg_res;
-  A.sim_res = sim_res;
-  A.B = B;
-  A.K = K;
-  A.E = E;
-  A.Na = Na;
-  A.N = N;
-  A.iq = (double*)v;
-  A.signals = nullptr;
-  LAUNCH_TRY(c3p_launch_synth_vjp(A, (const double*)d_gs, A.iq + part, A.iq + 2 * part, (double*)d_ge, (double*)d_gc, st));
-  if (flags & C3P_HOST_PTRS) return sg.finish();
-  return 0;
-}
-
-
-// host-pointer checks shared by c3p_synth_chain and its vjp
+// ---- signal synthesis: one call record (SynthCall) and one function that runs it (synth_run) behind the six entries ----------
+// host-pointer checks of a call with a line chain
 static int chain_check_host(const int32_t* line_kind, const double* line_params, int B, int K, double sim_res) {
   for (int k = 0; k < K; ++k)
     if (line_kind[k] < 0 || line_kind[k] >= C3P_LINE_NKINDS) return fail("line_kind[%d]=%d is not a C3P_LINE_KIND_* id", k, line_kind[k]);
@@ -3823,137 +3718,6 @@ static int chain_check_host(const int32_t* line_kind, const double* line_params,
   return 0;
 }
 
-int c3p_synth_chain(const double* env_params, const int32_t* env_shapes, const double* carrier, const int32_t* line_kind,
-                    const double* line_params, double t_start, double t_end, double awg_res, double sim_res, int B, int K,
-                    int E, int flags, double* awg_iq_out, double* signals_out, void* stream) {
-  if (B < 0 || K <= 0 || E <= 0) return fail("bad sizes B=%d K=%d E=%d", B, K, E);
-  if (!(awg_res > 0.0) || !(sim_res > 0.0)) return fail("resolutions must be positive");
-  const double span = t_end > t_start ? t_end - t_start : t_start - t_end;
-  const int N = (int)(span * sim_res), Na = (int)(span * awg_res);  // devices.py:72-84
-  if (N <= 0 || Na <= 1) return fail("empty time grid: N=%d Na=%d", N, Na);
-  if (B == 0) return 0;
-  if (!env_params || !env_shapes || !carrier || !line_kind || !line_params || !signals_out) return fail("NULL pointer argument");
-  if ((flags & C3P_HOST_PTRS) && chain_check_host(line_kind, line_params, B, K, sim_res)) return -1;  // before any device work
-  hipStream_t st = (hipStream_t)stream;
-  WsLock lk(st);
-  DeviceWs* w = lk.w;
-  if (!w) return fail("no HIP device");
-  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-  Stage sg{w, st};
-  const void *d_env = env_params, *d_shape = env_shapes, *d_car = carrier, *d_kind = line_kind, *d_line = line_params;
-  void *d_iq = awg_iq_out, *d_sig = signals_out;
-  const size_t iq_elems = (size_t)B * K * 2 * Na;
-  if (flags & C3P_HOST_PTRS) {
-    for (int a = 0; a < K * E; ++a)
-      if (env_shapes[a] >= C3P_ENV_NSHAPES) return fail("env_shapes[%d]=%d is not a C3P_ENV_* id", a, env_shapes[a]);
-    if (sg.in(env_params, (size_t)B * K * E * C3P_ENV_NPAR * sizeof(double), &d_env)) return -1;
-    if (sg.in(env_shapes, (size_t)K * E * sizeof(int32_t), &d_shape)) return -1;
-    if (sg.in(carrier, (size_t)B * K * 2 * sizeof(double), &d_car)) return -1;
-    if (sg.in(line_kind, (size_t)K * sizeof(int32_t), &d_kind)) return -1;
-    if (sg.in(line_params, (size_t)B * K * C3P_LINE_NPAR * sizeof(double), &d_line)) return -1;
-    if (sg.out(signals_out, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
-    if (awg_iq_out && sg.out(awg_iq_out, iq_elems * sizeof(double), &d_iq)) return -1;
-  }
-  // scratch: taps [B,K,tap_stride] | iq (unless the caller takes it)
-  const size_t tap_stride = N > 1 ? (size_t)N - 1 : 1, tap_elems = (size_t)B * K * tap_stride;
-  void* v;
-  if (ws_get(w, SL_SCRATCH, (tap_elems + (d_iq ? 0 : iq_elems)) * sizeof(double), &v)) return -1;
-  SynthChainArgs C;
-  SynthArgs& A = C.S;
-  A.env = (const double*)d_env;
-  A.shape = (const int*)d_shape;
-  A.carrier = (const double*)d_car;
-  A.t_start = t_start;
-  A.t_end = t_end;
-  A.awg_res = awg_res;
-  A.sim_res = sim_res;
-  A.B = B;
-  A.K = K;
-  A.E = E;
-  A.Na = Na;
-  A.N = N;
-  A.iq = d_iq ? (double*)d_iq : (double*)v + tap_elems;
-  A.signals = (double*)d_sig;
-  C.kind = (const int*)d_kind;
-  C.line = (const double*)d_line;
-  C.taps = (double*)v;
-  C.tap_stride = (long)tap_stride;
-  LAUNCH_TRY(c3p_launch_chain(C, st));
-  if (flags & C3P_HOST_PTRS) return sg.finish();
-  return 0;
-}
-
-int c3p_synth_chain_vjp(const double* env_params, const int32_t* env_shapes, const double* carrier, const int32_t* line_kind,
-                        const double* line_params, double t_start, double t_end, double awg_res, double sim_res, int B,
-                        int K, int E, int flags, const double* grad_signals, double* grad_env, double* grad_carrier,
-                        double* grad_line, void* stream) {
-  if (B < 0 || K <= 0 || E <= 0) return fail("bad sizes B=%d K=%d E=%d", B, K, E);
-  if (!(awg_res > 0.0) || !(sim_res > 0.0)) return fail("resolutions must be positive");
-  const double span = t_end > t_start ? t_end - t_start : t_start - t_end;
-  const int N = (int)(span * sim_res), Na = (int)(span * awg_res);
-  if (N <= 0 || Na <= 1) return fail("empty time grid: N=%d Na=%d", N, Na);
-  if (B == 0) return 0;
-  if (!env_params || !env_shapes || !carrier || !line_kind || !line_params || !grad_signals || !grad_env || !grad_carrier || !grad_line)
-    return fail("NULL pointer argument");
-  if ((flags & C3P_HOST_PTRS) && chain_check_host(line_kind, line_params, B, K, sim_res)) return -1;  // before any device work
-  hipStream_t st = (hipStream_t)stream;
-  WsLock lk(st);
-  DeviceWs* w = lk.w;
-  if (!w) return fail("no HIP device");
-  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-  Stage sg{w, st};
-  const void *d_env = env_params, *d_shape = env_shapes, *d_car = carrier, *d_kind = line_kind, *d_line = line_params, *d_gs = grad_signals;
-  void *d_ge = grad_env, *d_gc = grad_carrier, *d_gl = grad_line;
-  if (flags & C3P_HOST_PTRS) {
-    for (int a = 0; a < K * E; ++a)
-      if (env_shapes[a] >= C3P_ENV_NSHAPES) return fail("env_shapes[%d]=%d is not a C3P_ENV_* id", a, env_shapes[a]);
-    if (sg.in(env_params, (size_t)B * K * E * C3P_ENV_NPAR * sizeof(double), &d_env)) return -1;
-    if (sg.in(env_shapes, (size_t)K * E * sizeof(int32_t), &d_shape)) return -1;
-    if (sg.in(carrier, (size_t)B * K * 2 * sizeof(double), &d_car)) return -1;
-    if (sg.in(line_kind, (size_t)K * sizeof(int32_t), &d_kind)) return -1;
-    if (sg.in(line_params, (size_t)B * K * C3P_LINE_NPAR * sizeof(double), &d_line)) return -1;
-    if (sg.in(grad_signals, (size_t)B * K * N * sizeof(double), &d_gs)) return -1;
-    if (sg.out(grad_env, (size_t)B * K * E * C3P_ENV_NPAR * sizeof(double), &d_ge)) return -1;
-    if (sg.out(grad_carrier, (size_t)B * K * 2 * sizeof(double), &d_gc)) return -1;
-    if (sg.out(grad_line, (size_t)B * K * C3P_LINE_NPAR * sizeof(double), &d_gl)) return -1;
-  }
-  // scratch: taps | iq | giq | gcar_part (B*K*2*Na each) | gcs [B,K,2,N] | part [B,K,tiles,stride]
-  const size_t lines = (size_t)B * K, tap_stride = N > 1 ? (size_t)N - 1 : 1, tap_elems = lines * tap_stride;
-  const size_t awg = lines * 2 * Na, gcs_elems = lines * 2 * N;
-  const size_t part_elems = lines * c3p_chain_tiles(N) * c3p_chain_part_stride();
-  void* v;
-  if (ws_get(w, SL_SCRATCH, (tap_elems + 3 * awg + gcs_elems + part_elems) * sizeof(double), &v)) return -1;
-  double* p = (double*)v;
-  SynthChainArgs C;
-  SynthArgs& A = C.S;
-  A.env = (const double*)d_env;
-  A.shape = (const int*)d_shape;
-  A.carrier = (const double*)d_car;
-  A.t_start = t_start;
-  A.t_end = t_end;
-  A.awg_res = awg_res;
-  A.sim_res = sim_res;
-  A.B = B;
-  A.K = K;
-  A.E = E;
-  A.Na = Na;
-  A.N = N;
-  C.taps = p;
-  C.tap_stride = (long)tap_stride;
-  A.iq = p + tap_elems;
-  A.signals = nullptr;
-  C.kind = (const int*)d_kind;
-  C.line = (const double*)d_line;
-  double* giq = A.iq + awg;
-  double* gcar_part = giq + awg;
-  double* gcs = gcar_part + awg;
-  double* part = gcs + gcs_elems;
-  LAUNCH_TRY(c3p_launch_chain_vjp(C, (const double*)d_gs, gcs, part, giq, gcar_part, (double*)d_ge, (double*)d_gc, (double*)d_gl, st));
-  if (flags & C3P_HOST_PTRS) return sg.finish();
-  return 0;
-}
-
-// ---- c3p_synth_tab / c3p_synth_tab_vjp: the chain entries with a coefficient table (C3P_ENVT_* shapes) ----------------------
 static int tab_block_len_host(int shape, int M) {
   switch (shape) {
     case C3P_ENVT_PWC:
@@ -3967,8 +3731,8 @@ static int tab_block_len_host(int shape, int M) {
   }
 }
 
-// host-pointer checks shared by c3p_synth_tab and its vjp: shape ids, blocks inside the row and apart from each other, the
-// per-shape sizes, the flags a table shape does not take
+// host-pointer checks of an entry that takes a coefficient table: shape ids, blocks inside the row and apart from each other,
+// the per-shape sizes, the flags a table shape does not take
 static int tab_check_host(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
                           int B, int K, int E, int Na) {
   std::vector<std::pair<long, long>> blocks;  // [begin, end)
@@ -4011,73 +3775,113 @@ static int tab_check_host(const double* env_params, const int32_t* env_shapes, c
   return 0;
 }
 
-// One call of either entry; grad_signals == NULL: the forward call.
-static int synth_tab_common(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
-                            const double* carrier, const int32_t* line_kind, const double* line_params, double t_start, double t_end,
-                            double awg_res, double sim_res, int B, int K, int E, int flags, double* awg_iq_out, double* signals_out,
-                            const double* grad_signals, double* grad_env, double* grad_carrier, double* grad_line, double* grad_tab,
-                            void* stream) {
-  const bool vjp = grad_signals != nullptr, chain = line_kind != nullptr;
+// One synthesis call, as its entry states it.  What the entry takes is a property of the entry, not of the arguments: a
+// table entry runs the table-aware AWG kernels at T = 0 too, a chain entry refuses a call without lines.
+struct SynthCall {
+  const double* env_params;   // [B,K,E,C3P_ENV_NPAR]
+  const int32_t* env_shapes;  // [K,E]
+  const double* carrier;      // [B,K,2]
+  struct {
+    bool has;  // c3p_synth_tab(_vjp): the C3P_ENVT_* ids are taken
+    const double* env_tab;  // [B,T]
+    const int32_t* tab_index;  // [K,E,2]
+    int T;
+  } table;
+  struct {
+    bool required;  // c3p_synth_chain(_vjp); otherwise the two go together, both NULL: the standard drive line
+    const int32_t* line_kind;  // [K]
+    const double* line_params;  // [B,K,C3P_LINE_NPAR]
+  } lines;
+  double t_start, t_end, awg_res, sim_res;
+  int B, K, E, flags;
+  struct {
+    double *awg_iq_out, *signals_out;  // [B,K,2,Na] (optional), [B,K,N]
+  } fwd;
+  struct {
+    bool on;
+    const double* grad_signals;  // [B,K,N]
+    double *grad_env, *grad_carrier, *grad_line, *grad_tab;  // grad_line with lines, grad_tab with T > 0
+  } vjp;
+  void* stream;
+};
+
+static int synth_run(const SynthCall& c) {
+  const int B = c.B, K = c.K, E = c.E, T = c.table.T, flags = c.flags;
+  const bool vjp = c.vjp.on;
   if (B < 0 || K <= 0 || E <= 0 || T < 0) return fail("bad sizes B=%d K=%d E=%d T=%d", B, K, E, T);
-  if (!(awg_res > 0.0) || !(sim_res > 0.0)) return fail("resolutions must be positive");
-  const double span = t_end > t_start ? t_end - t_start : t_start - t_end;
-  const int N = (int)(span * sim_res), Na = (int)(span * awg_res);  // devices.py:72-84
+  if (!(c.awg_res > 0.0) || !(c.sim_res > 0.0)) return fail("resolutions must be positive");
+  const double span = c.t_end > c.t_start ? c.t_end - c.t_start : c.t_start - c.t_end;
+  const int N = (int)(span * c.sim_res), Na = (int)(span * c.awg_res);  // devices.py:72-84
   if (N <= 0 || Na <= 1) return fail("empty time grid: N=%d Na=%d", N, Na);
   if (B == 0) return 0;
-  if (!env_params || !env_shapes || !carrier || !tab_index || (T > 0 && !env_tab)) return fail("NULL pointer argument");
-  if ((line_kind == nullptr) != (line_params == nullptr)) return fail("line_kind and line_params go together (both NULL: the standard drive line)");
-  if (!vjp && !signals_out) return fail("NULL pointer argument");
-  if (vjp && (!grad_env || !grad_carrier || (chain && !grad_line) || (T > 0 && !grad_tab))) return fail("NULL pointer argument");
-  if (flags & C3P_HOST_PTRS) {  // before any device work
-    if (chain && chain_check_host(line_kind, line_params, B, K, sim_res)) return -1;
-    if (tab_check_host(env_params, env_shapes, env_tab, tab_index, T, B, K, E, Na)) return -1;
+  if (!c.env_params || !c.env_shapes || !c.carrier) return fail("NULL pointer argument");
+  if (c.table.has && (!c.table.tab_index || (T > 0 && !c.table.env_tab))) return fail("NULL pointer argument");
+  if (c.lines.required && (!c.lines.line_kind || !c.lines.line_params)) return fail("NULL pointer argument");
+  if ((c.lines.line_kind == nullptr) != (c.lines.line_params == nullptr))
+    return fail("line_kind and line_params go together (both NULL: the standard drive line)");
+  const bool chain = c.lines.line_kind != nullptr;
+  if (!vjp && !c.fwd.signals_out) return fail("NULL pointer argument");
+  if (vjp && (!c.vjp.grad_signals || !c.vjp.grad_env || !c.vjp.grad_carrier || (chain && !c.vjp.grad_line) || (T > 0 && !c.vjp.grad_tab)))
+    return fail("NULL pointer argument");
+  if (flags & C3P_HOST_PTRS) {  // every look at host data comes before the workspace lock and any device work
+    if (chain && chain_check_host(c.lines.line_kind, c.lines.line_params, B, K, c.sim_res)) return -1;
+    if (c.table.has) {
+      if (tab_check_host(c.env_params, c.env_shapes, c.table.env_tab, c.table.tab_index, T, B, K, E, Na)) return -1;
+    } else {
+      for (int a = 0; a < K * E; ++a)
+        if (c.env_shapes[a] >= C3P_ENV_NSHAPES) return fail("env_shapes[%d]=%d is not a C3P_ENV_* id", a, c.env_shapes[a]);
+    }
   }
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)c.stream;
   WsLock lk(st);
   DeviceWs* w = lk.w;
   if (!w) return fail("no HIP device");
   if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
   Stage sg{w, st};
-  const void *d_env = env_params, *d_shape = env_shapes, *d_tab = env_tab, *d_tidx = tab_index, *d_car = carrier, *d_kind = line_kind,
-             *d_line = line_params, *d_gs = grad_signals;
-  void *d_iq = awg_iq_out, *d_sig = signals_out, *d_ge = grad_env, *d_gc = grad_carrier, *d_gl = grad_line, *d_gt = grad_tab;
+  const void *d_env = c.env_params, *d_shape = c.env_shapes, *d_tab = c.table.env_tab, *d_tidx = c.table.tab_index, *d_car = c.carrier,
+             *d_kind = c.lines.line_kind, *d_line = c.lines.line_params, *d_gs = c.vjp.grad_signals;
+  void *d_iq = c.fwd.awg_iq_out, *d_sig = c.fwd.signals_out, *d_ge = c.vjp.grad_env, *d_gc = c.vjp.grad_carrier, *d_gl = c.vjp.grad_line, *d_gt = c.vjp.grad_tab;
   const size_t lines = (size_t)B * K, awg = lines * 2 * Na;
-  if (flags & C3P_HOST_PTRS) {
-    if (sg.in(env_params, lines * E * C3P_ENV_NPAR * sizeof(double), &d_env)) return -1;
-    if (sg.in(env_shapes, (size_t)K * E * sizeof(int32_t), &d_shape)) return -1;
-    if (sg.in(env_tab, (size_t)B * T * sizeof(double), &d_tab)) return -1;
-    if (sg.in(tab_index, (size_t)K * E * 2 * sizeof(int32_t), &d_tidx)) return -1;
-    if (sg.in(carrier, lines * 2 * sizeof(double), &d_car)) return -1;
-    if (chain && sg.in(line_kind, (size_t)K * sizeof(int32_t), &d_kind)) return -1;
-    if (chain && sg.in(line_params, lines * C3P_LINE_NPAR * sizeof(double), &d_line)) return -1;
+  if (flags & C3P_HOST_PTRS) {  // a NULL or empty buffer takes no staging slot: each entry keeps the slots it always had
+    if (sg.in(c.env_params, lines * E * C3P_ENV_NPAR * sizeof(double), &d_env)) return -1;
+    if (sg.in(c.env_shapes, (size_t)K * E * sizeof(int32_t), &d_shape)) return -1;
+    if (sg.in(c.table.env_tab, (size_t)B * T * sizeof(double), &d_tab)) return -1;
+    if (sg.in(c.table.tab_index, (size_t)K * E * 2 * sizeof(int32_t), &d_tidx)) return -1;
+    if (sg.in(c.carrier, lines * 2 * sizeof(double), &d_car)) return -1;
+    if (sg.in(c.lines.line_kind, (size_t)K * sizeof(int32_t), &d_kind)) return -1;
+    if (sg.in(c.lines.line_params, lines * C3P_LINE_NPAR * sizeof(double), &d_line)) return -1;
     if (vjp) {
-      if (sg.in(grad_signals, lines * N * sizeof(double), &d_gs)) return -1;
-      if (sg.out(grad_env, lines * E * C3P_ENV_NPAR * sizeof(double), &d_ge)) return -1;
-      if (sg.out(grad_carrier, lines * 2 * sizeof(double), &d_gc)) return -1;
-      if (chain && sg.out(grad_line, lines * C3P_LINE_NPAR * sizeof(double), &d_gl)) return -1;
-      if (sg.out(grad_tab, (size_t)B * T * sizeof(double), &d_gt)) return -1;
+      if (sg.in(c.vjp.grad_signals, lines * N * sizeof(double), &d_gs)) return -1;
+      if (sg.out(c.vjp.grad_env, lines * E * C3P_ENV_NPAR * sizeof(double), &d_ge)) return -1;
+      if (sg.out(c.vjp.grad_carrier, lines * 2 * sizeof(double), &d_gc)) return -1;
+      if (chain && sg.out(c.vjp.grad_line, lines * C3P_LINE_NPAR * sizeof(double), &d_gl)) return -1;
+      if (sg.out(c.vjp.grad_tab, (size_t)B * T * sizeof(double), &d_gt)) return -1;
     } else {
-      if (sg.out(signals_out, lines * N * sizeof(double), &d_sig)) return -1;
-      if (awg_iq_out && sg.out(awg_iq_out, awg * sizeof(double), &d_iq)) return -1;
+      if (sg.out(c.fwd.signals_out, lines * N * sizeof(double), &d_sig)) return -1;
+      if (sg.out(c.fwd.awg_iq_out, awg * sizeof(double), &d_iq)) return -1;
     }
   }
-  // scratch: [taps] | iq (unless the caller takes it) | vjp: giq | gcar_part (B*K*2*Na each) | [gcs [B,K,2,N] | part]
+  // scratch: [taps [B,K,tap_stride]] | iq (unless the caller takes it) | vjp: giq | gcar_part (B*K*2*Na each) |
+  //          [gcs [B,K,2,N] | part [B,K,tiles,stride]]; the bracketed parts with a line chain only
   const size_t tap_stride = N > 1 ? (size_t)N - 1 : 1, tap_elems = chain ? lines * tap_stride : 0;
+  const size_t iq_elems = (!vjp && d_iq) ? 0 : awg;
   const size_t gcs_elems = chain && vjp ? lines * 2 * N : 0;
   const size_t part_elems = chain && vjp ? lines * c3p_chain_tiles(N) * c3p_chain_part_stride() : 0;
-  const size_t iq_elems = (!vjp && d_iq) ? 0 : awg;
-  void* v;
-  if (ws_get(w, SL_SCRATCH, (tap_elems + iq_elems + (vjp ? 2 * awg : 0) + gcs_elems + part_elems) * sizeof(double), &v)) return -1;
+  const size_t scratch = tap_elems + iq_elems + (vjp ? 2 * awg : 0) + gcs_elems + part_elems;
+  // A drive call into the caller's I/Q needs no scratch and asks for none: ws_get rounds an empty request up to 16 bytes,
+  // which on a fresh device allocates the slot and bumps c3p_workspace_generation.  The table entries have always asked.
+  void* v = nullptr;
+  if ((scratch || c.table.has) && ws_get(w, SL_SCRATCH, scratch * sizeof(double), &v)) return -1;
   double* p = (double*)v;
   SynthChainArgs C;
   SynthArgs& A = C.S;
   A.env = (const double*)d_env;
   A.shape = (const int*)d_shape;
   A.carrier = (const double*)d_car;
-  A.t_start = t_start;
-  A.t_end = t_end;
-  A.awg_res = awg_res;
-  A.sim_res = sim_res;
+  A.t_start = c.t_start;
+  A.t_end = c.t_end;
+  A.awg_res = c.awg_res;
+  A.sim_res = c.sim_res;
   A.B = B;
   A.K = K;
   A.E = E;
@@ -4087,38 +3891,67 @@ static int synth_tab_common(const double* env_params, const int32_t* env_shapes,
   A.signals = (double*)d_sig;
   C.kind = (const int*)d_kind;
   C.line = (const double*)d_line;
-  C.taps = p;
+  C.taps = chain ? p : nullptr;
   C.tap_stride = (long)tap_stride;
-  SynthTabArgs X;
-  X.tab = (const double*)d_tab;
-  X.tidx = (const int*)d_tidx;
-  X.T = T;
+  const SynthTabArgs X = {(const double*)d_tab, (const int*)d_tidx, T};
+  const SynthTabArgs* Xp = c.table.has ? &X : nullptr;
   if (!vjp) {
-    if (chain)
-      LAUNCH_TRY(c3p_launch_chain_tab(C, X, st));
-    else
-      LAUNCH_TRY(c3p_launch_synth_tab(A, X, st));
+    LAUNCH_TRY(c3p_launch_synth(C, Xp, st));
   } else {
-    double* giq = A.iq + awg;
-    double* gcar_part = giq + awg;
-    double* gcs = gcar_part + awg;
-    double* part = gcs + gcs_elems;
-    if (chain)
-      LAUNCH_TRY(c3p_launch_chain_tab_vjp(C, X, (const double*)d_gs, gcs, part, giq, gcar_part, (double*)d_ge, (double*)d_gc, (double*)d_gl,
-                                          (double*)d_gt, st));
-    else
-      LAUNCH_TRY(c3p_launch_synth_tab_vjp(A, X, (const double*)d_gs, giq, gcar_part, (double*)d_ge, (double*)d_gc, (double*)d_gt, st));
+    SynthVjpBufs V = {};
+    V.giq = A.iq + awg;
+    V.gcar_part = V.giq + awg;
+    if (chain) {
+      V.gcs = V.gcar_part + awg;
+      V.part = V.gcs + gcs_elems;
+    }
+    V.genv = (double*)d_ge;
+    V.gcar = (double*)d_gc;
+    V.gline = (double*)d_gl;
+    V.gtab = (double*)d_gt;
+    LAUNCH_TRY(c3p_launch_synth_vjp(C, Xp, (const double*)d_gs, V, st));
   }
   if (flags & C3P_HOST_PTRS) return sg.finish();
   return 0;
+}
+
+// The six entries: {rows}, {table}, {lines}, grid, sizes, {forward outputs}, {vjp input and outputs}, stream.
+int c3p_synth_signals(const double* env_params, const int32_t* env_shapes, const double* carrier,
+                      double t_start, double t_end, double awg_res, double sim_res, int B, int K,
+                      int E, int flags, double* awg_iq_out, double* signals_out, void* stream) {
+  return synth_run({env_params, env_shapes, carrier, {}, {}, t_start, t_end, awg_res, sim_res, B, K, E, flags,
+                    {awg_iq_out, signals_out}, {}, stream});
+}
+
+int c3p_synth_signals_vjp(const double* env_params, const int32_t* env_shapes, const double* carrier,
+                          double t_start, double t_end, double awg_res, double sim_res, int B, int K,
+                          int E, int flags, const double* grad_signals, double* grad_env, double* grad_carrier,
+                          void* stream) {
+  return synth_run({env_params, env_shapes, carrier, {}, {}, t_start, t_end, awg_res, sim_res, B, K, E, flags,
+                    {}, {true, grad_signals, grad_env, grad_carrier, nullptr, nullptr}, stream});
+}
+
+int c3p_synth_chain(const double* env_params, const int32_t* env_shapes, const double* carrier, const int32_t* line_kind,
+                    const double* line_params, double t_start, double t_end, double awg_res, double sim_res, int B, int K,
+                    int E, int flags, double* awg_iq_out, double* signals_out, void* stream) {
+  return synth_run({env_params, env_shapes, carrier, {}, {true, line_kind, line_params}, t_start, t_end, awg_res, sim_res, B, K, E, flags,
+                    {awg_iq_out, signals_out}, {}, stream});
+}
+
+int c3p_synth_chain_vjp(const double* env_params, const int32_t* env_shapes, const double* carrier, const int32_t* line_kind,
+                        const double* line_params, double t_start, double t_end, double awg_res, double sim_res, int B,
+                        int K, int E, int flags, const double* grad_signals, double* grad_env, double* grad_carrier,
+                        double* grad_line, void* stream) {
+  return synth_run({env_params, env_shapes, carrier, {}, {true, line_kind, line_params}, t_start, t_end, awg_res, sim_res, B, K, E, flags,
+                    {}, {true, grad_signals, grad_env, grad_carrier, grad_line, nullptr}, stream});
 }
 
 int c3p_synth_tab(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
                   const double* carrier, const int32_t* line_kind, const double* line_params, double t_start, double t_end,
                   double awg_res, double sim_res, int B, int K, int E, int flags, double* awg_iq_out, double* signals_out,
                   void* stream) {
-  return synth_tab_common(env_params, env_shapes, env_tab, tab_index, T, carrier, line_kind, line_params, t_start, t_end, awg_res, sim_res,
-                          B, K, E, flags, awg_iq_out, signals_out, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  return synth_run({env_params, env_shapes, carrier, {true, env_tab, tab_index, T}, {false, line_kind, line_params}, t_start, t_end,
+                    awg_res, sim_res, B, K, E, flags, {awg_iq_out, signals_out}, {}, stream});
 }
 
 int c3p_synth_tab_vjp(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
@@ -4126,8 +3959,8 @@ int c3p_synth_tab_vjp(const double* env_params, const int32_t* env_shapes, const
                       double awg_res, double sim_res, int B, int K, int E, int flags, const double* grad_signals,
                       double* grad_env, double* grad_carrier, double* grad_line, double* grad_tab, void* stream) {
   if (!grad_signals) return fail("NULL pointer argument");
-  return synth_tab_common(env_params, env_shapes, env_tab, tab_index, T, carrier, line_kind, line_params, t_start, t_end, awg_res, sim_res,
-                          B, K, E, flags, nullptr, nullptr, grad_signals, grad_env, grad_carrier, grad_line, grad_tab, stream);
+  return synth_run({env_params, env_shapes, carrier, {true, env_tab, tab_index, T}, {false, line_kind, line_params}, t_start, t_end,
+                    awg_res, sim_res, B, K, E, flags, {}, {true, grad_signals, grad_env, grad_carrier, grad_line, grad_tab}, stream});
 }
 
 int c3p_dress(const void* H, const void* ops, int64_t ops_bstride, int P, int M, int D, int flags, double* eig_out, void* T_out,

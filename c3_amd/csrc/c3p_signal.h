@@ -21,16 +21,6 @@ struct SynthTabArgs {
   int T;
 };
 
-hipError_t c3p_launch_synth(const SynthArgs& A, hipStream_t st);
-hipError_t c3p_launch_synth_tab(const SynthArgs& A, const SynthTabArgs& X, hipStream_t st);
-// d loss/d signals [B,K,N] -> d loss/d env_params [B,K,E,NPAR] (amp, xy_angle, freq_offset, delta slots) and
-// d loss/d carrier [B,K,2]; giq [B,K,2,Na] and gcar_part [B,K,Na,2] are scratch, A.iq is recomputed.
-hipError_t c3p_launch_synth_vjp(const SynthArgs& A, const double* gsig, double* giq, double* gcar_part, double* genv,
-                                double* gcar, hipStream_t st);
-// the same with a coefficient table, and gtab [B,T]: d loss/d env_tab (0 outside the blocks and in the t_bin slots)
-hipError_t c3p_launch_synth_tab_vjp(const SynthArgs& A, const SynthTabArgs& X, const double* gsig, double* giq, double* gcar_part,
-                                    double* genv, double* gcar, double* gtab, hipStream_t st);
-
 // The device chain behind a line: AWG -> DAC -> Response -> Mixer -> VoltsToHertz (kind 0) or FluxTuning (kind 1).
 struct SynthChainArgs {
   SynthArgs S;
@@ -41,12 +31,22 @@ struct SynthChainArgs {
 };
 int c3p_chain_tiles(int N);       // sample tiles per line
 int c3p_chain_part_stride(void);  // doubles per tile in `part`
-hipError_t c3p_launch_chain(const SynthChainArgs& C, hipStream_t st);
-hipError_t c3p_launch_chain_tab(const SynthChainArgs& C, const SynthTabArgs& X, hipStream_t st);
-// scratch: gcs [B,K,2,N], part [B,K,c3p_chain_tiles(N),c3p_chain_part_stride()], giq [B,K,2,Na], gcar_part [B,K,Na,2];
-// outputs genv [B,K,E,NPAR], gcar [B,K,2], gline [B,K,C3P_LINE_NPAR]
-hipError_t c3p_launch_chain_vjp(const SynthChainArgs& C, const double* gsig, double* gcs, double* part, double* giq, double* gcar_part,
-                                double* genv, double* gcar, double* gline, hipStream_t st);
-hipError_t c3p_launch_chain_tab_vjp(const SynthChainArgs& C, const SynthTabArgs& X, const double* gsig, double* gcs, double* part,
-                                    double* giq, double* gcar_part, double* genv, double* gcar, double* gline, double* gtab,
-                                    hipStream_t st);
+
+// Scratch and outputs of the vector-Jacobian product.  gcs, part and gline belong to a line chain and stay NULL without
+// one; gtab goes with a coefficient table.  The I/Q rows are recomputed into C.S.iq.
+struct SynthVjpBufs {
+  double* giq;        // [B,K,2,Na] scratch
+  double* gcar_part;  // [B,K,Na,2] scratch
+  double* gcs;        // [B,K,2,N] scratch
+  double* part;       // [B,K,c3p_chain_tiles(N),c3p_chain_part_stride()] scratch
+  double* genv;       // [B,K,E,NPAR]: the amp, xy_angle, freq_offset, delta slots
+  double* gcar;       // [B,K,2]
+  double* gline;      // [B,K,C3P_LINE_NPAR]
+  double* gtab;       // [B,T]: 0 outside the blocks and in the t_bin slots
+};
+
+// C.kind == NULL: the standard drive line (AWG -> DAC -> Mixer -> VoltsToHertz), only C.S is read.  X == NULL: no
+// coefficient table travels with the rows, and the table-free instantiations of the AWG kernels run.
+hipError_t c3p_launch_synth(const SynthChainArgs& C, const SynthTabArgs* X, hipStream_t st);
+// d loss/d signals gsig [B,K,N] -> V
+hipError_t c3p_launch_synth_vjp(const SynthChainArgs& C, const SynthTabArgs* X, const double* gsig, const SynthVjpBufs& V, hipStream_t st);

@@ -638,38 +638,7 @@ void launch_awg_bwd(const SynthArgs& A, const SynthTabArgs* X, const double* giq
   const int tiles = (X->T + 63) / 64;
   if (tiles > 0) C3P_LAUNCH(tab_bwd_kernel, dim3((unsigned)((long)A.B * (tiles + X->T))), dim3(64), 0, st, A, *X, giq, gtab, tiles);
 }
-
-hipError_t synth_vjp_impl(const SynthArgs& A, const SynthTabArgs* X, const double* gsig, double* giq, double* gcar_part, double* genv,
-                          double* gcar, double* gtab, hipStream_t st) {
-  const long ta = (long)A.B * A.K * A.Na;
-  if (ta == 0) return hipSuccess;
-  launch_awg_iq(A, X, ta, st);
-  C3P_LAUNCH(mix_bwd_kernel, dim3((unsigned)ta), dim3(64), 0, st, A, gsig, giq, gcar_part);
-  launch_awg_bwd(A, X, (const double*)giq, (const double*)gcar_part, genv, gcar, gtab, st);
-  return hipGetLastError();
-}
-
-hipError_t synth_impl(const SynthArgs& A, const SynthTabArgs* X, hipStream_t st) {
-  const long ta = (long)A.B * A.K * A.Na, ts = (long)A.B * A.K * A.N;
-  if (ta == 0 || ts == 0) return hipSuccess;
-  launch_awg_iq(A, X, ta, st);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  C3P_LAUNCH(mix_kernel, dim3((unsigned)((ts + 255) / 256)), dim3(256), 0, st, A);
-  return hipGetLastError();
-}
 }  // namespace
-
-hipError_t c3p_launch_synth_vjp(const SynthArgs& A, const double* gsig, double* giq, double* gcar_part, double* genv,
-                                double* gcar, hipStream_t st) {
-  return synth_vjp_impl(A, nullptr, gsig, giq, gcar_part, genv, gcar, nullptr, st);
-}
-hipError_t c3p_launch_synth(const SynthArgs& A, hipStream_t st) { return synth_impl(A, nullptr, st); }
-hipError_t c3p_launch_synth_tab(const SynthArgs& A, const SynthTabArgs& X, hipStream_t st) { return synth_impl(A, &X, st); }
-hipError_t c3p_launch_synth_tab_vjp(const SynthArgs& A, const SynthTabArgs& X, const double* gsig, double* giq, double* gcar_part,
-                                    double* genv, double* gcar, double* gtab, hipStream_t st) {
-  return synth_vjp_impl(A, &X, gsig, giq, gcar_part, genv, gcar, gtab, st);
-}
 
 // ---- the device chain of a flux line: AWG -> DAC -> Response -> Mixer -> VoltsToHertz | FluxTuning --------------------------
 // (reference: c3/generator/devices.py:585-642 Response, c3/utils/tf_utils.py:476-518 tf_convolve_legacy, devices.py:457-525
@@ -938,51 +907,45 @@ __global__ void __launch_bounds__(64) chain_bwd_awg_kernel(SynthChainArgs C, int
 
 }  // namespace
 
-namespace {
-hipError_t chain_impl(const SynthChainArgs& C, const SynthTabArgs* X, hipStream_t st) {
-  const SynthArgs& A = C.S;
-  const long lines = (long)A.B * A.K, ta = lines * A.Na;
-  const int nt = (A.N + CH_TN - 1) / CH_TN;
-  if (ta == 0 || A.N == 0) return hipSuccess;
-  launch_awg_iq(A, X, ta, st);
-  C3P_LAUNCH(chain_taps_kernel, dim3((unsigned)lines), dim3(64), 0, st, C);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  C3P_LAUNCH(chain_fwd_kernel, dim3((unsigned)(lines * nt)), dim3(CH_TN), 0, st, C, nt);
-  return hipGetLastError();
-}
-
-hipError_t chain_vjp_impl(const SynthChainArgs& C, const SynthTabArgs* X, const double* gsig, double* gcs, double* part, double* giq,
-                          double* gcar_part, double* genv, double* gcar, double* gline, double* gtab, hipStream_t st) {
-  const SynthArgs& A = C.S;
-  const long lines = (long)A.B * A.K, ta = lines * A.Na;
-  const int nt = c3p_chain_tiles(A.N);
-  if (ta == 0 || A.N == 0) return hipSuccess;
-  launch_awg_iq(A, X, ta, st);
-  C3P_LAUNCH(chain_taps_kernel, dim3((unsigned)lines), dim3(64), 0, st, C);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  C3P_LAUNCH(chain_bwd_sample_kernel, dim3((unsigned)(lines * nt)), dim3(CH_TN), 0, st, C, nt, gsig, gcs, part);
-  C3P_LAUNCH(chain_bwd_awg_kernel, dim3((unsigned)ta), dim3(64), 0, st, C, nt, (const double*)gcs, (const double*)part, giq,
-             gcar_part, gline);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  launch_awg_bwd(A, X, (const double*)giq, (const double*)gcar_part, genv, gcar, gtab, st);
-  return hipGetLastError();
-}
-}  // namespace
-
 int c3p_chain_tiles(int N) { return (N + CH_TN - 1) / CH_TN; }
 int c3p_chain_part_stride() { return CH_PS; }
 
-hipError_t c3p_launch_chain(const SynthChainArgs& C, hipStream_t st) { return chain_impl(C, nullptr, st); }
-hipError_t c3p_launch_chain_tab(const SynthChainArgs& C, const SynthTabArgs& X, hipStream_t st) { return chain_impl(C, &X, st); }
-hipError_t c3p_launch_chain_vjp(const SynthChainArgs& C, const double* gsig, double* gcs, double* part, double* giq, double* gcar_part,
-                                double* genv, double* gcar, double* gline, hipStream_t st) {
-  return chain_vjp_impl(C, nullptr, gsig, gcs, part, giq, gcar_part, genv, gcar, gline, nullptr, st);
+// ---- the two launchers: C.kind == NULL is the standard drive line, X == NULL a call without a coefficient table --------------
+hipError_t c3p_launch_synth(const SynthChainArgs& C, const SynthTabArgs* X, hipStream_t st) {
+  const SynthArgs& A = C.S;
+  const long lines = (long)A.B * A.K, ta = lines * A.Na, ts = lines * A.N;
+  if (ta == 0 || ts == 0) return hipSuccess;
+  launch_awg_iq(A, X, ta, st);
+  if (C.kind) C3P_LAUNCH(chain_taps_kernel, dim3((unsigned)lines), dim3(64), 0, st, C);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (C.kind) {
+    const int nt = c3p_chain_tiles(A.N);
+    C3P_LAUNCH(chain_fwd_kernel, dim3((unsigned)(lines * nt)), dim3(CH_TN), 0, st, C, nt);
+  } else {
+    C3P_LAUNCH(mix_kernel, dim3((unsigned)((ts + 255) / 256)), dim3(256), 0, st, A);
+  }
+  return hipGetLastError();
 }
-hipError_t c3p_launch_chain_tab_vjp(const SynthChainArgs& C, const SynthTabArgs& X, const double* gsig, double* gcs, double* part,
-                                    double* giq, double* gcar_part, double* genv, double* gcar, double* gline, double* gtab,
-                                    hipStream_t st) {
-  return chain_vjp_impl(C, &X, gsig, gcs, part, giq, gcar_part, genv, gcar, gline, gtab, st);
+
+hipError_t c3p_launch_synth_vjp(const SynthChainArgs& C, const SynthTabArgs* X, const double* gsig, const SynthVjpBufs& V, hipStream_t st) {
+  const SynthArgs& A = C.S;
+  const long lines = (long)A.B * A.K, ta = lines * A.Na;
+  if (ta == 0 || A.N == 0) return hipSuccess;
+  launch_awg_iq(A, X, ta, st);
+  if (C.kind) {
+    const int nt = c3p_chain_tiles(A.N);
+    C3P_LAUNCH(chain_taps_kernel, dim3((unsigned)lines), dim3(64), 0, st, C);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    C3P_LAUNCH(chain_bwd_sample_kernel, dim3((unsigned)(lines * nt)), dim3(CH_TN), 0, st, C, nt, gsig, V.gcs, V.part);
+    C3P_LAUNCH(chain_bwd_awg_kernel, dim3((unsigned)ta), dim3(64), 0, st, C, nt, (const double*)V.gcs, (const double*)V.part, V.giq,
+               V.gcar_part, V.gline);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  } else {
+    C3P_LAUNCH(mix_bwd_kernel, dim3((unsigned)ta), dim3(64), 0, st, A, gsig, V.giq, V.gcar_part);
+  }
+  launch_awg_bwd(A, X, (const double*)V.giq, (const double*)V.gcar_part, V.genv, V.gcar, V.gtab, st);
+  return hipGetLastError();
 }

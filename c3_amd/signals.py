@@ -67,7 +67,7 @@ LINE_NPAR = 6
 
 def slice_num(t_start: float, t_end: float, resolution: float) -> int:
     """Device.calc_slice_num (devices.py:72-84)."""
-    return int(np.abs(t_start - t_end) * resolution)
+    return int(abs(t_start - t_end) * resolution)
 
 
 def pack_components(channels: Sequence[Sequence[Dict]], B: int = 1):
@@ -338,6 +338,54 @@ def _lines(call, line_kinds, line_params, B: int, K: int, sim_res: float):
     return knd, par
 
 
+def _begin(env_params, env_shapes, carrier, t_start, t_end, awg_res, sim_res, grad_signals, line_kinds, line_params, env_tables, table_index):
+    """What `synthesize_signals` and `synthesize_signals_vjp` (the call with `grad_signals`) share: the argument checks, and the
+    one place that picks the C entry -- `c3p_synth_tab` with a coefficient table, `c3p_synth_chain` with lines alone, else
+    `c3p_synth_signals`, `_vjp` appended for the vjp -- and builds the arguments all six start with.
+
+    -> (call, entry, leading arguments, the arrays behind them (the caller holds them over the call), B, K, E, N, Na, T); T is
+    None without a table.  A vjp's leading arguments end with grad_signals [B,K,N]."""
+    if (line_kinds is None) != (line_params is None):
+        raise C3PropError("C3:Error: line_kinds and line_params go together")
+    if (env_tables is None) != (table_index is None):
+        raise C3PropError("C3:Error: env_tables and table_index go together")
+    call = _Call(env_params, carrier, grad_signals, line_params, env_tables)
+    env = call.f64(env_params)
+    if env.ndim != 4 or env.shape[-1] != ENV_NPAR:
+        raise C3PropError(f"C3:Error: env_params must be [B,K,E,{ENV_NPAR}], got {tuple(env.shape)}")
+    B, K, E, _ = env.shape
+    shapes_np, shp = _shapes(call, env_shapes, K, E, tables=env_tables is not None)
+    car = call.f64(carrier)
+    if tuple(car.shape) != (B, K, 2):
+        raise C3PropError(f"C3:Error: carrier must be [{B},{K},2], got {tuple(car.shape)}")
+    N, Na = slice_num(t_start, t_end, sim_res), slice_num(t_start, t_end, awg_res)
+    if N <= 0 or Na <= 1:
+        raise C3PropError(f"C3:Error: empty time grid (N={N}, AWG samples={Na})")
+    gs = call.f64(grad_signals)
+    if gs is not None and tuple(gs.shape) != (B, K, N):
+        raise C3PropError(f"C3:Error: grad_signals must be [{B},{K},{N}], got {tuple(gs.shape)}")
+    tab = tidx = T = knd = par = None
+    if env_tables is not None:
+        tab, tidx, T = _tables(call, env_tables, table_index, shapes_np, B, Na)
+    if line_kinds is not None:
+        knd, par = _lines(call, line_kinds, line_params, B, K, sim_res)
+    if T is not None:
+        name, head = "c3p_synth_tab", (_ptr(env), _ptr(shp), _ptr(tab), _ptr(tidx), T, _ptr(car), _ptr(knd), _ptr(par))
+    elif knd is not None:
+        name, head = "c3p_synth_chain", (_ptr(env), _ptr(shp), _ptr(car), _ptr(knd), _ptr(par))
+    else:
+        name, head = "c3p_synth_signals", (_ptr(env), _ptr(shp), _ptr(car))
+    head += (float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags)
+    if gs is not None:
+        name, head = name + "_vjp", head + (_ptr(gs),)
+    return call, getattr(_lib.load(), name), head, (env, shp, tab, tidx, car, knd, par, gs), B, K, E, N, Na, T
+
+
+def _empty(call, shape):
+    """an uninitialised f64 output where the call's inputs live"""
+    return call.torch.empty(shape, dtype=call.torch.float64, device=call.dev) if call.device else np.empty(shape, dtype=np.float64)
+
+
 def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, *, want_iq: bool = False, device=None, line_kinds=None, line_params=None, env_tables=None, table_index=None):
     """signals [B,K,N] (and optionally the AWG-resolution I/Q [B,K,2,Na]) from parameter rows.
 
@@ -356,52 +404,12 @@ def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: f
         import torch
 
         env_params = torch.as_tensor(np.asarray(env_params, dtype=np.float64) if not _is_torch(env_params) else env_params, device=device)
-    if (line_kinds is None) != (line_params is None):
-        raise C3PropError("C3:Error: line_kinds and line_params go together")
-    if (env_tables is None) != (table_index is None):
-        raise C3PropError("C3:Error: env_tables and table_index go together")
-    if device is not None and env_tables is not None and not _is_torch(env_tables):
-        env_tables = torch.as_tensor(np.asarray(env_tables, dtype=np.float64), device=device)
-    call = _Call(env_params, carrier, line_params, env_tables)
-    env = call.f64(env_params)
-    if env.ndim != 4 or env.shape[-1] != ENV_NPAR:
-        raise C3PropError(f"C3:Error: env_params must be [B,K,E,{ENV_NPAR}], got {tuple(env.shape)}")
-    B, K, E = (int(x) for x in env.shape[:3])
-    shapes_np, shp = _shapes(call, env_shapes, K, E, tables=env_tables is not None)
-    car = call.f64(carrier)
-    if tuple(car.shape) != (B, K, 2):
-        raise C3PropError(f"C3:Error: carrier must be [{B},{K},2], got {tuple(car.shape)}")
-    N, Na = slice_num(t_start, t_end, sim_res), slice_num(t_start, t_end, awg_res)
-    if N <= 0 or Na <= 1:
-        raise C3PropError(f"C3:Error: empty time grid (N={N}, AWG samples={Na})")
-    if call.device:
-        sig = call.torch.empty((B, K, N), dtype=call.torch.float64, device=call.dev)
-        iq = call.torch.empty((B, K, 2, Na), dtype=call.torch.float64, device=call.dev) if want_iq else None
-    else:
-        sig = np.empty((B, K, N), dtype=np.float64)
-        iq = np.empty((B, K, 2, Na), dtype=np.float64) if want_iq else None
-    if env_tables is not None:
-        tab, tidx, T = _tables(call, env_tables, table_index, shapes_np, B, Na)
-        knd, par = _lines(call, line_kinds, line_params, B, K, sim_res) if line_kinds is not None else (None, None)
-        _lib.check(
-            _lib.load().c3p_synth_tab(
-                _ptr(env), _ptr(shp), _ptr(tab), _ptr(tidx), T, _ptr(car), _ptr(knd), _ptr(par), float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags, _ptr(iq), _ptr(sig), call.stream
-            )
-        )
-        return (sig, iq) if want_iq else sig
-    if line_kinds is not None:
-        knd, par = _lines(call, line_kinds, line_params, B, K, sim_res)
-        _lib.check(
-            _lib.load().c3p_synth_chain(
-                _ptr(env), _ptr(shp), _ptr(car), _ptr(knd), _ptr(par), float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags, _ptr(iq), _ptr(sig), call.stream
-            )
-        )
-        return (sig, iq) if want_iq else sig
-    _lib.check(
-        _lib.load().c3p_synth_signals(
-            _ptr(env), _ptr(shp), _ptr(car), float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags, _ptr(iq), _ptr(sig), call.stream
-        )
-    )
+        if env_tables is not None and table_index is not None and not _is_torch(env_tables):
+            env_tables = torch.as_tensor(np.asarray(env_tables, dtype=np.float64), device=device)
+    call, entry, head, held, B, K, _, N, Na, _ = _begin(env_params, env_shapes, carrier, t_start, t_end, awg_res, sim_res, None, line_kinds, line_params, env_tables, table_index)
+    sig = _empty(call, (B, K, N))
+    iq = _empty(call, (B, K, 2, Na)) if want_iq else None
+    _lib.check(entry(*head, _ptr(iq), _ptr(sig), call.stream))
     return (sig, iq) if want_iq else sig
 
 
@@ -417,60 +425,16 @@ def synthesize_signals_vjp(env_params, env_shapes, carrier, t_start: float, t_en
     reference gets the same numbers from the tape that also covers the propagation
     (optimizers/optimizer.py:206-216, gates.py:341-370).  Chain with `propagate_batch_vjp`.
     """
-    if (line_kinds is None) != (line_params is None):
-        raise C3PropError("C3:Error: line_kinds and line_params go together")
-    if (env_tables is None) != (table_index is None):
-        raise C3PropError("C3:Error: env_tables and table_index go together")
-    call = _Call(env_params, carrier, grad_signals, line_params, env_tables)
-    env = call.f64(env_params)
-    if env.ndim != 4 or env.shape[-1] != ENV_NPAR:
-        raise C3PropError(f"C3:Error: env_params must be [B,K,E,{ENV_NPAR}], got {tuple(env.shape)}")
-    B, K, E = (int(x) for x in env.shape[:3])
-    shapes_np, shp = _shapes(call, env_shapes, K, E, tables=env_tables is not None)
-    car = call.f64(carrier)
-    if tuple(car.shape) != (B, K, 2):
-        raise C3PropError(f"C3:Error: carrier must be [{B},{K},2], got {tuple(car.shape)}")
-    N, Na = slice_num(t_start, t_end, sim_res), slice_num(t_start, t_end, awg_res)
-    if N <= 0 or Na <= 1:
-        raise C3PropError(f"C3:Error: empty time grid (N={N}, AWG samples={Na})")
-    gs = call.f64(grad_signals)
-    if tuple(gs.shape) != (B, K, N):
-        raise C3PropError(f"C3:Error: grad_signals must be [{B},{K},{N}], got {tuple(gs.shape)}")
-    if call.device:
-        t = call.torch
-        genv = t.empty((B, K, E, ENV_NPAR), dtype=t.float64, device=call.dev)
-        gcar = t.empty((B, K, 2), dtype=t.float64, device=call.dev)
-    else:
-        genv = np.empty((B, K, E, ENV_NPAR), dtype=np.float64)
-        gcar = np.empty((B, K, 2), dtype=np.float64)
-    if env_tables is not None:
-        tab, tidx, T = _tables(call, env_tables, table_index, shapes_np, B, Na)
-        knd = par = gline = None
-        if line_kinds is not None:
-            knd, par = _lines(call, line_kinds, line_params, B, K, sim_res)
-            gline = call.torch.empty((B, K, LINE_NPAR), dtype=call.torch.float64, device=call.dev) if call.device else np.empty((B, K, LINE_NPAR), dtype=np.float64)
-        gtab = call.torch.empty((B, T), dtype=call.torch.float64, device=call.dev) if call.device else np.empty((B, T), dtype=np.float64)
-        _lib.check(
-            _lib.load().c3p_synth_tab_vjp(
-                _ptr(env), _ptr(shp), _ptr(tab), _ptr(tidx), T, _ptr(car), _ptr(knd), _ptr(par), float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags, _ptr(gs), _ptr(genv), _ptr(gcar), _ptr(gline), _ptr(gtab), call.stream
-            )
-        )
-        return (genv, gcar, gline, gtab) if line_kinds is not None else (genv, gcar, gtab)
+    call, entry, head, held, B, K, E, _, _, T = _begin(env_params, env_shapes, carrier, t_start, t_end, awg_res, sim_res, grad_signals, line_kinds, line_params, env_tables, table_index)
+    outs = (_empty(call, (B, K, E, ENV_NPAR)), _empty(call, (B, K, 2)))
     if line_kinds is not None:
-        knd, par = _lines(call, line_kinds, line_params, B, K, sim_res)
-        gline = call.torch.empty((B, K, LINE_NPAR), dtype=call.torch.float64, device=call.dev) if call.device else np.empty((B, K, LINE_NPAR), dtype=np.float64)
-        _lib.check(
-            _lib.load().c3p_synth_chain_vjp(
-                _ptr(env), _ptr(shp), _ptr(car), _ptr(knd), _ptr(par), float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags, _ptr(gs), _ptr(genv), _ptr(gcar), _ptr(gline), call.stream
-            )
-        )
-        return genv, gcar, gline
-    _lib.check(
-        _lib.load().c3p_synth_signals_vjp(
-            _ptr(env), _ptr(shp), _ptr(car), float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags, _ptr(gs), _ptr(genv), _ptr(gcar), call.stream
-        )
-    )
-    return genv, gcar
+        outs += (_empty(call, (B, K, LINE_NPAR)),)
+    if T is None:
+        _lib.check(entry(*head, *map(_ptr, outs), call.stream))
+    else:  # the table entry takes grad_line whether lines travel or not
+        outs += (_empty(call, (B, T)),)
+        _lib.check(entry(*head, _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]) if line_kinds is not None else None, _ptr(outs[-1]), call.stream))
+    return outs
 
 
 def create_ts(t_start: float, t_end: float, resolution: float) -> np.ndarray:

@@ -171,3 +171,18 @@ def test_host_pointer_checks(lib, vjp):
     par[0, 0, sg.LINE_SLOTS["rise_time"]] = 0.0
     rc, msg = _host_call(lib, vjp, [1], par)
     assert rc != 0 and "phi_0" in msg
+
+
+@pytest.mark.parametrize("vjp", [False, True])
+def test_drive_entries_check_shape_ids_before_any_device_work(lib, vjp):
+    """c3p_synth_signals[_vjp] on host pointers refuse an unknown shape id by its own message, with no GPU present: the look
+    at env_shapes comes before the workspace lock, as in the chain and table entries."""
+    env, shapes = sg.pack_components([[dict(shape="rect", amp=1.0, t_final=1e-9)]])
+    shapes[0, 0] = 12
+    car = np.array([[[5e9 * TWO_PI, 1.0]]])
+    p = lambda a: a.ctypes.data
+    sig, genv, gcar = np.zeros((1, 1, 100)), np.zeros_like(env), np.zeros_like(car)
+    head = (p(env), p(shapes), p(car), 0.0, 1e-9, 2.4e9 * 5, 100e9, 1, 1, 1, _lib.HOST_PTRS)
+    rc = lib.c3p_synth_signals_vjp(*head, p(sig), p(genv), p(gcar), None) if vjp else lib.c3p_synth_signals(*head, None, p(sig), None)
+    msg = lib.c3p_last_error().decode()
+    assert rc != 0 and "env_shapes[0]=12 is not a C3P_ENV_* id" in msg
