@@ -2375,51 +2375,95 @@ int c3p_superop(const void* A, int n, int D, int which, int flags, void* out, vo
 
 }  // extern "C"
 
+// ---- ODE state solvers: one call record (OdeCall), the route as a value (ode_route) and one launch (ode_launch) behind
+// c3p_ode_solve, c3p_ode_solve_vjp and c3p_rk4_unitary ------------------------------------------------------------------------
 namespace {
-// Segmented integration (see c3p_ode_solve): `a` describes the plain problem (M = 1: a state, or M = D: rk4_unitary).
-// U_out (or NULL) receives the step map of the whole interval [B,D,D]; psi_out (or NULL) = map x init.
-int ode_segmented(DeviceWs* w, OdeArgs a, int nseg, const cplx* init, long init_bstride, cplx* U_out, cplx* psi_out, hipStream_t st) {
-  const int D = a.D, B = a.B;
-  const size_t cs = sizeof(cplx);
-  void *v_id, *v_maps, *v_U = U_out;
-  if (ws_get(w, SL_CLP, (size_t)D * D * cs, &v_id)) return -1;
-  if (ws_get(w, SL_SEG_A, (size_t)B * nseg * D * D * cs, &v_maps)) return -1;
-  if (!v_U && ws_get(w, SL_SCRATCH, (size_t)B * D * D * cs, &v_U)) return -1;
-  if (g_dry) return 0;
-  LAUNCH_TRY(c3p_launch_ode_identity((cplx*)v_id, D, st));
-  a.M = D;
-  a.init = (const cplx*)v_id;
-  a.init_bstride = 0;
-  a.want_all = 0;
-  a.seg_count = nseg;
-  a.seg_len = (a.n_steps + nseg - 1) / nseg;
-  a.states = (cplx*)v_maps;
-  if (D > 16) {
-    // 17 <= D <= 48: the segment maps on the matrix-core kernel (propagator step: one product per stage), combined on the
-    // mid-D chain kernel
-    a.step = C3P_STEP_PROPAGATOR_ID;
-    LAUNCH_TRY(c3p_launch_ode_rhoq(a, st));
-    if (combine_chain(c3p_launch_midd_chain, w, (const cplx*)v_maps, B, nseg, D, 0, nullptr, (cplx*)v_U, st)) return -1;
-  } else {
-    LAUNCH_TRY(c3p_launch_ode_row(a, nullptr, st));
-    if (combine_chain(c3p_launch_smalld_chain, w, (const cplx*)v_maps, B, nseg, D, 0, nullptr, (cplx*)v_U, st)) return -1;
-  }
-  if (psi_out) HIP_TRY(c3p_launch_ode_apply((const cplx*)v_U, init, init_bstride, psi_out, B, D, st));
-  return 0;
-}
+// One ODE call between its argument checks and its result: the workspace lock, the staging of host operands, the flags and the
+// problem record the kernels take.
+struct OdeCall {
+  std::optional<WsLock> lk;
+  DeviceWs* w = nullptr;
+  hipStream_t st = nullptr;
+  Stage sg{nullptr, nullptr};
+  int flags = 0;
+  OdeArgs a = {};
 
-// Trajectory (want_all) of a small batch of Schroedinger states at D <= 12 in time segments: the segment maps as above, the
-// state at the start of every segment from them, then the B x nseg pieces of the trajectory side by side (lane-row kernel).
-int ode_trajectory_segmented(DeviceWs* w, OdeArgs a, int nseg, hipStream_t st) {
-  const int D = a.D, B = a.B;
-  const size_t cs = sizeof(cplx);
-  void *v_id, *v_maps, *v_st;
-  if (ws_get(w, SL_CLP, (size_t)D * D * cs, &v_id)) return -1;
-  if (ws_get(w, SL_SEG_A, (size_t)B * nseg * D * D * cs, &v_maps)) return -1;
-  if (ws_get(w, SL_SEG_B, (size_t)B * nseg * D * cs, &v_st)) return -1;
-  if (g_dry) return 0;
-  LAUNCH_TRY(c3p_launch_ode_identity((cplx*)v_id, D, st));
-  OdeArgs m = a;
+  bool host() const { return flags & C3P_HOST_PTRS; }
+  int lock(int flags_, void* stream) {
+    flags = flags_;
+    st = (hipStream_t)stream;
+    lk.emplace(st);
+    w = lk->w;
+    if (!w) return fail("no HIP device");
+    if (!lk->ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
+    sg.w = w, sg.st = st;
+    return 0;
+  }
+  // host pointers: the operands every entry takes, in slot order (each pointer becomes its staged copy)
+  int stage_h(const void*& h0, const void*& hks, const void*& signals, int B, int K, int N, int D) {
+    if (sg.in(h0, (size_t)D * D * sizeof(cplx), &h0)) return -1;
+    if (sg.in(hks, (size_t)K * D * D * sizeof(cplx), &hks)) return -1;
+    return sg.in(signals, (size_t)B * K * N * sizeof(double), &signals);
+  }
+  // the fields of the problem record every entry sets; the rest (states, want_all, hs, ...) stay zero for the entry to set
+  void fill(const void* h0, const void* hks, const void* signals, const void* col_ops, const void* init, long init_bstride, double dt,
+            int B, int K, int N, int D, int M, int C, int solver, int step, int n_steps, int u_stride) {
+    a = {};
+    a.h0 = (const cplx*)h0;
+    a.hks = (const cplx*)hks;
+    a.signals = (const double*)signals;
+    a.col_ops = (const cplx*)col_ops;
+    a.init = (const cplx*)init;
+    a.init_bstride = init_bstride;
+    a.dt = dt;
+    a.B = B, a.K = K, a.N = N, a.D = D, a.M = M, a.C = C;
+    a.solver = solver;
+    a.step = step;
+    a.n_steps = n_steps;
+    a.u_stride = u_stride;
+  }
+  // The two solve entries: the checks they share (`own`: the vjp's extra ones, in their place), lock, staging of the operands they
+  // share (SL_IN0 .. SL_IN4), fill.  0 = go on, 1 = nothing to do (B = 0), -1 = error.  The forward entry needs `states`, the vjp
+  // `grad_signals` where K > 0.
+  template <class Own>
+  int open(bool vjp, Own&& own, const void* h0, const void* hks, const void* signals, const void* col_ops, int C, double dt, int B, int K,
+           int N, int D, int solver, int step, const void* init, int64_t init_bstride, int flags_, const void* states,
+           const void* grad_signals, void* stream) {
+    if (B < 0 || N < 0 || D <= 0 || K < 0 || K > 32) return fail("bad sizes B=%d K=%d N=%d D=%d", B, K, N, D);
+    if (solver < 0 || solver > 3) return fail("unknown solver id %d", solver);
+    if (step < 0 || step > 2) return fail("unknown step function id %d", step);
+    if (flags_ & C3P_COL_PER_SAMPLE)
+      return fail("%s: C3P_COL_PER_SAMPLE is not served (one col_ops [C,D,D] for the batch)", vjp ? "c3p_ode_solve_vjp" : "c3p_ode_solve");
+    if (B == 0) return 1;
+    if (own()) return -1;
+    if (N < 2) return fail("the ODE solver needs at least two time samples (N=%d)", N);
+    if (!h0 || !init || (!vjp && !states)) return fail("NULL pointer argument");
+    if (K > 0 && (!hks || !signals || (vjp && !grad_signals))) return fail("K > 0 but hks/signals%s missing", vjp ? "/grad_signals" : "");
+    if (step == C3P_STEP_LINDBLAD && (!col_ops || C <= 0)) return fail("lindblad step needs col_ops");
+    if (step != C3P_STEP_LINDBLAD) C = 0;
+    const int M = (step == C3P_STEP_SCHRODINGER) ? 1 : D;
+    if (lock(flags_, stream)) return -1;
+    if (host()) {
+      const size_t init_elems = init_bstride ? (size_t)(B - 1) * init_bstride + (size_t)D * M : (size_t)D * M;
+      if (stage_h(h0, hks, signals, B, K, N, D)) return -1;
+      if (sg.in(col_ops, (size_t)C * D * D * sizeof(cplx), &col_ops)) return -1;
+      if (sg.in(init, init_elems * sizeof(cplx), &init)) return -1;
+    }
+    fill(h0, hks, signals, col_ops, init, init_bstride, dt, B, K, N, D, M, C, solver, step, N, 1);
+    return 0;
+  }
+  int finish() { return host() ? sg.finish() : 0; }
+};
+
+// The step maps of nseg time segments of every sample, [B, nseg, D, D] in SL_SEG_A: each segment integrates the D columns of the
+// identity (SL_CLP).  17 <= D <= 48: on the matrix-core kernel (propagator step: one product per stage), below on the lane rows.
+int ode_segment_maps(DeviceWs* w, const OdeArgs& a, int nseg, OdeArgs* maps, hipStream_t st) {
+  const int D = a.D;
+  void *v_id, *v_maps;
+  if (ws_get(w, SL_CLP, (size_t)D * D * sizeof(cplx), &v_id)) return -1;
+  if (ws_get(w, SL_SEG_A, (size_t)a.B * nseg * D * D * sizeof(cplx), &v_maps)) return -1;
+  HIP_TRY(c3p_launch_ode_identity((cplx*)v_id, D, st));
+  OdeArgs& m = *maps = a;
   m.M = D;
   m.init = (const cplx*)v_id;
   m.init_bstride = 0;
@@ -2428,60 +2472,185 @@ int ode_trajectory_segmented(DeviceWs* w, OdeArgs a, int nseg, hipStream_t st) {
   m.seg_len = (a.n_steps + nseg - 1) / nseg;
   m.states = (cplx*)v_maps;
   if (D > 16) {
-    m.step = C3P_STEP_PROPAGATOR_ID;  // 17 <= D <= 48: the segment maps on the matrix-core kernel (one product per stage)
-    LAUNCH_TRY(c3p_launch_ode_rhoq(m, st));
+    m.step = C3P_STEP_PROPAGATOR_ID;
+    HIP_TRY(c3p_launch_ode_rhoq(m, st));
   } else {
-    LAUNCH_TRY(c3p_launch_ode_row(m, nullptr, st));
+    HIP_TRY(c3p_launch_ode_row(m, nullptr, st));
   }
-  LAUNCH_TRY(c3p_launch_ode_starts((const cplx*)v_maps, a.init, a.init_bstride, (cplx*)v_st, B, nseg, D, st));
+  return 0;
+}
+
+// Segmented integration of a small batch, final state / propagator only.  The equations are linear, so the interval is cut into
+// nseg time segments, the segment maps are multiplied in order by the chain kernel of their size and, for a vector state (M = 1),
+// the product is applied to the initial state -- D x the arithmetic on nseg x D x the lanes.  M = D (rk4_unitary): the product is
+// the result.
+int ode_segmented(DeviceWs* w, const OdeArgs& a, int nseg, hipStream_t st) {
+  const int D = a.D, B = a.B;
+  void* v_U = a.M == 1 ? nullptr : a.states;
+  if (!v_U && ws_get(w, SL_SCRATCH, (size_t)B * D * D * sizeof(cplx), &v_U)) return -1;
+  OdeArgs m;
+  if (ode_segment_maps(w, a, nseg, &m, st)) return -1;
+  if (D > 16 ? combine_chain(c3p_launch_midd_chain, w, m.states, B, nseg, D, 0, nullptr, (cplx*)v_U, st)
+             : combine_chain(c3p_launch_smalld_chain, w, m.states, B, nseg, D, 0, nullptr, (cplx*)v_U, st))
+    return -1;
+  if (a.M == 1) HIP_TRY(c3p_launch_ode_apply((const cplx*)v_U, a.init, a.init_bstride, a.states, B, D, st));
+  return 0;
+}
+
+// Trajectory (want_all) of a small batch of Schroedinger states in time segments: the segment maps as above, the state at the
+// start of every segment from them, then the B x nseg pieces of the trajectory side by side (one time segment per lane row; at
+// 17 <= D <= 48 per wavefront of c3p_ode_rowq.hip).
+int ode_trajectory_segmented(DeviceWs* w, const OdeArgs& a, int nseg, hipStream_t st) {
+  const int D = a.D, B = a.B;
+  void* v_st;
+  if (ws_get(w, SL_SEG_B, (size_t)B * nseg * D * sizeof(cplx), &v_st)) return -1;
+  OdeArgs m;
+  if (ode_segment_maps(w, a, nseg, &m, st)) return -1;
+  HIP_TRY(c3p_launch_ode_starts(m.states, a.init, a.init_bstride, (cplx*)v_st, B, nseg, D, st));
   OdeArgs t = a;
   t.init = (const cplx*)v_st;
   t.init_bstride = D;
   t.seg_count = nseg;
   t.seg_len = m.seg_len;
   t.seg_traj = 1;
-  if (D > 16)
-    LAUNCH_TRY(c3p_launch_ode_rowq(t, st));
-  else
-    LAUNCH_TRY(c3p_launch_ode_row(t, nullptr, st));
+  HIP_TRY(D > 16 ? c3p_launch_ode_rowq(t, st) : c3p_launch_ode_row(t, nullptr, st));
   return 0;
 }
 
-// trajectories of few Schroedinger states at 17 <= D <= 48: segment maps on the matrix-core kernel, pieces on the lane-row
-// kernel of c3p_ode_rowq.hip (one time segment per wavefront)
-int ode_mfma_traj_segments(const OdeArgs& a0) {
+// Time segments for few samples at 17 <= D <= 48: one workgroup per (sample, segment) on the matrix-core kernel.  A sample alone
+// keeps ONE CU busy for n_steps x ~5 us; S segments spread it over S CUs (the chip has 256), at the price of the ordered product of
+// S maps (final state / propagator) or of the second pass over the pieces on the lane rows of c3p_ode_rowq.hip (`trajectory`).
+// min_segments: how many segments the change has to offer at least.
+int ode_mfma_segments(const OdeArgs& a0, bool trajectory, int min_segments) {
   if (c3p_opt_on(C3P_OPT_ode_no_seg)) return 0;
-  if (a0.D < 17 || a0.D > 48 || !a0.want_all || a0.M != 1 || a0.reset_each_step || a0.transpose_out || a0.hs || a0.K > 4 || a0.n_steps < 64) return 0;
+  if (a0.D < 17 || a0.D > 48 || (a0.want_all != 0) != trajectory || a0.reset_each_step || a0.transpose_out || a0.hs || a0.K > 4 || a0.n_steps < 64)
+    return 0;
+  int nig, nj, wd;
+  if (trajectory ? a0.M != 1 || !c3p_ode_rowq_supported(a0)
+                 : !c3p_midd_geometry(a0.D, &nig, &nj, &wd))  // (the ordered product of the maps runs on the mid-D chain kernel: D <= 40)
+    return 0;
   OdeArgs a = a0;
   a.step = C3P_STEP_PROPAGATOR_ID;
   a.M = a.D;
   a.want_all = 0;
-  a.seg_count = 2;
-  if (!c3p_ode_rhoq_supported(a) || !c3p_ode_rowq_supported(a0)) return 0;
-  long S = 512 / a0.B;
-  if (S > a0.n_steps / 16) S = a0.n_steps / 16;
-  if (S > 64) S = 64;
-  return S >= 4 ? (int)S : 0;
-}
-
-// Time segments for few samples at 17 <= D <= 48 (final state / propagator only): one workgroup per (sample, segment) on the
-// matrix-core kernel.  A sample alone keeps ONE CU busy for n_steps x ~5 us; S segments spread it over S CUs (the chip has
-// 256), at the price of the ordered product of S maps.  min_gain: how many segments the change has to offer at least
-// (a vector state that would otherwise run on the lane-row kernel pays 1.5x per step for becoming a matrix).
-int ode_mfma_segments(const OdeArgs& a0, int min_segments) {
-  if (c3p_opt_on(C3P_OPT_ode_no_seg)) return 0;
-  if (a0.D < 17 || a0.D > 48 || a0.want_all || a0.reset_each_step || a0.transpose_out || a0.hs || a0.K > 4 || a0.n_steps < 64) return 0;
-  int nig, nj, wd;
-  if (!c3p_midd_geometry(a0.D, &nig, &nj, &wd)) return 0;  // (the ordered product of the maps runs on the mid-D chain kernel: D <= 40)
-  OdeArgs a = a0;
-  a.step = C3P_STEP_PROPAGATOR_ID;
-  a.M = a.D;
   a.seg_count = 2;
   if (!c3p_ode_rhoq_supported(a)) return 0;
   long S = 512 / a.B;
   if (S > a.n_steps / 16) S = a.n_steps / 16;
   if (S > 64) S = 64;
   return S >= min_segments ? (int)S : 0;
+}
+
+enum OdeRouteId {
+  ODE_RT_ROW,        // lane-row kernels (c3p_ode_row.hip): one sample per 16-lane row, state and operator rows in registers
+  ODE_RT_ROW_SEG,    // ... final state / propagator of a small batch in time segments (ode_segmented)
+  ODE_RT_ROW_TRAJ,   // ... trajectory of a small batch in time segments (ode_trajectory_segmented)
+  ODE_RT_ROW_OR_WG,  // lane rows for real operators, workgroup kernel for complex ones: the device decides
+  ODE_RT_ROWQ,       // 17 <= D <= 48 vector states: several DPP rows per sample, operators in LDS (c3p_ode_rowq.hip)
+  ODE_RT_RHOQ,       // 17 <= D <= 48 matrix states: register tiles + 16x16x4 fp64 MFMA products (c3p_ode_rhoq.hip)
+  ODE_RT_MFMA_SEG,   // ... final state / propagator of few samples in time segments
+  ODE_RT_MFMA_TRAJ,  // ... trajectory of few Schroedinger states in time segments
+  ODE_RT_WG          // one workgroup per sample (c3p_ode.hip)
+};
+struct OdeRoute {
+  OdeRouteId route;
+  int nseg;
+};
+
+// Which kernel serves the problem: host arithmetic on the record and the option table.  Segments are for vector states (a state, or
+// the D columns of rk4_unitary's propagator).  A state that would otherwise run on the lane rows of c3p_ode_rowq.hip pays 1.5x per
+// step for becoming a matrix, so it needs four matrix-core segments; the propagator is a matrix already and takes two.  The
+// matrix-core and the rowq kernel both take a propagator step (the former wins unless ode_prop_rows is set); for every other step
+// at most one of them does (matrix states need M = D, rowq takes vector steps only).
+OdeRoute ode_route(const OdeArgs& a) {
+  const bool vec = a.step == C3P_STEP_SCHRODINGER || a.step == C3P_STEP_PROPAGATOR_ID;
+  OdeRoute r = {ODE_RT_WG, 0};
+  if (c3p_ode_row_supported(a)) {
+    r.route = ODE_RT_ROW;
+    if (vec && (r.nseg = c3p_ode_row_segments(a)) > 0) r.route = ODE_RT_ROW_SEG;
+    else if (vec && (r.nseg = c3p_ode_row_traj_segments(a)) > 0) r.route = ODE_RT_ROW_TRAJ;
+    // rho-valued states, more than four control lines, no collapse operators, a batch that leaves SIMDs idle on the lane rows
+    // (one wave = four samples; measured crossover between 2048 and 16 384 samples, profiles/r04/ode_fallbacks.json): COMPLEX
+    // operators run 1.1 - 1.3x faster on the workgroup kernel there, real ones 1.4 - 1.7x faster on the lane rows.
+    else if (a.step == C3P_STEP_VON_NEUMANN && a.K > 4 && a.C == 0 && a.B <= 4096 && !c3p_opt_on(C3P_OPT_ode_no_split)) r.route = ODE_RT_ROW_OR_WG;
+  } else if (vec && (r.nseg = ode_mfma_segments(a, true, 4)) > 0) {
+    r.route = ODE_RT_MFMA_TRAJ;
+  } else if (vec && (r.nseg = ode_mfma_segments(a, false, a.M == 1 ? 4 : 2)) > 0) {
+    r.route = ODE_RT_MFMA_SEG;
+  } else if (c3p_ode_rhoq_supported(a)) {
+    r.route = ODE_RT_RHOQ;
+  } else if (c3p_ode_rowq_supported(a)) {
+    r.route = ODE_RT_ROWQ;
+  }
+  // (ROW_OR_WG: the host cannot know which of the two did the work -- a distinct id, so that profiles do not book a workgroup-kernel
+  // run on the lane rows; MFMA_TRAJ: the pieces, the longer pass, run on the lane rows)
+  static const int kernel[] = {C3P_KERNEL_ODE_ROW, C3P_KERNEL_ODE_ROW, C3P_KERNEL_ODE_ROW, C3P_KERNEL_ODE_ROW_OR_WG, C3P_KERNEL_ODE_ROW,
+                               C3P_KERNEL_ODE_MFMA, C3P_KERNEL_ODE_MFMA, C3P_KERNEL_ODE_ROW, C3P_KERNEL_ODE_WG};
+  g_last_kernel = kernel[r.route];
+  return r;
+}
+
+// the workgroup kernel's per-sample scratch: LDS up to 150 KiB, beyond it SL_SCRATCH
+int ode_wg_scratch(DeviceWs* w, OdeArgs& a, bool* global) {
+  const size_t elems = c3p_ode_elems(a.D, a.M, a.C);
+  *global = elems * sizeof(cplx) > (size_t)(150 * 1024);
+  if (!*global) return 0;
+  void* v;
+  if (ws_get(w, SL_SCRATCH, (size_t)a.B * elems * sizeof(cplx), &v)) return -1;
+  a.scratch = (cplx*)v;
+  a.scratch_stride = (long)elems;
+  return 0;
+}
+
+int ode_launch_pass(OdeCall& c, OdeArgs a, OdeRoute r) {
+  DeviceWs* w = c.w;
+  hipStream_t st = c.st;
+  bool global = false;
+  switch (r.route) {
+    case ODE_RT_ROW:
+    case ODE_RT_ROW_OR_WG: {
+      void* aux = nullptr;
+      if (a.C > 0 && ws_get(w, SL_TABLES, c3p_ode_row_aux_bytes(a.D, a.C), &aux)) return -1;
+      // both kernels look at the operators and one of them leaves at once, as regr_prep_kernel does for the PWC path; the second
+      // launch -- B workgroups of 256 threads that leave at once for real operators -- is paid on every such call
+      a.complex_to_wg = r.route == ODE_RT_ROW_OR_WG;
+      HIP_TRY(c3p_launch_ode_row(a, aux, st));
+      if (r.route == ODE_RT_ROW) return 0;
+      a.complex_to_wg = 0;
+      a.wg_if_complex = 1;
+      if (ode_wg_scratch(w, a, &global)) return -1;
+      HIP_TRY(c3p_launch_ode(a, global, st));
+      return 0;
+    }
+    case ODE_RT_ROW_SEG:
+    case ODE_RT_MFMA_SEG: return ode_segmented(w, a, r.nseg, st);
+    case ODE_RT_ROW_TRAJ:
+    case ODE_RT_MFMA_TRAJ: return ode_trajectory_segmented(w, a, r.nseg, st);
+    case ODE_RT_ROWQ: HIP_TRY(c3p_launch_ode_rowq(a, st)); return 0;
+    case ODE_RT_RHOQ: HIP_TRY(c3p_launch_ode_rhoq(a, st)); return 0;
+    case ODE_RT_WG:
+      if (ode_wg_scratch(w, a, &global)) return -1;
+      HIP_TRY(c3p_launch_ode(a, global, st));
+      return 0;
+  }
+  return fail("internal: unknown ODE route %d", (int)r.route);
+}
+
+// The launches of a routed call inside the timing event pair.  per_step (rk4_unitary's dUs, [B,n_steps,D,D]): a second pass on the
+// same kernel that restarts from the identity after every step and stores the per-step propagators transposed; never segmented.
+int ode_launch(OdeCall& c, const OdeArgs& a, OdeRoute r, cplx* per_step = nullptr) {
+  if (record_start(c.w, c.st)) return -1;
+  if (ode_launch_pass(c, a, r)) return -1;
+  if (per_step) {
+    OdeArgs p = a;
+    p.want_all = 1;
+    p.reset_each_step = 1;
+    p.transpose_out = 1;
+    p.states = per_step;
+    const OdeRouteId whole = r.route == ODE_RT_ROW_SEG ? ODE_RT_ROW : r.route == ODE_RT_MFMA_SEG ? ODE_RT_RHOQ : r.route;
+    if (ode_launch_pass(c, p, {whole, 0})) return -1;
+  }
+  return record_stop(c.w, c.st);
 }
 }  // namespace
 
@@ -2491,57 +2660,17 @@ int c3p_ode_solve(const void* h0, const void* hks, const double* signals, const 
                   int C, double dt, int B, int K, int N, int D, int solver, int step,
                   const void* init, int64_t init_bstride, int want_all, int flags, void* states,
                   void* stream) {
-  if (B < 0 || N < 0 || D <= 0 || K < 0 || K > 32) return fail("bad sizes B=%d K=%d N=%d D=%d", B, K, N, D);
-  if (solver < 0 || solver > 3) return fail("unknown solver id %d", solver);
-  if (step < 0 || step > 2) return fail("unknown step function id %d", step);
-  if (flags & C3P_COL_PER_SAMPLE) return fail("c3p_ode_solve: C3P_COL_PER_SAMPLE is not served (one col_ops [C,D,D] for the batch)");
-  if (B == 0) return 0;
-  if (N < 2) return fail("the ODE solver needs at least two time samples (N=%d)", N);
-  if (!h0 || !init || !states) return fail("NULL pointer argument");
-  if (K > 0 && (!hks || !signals)) return fail("K > 0 but hks/signals missing");
-  if (step == C3P_STEP_LINDBLAD && (!col_ops || C <= 0)) return fail("lindblad step needs col_ops");
-  if (step != C3P_STEP_LINDBLAD) C = 0;
-  const int M = (step == C3P_STEP_SCHRODINGER) ? 1 : D;
+  OdeCall c;
+  const int rc = c.open(false, [] { return 0; }, h0, hks, signals, col_ops, C, dt, B, K, N, D, solver, step, init, init_bstride, flags,
+                        states, nullptr, stream);
+  if (rc) return rc < 0 ? -1 : 0;
+  OdeArgs& a = c.a;
   const size_t cs = sizeof(cplx);
-  hipStream_t st = (hipStream_t)stream;
-  WsLock lk(st);
-  DeviceWs* w = lk.w;
-  if (!w) return fail("no HIP device");
-  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-  Stage sg{w, st};
-  const void *d_h0 = h0, *d_hks = hks, *d_sig = signals, *d_col = col_ops, *d_init = init;
   void* d_states = states;
-  const size_t out_elems = (size_t)B * (want_all ? N : 1) * D * M;
-  if (flags & C3P_HOST_PTRS) {
-    const size_t init_elems = init_bstride ? (size_t)(B - 1) * init_bstride + (size_t)D * M : (size_t)D * M;
-    if (sg.in(h0, (size_t)D * D * cs, &d_h0)) return -1;
-    if (sg.in(hks, (size_t)K * D * D * cs, &d_hks)) return -1;
-    if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
-    if (sg.in(col_ops, (size_t)C * D * D * cs, &d_col)) return -1;
-    if (sg.in(init, init_elems * cs, &d_init)) return -1;
-    if (sg.out(states, out_elems * cs, &d_states)) return -1;
-  }
-  OdeArgs a = {};
-  a.h0 = (const cplx*)d_h0;
-  a.hks = (const cplx*)d_hks;
-  a.signals = (const double*)d_sig;
-  a.col_ops = (const cplx*)d_col;
-  a.init = (const cplx*)d_init;
-  a.init_bstride = init_bstride;
-  a.dt = dt;
-  a.B = B;
-  a.K = K;
-  a.N = N;
-  a.D = D;
-  a.M = M;
-  a.C = C;
-  a.solver = solver;
-  a.step = step;
+  if (c.host() && c.sg.out(states, (size_t)B * (want_all ? N : 1) * D * a.M * cs, &d_states)) return -1;
   a.want_all = want_all ? 1 : 0;
-  a.n_steps = N;
-  a.u_stride = 1;
   a.states = (cplx*)d_states;
-  if (K > 4 && D <= 16 && N >= 2 && step == C3P_STEP_SCHRODINGER && !c3p_opt_on(C3P_OPT_ode_wg)) {
+  if (K > 4 && D <= 16 && step == C3P_STEP_SCHRODINGER && !c3p_opt_on(C3P_OPT_ode_wg)) {
     // more than four control lines, vector states: the lane-row kernels hold the rows of four operators in registers; H is
     // assembled for every sample index first (B N D^2 numbers) and the kernel interpolates it between consecutive samples --
     // the same linear interpolation, taken after the sum instead of before it.  Beyond 8 GB, and for rho-valued states (no
@@ -2549,8 +2678,8 @@ int c3p_ode_solve(const void* h0, const void* hks, const double* signals, const 
     const size_t hb = (size_t)B * N * D * D * cs;
     if (hb <= ((size_t)8 << 30)) {
       void* hv;
-      if (ws_get(w, SL_SEG_F, hb, &hv)) return -1;
-      LAUNCH_TRY(c3p_launch_ode_assemble_hs(a, (cplx*)hv, st));
+      if (ws_get(c.w, SL_SEG_F, hb, &hv)) return -1;
+      HIP_TRY(c3p_launch_ode_assemble_hs(a, (cplx*)hv, c.st));
       a.hs = (const cplx*)hv;
       a.hs_bstride = (long)N * D * D;
       a.hs_lerp = 1;
@@ -2561,168 +2690,39 @@ int c3p_ode_solve(const void* h0, const void* hks, const double* signals, const 
       }
     }
   }
-  if (c3p_ode_row_supported(a)) {
-    // lane-row kernels (c3p_ode_row.hip): one sample per 16-lane row, state and operator rows in registers
-    void* aux = nullptr;
-    if (C > 0 && ws_get(w, SL_TABLES, c3p_ode_row_aux_bytes(D, C), &aux)) return -1;
-    g_last_kernel = C3P_KERNEL_ODE_ROW;
-    if (record_start(w, st)) return -1;
-    const int nseg = (step == C3P_STEP_SCHRODINGER) ? c3p_ode_row_segments(a) : 0;
-    const int tseg = (step == C3P_STEP_SCHRODINGER && nseg == 0) ? c3p_ode_row_traj_segments(a) : 0;
-    if (tseg > 0) {
-      // small batch, whole trajectory: segment maps -> start state of every segment -> the pieces side by side
-      if (ode_trajectory_segmented(w, a, tseg, st)) return -1;
-    } else if (nseg > 0) {
-      // small batch, final state only: the equations are linear, so the interval is cut into nseg time segments, every
-      // segment integrates the D columns of the identity (its step map), the maps are multiplied in order by the small-D
-      // chain kernel and the product is applied to the initial state -- D x the arithmetic on nseg x D x the lanes
-      if (ode_segmented(w, a, nseg, (const cplx*)d_init, init_bstride, nullptr, (cplx*)d_states, st)) return -1;
-    } else {
-      // rho-valued states, more than four control lines, no collapse operators, a batch that leaves SIMDs idle on the lane rows
-      // (one wave = four samples; measured crossover between 2048 and 16 384 samples, profiles/r04/ode_fallbacks.json): COMPLEX
-      // operators run 1.1 - 1.3x faster on the workgroup kernel there, real ones 1.4 - 1.7x faster on the lane rows.  The device
-      // decides (both kernels look at the operators and one of them leaves at once), as regr_prep_kernel does for the PWC path.
-      const bool split = step == C3P_STEP_VON_NEUMANN && K > 4 && C == 0 && B <= 4096 && !c3p_opt_on(C3P_OPT_ode_no_split);
-      a.complex_to_wg = split ? 1 : 0;
-      // (the host cannot know which of the two did the work: a distinct id, so that profiles do not book a workgroup-kernel
-      // run on the lane rows; the second launch -- B workgroups of 256 threads that leave at once for real operators -- is paid
-      // on every such call)
-      if (split) g_last_kernel = C3P_KERNEL_ODE_ROW_OR_WG;
-      LAUNCH_TRY(c3p_launch_ode_row(a, aux, st));
-      if (split) {
-        OdeArgs g = a;
-        g.complex_to_wg = 0;
-        g.wg_if_complex = 1;
-        const size_t elems = c3p_ode_elems(D, M, C);
-        const bool global = elems * cs > (size_t)(150 * 1024);
-        if (global) {
-          void* v;
-          if (ws_get(w, SL_SCRATCH, (size_t)B * elems * cs, &v)) return -1;
-          g.scratch = (cplx*)v;
-          g.scratch_stride = (long)elems;
-        }
-        LAUNCH_TRY(c3p_launch_ode(g, global, st));
-      }
-    }
-    if (record_stop(w, st)) return -1;
-    if (flags & C3P_HOST_PTRS) return sg.finish();
-    return 0;
-  }
-  if (step == C3P_STEP_SCHRODINGER) {
-    const int tseg = ode_mfma_traj_segments(a);
-    if (tseg > 0) {
-      g_last_kernel = C3P_KERNEL_ODE_ROW;
-      if (record_start(w, st)) return -1;
-      if (ode_trajectory_segmented(w, a, tseg, st)) return -1;
-      if (record_stop(w, st)) return -1;
-      if (flags & C3P_HOST_PTRS) return sg.finish();
-      return 0;
-    }
-    const int nseg = ode_mfma_segments(a, 4);
-    if (nseg > 0) {
-      // few states at 17 <= D <= 48, final state only: segment maps on the matrix-core kernel, psi = U psi0
-      g_last_kernel = C3P_KERNEL_ODE_MFMA;
-      if (record_start(w, st)) return -1;
-      if (ode_segmented(w, a, nseg, (const cplx*)d_init, init_bstride, nullptr, (cplx*)d_states, st)) return -1;
-      if (record_stop(w, st)) return -1;
-      if (flags & C3P_HOST_PTRS) return sg.finish();
-      return 0;
-    }
-  }
-  if (c3p_ode_rowq_supported(a)) {
-    // 17 <= D <= 48 vector states: several DPP rows per sample, operators in LDS (c3p_ode_rowq.hip)
-    g_last_kernel = C3P_KERNEL_ODE_ROW;
-    if (record_start(w, st)) return -1;
-    LAUNCH_TRY(c3p_launch_ode_rowq(a, st));
-    if (record_stop(w, st)) return -1;
-    if (flags & C3P_HOST_PTRS) return sg.finish();
-    return 0;
-  }
-  if (c3p_ode_rhoq_supported(a)) {
-    // 17 <= D <= 48 rho-valued states: register tiles + 16x16x4 fp64 MFMA products (c3p_ode_rhoq.hip)
-    g_last_kernel = C3P_KERNEL_ODE_MFMA;
-    if (record_start(w, st)) return -1;
-    LAUNCH_TRY(c3p_launch_ode_rhoq(a, st));
-    if (record_stop(w, st)) return -1;
-    if (flags & C3P_HOST_PTRS) return sg.finish();
-    return 0;
-  }
-  g_last_kernel = C3P_KERNEL_ODE_WG;
-  const size_t elems = c3p_ode_elems(D, M, C);
-  const bool global = elems * cs > (size_t)(150 * 1024);
-  if (global) {
-    void* v;
-    if (ws_get(w, SL_SCRATCH, (size_t)B * elems * cs, &v)) return -1;
-    a.scratch = (cplx*)v;
-    a.scratch_stride = (long)elems;
-  }
-  LAUNCH_TRY(c3p_launch_ode(a, global, st));
-  if (flags & C3P_HOST_PTRS) return sg.finish();
-  return 0;
+  if (ode_launch(c, a, ode_route(a))) return -1;
+  return c.finish();
 }
 
 int c3p_ode_solve_vjp(const void* h0, const void* hks, const double* signals, const void* col_ops, int C, double dt, int B, int K,
                       int N, int D, int solver, int step, const void* init, int64_t init_bstride, const void* states_bar,
                       int bar_all, const void* target, int64_t target_bstride, int flags, double* grad_signals, void* init_bar,
                       double* infid_out, void* final_out, void* stream) {
-  if (B < 0 || N < 0 || D <= 0 || K < 0 || K > 32) return fail("bad sizes B=%d K=%d N=%d D=%d", B, K, N, D);
-  if (solver < 0 || solver > 3) return fail("unknown solver id %d", solver);
-  if (step < 0 || step > 2) return fail("unknown step function id %d", step);
-  if (flags & C3P_COL_PER_SAMPLE) return fail("c3p_ode_solve_vjp: C3P_COL_PER_SAMPLE is not served (one col_ops [C,D,D] for the batch)");
-  if (B == 0) return 0;
-  if ((states_bar != nullptr) == (target != nullptr)) return fail("exactly one of states_bar and target must be given");
-  if (target && bar_all) return fail("bar_all needs states_bar");
-  if (init_bstride < 0 || target_bstride < 0) return fail("negative stride");
-  if (N < 2) return fail("the ODE solver needs at least two time samples (N=%d)", N);
-  if (!h0 || !init) return fail("NULL pointer argument");
-  if (K > 0 && (!hks || !signals || !grad_signals)) return fail("K > 0 but hks/signals/grad_signals missing");
-  if (step == C3P_STEP_LINDBLAD && (!col_ops || C <= 0)) return fail("lindblad step needs col_ops");
-  if (step != C3P_STEP_LINDBLAD) C = 0;
-  const int M = (step == C3P_STEP_SCHRODINGER) ? 1 : D;
+  OdeCall c;
+  const int rc = c.open(true, [&] {
+        if ((states_bar != nullptr) == (target != nullptr)) return fail("exactly one of states_bar and target must be given");
+        if (target && bar_all) return fail("bar_all needs states_bar");
+        if (init_bstride < 0 || target_bstride < 0) return fail("negative stride");
+        return 0;
+      }, h0, hks, signals, col_ops, C, dt, B, K, N, D, solver, step, init, init_bstride, flags, nullptr, grad_signals, stream);
+  if (rc) return rc < 0 ? -1 : 0;
+  const int M = c.a.M;
   const size_t cs = sizeof(cplx);
-  hipStream_t st = (hipStream_t)stream;
-  WsLock lk(st);
-  DeviceWs* w = lk.w;
-  if (!w) return fail("no HIP device");
-  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-  Stage sg{w, st};
-  const void *d_h0 = h0, *d_hks = hks, *d_sig = signals, *d_col = col_ops, *d_init = init, *d_bar = states_bar, *d_tgt = target;
+  const void *d_bar = states_bar, *d_tgt = target;
   void *d_grad = grad_signals, *d_ib = init_bar, *d_inf = infid_out, *d_fin = final_out;
   const size_t state_bytes = (size_t)B * D * M * cs;
-  if (flags & C3P_HOST_PTRS) {
-    const size_t init_elems = init_bstride ? (size_t)(B - 1) * init_bstride + (size_t)D * M : (size_t)D * M;
+  if (c.host()) {
     const size_t tgt_elems = target_bstride ? (size_t)(B - 1) * target_bstride + (size_t)D : (size_t)D;
-    if (sg.in(h0, (size_t)D * D * cs, &d_h0)) return -1;
-    if (sg.in(hks, (size_t)K * D * D * cs, &d_hks)) return -1;
-    if (sg.in(signals, (size_t)B * K * N * sizeof(double), &d_sig)) return -1;
-    if (sg.in(col_ops, (size_t)C * D * D * cs, &d_col)) return -1;
-    if (sg.in(init, init_elems * cs, &d_init)) return -1;
-    if (states_bar && sg.in(states_bar, state_bytes * (bar_all ? (size_t)N : 1), &d_bar)) return -1;
-    if (target && sg.in(target, tgt_elems * cs, &d_tgt)) return -1;
-    if (sg.out(grad_signals, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
-    if (sg.out(init_bar, state_bytes, &d_ib)) return -1;
-    if (sg.out(infid_out, (size_t)B * sizeof(double), &d_inf)) return -1;
-    if (sg.out(final_out, state_bytes, &d_fin)) return -1;
+    if (states_bar && c.sg.in(states_bar, state_bytes * (bar_all ? (size_t)N : 1), &d_bar)) return -1;
+    if (target && c.sg.in(target, tgt_elems * cs, &d_tgt)) return -1;
+    if (c.sg.out(grad_signals, (size_t)B * K * N * sizeof(double), &d_grad)) return -1;
+    if (c.sg.out(init_bar, state_bytes, &d_ib)) return -1;
+    if (c.sg.out(infid_out, (size_t)B * sizeof(double), &d_inf)) return -1;
+    if (c.sg.out(final_out, state_bytes, &d_fin)) return -1;
   }
-  const OdeVjpPlan pl = c3p_ode_vjp_plan(B, K, N, D, M, C, step);
+  const OdeVjpPlan pl = c3p_ode_vjp_plan(B, K, N, D, M, c.a.C, step);
   OdeVjpArgs v = {};
-  v.f.h0 = (const cplx*)d_h0;
-  v.f.hks = (const cplx*)d_hks;
-  v.f.signals = (const double*)d_sig;
-  v.f.col_ops = (const cplx*)d_col;
-  v.f.init = (const cplx*)d_init;
-  v.f.init_bstride = init_bstride;
-  v.f.dt = dt;
-  v.f.B = B;
-  v.f.K = K;
-  v.f.N = N;
-  v.f.D = D;
-  v.f.M = M;
-  v.f.C = C;
-  v.f.solver = solver;
-  v.f.step = step;
-  v.f.n_steps = N;
-  v.f.u_stride = 1;
+  v.f = c.a;
   v.states_bar = (const cplx*)d_bar;
   v.bar_all = bar_all ? 1 : 0;
   v.target = (const cplx*)d_tgt;
@@ -2738,12 +2738,12 @@ int c3p_ode_solve_vjp(const void* h0, const void* hks, const double* signals, co
   const size_t ws_rows = pl.row ? (size_t)((pl.rows + 3) / 4) * 4 : (size_t)pl.rows;
   const size_t ws_bytes = ws_rows * pl.ws_elems * cs;
   void* ws;
-  if (ws_get(w, SL_ODE_VJP_WS, ws_bytes, &ws)) return -1;
+  if (ws_get(c.w, SL_ODE_VJP_WS, ws_bytes, &ws)) return -1;
   v.ws = (cplx*)ws;
   v.ws_stride = (long)pl.ws_elems;
   if (!pl.row && pl.wg_global) {
     void* sc;
-    if (ws_get(w, SL_SCRATCH, (size_t)pl.rows * pl.wg_elems * cs, &sc)) return -1;
+    if (ws_get(c.w, SL_SCRATCH, (size_t)pl.rows * pl.wg_elems * cs, &sc)) return -1;
     v.scratch = (cplx*)sc;
     v.scratch_stride = (long)pl.wg_elems;
   }
@@ -2751,11 +2751,10 @@ int c3p_ode_solve_vjp(const void* h0, const void* hks, const double* signals, co
   g_note_plan = "checkpoint interval C=" + std::to_string(pl.Cint) + " checkpoints=" + std::to_string(pl.nck) + " workspace=" +
                 std::to_string(ws_bytes) + " bytes (cap " + std::to_string((size_t)C3P_ODE_VJP_WS_CAP) + ") rows=" +
                 std::to_string(pl.rows);
-  if (record_start(w, st)) return -1;
-  LAUNCH_TRY(c3p_launch_ode_vjp(v, pl, st));
-  if (record_stop(w, st)) return -1;
-  if (flags & C3P_HOST_PTRS) return sg.finish();
-  return 0;
+  if (record_start(c.w, c.st)) return -1;
+  HIP_TRY(c3p_launch_ode_vjp(v, pl, c.st));
+  if (record_stop(c.w, c.st)) return -1;
+  return c.finish();
 }
 
 int c3p_rk4_unitary(const void* h0, const void* hks, const double* signals, const void* hs,
@@ -2768,127 +2767,32 @@ int c3p_rk4_unitary(const void* h0, const void* hks, const double* signals, cons
   if (!hs && (!h0 || (K > 0 && (!hks || !signals)))) return fail("NULL Hamiltonian input");
   const int n_steps = (Ns - 1) / 2;  // range(0, len(h) - 2, 2), propagation.py:79,251
   const size_t cs = sizeof(cplx);
-  hipStream_t st = (hipStream_t)stream;
-  WsLock lk(st);
-  DeviceWs* w = lk.w;
-  if (!w) return fail("no HIP device");
-  if (!lk.ok) return fail("hipStreamWaitEvent on the previous call's stream failed");
-  Stage sg{w, st};
-  const void *d_h0 = h0, *d_hks = hks, *d_sig = signals, *d_hs = hs;
+  OdeCall c;
+  if (c.lock(flags, stream)) return -1;
+  const void *d_sig = signals, *d_hs = hs;
   void *d_U = U_out, *d_dUs = dUs_out;
-  if (flags & C3P_HOST_PTRS) {
+  if (c.host()) {
     if (hs) {
       const size_t one = (size_t)Ns * D * D;
-      if (sg.in(hs, (hs_bstride ? (size_t)(B - 1) * hs_bstride + one : one) * cs, &d_hs)) return -1;
-    } else {
-      if (sg.in(h0, (size_t)D * D * cs, &d_h0)) return -1;
-      if (sg.in(hks, (size_t)K * D * D * cs, &d_hks)) return -1;
-      if (sg.in(signals, (size_t)B * K * Ns * sizeof(double), &d_sig)) return -1;
+      if (c.sg.in(hs, (hs_bstride ? (size_t)(B - 1) * hs_bstride + one : one) * cs, &d_hs)) return -1;
+    } else if (c.stage_h(h0, hks, d_sig, B, K, Ns, D)) {
+      return -1;
     }
-    if (sg.out(U_out, (size_t)B * D * D * cs, &d_U)) return -1;
-    if (sg.out(dUs_out, dUs_out ? (size_t)B * n_steps * D * D * cs : 0, &d_dUs)) return -1;
+    if (c.sg.out(U_out, (size_t)B * D * D * cs, &d_U)) return -1;
+    if (c.sg.out(dUs_out, dUs_out ? (size_t)B * n_steps * D * D * cs : 0, &d_dUs)) return -1;
   }
   // identity initial state, shared by all samples
   void* v_id;
-  if (ws_get(w, SL_CLP, (size_t)D * D * cs, &v_id)) return -1;
-  LAUNCH_TRY(c3p_launch_ode_identity((cplx*)v_id, D, st));  // (on the device: no host round trip, capturable)
-  OdeArgs a = {};
-  a.h0 = (const cplx*)d_h0;
-  a.hks = (const cplx*)d_hks;
-  a.signals = (const double*)d_sig;
-  a.hs = (const cplx*)d_hs;
-  a.hs_bstride = hs_bstride;
-  a.init = (const cplx*)v_id;
-  a.init_bstride = 0;
-  a.dt = dt;
-  a.B = B;
-  a.K = hs ? 0 : K;
-  a.N = Ns;
-  a.D = D;
-  a.M = D;
-  a.C = 0;
-  a.solver = C3P_SOLVER_RK4;
-  a.step = C3P_STEP_PROPAGATOR_ID;
-  a.n_steps = n_steps;
-  a.u_stride = 2;
-  if (c3p_ode_row_supported(a)) {
-    // every column of the propagator is an independent Schroedinger problem: B x D vector states on the lane-row kernel
-    g_last_kernel = C3P_KERNEL_ODE_ROW;
-    a.want_all = 0;
-    a.states = (cplx*)d_U;
-    const int nseg = c3p_ode_row_segments(a);
-    if (nseg > 0) {  // few gates: time segments fill the chip (see c3p_ode_solve)
-      if (ode_segmented(w, a, nseg, nullptr, 0, (cplx*)d_U, nullptr, st)) return -1;
-    } else {
-      LAUNCH_TRY(c3p_launch_ode_row(a, nullptr, st));
-    }
-    if (d_dUs) {
-      a.want_all = 1;
-      a.reset_each_step = 1;
-      a.transpose_out = 1;
-      a.states = (cplx*)d_dUs;
-      LAUNCH_TRY(c3p_launch_ode_row(a, nullptr, st));
-    }
-    if (flags & C3P_HOST_PTRS) return sg.finish();
-    return 0;
-  }
-  if (c3p_ode_rhoq_supported(a)) {
-    // 17 <= D <= 48: the propagator is a D x D matrix state with ONE product per stage: matrix-core kernel (c3p_ode_rhoq.hip)
-    g_last_kernel = C3P_KERNEL_ODE_MFMA;
-    a.want_all = 0;
-    a.states = (cplx*)d_U;
-    const int nseg = ode_mfma_segments(a, 2);
-    if (nseg > 0) {  // few gates: one workgroup per (gate, time segment)
-      if (ode_segmented(w, a, nseg, nullptr, 0, (cplx*)d_U, nullptr, st)) return -1;
-    } else {
-      LAUNCH_TRY(c3p_launch_ode_rhoq(a, st));
-    }
-    if (d_dUs) {
-      a.want_all = 1;
-      a.reset_each_step = 1;
-      a.transpose_out = 1;
-      a.states = (cplx*)d_dUs;
-      LAUNCH_TRY(c3p_launch_ode_rhoq(a, st));
-    }
-    if (flags & C3P_HOST_PTRS) return sg.finish();
-    return 0;
-  }
-  if (c3p_ode_rowq_supported(a)) {
-    g_last_kernel = C3P_KERNEL_ODE_ROW;
-    a.want_all = 0;
-    a.states = (cplx*)d_U;
-    LAUNCH_TRY(c3p_launch_ode_rowq(a, st));
-    if (d_dUs) {
-      a.want_all = 1;
-      a.reset_each_step = 1;
-      a.transpose_out = 1;
-      a.states = (cplx*)d_dUs;
-      LAUNCH_TRY(c3p_launch_ode_rowq(a, st));
-    }
-    if (flags & C3P_HOST_PTRS) return sg.finish();
-    return 0;
-  }
-  g_last_kernel = C3P_KERNEL_ODE_WG;
-  const size_t elems = c3p_ode_elems(D, D, 0);
-  const bool global = elems * cs > (size_t)(150 * 1024);
-  if (global) {
-    void* v;
-    if (ws_get(w, SL_SCRATCH, (size_t)B * elems * cs, &v)) return -1;
-    a.scratch = (cplx*)v;
-    a.scratch_stride = (long)elems;
-  }
-  a.want_all = 0;
-  a.states = (cplx*)d_U;
-  LAUNCH_TRY(c3p_launch_ode(a, global, st));
-  if (d_dUs) {
-    a.want_all = 1;
-    a.reset_each_step = 1;
-    a.transpose_out = 1;
-    a.states = (cplx*)d_dUs;
-    LAUNCH_TRY(c3p_launch_ode(a, global, st));
-  }
-  if (flags & C3P_HOST_PTRS) return sg.finish();
-  return 0;
+  if (ws_get(c.w, SL_CLP, (size_t)D * D * cs, &v_id)) return -1;
+  HIP_TRY(c3p_launch_ode_identity((cplx*)v_id, D, c.st));  // (on the device: no host round trip, capturable)
+  c.fill(h0, hks, d_sig, nullptr, v_id, 0, dt, B, hs ? 0 : K, Ns, D, D, 0, C3P_SOLVER_RK4, C3P_STEP_PROPAGATOR_ID, n_steps, 2);
+  c.a.hs = (const cplx*)d_hs;
+  c.a.hs_bstride = hs_bstride;
+  c.a.states = (cplx*)d_U;
+  // every column of the propagator is an independent Schroedinger problem (lane rows: B x D vector states; few gates: time
+  // segments fill the chip); the per-step propagators come from a second pass
+  if (ode_launch(c, c.a, ode_route(c.a), (cplx*)d_dUs)) return -1;
+  return c.finish();
 }
 
 int c3p_gate_overlap(const void* U, int B, int D, const int32_t* comp_rows, int L, const void* ideal,

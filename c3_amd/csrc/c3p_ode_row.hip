@@ -772,51 +772,41 @@ hipError_t c3p_launch_ode_row(const OdeArgs& A, void* aux, hipStream_t st) {
   }
 }
 
-// Time segments for small batches (final state / propagator only): how many segments to cut the time axis into.
-// 0 = integrate in one piece.  The segment maps cost D columns per sample instead of one state, and a wavefront that shares
+// Time segments for small batches: how many segments to cut the time axis into.  0 = integrate in one piece.
+// The segment maps cost D columns per sample instead of one state, and a wavefront that shares
 // its SIMD runs slower (one wave alone: 0.50 us per rk4 step at D = 9, i.e. ~70 % of the SIMD's fp64 issue rate already;
 // w waves per SIMD: ~0.14 + 0.34 w us), so the choice minimises  n_steps / S * c(waves per SIMD)  + the fixed cost of the
 // extra launches (identity, combine, apply: ~50 us) over S = 1..8 (the small-D chain kernel folds up to 8 maps in one launch).
 // Measured, D = 9, 1000 rk4 steps (direct 0.50 ms): B = 16 0.117 ms (S = 8), B = 64 0.128 ms (S = 7), B = 256 0.35 ms (S = 3).
-int c3p_ode_row_segments(const OdeArgs& A) {
+// `trajectory`: a second pass integrates the B x S pieces side by side from the segment start states (~60 us fixed).
+static int row_segment_search(const OdeArgs& A, bool trajectory) {
   if (c3p_opt_on(C3P_OPT_ode_no_seg)) return 0;
-  if (A.D < 2 || A.D > 12 || A.want_all || A.reset_each_step || A.n_steps < 64) return 0;  // (the combine runs on the small-D chain kernel)
+  if (A.D < 2 || A.D > 12 || A.reset_each_step || A.n_steps < 64) return 0;  // (the combine runs on the small-D chain kernel)
   auto step_cost = [](long rows) {  // relative time of one RK step when `rows` DPP rows (4 per wave) are spread over 1024 SIMDs
     const long w = (rows + 4095) / 4096;
     return w <= 1 ? 0.50 : 0.14 + 0.34 * (double)w;
   };
-  const double fixed = 50.0 * (A.solver == 0 || A.solver == 1 ? 1.0 : 0.55);  // in units of rk4 steps' microseconds (7-stage solvers: longer steps)
+  // in units of rk4 steps' microseconds (7-stage solvers: longer steps)
+  const double fixed = (trajectory ? 60.0 : 50.0) * (A.solver == 0 || A.solver == 1 ? 1.0 : 0.55);
   if ((long)A.B * A.M > 4096) return 0;  // more than one wave per SIMD already: throughput, not latency (not measured beyond)
   const double direct = (double)A.n_steps * step_cost((long)A.B * A.M);
   double best = direct * 0.8;  // a segmented launch has to win by a margin
   int pick = 0;
   for (int S = 2; S <= 8 && S <= A.n_steps / 32; ++S) {
-    const double c = (double)((A.n_steps + S - 1) / S) * step_cost((long)A.B * S * A.D) + fixed;
+    const double per_step = trajectory ? step_cost((long)A.B * S * A.D) + step_cost((long)A.B * S) : step_cost((long)A.B * S * A.D);
+    const double c = (double)((A.n_steps + S - 1) / S) * per_step + fixed;
     if (c < best) best = c, pick = S;
   }
   return pick;
 }
 
-// Trajectories (want_all) of small batches: the segment maps of ode_segmented give the state at the START of every segment
-// (one small kernel), and a second pass integrates the B x S pieces side by side, each writing its own range of the
-// trajectory.  Cost model as c3p_ode_row_segments, plus the second pass.
+// final state / propagator only: segment maps, their ordered product, psi = U psi0 (ode_segmented)
+int c3p_ode_row_segments(const OdeArgs& A) { return A.want_all ? 0 : row_segment_search(A, false); }
+
+// Trajectories (want_all) of small batches of vector states: the segment maps give the state at the START of every segment
+// (one small kernel), and the second pass writes every piece's own range of the trajectory.
 int c3p_ode_row_traj_segments(const OdeArgs& A) {
-  if (c3p_opt_on(C3P_OPT_ode_no_seg)) return 0;
-  if (A.D < 2 || A.D > 12 || !A.want_all || A.M != 1 || A.reset_each_step || A.transpose_out || A.n_steps < 64) return 0;
-  auto step_cost = [](long rows) {
-    const long w = (rows + 4095) / 4096;
-    return w <= 1 ? 0.50 : 0.14 + 0.34 * (double)w;
-  };
-  const double fixed = 60.0 * (A.solver == 0 || A.solver == 1 ? 1.0 : 0.55);
-  if ((long)A.B > 4096) return 0;
-  const double direct = (double)A.n_steps * step_cost((long)A.B);
-  double best = direct * 0.8;
-  int pick = 0;
-  for (int S = 2; S <= 8 && S <= A.n_steps / 32; ++S) {
-    const double c = (double)((A.n_steps + S - 1) / S) * (step_cost((long)A.B * S * A.D) + step_cost((long)A.B * S)) + fixed;
-    if (c < best) best = c, pick = S;
-  }
-  return pick;
+  return !A.want_all || A.M != 1 || A.transpose_out ? 0 : row_segment_search(A, true);
 }
 
 namespace {

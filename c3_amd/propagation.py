@@ -879,51 +879,9 @@ def pwc(model, gen, instr, folding_stack: list, batch_size=None) -> Dict:
 # --------------------------------------------------------------------------
 
 
-def ode_solve_batch(h0, hks, signals, dt, init_state, solver="rk4", step_function="schrodinger", col_ops=None, final_only=False):
-    """RK integration of B independent samples: signals [B,K,N]; init [D,M] or [B,D,M]."""
-    _shared_col_only(col_ops, "the ODE solver")
-    call = _Call(h0, hks, signals, init_state, col_ops)
-    lib = _lib.load()
-    if solver not in solver_dict:
-        raise C3PropError(f"C3:Error: unknown solver '{solver}'")
-    if col_ops is not None:
-        step_function = "lindblad"
-    if step_function not in step_dict:
-        raise C3PropError(f"C3:Error: unknown step function '{step_function}'")
-    h0 = call.c128(h0)
-    hks = call.c128(hks)
-    sig = call.f64(signals)
-    if sig.ndim != 3:
-        raise C3PropError(f"C3:Error: signals must be [B,K,N], got {tuple(sig.shape)}")
-    B, K, N = (int(s) for s in sig.shape)
-    D = int(h0.shape[-1])
-    # c3p_ode_solve takes ONE set of operators for the whole batch (no per-sample strides in the ABI)
-    if h0.ndim != 2 or tuple(h0.shape) != (D, D):
-        raise C3PropError(f"C3:Error: ode solvers take one drift Hamiltonian [D,D], got {tuple(h0.shape)}")
-    if hks.ndim != 3 or tuple(hks.shape) != (K, D, D):
-        raise C3PropError(f"C3:Error: {K} signal channels need control Hamiltonians [{K},{D},{D}], got {tuple(hks.shape)}")
-    M = 1 if step_function == "schrodinger" else D
-    init = call.c128(init_state)
-    if tuple(init.shape[-2:]) != (D, M):
-        raise C3PropError(f"C3:Error: initial state must be [..,{D},{M}] for step '{step_function}', got {tuple(init.shape)}")
-    init_bs = _bstride(init, 2, B, "init_state")
-    col = None
-    Cn = 0
-    if step_function == "lindblad":
-        if col_ops is None:
-            raise C3PropError("C3:Error: the lindblad step needs collapse operators")
-        col = call.c128(col_ops if _is_torch(col_ops) else np.asarray(col_ops))
-        Cn = int(col.shape[0])
-    out = call.empty((B, D, M) if final_only else (B, N, D, M))
-    rc = lib.c3p_ode_solve(
-        _ptr(h0), _ptr(hks), _ptr(sig), _ptr(col), Cn, float(dt), B, K, N, D, solver_dict[solver],
-        step_dict[step_function], _ptr(init), init_bs, 0 if final_only else 1, call.flags, _ptr(out), call.stream,
-    )
-    _lib.check(rc)
-    return out
-
-
-def _ode_vjp_call(h0, hks, signals, dt, init_state, solver, step_function, col_ops, states_bar, target, want_states):
+def _ode_operands(h0, hks, signals, init_state, solver, step_function, col_ops, states_bar=None, target=None, vjp=False):
+    """What c3p_ode_solve and c3p_ode_solve_vjp take in common, checked and converted: one flat tuple
+    (call, lib, h0, hks, sig, col, Cn, init, init_bs, B, K, N, D, M, solver id, step id)."""
     _shared_col_only(col_ops, "the ODE solver")
     call = _Call(h0, hks, signals, init_state, col_ops, states_bar, target)
     lib = _lib.load()
@@ -933,7 +891,7 @@ def _ode_vjp_call(h0, hks, signals, dt, init_state, solver, step_function, col_o
         step_function = "lindblad"
     if step_function not in step_dict:
         raise C3PropError(f"C3:Error: unknown step function '{step_function}'")
-    if (states_bar is None) == (target is None):
+    if vjp and (states_bar is None) == (target is None):
         raise C3PropError("C3:Error: exactly one of states_bar and target must be given")
     h0 = call.c128(h0)
     hks = call.c128(hks)
@@ -942,6 +900,7 @@ def _ode_vjp_call(h0, hks, signals, dt, init_state, solver, step_function, col_o
         raise C3PropError(f"C3:Error: signals must be [B,K,N], got {tuple(sig.shape)}")
     B, K, N = (int(s) for s in sig.shape)
     D = int(h0.shape[-1])
+    # both entries take ONE set of operators for the whole batch (no per-sample strides in the ABI)
     if h0.ndim != 2 or tuple(h0.shape) != (D, D):
         raise C3PropError(f"C3:Error: ode solvers take one drift Hamiltonian [D,D], got {tuple(h0.shape)}")
     if hks.ndim != 3 or tuple(hks.shape) != (K, D, D):
@@ -958,6 +917,25 @@ def _ode_vjp_call(h0, hks, signals, dt, init_state, solver, step_function, col_o
             raise C3PropError("C3:Error: the lindblad step needs collapse operators")
         col = call.c128(col_ops if _is_torch(col_ops) else np.asarray(col_ops))
         Cn = int(col.shape[0])
+    return call, lib, h0, hks, sig, col, Cn, init, init_bs, B, K, N, D, M, solver_dict[solver], step_dict[step_function]
+
+
+def ode_solve_batch(h0, hks, signals, dt, init_state, solver="rk4", step_function="schrodinger", col_ops=None, final_only=False):
+    """RK integration of B independent samples: signals [B,K,N]; init [D,M] or [B,D,M]."""
+    call, lib, h0, hks, sig, col, Cn, init, init_bs, B, K, N, D, M, solver_id, step_id = _ode_operands(
+        h0, hks, signals, init_state, solver, step_function, col_ops)
+    out = call.empty((B, D, M) if final_only else (B, N, D, M))
+    rc = lib.c3p_ode_solve(
+        _ptr(h0), _ptr(hks), _ptr(sig), _ptr(col), Cn, float(dt), B, K, N, D, solver_id, step_id, _ptr(init), init_bs,
+        0 if final_only else 1, call.flags, _ptr(out), call.stream,
+    )
+    _lib.check(rc)
+    return out
+
+
+def _ode_vjp_call(h0, hks, signals, dt, init_state, solver, step_function, col_ops, states_bar, target, want_states):
+    call, lib, h0, hks, sig, col, Cn, init, init_bs, B, K, N, D, M, solver_id, step_id = _ode_operands(
+        h0, hks, signals, init_state, solver, step_function, col_ops, states_bar, target, True)
     bar = tgt = None
     bar_all = 0
     tgt_bs = 0
@@ -985,7 +963,7 @@ def _ode_vjp_call(h0, hks, signals, dt, init_state, solver, step_function, col_o
     init_bar = call.empty((B, D, M))
     final = call.empty((B, D, M)) if want_states else None
     rc = lib.c3p_ode_solve_vjp(
-        _ptr(h0), _ptr(hks), _ptr(sig), _ptr(col), Cn, float(dt), B, K, N, D, solver_dict[solver], step_dict[step_function],
+        _ptr(h0), _ptr(hks), _ptr(sig), _ptr(col), Cn, float(dt), B, K, N, D, solver_id, step_id,
         _ptr(init), init_bs, _ptr(bar), bar_all, _ptr(tgt), tgt_bs, call.flags, _ptr(grad), _ptr(init_bar), _ptr(goal),
         _ptr(final), call.stream,
     )

@@ -116,9 +116,12 @@ int c3p_last_kernel(void);
  * characters + NUL into buf (may be NULL) and returns the full length.  Diagnostic: INTEGRATION.md's dispatch table is
  * generated from it (tools/dispatch_table.py).  No reference counterpart. */
 int c3p_last_kernel_detail(char* buf, int cap);
-/* Device time (ms) of the most recent c3p_pwc_* call's main kernel, measured
- * with hipEvents on the stream it was launched on; valid after that stream has
- * been synchronised.  Only recorded when profiling was enabled with
+/* Device time (ms) of the main kernel(s) of the most recent call that records
+ * it -- the c3p_pwc_* entries and their gradients, and c3p_ode_solve,
+ * c3p_ode_solve_vjp and c3p_rk4_unitary on every route -- measured with
+ * hipEvents on the stream it was launched on; valid after that stream has
+ * been synchronised.  An entry that does not record leaves the previous
+ * call's time in place.  Only recorded when profiling was enabled with
  * c3p_set_profiling(1).  Returns < 0 if nothing was recorded. */
 int c3p_set_profiling(int enable); /* per device: acts on the current device's workspace */
 double c3p_last_kernel_ms(void);
