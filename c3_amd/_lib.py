@@ -73,6 +73,8 @@ SIGNATURES = {
     "c3p_synth_chain_vjp": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "c3p_synth_tab": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp]),
     "c3p_synth_tab_vjp": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c3p_synth_filt": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "c3p_synth_filt_vjp": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c3p_seq_chain": (_i, [_vp, _i64, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "c3p_seq_chain_vjp": (_i, [_vp, _i64, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "c3p_seq_state_vjp": (_i, [_vp, _i64, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),

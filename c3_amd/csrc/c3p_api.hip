@@ -3707,12 +3707,47 @@ struct SynthCall {
     double *grad_env, *grad_carrier, *grad_line, *grad_tab;  // grad_line with lines, grad_tab with T > 0
   } vjp;
   void* stream;
+  // c3p_synth_filt(_vjp) alone set the two groups below
+  struct {
+    bool has;  // stage buffers between DAC and Mixer, F = 0 included
+    const int32_t* filt_kind;   // [K,F]
+    const double* filt_params;  // [B,K,F,C3P_FILT_NPAR]
+    int F;
+    double* grad_filt;  // [B,K,F,C3P_FILT_NPAR]
+  } filters;
+  struct {
+    const double *dc_offset, *xtalk;  // [B,K], [B,K,K], each optional
+    double *grad_dc, *grad_xtalk;     // each iff its input
+  } post;
 };
+
+// host-pointer checks of the stage slots
+static int filt_check_host(const int32_t* filt_kind, const double* filt_params, int B, int K, int F, double sim_res) {
+  for (int a = 0; a < K * F; ++a)
+    if (filt_kind[a] >= C3P_FILT_NKINDS) return fail("filt_kind[%d,%d]=%d is not a C3P_FILT_* id", a / F, a % F, filt_kind[a]);
+  for (long r = 0; r < (long)B * K * F; ++r) {
+    const int kind = filt_kind[r % ((long)K * F)];
+    if (kind < 0) continue;
+    const int b = (int)(r / ((long)K * F)), k = (int)(r / F % K), f = (int)(r % F);
+    const double tau = filt_params[r * C3P_FILT_NPAR + C3P_FILT_TAU], amp = filt_params[r * C3P_FILT_NPAR + C3P_FILT_AMP];
+    if (!std::isfinite(tau) || !std::isfinite(amp))
+      return fail("filt_params[%d,%d,%d]={%g,%g} is not finite", b, k, f, tau, amp);
+    if (kind != C3P_FILT_SKIN_EFFECT && !(tau > 0.0))
+      return fail("filt_params[%d,%d,%d]: a time constant must be positive, got %g", b, k, f, tau);
+    if (kind == C3P_FILT_RESPONSE_FFT && !(std::floor(tau * sim_res) >= 1.0))
+      return fail("filt_params[%d,%d,%d]: rise_time=%g gives no ResponseFFT tap at sim_res=%g (floor(rise_time * sim_res) = 0)", b, k,
+                  f, tau, sim_res);
+  }
+  return 0;
+}
 
 static int synth_run(const SynthCall& c) {
   const int B = c.B, K = c.K, E = c.E, T = c.table.T, flags = c.flags;
   const bool vjp = c.vjp.on;
   if (B < 0 || K <= 0 || E <= 0 || T < 0) return fail("bad sizes B=%d K=%d E=%d T=%d", B, K, E, T);
+  const bool filt = c.filters.has;
+  const int F = c.filters.F;
+  if (F < 0) return fail("bad sizes F=%d", F);
   if (!(c.awg_res > 0.0) || !(c.sim_res > 0.0)) return fail("resolutions must be positive");
   const double span = c.t_end > c.t_start ? c.t_end - c.t_start : c.t_start - c.t_end;
   const int N = (int)(span * c.sim_res), Na = (int)(span * c.awg_res);  // devices.py:72-84
@@ -3724,6 +3759,10 @@ static int synth_run(const SynthCall& c) {
   if ((c.lines.line_kind == nullptr) != (c.lines.line_params == nullptr))
     return fail("line_kind and line_params go together (both NULL: the standard drive line)");
   const bool chain = c.lines.line_kind != nullptr;
+  if ((c.filters.filt_kind == nullptr) != (c.filters.filt_params == nullptr)) return fail("filt_kind and filt_params go together");
+  if (F > 0 && !c.filters.filt_kind) return fail("NULL pointer argument");
+  if (vjp && ((F > 0 && !c.filters.grad_filt) || (c.post.dc_offset && !c.post.grad_dc) || (c.post.xtalk && !c.post.grad_xtalk)))
+    return fail("NULL pointer argument");
   if (!vjp && !c.fwd.signals_out) return fail("NULL pointer argument");
   if (vjp && (!c.vjp.grad_signals || !c.vjp.grad_env || !c.vjp.grad_carrier || (chain && !c.vjp.grad_line) || (T > 0 && !c.vjp.grad_tab)))
     return fail("NULL pointer argument");
@@ -3735,6 +3774,7 @@ static int synth_run(const SynthCall& c) {
       for (int a = 0; a < K * E; ++a)
         if (c.env_shapes[a] >= C3P_ENV_NSHAPES) return fail("env_shapes[%d]=%d is not a C3P_ENV_* id", a, c.env_shapes[a]);
     }
+    if (F > 0 && filt_check_host(c.filters.filt_kind, c.filters.filt_params, B, K, F, c.sim_res)) return -1;
   }
   hipStream_t st = (hipStream_t)c.stream;
   WsLock lk(st);
@@ -3745,6 +3785,7 @@ static int synth_run(const SynthCall& c) {
   const void *d_env = c.env_params, *d_shape = c.env_shapes, *d_tab = c.table.env_tab, *d_tidx = c.table.tab_index, *d_car = c.carrier,
              *d_kind = c.lines.line_kind, *d_line = c.lines.line_params, *d_gs = c.vjp.grad_signals;
   void *d_iq = c.fwd.awg_iq_out, *d_sig = c.fwd.signals_out, *d_ge = c.vjp.grad_env, *d_gc = c.vjp.grad_carrier, *d_gl = c.vjp.grad_line, *d_gt = c.vjp.grad_tab;
+  void *d_gf = c.filters.grad_filt, *d_gdc = c.post.grad_dc, *d_gxt = c.post.grad_xtalk;
   const size_t lines = (size_t)B * K, awg = lines * 2 * Na;
   if (flags & C3P_HOST_PTRS) {  // a NULL or empty buffer takes no staging slot: each entry keeps the slots it always had
     if (sg.in(c.env_params, lines * E * C3P_ENV_NPAR * sizeof(double), &d_env)) return -1;
@@ -3760,6 +3801,9 @@ static int synth_run(const SynthCall& c) {
       if (sg.out(c.vjp.grad_carrier, lines * 2 * sizeof(double), &d_gc)) return -1;
       if (chain && sg.out(c.vjp.grad_line, lines * C3P_LINE_NPAR * sizeof(double), &d_gl)) return -1;
       if (sg.out(c.vjp.grad_tab, (size_t)B * T * sizeof(double), &d_gt)) return -1;
+      if (F > 0 && sg.out(c.filters.grad_filt, lines * F * C3P_FILT_NPAR * sizeof(double), &d_gf)) return -1;
+      if (c.post.dc_offset && sg.out(c.post.grad_dc, lines * sizeof(double), &d_gdc)) return -1;
+      if (c.post.xtalk && sg.out(c.post.grad_xtalk, lines * K * sizeof(double), &d_gxt)) return -1;
     } else {
       if (sg.out(c.fwd.signals_out, lines * N * sizeof(double), &d_sig)) return -1;
       if (sg.out(c.fwd.awg_iq_out, awg * sizeof(double), &d_iq)) return -1;
@@ -3769,9 +3813,17 @@ static int synth_run(const SynthCall& c) {
   //          [gcs [B,K,2,N] | part [B,K,tiles,stride]]; the bracketed parts with a line chain only
   const size_t tap_stride = N > 1 ? (size_t)N - 1 : 1, tap_elems = chain ? lines * tap_stride : 0;
   const size_t iq_elems = (!vjp && d_iq) ? 0 : awg;
-  const size_t gcs_elems = chain && vjp ? lines * 2 * N : 0;
-  const size_t part_elems = chain && vjp ? lines * c3p_chain_tiles(N) * c3p_chain_part_stride() : 0;
-  const size_t scratch = tap_elems + iq_elems + (vjp ? 2 * awg : 0) + gcs_elems + part_elems;
+  const size_t gcs_elems = (chain || filt) && vjp ? lines * 2 * N : 0;
+  const size_t part_elems = (chain || filt) && vjp ? lines * c3p_chain_tiles(N) * c3p_chain_part_stride() : 0;
+  // c3p_synth_filt appends: h [B,K,F,N] | buf [F+1,B,K,2,N] | pre [B,K,N] (xtalk) | vjp: gbuf [B,K,2,N] | gh [B,K,N] |
+  // gpre [B,K,N] (xtalk) | host-pointer calls: the four inputs that have no staging slot left (filt_kind rounded up to doubles)
+  const bool xt = c.post.xtalk != nullptr, host = (flags & C3P_HOST_PTRS) != 0;
+  const size_t sig = lines * N, h_elems = filt ? sig * F : 0, buf_elems = filt ? 2 * sig * (F + 1) : 0, pre_elems = filt && xt ? sig : 0;
+  const size_t gbuf_elems = filt && vjp ? 2 * sig : 0, gh_elems = filt && vjp ? sig : 0, gpre_elems = filt && vjp && xt ? sig : 0;
+  const size_t fk_elems = filt && host && F > 0 ? ((size_t)K * F + 1) / 2 : 0, fp_elems = filt && host ? lines * F * C3P_FILT_NPAR : 0;
+  const size_t dc_elems = filt && host && c.post.dc_offset ? lines : 0, xt_elems = filt && host && xt ? lines * K : 0;
+  const size_t filt_elems = h_elems + buf_elems + pre_elems + gbuf_elems + gh_elems + gpre_elems + fk_elems + fp_elems + dc_elems + xt_elems;
+  const size_t scratch = tap_elems + iq_elems + (vjp ? 2 * awg : 0) + gcs_elems + part_elems + filt_elems;
   // A drive call into the caller's I/Q needs no scratch and asks for none: ws_get rounds an empty request up to 16 bytes,
   // which on a fresh device allocates the slot and bumps c3p_workspace_generation.  The table entries have always asked.
   void* v = nullptr;
@@ -3799,13 +3851,46 @@ static int synth_run(const SynthCall& c) {
   C.tap_stride = (long)tap_stride;
   const SynthTabArgs X = {(const double*)d_tab, (const int*)d_tidx, T};
   const SynthTabArgs* Xp = c.table.has ? &X : nullptr;
+  SynthFiltArgs Fa = {};
+  SynthFiltVjpBufs W = {};
+  if (filt) {
+    double* q = p + (scratch - filt_elems);
+    Fa.F = F;
+    Fa.h = q;
+    Fa.buf = Fa.h + h_elems;
+    Fa.pre = xt ? Fa.buf + buf_elems : nullptr;
+    W.gbuf = Fa.buf + buf_elems + pre_elems;
+    W.gh = W.gbuf + gbuf_elems;
+    W.gpre = gpre_elems ? W.gh + gh_elems : nullptr;
+    Fa.fkind = (const int*)c.filters.filt_kind;
+    Fa.fpar = c.filters.filt_params;
+    Fa.dc = c.post.dc_offset;
+    Fa.xtalk = c.post.xtalk;
+    if (host) {  // the staging slots are taken: these four travel in the scratch
+      double* in = W.gh + gh_elems + gpre_elems;
+      if (fk_elems) HIP_TRY(hipMemcpyAsync(in, c.filters.filt_kind, (size_t)K * F * sizeof(int32_t), hipMemcpyHostToDevice, st));
+      if (fp_elems) HIP_TRY(hipMemcpyAsync(in + fk_elems, c.filters.filt_params, fp_elems * sizeof(double), hipMemcpyHostToDevice, st));
+      if (dc_elems) HIP_TRY(hipMemcpyAsync(in + fk_elems + fp_elems, c.post.dc_offset, dc_elems * sizeof(double), hipMemcpyHostToDevice, st));
+      if (xt_elems) HIP_TRY(hipMemcpyAsync(in + fk_elems + fp_elems + dc_elems, c.post.xtalk, xt_elems * sizeof(double), hipMemcpyHostToDevice, st));
+      Fa.fkind = fk_elems ? (const int*)in : nullptr;
+      Fa.fpar = fp_elems ? in + fk_elems : nullptr;
+      Fa.dc = dc_elems ? in + fk_elems + fp_elems : nullptr;
+      Fa.xtalk = xt_elems ? in + fk_elems + fp_elems + dc_elems : nullptr;
+    }
+    W.gfilt = (double*)d_gf;
+    W.gdc = (double*)d_gdc;
+    W.gxtalk = (double*)d_gxt;
+  }
   if (!vjp) {
-    LAUNCH_TRY(c3p_launch_synth(C, Xp, st));
+    if (filt)
+      LAUNCH_TRY(c3p_launch_synth_filt(C, X, Fa, st));
+    else
+      LAUNCH_TRY(c3p_launch_synth(C, Xp, st));
   } else {
     SynthVjpBufs V = {};
     V.giq = A.iq + awg;
     V.gcar_part = V.giq + awg;
-    if (chain) {
+    if (chain || filt) {
       V.gcs = V.gcar_part + awg;
       V.part = V.gcs + gcs_elems;
     }
@@ -3813,7 +3898,10 @@ static int synth_run(const SynthCall& c) {
     V.gcar = (double*)d_gc;
     V.gline = (double*)d_gl;
     V.gtab = (double*)d_gt;
-    LAUNCH_TRY(c3p_launch_synth_vjp(C, Xp, (const double*)d_gs, V, st));
+    if (filt)
+      LAUNCH_TRY(c3p_launch_synth_filt_vjp(C, X, Fa, (const double*)d_gs, V, W, st));
+    else
+      LAUNCH_TRY(c3p_launch_synth_vjp(C, Xp, (const double*)d_gs, V, st));
   }
   if (flags & C3P_HOST_PTRS) return sg.finish();
   return 0;
@@ -3865,6 +3953,28 @@ int c3p_synth_tab_vjp(const double* env_params, const int32_t* env_shapes, const
   if (!grad_signals) return fail("NULL pointer argument");
   return synth_run({env_params, env_shapes, carrier, {true, env_tab, tab_index, T}, {false, line_kind, line_params}, t_start, t_end,
                     awg_res, sim_res, B, K, E, flags, {}, {true, grad_signals, grad_env, grad_carrier, grad_line, grad_tab}, stream});
+}
+
+int c3p_synth_filt(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
+                   const double* carrier, const int32_t* line_kind, const double* line_params, const int32_t* filt_kind,
+                   const double* filt_params, int F, const double* dc_offset, const double* xtalk, double t_start, double t_end,
+                   double awg_res, double sim_res, int B, int K, int E, int flags, double* awg_iq_out, double* signals_out,
+                   void* stream) {
+  return synth_run({env_params, env_shapes, carrier, {true, env_tab, tab_index, T}, {false, line_kind, line_params}, t_start, t_end,
+                    awg_res, sim_res, B, K, E, flags, {awg_iq_out, signals_out}, {}, stream, {true, filt_kind, filt_params, F, nullptr},
+                    {dc_offset, xtalk, nullptr, nullptr}});
+}
+
+int c3p_synth_filt_vjp(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
+                       const double* carrier, const int32_t* line_kind, const double* line_params, const int32_t* filt_kind,
+                       const double* filt_params, int F, const double* dc_offset, const double* xtalk, double t_start,
+                       double t_end, double awg_res, double sim_res, int B, int K, int E, int flags, const double* grad_signals,
+                       double* grad_env, double* grad_carrier, double* grad_line, double* grad_tab, double* grad_filt,
+                       double* grad_dc, double* grad_xtalk, void* stream) {
+  if (!grad_signals) return fail("NULL pointer argument");
+  return synth_run({env_params, env_shapes, carrier, {true, env_tab, tab_index, T}, {false, line_kind, line_params}, t_start, t_end,
+                    awg_res, sim_res, B, K, E, flags, {}, {true, grad_signals, grad_env, grad_carrier, grad_line, grad_tab}, stream,
+                    {true, filt_kind, filt_params, F, grad_filt}, {dc_offset, xtalk, grad_dc, grad_xtalk}});
 }
 
 int c3p_dress(const void* H, const void* ops, int64_t ops_bstride, int P, int M, int D, int flags, double* eig_out, void* T_out,

@@ -45,6 +45,31 @@ struct SynthVjpBufs {
   double* gtab;       // [B,T]: 0 outside the blocks and in the t_bin slots
 };
 
+// Line filters, DC offset and crosstalk (c3p_synth_filt): F stage slots per line between DAC (and the legacy Response) and
+// Mixer, each a causal convolution over a materialised [B,K,2,N] buffer.
+struct SynthFiltArgs {
+  const int* fkind;     // [K,F] C3P_FILT_*, < 0 = unused slot
+  const double* fpar;   // [B,K,F,C3P_FILT_NPAR]
+  int F;
+  const double* dc;     // [B,K] or NULL
+  const double* xtalk;  // [B,K,K] or NULL
+  double* h;            // [B,K,F,N] scratch: every stage's impulse response
+  double* buf;          // [F+1,B,K,2,N] scratch: the upsampled DAC (and legacy Response) output, then every stage's output
+  double* pre;          // [B,K,N] scratch: the signals before the crosstalk (with xtalk only)
+};
+struct SynthFiltVjpBufs {
+  double* gbuf;    // [B,K,2,N] scratch: the second cotangent buffer (V.gcs is the first)
+  double* gh;      // [B,K,N] scratch: d loss / d h of the stage at hand
+  double* gpre;    // [B,K,N] scratch: the cotangent before the crosstalk (with xtalk only)
+  double* gfilt;   // [B,K,F,C3P_FILT_NPAR]
+  double* gdc;     // [B,K] (with dc only)
+  double* gxtalk;  // [B,K,K] (with xtalk only)
+};
+// C.kind == NULL: drive lines without a legacy Response.  V.gcs and V.part are needed whether lines travel or not.
+hipError_t c3p_launch_synth_filt(const SynthChainArgs& C, const SynthTabArgs& X, const SynthFiltArgs& Fa, hipStream_t st);
+hipError_t c3p_launch_synth_filt_vjp(const SynthChainArgs& C, const SynthTabArgs& X, const SynthFiltArgs& Fa, const double* gsig,
+                                     const SynthVjpBufs& V, const SynthFiltVjpBufs& W, hipStream_t st);
+
 // C.kind == NULL: the standard drive line (AWG -> DAC -> Mixer -> VoltsToHertz), only C.S is read.  X == NULL: no
 // coefficient table travels with the rows, and the table-free instantiations of the AWG kernels run.
 hipError_t c3p_launch_synth(const SynthChainArgs& C, const SynthTabArgs* X, hipStream_t st);

@@ -949,3 +949,6 @@ hipError_t c3p_launch_synth_vjp(const SynthChainArgs& C, const SynthTabArgs* X, 
   launch_awg_bwd(A, X, (const double*)V.giq, (const double*)V.gcar_part, V.genv, V.gcar, V.gtab, st);
   return hipGetLastError();
 }
+
+// ---- line filters, DC offset and crosstalk (c3p_synth_filt): the stage kernels and their two launchers ------------------------
+#include "c3p_signal_filt.inc"

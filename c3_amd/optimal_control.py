@@ -47,6 +47,9 @@ def goal_run_with_grad(
     line_params=None,
     env_tables=None,
     table_index=None,
+    line_filters=None,
+    dc_offset=None,
+    crosstalk=None,
 ) -> Dict:
     """goals [B] and their gradients w.r.t. every envelope row, carrier pair and frame-rotation phase.
 
@@ -64,6 +67,11 @@ def goal_run_with_grad(
     `env_tables` [B,T] / `table_index` [K,E,2] (signals.pack_table_components) bring the coefficients of sampled and Fourier
     envelopes (pwc, pwc_shape, pwc_symmetric, fourier_sin, fourier_cos): the result then holds "grad_tables" [B,T], the
     gradient w.r.t. every coefficient in the layout of env_tables -- what a GRAPE-style optimiser of the AWG samples steps along.
+
+    `line_filters` = (filt_kind [K,F], filt_params [B,K,F,FILT_NPAR]) (signals.pack_line_filters), `dc_offset` [B,K] and
+    `crosstalk` [K,K] | [B,K,K] (signals.pack_crosstalk) add distortion stages between DAC and Mixer, an offset behind the
+    Mixer and a mixing matrix over the finished lines (`signals.synthesize_signals`); the result then holds "grad_filters"
+    [B,K,F,FILT_NPAR], "grad_dc_offset" [B,K] and "grad_crosstalk" [B,K,K] for those passed, on every route below.
 
     `fused` (closed systems; default: wherever the library serves the shape) takes goal and gradient from ONE pass over the
     chains (`propagation.propagate_batch_goal_vjp`); False runs forward pass, cotangent and vector-Jacobian product as three
@@ -93,10 +101,20 @@ def goal_run_with_grad(
             raise C3PropError("C3:Error: env_tables and table_index go together")
         chain = dict(chain, env_tables=as_dev(env_tables, np.float64), table_index=table_index)
         names += ("grad_tables",)
+    if line_filters is not None:
+        chain = dict(chain, line_filters=(line_filters[0], as_dev(line_filters[1], np.float64)))
+        names += ("grad_filters",)
+    if dc_offset is not None:
+        chain = dict(chain, dc_offset=as_dev(dc_offset, np.float64))
+        names += ("grad_dc_offset",)
+    if crosstalk is not None:
+        chain = dict(chain, crosstalk=as_dev(crosstalk, np.float64))
+        names += ("grad_crosstalk",)
     sig = signals.synthesize_signals(env, env_shapes, car, t_start, t_end, awg_res, sim_res, **chain)
 
     def synth_vjp(g_sig):
-        """{"grad_env", "grad_carrier"[, "grad_line"][, "grad_tables"]} from d goal / d signals"""
+        """{"grad_env", "grad_carrier"[, "grad_line"][, "grad_tables"][, "grad_filters"][, "grad_dc_offset"][, "grad_crosstalk"]}
+        from d goal / d signals"""
         g = signals.synthesize_signals_vjp(env, env_shapes, car, t_start, t_end, awg_res, sim_res, g_sig, **chain)
         return dict(zip(names, g))
 
@@ -209,6 +227,7 @@ def robust_goal_run_with_grad(*args, **kwargs) -> Dict:
         out["grad_fr_phase"] = r["grad_fr_phase"].mean(dim=0)
     if "grad_line" in r:
         out["grad_line"] = r["grad_line"].mean(dim=0)
-    if "grad_tables" in r:
-        out["grad_tables"] = r["grad_tables"].mean(dim=0)
+    for key in ("grad_tables", "grad_filters", "grad_dc_offset", "grad_crosstalk"):
+        if key in r:
+            out[key] = r[key].mean(dim=0)
     return out

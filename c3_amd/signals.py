@@ -63,6 +63,17 @@ ENVF_DRAG = 2
 LINE_KINDS = {"drive": 0, "flux": 1}
 LINE_SLOTS = {"rise_time": 0, "phi_0": 1, "phi": 2, "omega_0": 3, "anhar": 4, "d": 5}
 LINE_NPAR = 6
+# distortion stages between DAC and Mixer and their parameter slots (C3P_FILT_* of include/c3prop.h; `pack_line_filters`)
+FILT_KINDS = {"response_fft": 0, "exp_iir": 1, "highpass_exp": 2, "skin_effect": 3}
+FILT_SLOTS = {"tau": 0, "amp": 1}
+FILT_NPAR = 2
+# the reference's parameter names per kind -> slot (devices.py:651, :741-743, :761, :786)
+_FILT_KEYS = {
+    "response_fft": {"rise_time": "tau"},
+    "exp_iir": {"time_iir": "tau", "amp": "amp"},
+    "highpass_exp": {"time_hp": "tau"},
+    "skin_effect": {"alpha": "tau"},
+}
 
 
 def slice_num(t_start: float, t_end: float, resolution: float) -> int:
@@ -226,6 +237,76 @@ def pack_lines(lines: Sequence[Dict], B: int = 1, sim_res: Optional[float] = Non
     return kinds, params
 
 
+def _check_filters(kinds: np.ndarray, params: Optional[np.ndarray], sim_res: Optional[float]) -> None:
+    """what the library refuses on host-pointer calls; `params` None: the kinds alone (device rows are not looked at)"""
+    if kinds.size and kinds.max() >= len(FILT_KINDS):
+        raise C3PropError(f"C3:Error: filter kinds hold an unknown kind id (have {FILT_KINDS})")
+    if params is None:
+        return
+    used = np.broadcast_to(kinds >= 0, params.shape[:-1])
+    tau, amp = params[..., FILT_SLOTS["tau"]], params[..., FILT_SLOTS["amp"]]
+    if (used & ~(np.isfinite(tau) & np.isfinite(amp))).any():
+        raise C3PropError("C3:Error: a filter parameter is not finite")
+    if (used & (kinds != FILT_KINDS["skin_effect"]) & ~(tau > 0)).any():
+        raise C3PropError("C3:Error: a filter's time constant must be positive")
+    if sim_res is not None and (used & (kinds == FILT_KINDS["response_fft"]) & (np.floor(tau * float(sim_res)) < 1)).any():
+        raise C3PropError(f"C3:Error: a response_fft rise_time gives no tap at sim_res={sim_res:g}")
+
+
+def pack_line_filters(lines: Sequence[Sequence[Dict]], B: int = 1, sim_res: Optional[float] = None):
+    """Distortion stages per line -> (filt_kind int32 [K,F], filt_params [B,K,F,FILT_NPAR]).
+
+    `lines[k]` lists the stages of line k in the order they act, between DAC (and the legacy Response of `pack_lines`) and
+    Mixer, as dicts keyed like the reference's devices: `{"kind": "exp_iir", "time_iir": .., "amp": ..}` (ExponentialIIR,
+    devices.py:735-751), `{"kind": "highpass_exp", "time_hp": ..}` (:755-769), `{"kind": "skin_effect", "alpha": ..}`
+    (:773-787), `{"kind": "response_fft", "rise_time": ..}` (:646-701).  Values are scalars or arrays of B per-sample values.
+    Lines with fewer stages than the longest keep unused slots (kind -1) at the end.
+    """
+    K = len(lines)
+    F = max([len(st) for st in lines] + [0])
+    kinds = np.full((K, F), -1, dtype=np.int32)
+    params = np.zeros((B, K, F, FILT_NPAR), dtype=np.float64)
+    for k, stages in enumerate(lines):
+        for f, stage in enumerate(stages):
+            name = stage.get("kind")
+            if name not in FILT_KINDS:
+                raise C3PropError(f"C3:Error: filter kind {name!r} is not available on the device (have {sorted(FILT_KINDS)})")
+            keys = _FILT_KEYS[name]
+            for key, val in stage.items():
+                if key == "kind":
+                    continue
+                if key not in keys:
+                    raise C3PropError(f"C3:Error: filter kind {name!r} takes no parameter {key!r} (takes {sorted(keys)})")
+                v = np.asarray(val, dtype=np.float64)
+                if v.shape not in ((), (B,)):
+                    raise C3PropError(f"C3:Error: '{key}' must be a scalar or [{B}], got {v.shape}")
+                params[:, k, f, FILT_SLOTS[keys[key]]] = v
+            for key in keys:
+                if key not in stage:
+                    raise C3PropError(f"C3:Error: filter kind {name!r} needs '{key}'")
+            kinds[k, f] = FILT_KINDS[name]
+    _check_filters(kinds, params, sim_res)
+    return kinds, params
+
+
+def pack_crosstalk(channels: Sequence[str], crossed_channels: Sequence[str], matrix) -> np.ndarray:
+    """Crosstalk.process (devices.py:262-292) as one [K,K] matrix over all lines: `matrix` [C,C] mixes the lines named in
+    `crossed_channels` (in that order) among themselves, every other line keeps its identity row."""
+    channels, crossed = list(channels), list(crossed_channels)
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.shape != (len(crossed), len(crossed)):
+        raise C3PropError(f"C3:Error: the crosstalk matrix must be [{len(crossed)},{len(crossed)}], got {m.shape}")
+    if len(set(crossed)) != len(crossed):
+        raise C3PropError("C3:Error: a crossed channel is named twice")
+    for ch in crossed:
+        if ch not in channels:
+            raise C3PropError(f"C3:Error: crossed channel {ch!r} is not a line (have {channels})")
+    idx = [channels.index(ch) for ch in crossed]
+    out = np.eye(len(channels), dtype=np.float64)
+    out[np.ix_(idx, idx)] = m
+    return out
+
+
 _shapes_memo = TensorMemo()  # device shape tables: per tensor object (weak reference + version), never per address
 _shapes_upload: Dict[tuple, object] = {}  # content-keyed uploads of host tables
 
@@ -338,10 +419,57 @@ def _lines(call, line_kinds, line_params, B: int, K: int, sim_res: float):
     return knd, par
 
 
-def _begin(env_params, env_shapes, carrier, t_start, t_end, awg_res, sim_res, grad_signals, line_kinds, line_params, env_tables, table_index):
+def _filters(call, line_filters, B: int, K: int, sim_res: float):
+    """(kinds, params, F) as the library call takes them, treated as `_lines` treats the line rows"""
+    if not isinstance(line_filters, (tuple, list)) or len(line_filters) != 2:
+        raise C3PropError("C3:Error: line_filters is the pair (filt_kind [K,F], filt_params [B,K,F,2]) of pack_line_filters")
+    fk, fp = line_filters
+    kinds_np = np.ascontiguousarray(np.asarray(fk.cpu() if _is_torch(fk) else fk, dtype=np.int32))
+    if kinds_np.ndim != 2 or kinds_np.shape[0] != K:
+        raise C3PropError(f"C3:Error: filter kinds must be [{K},F], got {kinds_np.shape}")
+    F = int(kinds_np.shape[1])
+    par = call.f64(fp)
+    if tuple(par.shape) != (B, K, F, FILT_NPAR):
+        raise C3PropError(f"C3:Error: filter parameters must be [{B},{K},{F},{FILT_NPAR}], got {tuple(par.shape)}")
+    if _is_torch(fp) and fp.is_cuda:
+        _check_filters(kinds_np, None, None)
+    else:
+        _check_filters(kinds_np, np.asarray(fp.numpy() if _is_torch(fp) else fp, dtype=np.float64), sim_res)
+    if F == 0:
+        return None, None, 0
+    if not call.device:
+        return kinds_np, par, F
+    key = ("fkinds", kinds_np.tobytes(), kinds_np.shape, str(call.dev))
+    knd = _shapes_upload.get(key)
+    if knd is None:
+        if len(_shapes_upload) > 64:
+            _shapes_upload.clear()
+        knd = _shapes_upload[key] = call.torch.as_tensor(kinds_np, device=call.dev)
+    return knd, par, F
+
+
+def _no_table_index(call, K: int, E: int):
+    """the index table of a c3p_synth_filt call without a coefficient table: every component (-1, 0)"""
+    idx = np.zeros((K, E, 2), dtype=np.int32)
+    idx[..., 0] = -1
+    if not call.device:
+        return idx
+    key = ("notab", K, E, str(call.dev))
+    up = _shapes_upload.get(key)
+    if up is None:
+        if len(_shapes_upload) > 64:
+            _shapes_upload.clear()
+        up = _shapes_upload[key] = call.torch.as_tensor(idx, device=call.dev)
+    return up
+
+
+def _begin(env_params, env_shapes, carrier, t_start, t_end, awg_res, sim_res, grad_signals, line_kinds, line_params, env_tables, table_index,
+           line_filters=None, dc_offset=None, crosstalk=None):
     """What `synthesize_signals` and `synthesize_signals_vjp` (the call with `grad_signals`) share: the argument checks, and the
     one place that picks the C entry -- `c3p_synth_tab` with a coefficient table, `c3p_synth_chain` with lines alone, else
     `c3p_synth_signals`, `_vjp` appended for the vjp -- and builds the arguments all six start with.
+
+    With any of `line_filters`, `dc_offset`, `crosstalk` the entry is `c3p_synth_filt`, whatever else travels.
 
     -> (call, entry, leading arguments, the arrays behind them (the caller holds them over the call), B, K, E, N, Na, T); T is
     None without a table.  A vjp's leading arguments end with grad_signals [B,K,N]."""
@@ -349,7 +477,8 @@ def _begin(env_params, env_shapes, carrier, t_start, t_end, awg_res, sim_res, gr
         raise C3PropError("C3:Error: line_kinds and line_params go together")
     if (env_tables is None) != (table_index is None):
         raise C3PropError("C3:Error: env_tables and table_index go together")
-    call = _Call(env_params, carrier, grad_signals, line_params, env_tables)
+    filt = line_filters is not None or dc_offset is not None or crosstalk is not None
+    call = _Call(env_params, carrier, grad_signals, line_params, env_tables, line_filters[1] if line_filters is not None and len(line_filters) == 2 else None, dc_offset, crosstalk)
     env = call.f64(env_params)
     if env.ndim != 4 or env.shape[-1] != ENV_NPAR:
         raise C3PropError(f"C3:Error: env_params must be [B,K,E,{ENV_NPAR}], got {tuple(env.shape)}")
@@ -369,6 +498,28 @@ def _begin(env_params, env_shapes, carrier, t_start, t_end, awg_res, sim_res, gr
         tab, tidx, T = _tables(call, env_tables, table_index, shapes_np, B, Na)
     if line_kinds is not None:
         knd, par = _lines(call, line_kinds, line_params, B, K, sim_res)
+    if filt:
+        fk = fp = None
+        F = 0
+        if line_filters is not None:
+            fk, fp, F = _filters(call, line_filters, B, K, sim_res)
+        dc, xt = call.f64(dc_offset), call.f64(crosstalk)
+        if dc is not None and tuple(dc.shape) != (B, K):
+            raise C3PropError(f"C3:Error: dc_offset must be [{B},{K}], got {tuple(dc.shape)}")
+        if xt is not None and tuple(xt.shape) == (K, K):  # one matrix for the batch
+            xt = (xt.expand(B, K, K) if call.device else np.broadcast_to(xt, (B, K, K)))
+            xt = xt.contiguous() if call.device else np.ascontiguousarray(xt)
+        if xt is not None and tuple(xt.shape) != (B, K, K):
+            raise C3PropError(f"C3:Error: crosstalk must be [{K},{K}] or [{B},{K},{K}], got {tuple(xt.shape)}")
+        if T is None:
+            tidx = _no_table_index(call, K, E)
+        name = "c3p_synth_filt"
+        head = (_ptr(env), _ptr(shp), _ptr(tab), _ptr(tidx), T or 0, _ptr(car), _ptr(knd), _ptr(par), _ptr(fk), _ptr(fp), F, _ptr(dc), _ptr(xt))
+        held = (env, shp, tab, tidx, car, knd, par, gs, fk, fp, dc, xt)
+        head += (float(t_start), float(t_end), float(awg_res), float(sim_res), B, K, E, call.flags)
+        if gs is not None:
+            name, head = name + "_vjp", head + (_ptr(gs),)
+        return call, getattr(_lib.load(), name), head, held, B, K, E, N, Na, T
     if T is not None:
         name, head = "c3p_synth_tab", (_ptr(env), _ptr(shp), _ptr(tab), _ptr(tidx), T, _ptr(car), _ptr(knd), _ptr(par))
     elif knd is not None:
@@ -386,7 +537,8 @@ def _empty(call, shape):
     return call.torch.empty(shape, dtype=call.torch.float64, device=call.dev) if call.device else np.empty(shape, dtype=np.float64)
 
 
-def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, *, want_iq: bool = False, device=None, line_kinds=None, line_params=None, env_tables=None, table_index=None):
+def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, *, want_iq: bool = False, device=None, line_kinds=None, line_params=None, env_tables=None, table_index=None,
+                       line_filters=None, dc_offset=None, crosstalk=None):
     """signals [B,K,N] (and optionally the AWG-resolution I/Q [B,K,2,Na]) from parameter rows.
 
     With `line_kinds` [K] int32 and `line_params` [B,K,LINE_NPAR] (see `pack_lines`) every line runs the chain
@@ -395,6 +547,12 @@ def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: f
     With `env_tables` [B,T] f64 and `table_index` [K,E,2] int32 (see `pack_table_components`) `env_shapes` may hold TAB_SHAPES
     ids: sampled (pwc, pwc_shape, pwc_symmetric) and Fourier envelopes that read their coefficients from the table
     (`c3p_synth_tab`, on either kind of line).  Without the two keywords every call goes where it went before them.
+
+    With `line_filters` = (filt_kind [K,F] int32, filt_params [B,K,F,FILT_NPAR]) (see `pack_line_filters`), `dc_offset` [B,K]
+    or `crosstalk` [K,K] | [B,K,K] (see `pack_crosstalk`) the call goes to `c3p_synth_filt`: the stages act on the I/Q pair
+    between DAC (after the legacy Response) and Mixer, each the causal convolution of tf_convolve with the stage's impulse
+    response on the signal's own time grid; the offset is added to the mixer output (DC_Offset, devices.py:1039-1059), and
+    the matrix mixes the finished lines (Crosstalk, devices.py:225-292).  Without the three the call goes where it went before.
 
     env_params [B,K,E,NPAR] f64, env_shapes [K,E] int32, carrier [B,K,2] f64 = (LO angular
     frequency, V_to_Hz).  numpy in -> numpy out (staged by the library); with `device` (or any torch
@@ -406,14 +564,16 @@ def synthesize_signals(env_params, env_shapes, carrier, t_start: float, t_end: f
         env_params = torch.as_tensor(np.asarray(env_params, dtype=np.float64) if not _is_torch(env_params) else env_params, device=device)
         if env_tables is not None and table_index is not None and not _is_torch(env_tables):
             env_tables = torch.as_tensor(np.asarray(env_tables, dtype=np.float64), device=device)
-    call, entry, head, held, B, K, _, N, Na, _ = _begin(env_params, env_shapes, carrier, t_start, t_end, awg_res, sim_res, None, line_kinds, line_params, env_tables, table_index)
+    call, entry, head, held, B, K, _, N, Na, _ = _begin(env_params, env_shapes, carrier, t_start, t_end, awg_res, sim_res, None, line_kinds, line_params, env_tables, table_index,
+                                                        line_filters, dc_offset, crosstalk)
     sig = _empty(call, (B, K, N))
     iq = _empty(call, (B, K, 2, Na)) if want_iq else None
     _lib.check(entry(*head, _ptr(iq), _ptr(sig), call.stream))
     return (sig, iq) if want_iq else sig
 
 
-def synthesize_signals_vjp(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, grad_signals, *, line_kinds=None, line_params=None, env_tables=None, table_index=None):
+def synthesize_signals_vjp(env_params, env_shapes, carrier, t_start: float, t_end: float, awg_res: float, sim_res: float, grad_signals, *, line_kinds=None, line_params=None, env_tables=None, table_index=None,
+                           line_filters=None, dc_offset=None, crosstalk=None):
     """(grad_env [B,K,E,NPAR], grad_carrier [B,K,2]) from d loss / d signals [B,K,N]; with `line_kinds` / `line_params`
     (the chain of `synthesize_signals`) also grad_line [B,K,LINE_NPAR]: phi_0, phi, omega_0, anhar, d in their LINE_SLOTS,
     0 for rise_time (the tap count is a floor) and, in grad_carrier, for V_to_Hz on a flux line.  With `env_tables` /
@@ -421,14 +581,28 @@ def synthesize_signals_vjp(env_params, env_shapes, carrier, t_start: float, t_en
     cotangent of every coefficient in the layout of env_tables, exactly 0 in the t_bin_start / t_bin_end slots (they are
     not differentiated) and outside the blocks.
 
+    With `line_filters`, `dc_offset`, `crosstalk` (as `synthesize_signals` takes them) the values above are followed by
+    grad_filt [B,K,F,FILT_NPAR] (time_iir and amp of exp_iir, time_hp, alpha; exactly 0 for a response_fft rise_time and in
+    unused slots), grad_dc [B,K] and grad_xtalk [B,K,K], for those of the three that were passed, in that order.
+
     Differentiates amp, xy_angle, freq_offset, delta (their ENV_SLOTS) and the carrier pair; the
     reference gets the same numbers from the tape that also covers the propagation
     (optimizers/optimizer.py:206-216, gates.py:341-370).  Chain with `propagate_batch_vjp`.
     """
-    call, entry, head, held, B, K, E, _, _, T = _begin(env_params, env_shapes, carrier, t_start, t_end, awg_res, sim_res, grad_signals, line_kinds, line_params, env_tables, table_index)
+    call, entry, head, held, B, K, E, _, _, T = _begin(env_params, env_shapes, carrier, t_start, t_end, awg_res, sim_res, grad_signals, line_kinds, line_params, env_tables, table_index,
+                                                       line_filters, dc_offset, crosstalk)
     outs = (_empty(call, (B, K, E, ENV_NPAR)), _empty(call, (B, K, 2)))
     if line_kinds is not None:
         outs += (_empty(call, (B, K, LINE_NPAR)),)
+    if line_filters is not None or dc_offset is not None or crosstalk is not None:
+        F = int(held[9].shape[2]) if held[9] is not None else 0
+        gl = outs[2] if line_kinds is not None else None
+        gt = _empty(call, (B, T)) if T is not None else None
+        gf = (_empty(call, (B, K, F, FILT_NPAR)) if line_filters is not None else None)
+        gd = _empty(call, (B, K)) if dc_offset is not None else None
+        gx = _empty(call, (B, K, K)) if crosstalk is not None else None
+        _lib.check(entry(*head, _ptr(outs[0]), _ptr(outs[1]), _ptr(gl), _ptr(gt) if T else None, _ptr(gf) if F else None, _ptr(gd), _ptr(gx), call.stream))
+        return outs + tuple(g for g in (gt, gf, gd, gx) if g is not None)
     if T is None:
         _lib.check(entry(*head, *map(_ptr, outs), call.stream))
     else:  # the table entry takes grad_line whether lines travel or not

@@ -528,6 +528,60 @@ int c3p_synth_tab_vjp(const double* env_params, const int32_t* env_shapes, const
                       double awg_res, double sim_res, int B, int K, int E, int flags, const double* grad_signals,
                       double* grad_env, double* grad_carrier, double* grad_line, double* grad_tab, void* stream);
 
+/* Line filters, DC offset and crosstalk: c3p_synth_tab with distortion stages between DAC and Mixer, an offset between Mixer
+ * and VoltsToHertz | FluxTuning, and a mixing matrix over the finished lines.  The arguments of c3p_synth_tab (table and line
+ * arguments may be NULL as there) plus
+ *   filt_kind    int32 [K,F]                  C3P_FILT_* id per stage slot, negative = unused slot; shared by the batch
+ *   filt_params  f64 [B,K,F,C3P_FILT_NPAR]    {C3P_FILT_TAU, C3P_FILT_AMP} per slot
+ *   F            stage slots per line; 0 allowed (then both pointers may be NULL)
+ *   dc_offset    f64 [B,K] or NULL            DC_Offset (devices.py:1039-1059): added to the mixer output
+ *   xtalk        f64 [B,K,K] or NULL          Crosstalk (devices.py:225-292): out[b,k,:] = sum_j xtalk[b,k,j] s[b,j,:]
+ * Chain per line, the stages acting on the I and Q pair: AWG -> DAC -> legacy Response (rise_time slot > 0) -> stage 0 ..
+ * stage F-1 -> Mixer -> + dc_offset -> VoltsToHertz | FluxTuning; then the crosstalk over all lines.
+ * Every stage is the causal convolution y[n] = sum_{m=0..n} h[m] x[n-m] (tf_convolve, tf_utils.py:439-473: zero-padded, no
+ * wrap-around, no delay), summed directly with m ascending.  With ts[m] the signal's own centred grid (absolute time, as
+ * StepFuncFilter.process reads it, devices.py:719-731):
+ *   C3P_FILT_RESPONSE_FFT   ResponseFFT (devices.py:646-701): M = floor(TAU * sim_res) taps, h = r / sum r,
+ *                           r[m] = exp(-(lin[m] - cen)^2 / (2 sg^2)) - exp(-(-1 - cen)^2 / (2 sg^2)), lin = linspace(0, TAU, M),
+ *                           cen = (TAU - 1/sim_res) / 2, sg = TAU / 4; h[m] = 0 for m >= M
+ *   C3P_FILT_EXP_IIR        ExponentialIIR (:735-751):       s(t) = 1 + AMP exp(-t / TAU)
+ *   C3P_FILT_HIGHPASS_EXP   HighpassExponential (:755-769):  s(t) = exp(-t / TAU)
+ *   C3P_FILT_SKIN_EFFECT    SkinEffectResponse (:773-787):   s(t) = erfc(TAU / 21 / sqrt|t|), the TAU slot holding alpha
+ * and for the three step responses h[0] = s(ts[0]), h[m] = s(ts[m]) - s(ts[m-1]).
+ * Refused on host-pointer calls: an unknown kind, TAU <= 0 or non-finite (kinds 0-2), M = 0 (kind 0), a non-finite alpha or
+ * AMP, filt_kind without filt_params or the reverse.  Device-pointer calls do not synchronise: an unknown kind runs as an
+ * unused slot.
+ */
+#define C3P_FILT_RESPONSE_FFT 0
+#define C3P_FILT_EXP_IIR 1
+#define C3P_FILT_HIGHPASS_EXP 2
+#define C3P_FILT_SKIN_EFFECT 3
+#define C3P_FILT_NKINDS 4
+
+#define C3P_FILT_TAU 0
+#define C3P_FILT_AMP 1
+#define C3P_FILT_NPAR 2
+
+int c3p_synth_filt(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
+                   const double* carrier, const int32_t* line_kind, const double* line_params, const int32_t* filt_kind,
+                   const double* filt_params, int F, const double* dc_offset, const double* xtalk, double t_start, double t_end,
+                   double awg_res, double sim_res, int B, int K, int E, int flags, double* awg_iq_out, double* signals_out,
+                   void* stream);
+
+/* Vector-Jacobian product of c3p_synth_filt: the outputs of c3p_synth_tab_vjp, taken through the stages, plus
+ *   grad_filt  f64 [B,K,F,C3P_FILT_NPAR]  TAU and AMP of EXP_IIR, TAU of HIGHPASS_EXP, alpha of SKIN_EFFECT; 0 in every other
+ *                                         slot (RESPONSE_FFT's tap count is a floor) and in unused slots
+ *   grad_dc    f64 [B,K]                  iff dc_offset
+ *   grad_xtalk f64 [B,K,K]                iff xtalk
+ * Every sum runs in a fixed order without atomics: repeated calls return the same bits.
+ */
+int c3p_synth_filt_vjp(const double* env_params, const int32_t* env_shapes, const double* env_tab, const int32_t* tab_index, int T,
+                       const double* carrier, const int32_t* line_kind, const double* line_params, const int32_t* filt_kind,
+                       const double* filt_params, int F, const double* dc_offset, const double* xtalk, double t_start,
+                       double t_end, double awg_res, double sim_res, int B, int K, int E, int flags, const double* grad_signals,
+                       double* grad_env, double* grad_carrier, double* grad_line, double* grad_tab, double* grad_filt,
+                       double* grad_dc, double* grad_xtalk, void* stream);
+
 /* Fidelity epilogue: overlap[b] = tr(P^T U[b] P G^+), the number behind
  * unitary_infid = 1 - |overlap/L|^2 (c3/libraries/fidelities.py:154-184, tf_unitary_overlap
  * c3/utils/tf_utils.py:330-366) and average_infid = 1 - (|overlap|^2/L + 1)/(L + 1)
