@@ -2312,8 +2312,9 @@ __global__ void __launch_bounds__(256, 1) midd_grad_general_kernel(MidGradArgs A
 // (+ 2 forward and 3 backward per squaring) against 18 + 3 s COMPLEX ones of the pair evaluation above.
 // Eight real images: slots 0..3 hold the operands of the running product, 4 / 5 the products to be transposed,
 // 6 / 7 the product R = dU N for the update N <- R conj(dU) (stored transposed in the swizzled layout, whose left
-// operands are read in the B pattern).  Always the economised degree-8 pair, up to MGR<NIG>::MAXS squarings; other chains
-// are left to midd_grad_kernel (same tables, same norm bound: same decision).
+// operands are read in the B pattern).  This sweep takes the economised degree-8 pair at every norm (the small-D one also has the
+// degree-6 pair below C3P_MM6_THETA), with up to MGR<NIG>::MAXS squarings; other chains are left to midd_grad_kernel (same tables,
+// same norm bound: same decision).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ int mgr_tswz(int x) { return x & 15; }
 

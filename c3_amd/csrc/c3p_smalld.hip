@@ -3372,9 +3372,9 @@ __global__ void __launch_bounds__(64, 1) smalld_grad_general_kernel(SmallGradArg
 //   (two upper-triangle products whose left operands come from registers, as in the forward kernel);
 //   grad[k, n] = scale <Y_bar, Y_k> + Re(mu_k conj(tr N));   N <- R conj(dU)  (the only product with a general LEFT operand:
 //   R goes through a real LDS image).
-// ~600 MFMAs per slice at D = 9 against ~1500 of the complex pair evaluation.  Always the economised degree-8 cos / sin pair
-// (radius C3P_MM8_THETA) with up to SDG_MAXS squarings; samples that are not real, or need more squarings, are left to the
-// complex kernel (same norm bound, same decision).
+// ~600 MFMAs per slice at D = 9 against ~1500 of the complex pair evaluation.  The economised degree-6 cos / sin pair while the
+// segment's bound stays within C3P_MM6_THETA (no squaring), otherwise the degree-8 pair (radius C3P_MM8_THETA) with up to SDG_MAXS
+// squarings; samples that are not real, or need more squarings, are left to the complex kernel (same norm bound, same decision).
 // ---------------------------------------------------------------------------------------------
 template <int D>
 __global__ void __launch_bounds__(64, 1) smalld_grad_real_kernel(SmallGradArgs A) {

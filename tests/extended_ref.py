@@ -5,6 +5,8 @@ precision of the kernels under test, so an error of a few units of 2^-53 is meas
 
 * the references: `expm_ld`, `chain_ld`, `kron_ld`, `overlap_ld`, `infid_ld`, and `pwc_ld` (the assembled piecewise-constant
   propagators of `propagate_batch`, unitary and Lindblad; cases in tests/pwc_cases.py, GPU tests in tests/test_gpu_pwc_extended.py);
+  `expm_frechet_ld`, `pwc_signal_gradient_ld`, `pwc_per_slice_cotangents_ld` (the signal gradients of the `*_vjp` entries and the
+  Hamiltonian cotangents of branch B; cases in tests/grad_cases.py, GPU tests in tests/test_gpu_grad_extended.py);
 * the checkers shared by the CPU tests (tests/test_extended_ref.py) and the GPU tests
   (tests/test_gpu_matrix_routines.py, tests/test_gpu_fidelity_epilogue.py): each asserts its bar and RETURNS the
   ratio it asserted on, so it can be printed and recorded;
@@ -146,6 +148,124 @@ def pwc_ld(h0, hks, signals, dt, *, col_ops=None, fr_phase=None, want_dUs=False)
         assert ph.shape == U.shape[:2], (ph.shape, U.shape)
         U = (np.cos(ph) + CLD(1j) * np.sin(ph))[:, :, None] * U
     return (U, dUs) if want_dUs else U
+
+
+def expm_frechet_ld(A, E):
+    """L(A; E), the Frechet derivative of exp at A in the direction E (one matrix each), in complex long double: the
+    (value, derivative) pair of `expm_ld`'s own scheme.  A scaled to ||X||_1 <= 1/8, 25 Taylor terms of both (T_k = T_{k-1} X / k,
+    dT_k = (dT_{k-1} X + T_{k-1} Y) / k, Y = E / 2^s), then s squarings of the pair, F = exp - 1 carried as in `expm_ld`:
+    (F, L) <- (2 F + F^2, 2 L + F L + L F), then (E, L) <- (E^2, E L + L E).  The derivative is linear in E: the direction is scaled
+    to 1-norm 1 and the result scaled back, so that the roundings stay relative to ||L|| whatever the size of the cotangent.  Agrees
+    with the (0, 1) block of 40-digit mpmath's exp of [[A, E], [0, A]] to a few eps_ld (tests/test_extended_ref.py)."""
+    A, E = to_ld(A), to_ld(E)
+    assert A.ndim == 2 and A.shape == E.shape, (A.shape, E.shape)
+    D = A.shape[-1]
+    ne = norm1(E)
+    if ne == 0.0:
+        return np.zeros_like(A)
+    nrm = norm1(A)
+    s = 0
+    while nrm > 0.125 * 2.0**s:
+        s += 1
+    X = A / LD(2) ** s
+    Y = E / (LD(ne) * LD(2) ** s)
+    T, dT = X.copy(), Y.copy()
+    F, L = X.copy(), Y.copy()
+    for k in range(2, 26):
+        dT = (dT @ X + T @ Y) / LD(k)
+        T = (T @ X) / LD(k)
+        F = F + T
+        L = L + dT
+    k = 0
+    while k < s and norm1(F) < 0.5:
+        L = 2 * L + F @ L + L @ F
+        F = 2 * F + F @ F
+        k += 1
+    Ex = F + np.eye(D, dtype=CLD)
+    for _ in range(k, s):
+        L = Ex @ L + L @ Ex
+        Ex = Ex @ Ex
+    return L * LD(ne)
+
+
+def _adjoint_sweep_ld(X, dUs, lam):
+    """Z[N, Dm, Dm] of one sample: Z_n = L(X_n^H; W_n), W_n = lam_n P_n^H the cotangent of slice n, P_n = dU_{n-1} ... dU_0 the
+    prefix product and lam_n = (dU_{N-1} ... dU_{n+1})^H lam the running adjoint, all in long double.  d loss = Re sum conj(lam) dU
+    for U = dU_{N-1} ... dU_0 then gives d loss = sum_n Re <Z_n, dX_n>."""
+    N, Dm = X.shape[0], X.shape[-1]
+    H = lambda m: np.conj(np.swapaxes(m, -1, -2))
+    P = [np.eye(Dm, dtype=CLD)]
+    for n in range(N - 1):
+        P.append(dUs[n] @ P[-1])
+    Z = np.empty_like(X)
+    for n in range(N - 1, -1, -1):
+        Z[n] = expm_frechet_ld(H(X[n]), lam @ H(P[n]))
+        lam = H(dUs[n]) @ lam
+    return Z
+
+
+def _row_phases_adjoint(U_bar, fr_phase):
+    """FR^H U_bar[B, Dm, Dm] in long double: the cotangent of the chain product when U = diag(exp(i fr_phase)) x product."""
+    lam = to_ld(U_bar)
+    if fr_phase is not None:
+        ph = np.asarray(fr_phase, dtype=np.float64).astype(LD)
+        assert ph.shape == lam.shape[:2], (ph.shape, lam.shape)
+        lam = (np.cos(ph) - CLD(1j) * np.sin(ph))[:, :, None] * lam
+    return lam
+
+
+def pwc_signal_gradient_ld(h0, hks, signals, dt, U_bar, *, col_ops=None, fr_phase=None):
+    """g[B, K, N] in long double, d loss / d signals of `propagate_batch_vjp` / `propagate_batch_lindblad_vjp` for
+    d loss = Re sum conj(U_bar) dU.  Generators and slices are those of `pwc_ld` (`pwc_generators_ld`, `expm_ld`); prefix products
+    and the running adjoint in long double; per slice ONE adjoint Frechet derivative Z_n = L(X_n^H; W_n) (`expm_frechet_ld`) and
+    g[k, n] = Re <Z_n, G_k>, G_k = -i dt h_k or dt (-i)(h_k (x) 1 - 1 (x) h_k^T) with collapse operators.  Operators shared or per
+    sample, row phases as in `pwc_ld`."""
+    X = pwc_generators_ld(h0, hks, signals, dt, col_ops=col_ops)
+    dUs = expm_ld(X)
+    B, N = X.shape[:2]
+    K = np.asarray(signals).shape[1]
+    lam = _row_phases_adjoint(U_bar, fr_phase)
+    hks = to_ld(hks)
+    g = np.zeros((B, K, N), dtype=LD)
+    for b in range(B):
+        kb = hks[b] if hks.ndim == 4 else hks
+        if col_ops is None:
+            Gk = CLD(-1j) * LD(dt) * kb
+        else:
+            one = np.eye(kb.shape[-1], dtype=CLD)
+            Gk = CLD(-1j) * LD(dt) * (kron_ld(kb, one) - kron_ld(one, np.swapaxes(kb, -1, -2)))
+        Z = _adjoint_sweep_ld(X[b], dUs[b], lam[b])
+        for k in range(K):
+            g[b, k] = (np.conj(Z) * Gk[k][None]).sum(axis=(-2, -1)).real
+    return g
+
+
+def pwc_per_slice_cotangents_ld(hs, dt, U_bar, *, fr_phase=None):
+    """H_bar[B, N, D, D] in complex long double of branch B (`propagate_per_slice_vjp`, `oracle.pwc_per_slice_hamiltonian_cotangents`):
+    d loss = Re sum conj(H_bar) dH for d loss = Re sum conj(U_bar) dU; the slice generator is -i dt H_n, so H_bar_n = i dt Z_n."""
+    hs = to_ld(hs)
+    X = pwc_generators_ld(hs if hs.ndim == 4 else hs[None], None, None, dt)
+    dUs = expm_ld(X)
+    lam = _row_phases_adjoint(np.asarray(U_bar).reshape((X.shape[0],) + X.shape[-2:]), fr_phase)
+    return np.stack([CLD(1j) * LD(dt) * _adjoint_sweep_ld(X[b], dUs[b], lam[b]) for b in range(X.shape[0])])
+
+
+def grad_err(g, ref) -> float:
+    """Worst max|g_b - ref_b| / max|ref_b| over the samples (first axis), in long double."""
+    g = np.asarray(g)
+    assert g.shape == ref.shape, (g.shape, ref.shape)
+    assert np.all(np.isfinite(g)), "non-finite gradient"
+    return max(float(np.abs(g[b].astype(ref.dtype) - ref[b]).max() / np.abs(ref[b]).max()) for b in range(ref.shape[0]))
+
+
+def check_grad(g, ref, e_cpu: float, factor: float = None) -> float:
+    """Every sample of a gradient within factor x e_cpu of the long-double one, e_cpu the worst `grad_err` of the double-precision
+    CPU routes.  Returns the ratio."""
+    factor = CHAIN_FACTOR if factor is None else factor
+    e = grad_err(g, ref)
+    ratio = 0.0 if e == 0.0 else (np.inf if e_cpu == 0.0 else e / e_cpu)
+    assert ratio <= factor, f"gradient error {e:.3g} is {ratio:.3g} x the double-precision routes' {e_cpu:.3g} (bar {factor:g})"
+    return ratio
 
 
 def kron_ld(A, B):

@@ -4,6 +4,8 @@
 * scipy's and the oracle's double-precision `expm` through `check_expm` over the case list of the GPU test: their worst
   ratios per class are the recorded `R_CPU_EXPM`, and must stay within them;
 * the oracle's folds through `check_chain` over the chain case list;
+* the long-double gradient references (`pwc_signal_gradient_ld`, `pwc_per_slice_cotangents_ld`) against a forward-mode 40-digit
+  mpmath gradient and against central differences in long double;
 * sensitivity: every checker passes on a double-precision result and FAILS on a subtly wrong one -- the proof that the
   GPU tests (tests/test_gpu_matrix_routines.py, tests/test_gpu_fidelity_epilogue.py) would notice a wrong kernel.
 """
@@ -283,3 +285,171 @@ def test_check_infid_lindbladian_sensitivity():
     bad[1] = rows[0] * D + 2
     tb = (S[:, bad[:, None], bad[None, :]] * np.conj(Gs)).sum(axis=(-2, -1))
     _fails(x.check_infid, 1 - np.abs(tb) / L**2, S, srows, Gs, "lindbladian", L=L)
+
+
+# --------------------------------------------------------------------------
+# the gradient references (pwc_signal_gradient_ld, pwc_per_slice_cotangents_ld)
+# --------------------------------------------------------------------------
+
+
+def _mp_kron(mp, A, B):
+    n, m = A.rows, B.rows
+    out = mp.matrix(n * m, n * m)
+    for i in range(n):
+        for j in range(n):
+            for p in range(m):
+                for q in range(m):
+                    out[i * m + p, j * m + q] = A[i, j] * B[p, q]
+    return out
+
+
+def _mp_sup(mp, H, one):
+    return mp.mpc(0, -1) * (_mp_kron(mp, H, one) - _mp_kron(mp, one, H.T))
+
+
+def _mp_signal_gradient(mp, h0, hks, sig, dt, col, ph, Ubar):
+    """One sample in 40 digits, FORWARD mode (nothing shared with the adjoint form under test): dU / dc_k(n) = post_n L(X_n; G_k) pre_n
+    with L the (0, 1) block of mp.expm([[X, G], [0, X]]); g[k, n] = Re sum conj(Ubar) FR dU.  Returns (g, sum_n ||X_n||_1,
+    max_k ||G_k||_F) with g a K x N list of mpf."""
+    D = h0.shape[-1]
+    K, N = sig.shape
+    one = mp.eye(D)
+    Hk = [_mp_matrix(mp, hks[k]) for k in range(K)]
+    if col is None:
+        Gk = [mp.mpc(0, -1) * mp.mpf(dt) * h for h in Hk]
+        diss = None
+    else:
+        Gk = [mp.mpf(dt) * _mp_sup(mp, h, one) for h in Hk]
+        diss = mp.zeros(D * D)
+        for C in col:
+            C = _mp_matrix(mp, C)
+            CC = C.H * C
+            diss = diss + _mp_kron(mp, C, C.conjugate()) - (_mp_kron(mp, CC, one) + _mp_kron(mp, one, CC.T)) / 2
+    Dm = Gk[0].rows
+    Xs = []
+    for n in range(N):
+        H = _mp_matrix(mp, h0)
+        for k in range(K):
+            H = H + mp.mpf(float(sig[k, n])) * Hk[k]
+        Xs.append(mp.mpc(0, -1) * mp.mpf(dt) * H if col is None else mp.mpf(dt) * (_mp_sup(mp, H, one) + diss))
+    Es = [mp.expm(X) for X in Xs]
+    pre = [mp.eye(Dm)]
+    for n in range(N):
+        pre.append(Es[n] * pre[-1])
+    post = [None] * N
+    acc = mp.eye(Dm)
+    for n in range(N - 1, -1, -1):
+        post[n] = acc
+        acc = acc * Es[n]
+    rows = [mp.expj(mp.mpf(float(p))) for p in ph] if ph is not None else [mp.mpf(1)] * Dm
+    Ub = _mp_matrix(mp, Ubar)
+    g = [[None] * N for _ in range(K)]
+    for n in range(N):
+        for k in range(K):
+            blk = mp.zeros(2 * Dm)
+            for i in range(Dm):
+                for j in range(Dm):
+                    blk[i, j] = blk[Dm + i, Dm + j] = Xs[n][i, j]
+                    blk[i, Dm + j] = Gk[k][i, j]
+            Eb = mp.expm(blk)
+            dU = post[n] * Eb[0:Dm, Dm : 2 * Dm] * pre[n]
+            g[k][n] = sum(mp.re(mp.conj(Ub[i, j]) * rows[i] * dU[i, j]) for i in range(Dm) for j in range(Dm))
+    nsum = sum(max(sum(abs(X[i, j]) for i in range(Dm)) for j in range(Dm)) for X in Xs)
+    gmax = max(mp.sqrt(sum(abs(G[i, j]) ** 2 for i in range(Dm) for j in range(Dm))) for G in Gk)
+    return g, float(nsum), float(gmax)
+
+
+def _grad_pin_problem(D, lind, phase, seed=0):
+    rng = np.random.default_rng([D, int(lind), int(phase), seed])
+    B, K, N = 2, 2, 3
+    h0 = rng.normal(size=(D, D)) + 1j * rng.normal(size=(D, D))
+    h0 = (h0 + h0.conj().T) / 2 + 0.7 * np.eye(D)
+    hks = rng.normal(size=(K, D, D)) + 1j * rng.normal(size=(K, D, D))  # not Hermitian: nothing is assumed of the operators
+    sig = rng.uniform(-1, 1, size=(B, K, N))
+    col = 0.3 * (rng.normal(size=(2, D, D)) + 1j * rng.normal(size=(2, D, D))) if lind else None
+    Dm = D * D if lind else D
+    ph = rng.uniform(0, 6.28, size=(B, Dm)) if phase else None
+    Ubar = rng.normal(size=(B, Dm, Dm)) + 1j * rng.normal(size=(B, Dm, Dm))
+    return h0, hks, sig, 0.37, col, ph, Ubar
+
+
+GRAD_PINS = [(D, lind, phase) for D in (2, 3, 4) for lind in (False, True) for phase in (False, True)]
+
+
+@pytest.mark.parametrize("D,lind,phase", GRAD_PINS, ids=[f"D{d}-{'lindblad' if l else 'unitary'}{'-phase' if p else ''}" for d, l, p in GRAD_PINS])
+def test_pwc_signal_gradient_ld_against_mpmath(D, lind, phase):
+    """The form of the `pwc_ld` pin with the scale of a gradient entry (|g| <= ||U_bar||_F ||G_k||_F for unitary slices):
+    |g_ld - exact| <= 4 eps_ld max(1, sum_n ||X_n||_1) ||U_bar||_F max_k ||G_k||_F.  Measured: at most 0.48 of that bar over these
+    twelve cases (D = 4 Lindblad: one sample, 40-digit exponentials of 32 x 32 block matrices are slow)."""
+    mp = pytest.importorskip("mpmath")
+    h0, hks, sig, dt, col, ph, Ubar = _grad_pin_problem(D, lind, phase)
+    g = x.pwc_signal_gradient_ld(h0, hks, sig, dt, Ubar, col_ops=col, fr_phase=ph)
+    assert g.dtype == np.longdouble and g.shape == sig.shape
+    worst = 0.0
+    with mp.workdps(40):
+        for b in range(1 if (lind and D == 4) else sig.shape[0]):
+            gm, nsum, gmax = _mp_signal_gradient(mp, h0, hks, sig[b], dt, col, None if ph is None else ph[b], Ubar[b])
+            diff = max(abs(_ld_to_mp(mp, g[b, k, n]) - gm[k][n]) for k in range(sig.shape[1]) for n in range(sig.shape[2]))
+            worst = max(worst, float(diff) / (x.EPS_LD * max(1.0, nsum) * float(np.linalg.norm(Ubar[b])) * gmax))
+    print(f"pwc_signal_gradient_ld vs mpmath D={D} lindblad={lind} phase={phase}: worst error / (eps_ld max(1, sum ||X_n||) ||Ubar||_F max ||G_k||_F) = {worst:.3g}")
+    assert worst <= 4.0
+
+
+def test_per_slice_cotangents_ld_are_the_signal_gradient_contracted():
+    """Branch B: Re <H_bar_n, h_k> of the per-slice cotangents is the signal gradient of the same problem (two evaluations of the same
+    long-double sweep on differently assembled inputs), and the cotangents follow the oracle's convention."""
+    h0, hks, sig, dt, _, ph, Ubar = _grad_pin_problem(3, False, True, seed=1)
+    hks = (hks + hks.conj().transpose(0, 2, 1)) / 2
+    g = x.pwc_signal_gradient_ld(h0, hks, sig, dt, Ubar, fr_phase=ph)
+    Hs = np.stack([o.sum_h0_hks(h0, hks, sig[b]) for b in range(sig.shape[0])])
+    Hbar = x.pwc_per_slice_cotangents_ld(Hs, dt, Ubar, fr_phase=ph)
+    assert Hbar.dtype == np.clongdouble and Hbar.shape == Hs.shape
+    gc = np.einsum("bnij,kij->bkn", np.conj(Hbar), x.to_ld(hks)).real
+    # (the slice Hamiltonians handed over are the DOUBLE sums h0 + sum_k c_k h_k: the two problems differ by their rounding, u ||H||)
+    assert np.abs(gc - g).max() <= 1e-15 * np.abs(g).max()
+    for b in range(sig.shape[0]):
+        want = o.pwc_per_slice_hamiltonian_cotangents(Hs[b], dt, Ubar[b], ph[b])
+        assert np.abs(Hbar[b].astype(np.complex128) - want).max() <= 1e-13 * np.abs(want).max()
+
+
+def test_pwc_signal_gradient_ld_against_central_differences():
+    """One mid-size case (D = 9, N = 12, Lindblad D = 3 likewise): central differences of `pwc_ld`'s steps in long double with
+    h = 2^-20 (truncation h^2 |g'''| / 6 ~ 1e-13, rounding eps_ld / h = 1e-13): 1e-10 of the largest entry."""
+    for D, lind in ((9, False), (3, True)):
+        rng = np.random.default_rng([77, D])
+        B, K, N = 1, 2, 12
+        herm = lambda s: (lambda m: s * (m + m.conj().T) / 2)(rng.normal(size=(D, D)) + 1j * rng.normal(size=(D, D)))
+        h0, hks = herm(0.5), np.stack([herm(0.3) for _ in range(K)])
+        col = 0.2 * (rng.normal(size=(1, D, D)) + 1j * rng.normal(size=(1, D, D))) if lind else None
+        Dm = D * D if lind else D
+        sig = rng.uniform(-1, 1, size=(B, K, N))
+        ph = rng.uniform(0, 6.28, size=(B, Dm))
+        Ubar = rng.normal(size=(B, Dm, Dm)) + 1j * rng.normal(size=(B, Dm, Dm))
+        g = x.pwc_signal_gradient_ld(h0, hks, sig, 0.4, Ubar, col_ops=col, fr_phase=ph)
+        # the step is a double: s + h and s - h are formed in long double so that the difference is exactly 2 h
+        h = np.longdouble(2.0**-20)
+        worst = 0.0
+        for k, n in ((0, 0), (1, 5), (0, N - 1), (1, 7)):
+            e = np.zeros(sig.shape, dtype=np.longdouble)
+            e[0, k, n] = h
+            fd = (_loss_ld(h0, hks, sig.astype(np.longdouble) + e, 0.4, col, ph, Ubar) - _loss_ld(h0, hks, sig.astype(np.longdouble) - e, 0.4, col, ph, Ubar)) / (2 * h)
+            worst = max(worst, float(abs(fd - g[0, k, n]) / np.abs(g[0]).max()))
+        print(f"pwc_signal_gradient_ld vs central differences D={D} lindblad={lind}: {worst:.3g}")
+        assert worst <= 1e-10
+
+
+def _loss_ld(h0, hks, sig_ld, dt, col, ph, Ubar):
+    """Re sum conj(Ubar) U of `pwc_ld`'s own steps with amplitudes that are long doubles already (`pwc_generators_ld` converts its
+    amplitudes from double: a step of 2^-20 on an amplitude of order 1 would be exact there too, but the sum is formed here without
+    the detour)."""
+    D = h0.shape[-1]
+    H = x.to_ld(h0)[None, None] + (sig_ld[:, :, :, None, None] * x.to_ld(hks)[None, :, None]).sum(axis=1)
+    if col is None:
+        X = np.clongdouble(-1j) * np.longdouble(dt) * H
+    else:
+        X = np.stack([np.longdouble(dt) * x.lindblad_generator_ld(H[b], col) for b in range(H.shape[0])])
+    dUs = x.expm_ld(X)
+    U = np.stack([x.chain_ld(dUs[b]) for b in range(X.shape[0])])
+    phl = np.asarray(ph).astype(np.longdouble)
+    U = (np.cos(phl) + np.clongdouble(1j) * np.sin(phl))[:, :, None] * U
+    return (np.conj(x.to_ld(Ubar)) * U).sum().real
